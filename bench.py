@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py - DDIM sampling throughput of the MI355X-native sampler (BASELINE.json's metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path over one batch: a full DDIM-50 sampling loop (x_T -> x_0) for
 bs=32 clips of 60 s (T=1800 frames) per GPU - BASELINE.json configs[1].  Conditioning (xf_proj',
@@ -21,7 +21,13 @@ distinct), ms_per_step_by_rank (min, max), gather_block_equals_local (every rank
 to its local result), sharded_equals_single_gpu (rank 0 re-sampled the LAST rank's shard alone and found it bit-equal to that
 rank's block - SURVEY.md section 8d, config 3)}.
 
-Extra objects on the JSON line:
+A plain run sets up, warms up, times the K steps and prints the line (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` = milliseconds per timed step, `config`).  `--dump-outputs DIR`
+writes what the timed path returned in its last step - x0 [clips, T, 26], all ranks' clips at N > 1 - as
+DIR/x0.npy (float32; above 64 MB a fixed seeded sample of whole clips, DIR/x0_sample.npy); the inputs are
+seeded, so two builds given the same arguments can be compared output for output.
+
+Extra objects on the JSON line, measured only with `--full` (each takes runs of its own):
   roofline        the kernel with the largest share of the loop (k_layer, HBM roof; or k_film_gemm, MFMA
                   roof): algorithmic bytes / FLOPs per launch over its mean duration, measured with HIP
                   events on the library's own stream in a separate eager pass; `traffic` = HBM bytes per
@@ -119,8 +125,11 @@ def parse_args(argv=None):
     ap.add_argument("--frames", type=int, default=1800)
     ap.add_argument("--ddim", type=int, default=50)
     ap.add_argument("--precision", default="fp16", choices=["fp16", "mixed", "bf16", "bf16x3"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the bf16_mode / bs1 / end_to_end side measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: roofline pass, cpu_baseline, end_to_end, bs1, flat_units, bf16_mode / split_mode")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the bf16_mode / bs1 / end_to_end side measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's x0 as DIR/x0.npy (float32)")
     ap.add_argument("--no-eff", action="store_true", help="full T x T attention variant (reference --no_eff)")
     return ap.parse_args(argv)
 
@@ -220,6 +229,22 @@ def time_loops(nat, noise, coef, n, warm=1):
     return (time.perf_counter() - t0) / n, out
 
 
+DUMP_BYTES = 64 * 10**6          # --dump-outputs: at most 64 MB in all
+
+
+def dump_outputs(out_dir, arrays):
+    """Each array as out_dir/<name>.npy in float32; one larger than DUMP_BYTES becomes <name>_sample.npy, a fixed seeded
+    (default_rng(0)) sample of whole rows along its first axis (clips), in index order."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = a.detach().float().cpu().numpy() if hasattr(a, "detach") else np.asarray(a, np.float32)
+        if a.nbytes > DUMP_BYTES:
+            keep = max(1, DUMP_BYTES // (a.nbytes // a.shape[0]))
+            a, name = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))], name + "_sample"
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, np.float32))
+
+
 def rel_l2(a, b):
     import torch
     a, b = a.detach().cpu().double(), b.detach().cpu().double()
@@ -301,6 +326,8 @@ def main():
         dt = float(tmax.item())
     assert torch.isfinite(out).all() or os.environ.get("DC_BENCH_ANY_STATUS")
     log(f"timed region: {dt:.3f} s for {args.steps} steps")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"x0": out})
     multi = None
     if world > 1 or selftest_multi:
         def resample_shard(r):
@@ -332,7 +359,7 @@ def main():
     }
     if multi is not None:
         line["multi_gpu"] = multi
-    if rank == 0:
+    if rank == 0 and args.full:
         from diffusion_conductor_amd import native
         extras = not args.no_extras
         if extras:
@@ -501,6 +528,7 @@ def main():
                 line["split_mode"] = {"precision": "mixed", "ms_per_step": round(1e3 * t4, 3), "frames_per_s": round(B * T / t4, 1),
                                       "rel_l2": float(f"{rel_l2(o4[:1], cpu_x0):.3e}") if cpu_x0 is not None else None}
                 log(f"bf16 mode: {line['bf16_mode']}; split mode: {line['split_mode']}")
+    if rank == 0:
         print(json.dumps(line), file=result_out, flush=True)
     if world > 1 or selftest_multi:
         dist.barrier()

@@ -82,6 +82,10 @@ def main():
 
     torch.set_num_threads(8)
     os.makedirs(OUT, exist_ok=True)
+    if want("g0"):      # this machine's CPU GEMM rounding: the tests ask for the fixtures' exact bits where it is reproduced
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        from helpers import cpu_gemm_probe
+        np.savez(os.path.join(OUT, "g0_cpu_gemm_probe.npz"), y=cpu_gemm_probe())
     sd_np = synthetic_state_dict(DenoiserConfig(), seed=0)
     sd_t = {k: torch.from_numpy(np.asarray(v)) for k, v in sd_np.items()}
     p = O.to_torch_params(sd_np)

@@ -28,6 +28,24 @@ def rel_l2(a, b):
     return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30))
 
 
+def cpu_gemm_probe():
+    """One float32 F.linear on seeded operands (K = 512, as in the denoiser's GEMMs): its bits tell which CPU GEMM kernel runs."""
+    rng = np.random.default_rng(7)
+    x = torch.from_numpy(rng.standard_normal((8, 512), dtype=np.float32))
+    w = torch.from_numpy(rng.standard_normal((512, 512), dtype=np.float32) / np.float32(np.sqrt(512)))
+    b = torch.from_numpy(rng.standard_normal(512, dtype=np.float32))
+    return torch.nn.functional.linear(x, w, b).numpy()
+
+
+def cpu_gemm_matches_fixtures():
+    """The golden fixtures carry the float32 rounding of the CPU GEMMs of the machine that made them (MKL's AVX-512 sgemm).  True
+    when this machine's GEMM reproduces g0_cpu_gemm_probe.npz bit for bit: the oracle tests then ask for the fixtures' exact bits.
+    Where another kernel sums in another order (MKL takes its AVX2 kernels on AMD CPUs), only a float32 rounding bound can hold."""
+    if "gemm" not in _cache:
+        _cache["gemm"] = bool(np.array_equal(cpu_gemm_probe(), golden("g0_cpu_gemm_probe.npz")["y"]))
+    return _cache["gemm"]
+
+
 def state_dict_np():
     if "sd" not in _cache:
         _cache["sd"] = synthetic_state_dict(DenoiserConfig(), seed=0)

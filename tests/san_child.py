@@ -1,5 +1,5 @@
-"""Child of tests/test_host_sanitize.py: drives the HOST half of libdc_ddim (built with -fsanitize=address,undefined -DDC_HOST_SANITIZE,
-loaded from DC_DDIM_LIB with the ASan runtime preloaded) through raw ctypes - no torch, no device.  Any sanitizer report aborts
+"""Child of tests/test_host_sanitize.py: drives the HOST half of libdc_ddim (built with host-side ASan + UBSan and -DDC_HOST_SANITIZE,
+loaded from DC_DDIM_LIB by an interpreter that carries the sanitizer runtime) through raw ctypes - no torch, no device.  Any sanitizer report aborts
 the process (halt_on_error / -fno-sanitize-recover), so exit code 0 means a clean pass."""
 import ctypes as C
 import os

@@ -3,7 +3,11 @@ see oracle/make_golden.py and tests/golden/PINNING.txt).  CPU only."""
 import numpy as np
 import torch
 
-from helpers import O, batch_mel, batch_noise, golden, oracle_params, rel_l2, xf_pair
+from helpers import O, batch_mel, batch_noise, cpu_gemm_matches_fixtures, golden, oracle_params, rel_l2, xf_pair
+
+# where the CPU GEMM sums in another order than on the fixtures' machine: float32 dot products of length <= 512 in another order
+# (observed: 1.4e-6 ... 3.8e-6 rel-L2 with MKL's AVX2 kernels)
+OTHER_GEMM_BOUND = 1e-5
 
 
 def test_schedule_tables_g1():
@@ -25,7 +29,10 @@ def test_time_embed_table_g2():
     te = O.timestep_embedding(torch.arange(1000), 128)
     table = F.linear(F.silu(F.linear(te, p["time_embed.0.weight"], p["time_embed.0.bias"])),
                      p["time_embed.2.weight"], p["time_embed.2.bias"]).numpy()
-    assert np.array_equal(table[g["rows"]], g["table_rows"])
+    if cpu_gemm_matches_fixtures():
+        assert np.array_equal(table[g["rows"]], g["table_rows"])
+    else:
+        assert rel_l2(table[g["rows"]], g["table_rows"]) < OTHER_GEMM_BOUND
     assert abs(table.astype(np.float64).sum() - float(g["table_sum"])) < 1e-6 * float(g["table_abs_sum"])
 
 
@@ -49,8 +56,9 @@ def test_blocks_g3():
         xfp, xfo = torch.from_numpy(g["xf_proj"]), torch.from_numpy(g["xf_out"])
         got["forward"] = O.denoiser_forward(p, x, t, ln, xfp, xfo)
         got["forward_no_eff"] = O.denoiser_forward(p, x, t, ln, xfp, xfo, no_eff=True)
+    bound = 1e-6 if cpu_gemm_matches_fixtures() else OTHER_GEMM_BOUND
     for k, v in got.items():
-        assert rel_l2(v, g[k]) < 1e-6, k
+        assert rel_l2(v, g[k]) < bound, k
     # the ragged clip really exercises the mask: masked tokens change the answer
     with torch.no_grad():
         unmasked = O.linear_self_attention(p, pre + ".sa_block", h, emb, torch.ones_like(mask), 8)

@@ -1,7 +1,7 @@
 #!/bin/bash
 # GPU box: SQ counters of the no_eff layer kernel (two --pmc passes, kernel trace only beside them, program directly after --)
 R="$(pwd)"; OUT="$R/gpurun_out/pmc_noeff"; mkdir -p "$OUT"; export TMPDIR=/tmp; cd /tmp
-BENCH="/usr/bin/python3 $R/bench.py --no-eff --steps 1 --warmup 1 --no-cpu-baseline --no-extras"
+BENCH="python3 $R/bench.py --full --no-eff --steps 1 --warmup 1 --no-cpu-baseline --no-extras"
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES \
     --kernel-trace --output-format csv -d "$OUT/sq" -- $BENCH > "$OUT/sq.log" 2>&1
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_INST_CYCLES_VMEM SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_SCA SQ_INSTS_SMEM SQ_ACTIVE_INST_LDS SQ_VALU_MFMA_COEXEC_CYCLES \
