@@ -1278,6 +1278,9 @@ std::vector<float> widen_coef(const float* h_coef, int S) {
 
 }  // namespace
 
+// the other translation units' way to set dc_last_error's message (dc_stgcn.hip); not exported
+int dc_set_error(int code, const char* msg) { return fail(code, "%s", msg); }
+
 // ======================================================================================
 // C ABI
 // ======================================================================================

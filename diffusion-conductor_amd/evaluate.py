@@ -129,6 +129,42 @@ class _Prefetcher:
         return self.result
 
 
+def _with_latents(res, gen_lat, real_lat):
+    """[(clip id, mse)] -> [(clip id, mse, latent_mse, generated latent [64, T], real latent [64, T])] (metrics.py)."""
+    from .metrics import latent_mse
+    out = []
+    for i, (cid, cur) in enumerate(res):
+        g, r = np.array(gen_lat[i]), np.array(real_lat[i])
+        out.append((cid, cur, latent_mse(g, r), g, r))
+    return out
+
+
+def _encode_pair(motion_encoder, pred, gts, dim_pose, ids):
+    """Latents [B, 64, T] of the sampled poses and of the ground truth, enqueued on the current stream right behind the sampling
+    (the ground truth is uploaded to the poses' device first)."""
+    T = pred.shape[1]
+    bad = [(cid, np.shape(g)) for cid, g in zip(ids, gts) if tuple(np.shape(g)) != (T, dim_pose // 2, 2)]
+    if bad:
+        raise ValueError(f"the latent metrics compare clips of {T} frames ([T, {dim_pose // 2}, 2] motions; the reference stacks the "
+                         f"latents with np.vstack), but these ground truths differ: {bad[:4]}")
+    gt = torch.from_numpy(np.ascontiguousarray(np.stack(gts), np.float32))
+    if pred.is_cuda:
+        gt = gt.pin_memory().to(pred.device, non_blocking=True)
+    B = pred.shape[0]
+    gen_lat = motion_encoder.latent(pred.reshape(B, T, dim_pose // 2, 2))
+    real_lat = motion_encoder.latent(gt)
+    return gen_lat, real_lat
+
+
+def _latent_scores(results, nb, diversity_seed):
+    """FGD, feat_dist and diversity (metrics.py) over every clip's latents in clip order."""
+    from .metrics import diversity_score, frechet_gesture_distance
+    gen = [r[3] for k in range(nb) for r in results[k]]
+    real = [r[4] for k in range(nb) for r in results[k]]
+    fgd, feat_dist = frechet_gesture_distance(gen, real)
+    return float(fgd), float(feat_dist), float(diversity_score(gen, diversity_seed))
+
+
 class _Scorer:
     """Per-clip MSE of a batch (eval_new.py:124-131) on a background thread, behind the event that says the batch's poses have
     landed in the pinned buffer - the main thread is enqueueing the next batch meanwhile."""
@@ -147,7 +183,7 @@ class _Scorer:
             job = self.q.get()
             if job is None:
                 return
-            k, bid, gts, pred_h, event, _keep = job
+            k, bid, gts, pred_h, event, _keep, lat_h = job
             try:
                 if event is not None:
                     event.synchronize()
@@ -158,14 +194,16 @@ class _Scorer:
                 for i, cid in enumerate(bid):
                     pm = pred[i].reshape([pred[i].shape[0], self.dim_pose // 2, 2])          # eval_new.py:124-125
                     res.append((cid, mse_loss(gts[i], pm)))
+                if lat_h is not None:           # (copies: the pinned slot is reused two batches later)
+                    res = _with_latents(res, lat_h[0].numpy(), lat_h[1].numpy())
             except BaseException as e:
                 res = e
             with self.cv:
                 self.done[k] = res
                 self.cv.notify_all()
 
-    def submit(self, k, bid, gts, pred_h, event, keep):
-        self.q.put((k, bid, gts, pred_h, event, keep))
+    def submit(self, k, bid, gts, pred_h, event, keep, lat_h=None):
+        self.q.put((k, bid, gts, pred_h, event, keep, lat_h))
 
     def wait_for(self, k, reraise=True):
         """Blocks until batch k has been scored (k < 0: nothing to wait for); returns its [(clip id, mse)] or raises its error.
@@ -186,10 +224,20 @@ class _Scorer:
         self.q.put(None)
 
 
-def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed=0, smooth=False, verbose=True):
+def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed=0, smooth=False, verbose=True, motion_encoder=None,
+                     diversity_seed=0):
     """Samples every clip under `root` and returns {"per_clip": {id: mse}, "total_loss", "final_mse", "clips",
     "seconds", "frames_per_s"}.  Clip i (in sorted order) starts from noise seeded with (seed, i), so the result
     does not depend on batch_size or on the number of ranks.
+
+    `motion_encoder` (a motion_encoder.MotionEncoder_STGCN, or anything with its `latent(x)` -> [B, 64, T]): the latent-space
+    scores of the paper's table as well (metrics.py), added as "latent_mse" ({id: the clip's Sync Error term},
+    eval_old_metrics.py:90-100), "final_latent_mse" (SE), "fgd", "feat_dist" (eval_new_metrics.py:169-199), "diversity"
+    (:159-166, permutation drawn with `diversity_seed`) and "metrics_s" (host seconds spent on FGD, feat_dist and diversity after
+    the last batch).  The sampled poses and the ground truth are encoded on the device right after each batch's sampling, on the
+    same stream, and the latents come back with the poses.  Every clip must have the poses' T frames (ValueError otherwise).
+    With `smooth` the latents are those of the SMOOTHED poses - the reference scores the unsmoothed output.  Without an encoder
+    the result is exactly what it was before these scores existed.
 
     The host stays out of the GPU's way: batch k + 1's files and noise are prepared, and batch k - 1's MSEs computed, on
     background threads while batch k is sampled; the poses come back through a pinned double buffer behind an event, not a stream
@@ -213,6 +261,7 @@ def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed
     dev = getattr(trainer, "device", None)
     on_gpu = dev is not None and torch.device(dev).type == "cuda"
     out_h = [None, None]
+    lat_buf = [None, None]               # pinned [2 (generated, real), batch_size, 64, T] latent slots (motion_encoder only)
     slot_free = [None, None]             # event: the GPU has consumed the slot's pinned mel / noise buffers
     results = {}
     exchange_before = getattr(enc, "combine_exchange", None)
@@ -246,6 +295,14 @@ def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed
             if out_h[s] is None or out_h[s].shape[0] < pred.shape[0] or out_h[s].shape[1:] != pred.shape[1:]:
                 out_h[s] = torch.empty((batch_size,) + tuple(pred.shape[1:]), dtype=pred.dtype, pin_memory=pred.is_cuda)     # pageable D2H costs ~3x the copy
             ph = out_h[s][:pred.shape[0]]
+            lat_h = None
+            if motion_encoder is not None:
+                lats = _encode_pair(motion_encoder, pred, gts, dim_pose, bid)
+                if lat_buf[s] is None or lat_buf[s].shape[1] < pred.shape[0] or lat_buf[s].shape[2:] != lats[0].shape[1:]:
+                    lat_buf[s] = torch.empty((2, batch_size) + tuple(lats[0].shape[1:]), dtype=torch.float32, pin_memory=pred.is_cuda)
+                lat_h = lat_buf[s][:, :pred.shape[0]]
+                lat_h[0].copy_(lats[0], non_blocking=True)
+                lat_h[1].copy_(lats[1], non_blocking=True)
             ph.copy_(pred, non_blocking=True)
             ev = None
             if pred.is_cuda:
@@ -254,7 +311,7 @@ def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed
                 slot_free[s] = ev
                 ev_first = ev_first or ev
                 ev_last, n_after_first = ev, (n_after_first + len(bid) if ev_first is not ev else 0)
-            scorer.submit(k, bid, gts, ph, ev, pred)
+            scorer.submit(k, bid, gts, ph, ev, (pred, lat_h), lat_h)
             if serial:
                 scorer.wait_for(k, reraise=False)
         for k in range(nb):
@@ -268,8 +325,12 @@ def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed
                 pf2 = _Prefetcher(root, ids, batch_size, mel_shape, noise=(seed, T, dim_pose))
                 pf2._load_batch(k, 0)
                 bid, mel, gts = pf2.result
-                pred = trainer.generate_music_motion(mel, dim_pose, noise=pf2.noise, smooth=19 if smooth else None).cpu().numpy()
+                pred_d = trainer.generate_music_motion(mel, dim_pose, noise=pf2.noise, smooth=19 if smooth else None)
+                lats = _encode_pair(motion_encoder, pred_d, gts, dim_pose, bid) if motion_encoder is not None else None
+                pred = pred_d.cpu().numpy()
                 results[k] = [(cid, mse_loss(gts[i], pred[i].reshape([pred[i].shape[0], dim_pose // 2, 2]))) for i, cid in enumerate(bid)]
+                if lats is not None:
+                    results[k] = _with_latents(results[k], lats[0].cpu().numpy(), lats[1].cpu().numpy())
                 enc.check_numerics = False
     finally:
         scorer.close()
@@ -279,7 +340,7 @@ def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed
     dt = time.perf_counter() - t0
     per_clip, total_loss = {}, 0.0
     for k in range(nb):
-        for cid, cur in results[k]:
+        for cid, cur, *_ in results[k]:
             per_clip[cid] = float(cur)
             total_loss += cur
             if verbose:
@@ -295,6 +356,17 @@ def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed
         # clips of batches 2 .. n over the time between the completion of batch 1 and of batch n ON THE GPU: the pipeline's rate
         # without the two things nothing can hide (the first batch's load before any GPU work, the last batch's scoring after it)
         out["steady_frames_per_s"] = n_after_first * T / (ev_first.elapsed_time(ev_last) * 1e-3)
+    if motion_encoder is not None:
+        from .metrics import sync_error
+        tm = time.perf_counter()
+        lmse = [(r[0], r[2]) for k in range(nb) for r in results[k]]
+        out["latent_mse"] = {cid: float(v) for cid, v in lmse}
+        out["final_latent_mse"] = float(sync_error([v for _, v in lmse]))
+        out["fgd"], out["feat_dist"], out["diversity"] = _latent_scores(results, nb, diversity_seed)
+        out["metrics_s"] = time.perf_counter() - tm
+        if verbose:
+            print("final_latent_mse: ", out["final_latent_mse"])
+            print(f"fgd: {out['fgd']}  feat_dist: {out['feat_dist']}  diversity: {out['diversity']}")
     return out
 
 
@@ -313,6 +385,10 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--smooth", action="store_true", help="Savitzky-Golay smoothing as tools/visualization.py:126")
     ap.add_argument("--no_eff", action="store_true")
+    ap.add_argument("--metrics", action="store_true", help="also SE, FGD, feat_dist and diversity on the ST-GCN latents (metrics.py)")
+    ap.add_argument("--m2snet", default=None, help="M2SNet checkpoint for --metrics (DataParallel state_dict, keys "
+                                                   "module.motion_encoder.*); omitted = seeded synthetic weights")
+    ap.add_argument("--diversity_seed", type=int, default=0)
     args = ap.parse_args(argv)
     from . import DDPMTrainer, MotionTransformer
     dev = torch.device("cuda", args.gpu_id)
@@ -327,7 +403,18 @@ def main(argv=None):
         from .synthetic import synthetic_state_dict
         enc.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in synthetic_state_dict().items()}, strict=True)
     tr.eval_mode()
-    r = evaluate_dataset(tr, args.data_root, 26, args.batch_size, args.limit, args.seed, args.smooth)
+    menc = None
+    if args.metrics or args.m2snet:
+        from .motion_encoder import MotionEncoder_STGCN, load_m2snet
+        if args.m2snet:
+            menc = load_m2snet(args.m2snet, dev)
+        else:
+            from .synthetic import synthetic_motion_encoder_state_dict
+            menc = MotionEncoder_STGCN(dev).load_state_dict(synthetic_motion_encoder_state_dict())
+            print("--metrics without --m2snet: the motion encoder has seeded synthetic weights, so SE / FGD / feat_dist / diversity "
+                  "only check the pipeline, they say nothing about the motions")
+    r = evaluate_dataset(tr, args.data_root, 26, args.batch_size, args.limit, args.seed, args.smooth, motion_encoder=menc,
+                         diversity_seed=args.diversity_seed)
     print(f"{r['clips']} clips in {r['seconds']:.2f} s = {r['frames_per_s']:.0f} frames/s")
     return 0
 

@@ -1,0 +1,106 @@
+"""Latent-space evaluation scores of the paper's results table: FGD, feature distance, diversity and Sync Error (SE).
+
+Host numpy / scipy over the ST-GCN latents of motion_encoder.py (``latent(x)`` = the reference's ``features(x)[-1]``, one
+[64, T] fp32 array per clip).  The arithmetic follows the reference's evaluation scripts step for step, dtypes included
+(Diffusion_Stage/tools/eval_new_metrics.py:159-252 for FGD, feature distance and diversity; tools/eval_old_metrics.py:89-100,
+171-197 for SE):
+
+* the per-clip latents are stacked ROW-wise, ``np.vstack`` of [64, T] arrays -> [64 n, T]: every row (one latent channel of one
+  clip) is a SAMPLE and the frames are the dimensions, so FGD is the Frechet distance between two T-dimensional Gaussians
+  (1800-D on the dataset).  That is the reference's convention and what the paper's numbers mean; it is kept, and it needs
+  clips of one length;
+* means are float32 (numpy's mean of float32 data), ``np.cov`` and ``scipy.linalg.sqrtm`` run in float64; feature distance,
+  diversity and SE are float32 reductions and come back as ``np.float32``, as in the reference.
+
+Beat consistency (BC) is not here: its music side is librosa's onset / beat tracker.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+
+def _stack(latents, what):
+    arrs = [np.asarray(a.detach().cpu() if hasattr(a, "detach") else a) for a in latents]
+    if not arrs:
+        raise ValueError(f"{what}: no clips")
+    shapes = {a.shape for a in arrs}
+    if len(shapes) != 1 or arrs[0].ndim != 2:
+        raise ValueError(f"{what}: the reference stacks the per-clip latents [64, T] row-wise (np.vstack), which needs one shape "
+                         f"for every clip; got {sorted(shapes)}")
+    return np.vstack(arrs)
+
+
+def calculate_frechet_distance(mu1, sigma1, mu2, sigma2, eps=1e-6):
+    """d^2 = |mu1 - mu2|^2 + Tr(sigma1 + sigma2 - 2 sqrt(sigma1 sigma2)), as Evaluator.calculate_frechet_distance
+    (eval_new_metrics.py:201-252, after pytorch-fid): when sqrtm of the product is not finite it is taken again with `eps` added to
+    both diagonals; a complex result whose diagonal has an imaginary part beyond 1e-3 raises ValueError, otherwise its real part
+    is used."""
+    from scipy import linalg
+    mu1, mu2 = np.atleast_1d(mu1), np.atleast_1d(mu2)
+    sigma1, sigma2 = np.atleast_2d(sigma1), np.atleast_2d(sigma2)
+    if mu1.shape != mu2.shape or sigma1.shape != sigma2.shape:
+        raise ValueError(f"mean / covariance shapes differ: {mu1.shape} vs {mu2.shape}, {sigma1.shape} vs {sigma2.shape}")
+    diff = mu1 - mu2
+    covmean = linalg.sqrtm(sigma1.dot(sigma2))
+    if not np.isfinite(covmean).all():
+        offset = np.eye(sigma1.shape[0]) * eps
+        covmean = linalg.sqrtm((sigma1 + offset).dot(sigma2 + offset))
+    if np.iscomplexobj(covmean):
+        if not np.allclose(np.diagonal(covmean).imag, 0, atol=1e-3):
+            raise ValueError(f"Imaginary component {np.max(np.abs(covmean.imag))}")
+        covmean = covmean.real
+    return diff.dot(diff) + np.trace(sigma1) + np.trace(sigma2) - 2 * np.trace(covmean)
+
+
+def frechet_gesture_distance(gen_latents, real_latents):
+    """(fgd, feat_dist) of Evaluator.get_scores (eval_new_metrics.py:169-199): per-clip latents [64, T] of the generated and the
+    real motions, in matching order.  fgd = 1e10 where calculate_frechet_distance raises ValueError (the reference's fallback);
+    feat_dist = the mean over stacked rows of sum |real - gen|, an np.float32."""
+    gen, real = _stack(gen_latents, "generated latents"), _stack(real_latents, "real latents")
+    if gen.shape != real.shape:
+        raise ValueError(f"generated {gen.shape} and real {real.shape} latents differ in shape")
+    try:
+        fgd = calculate_frechet_distance(np.mean(gen, axis=0), np.cov(gen, rowvar=False),
+                                         np.mean(real, axis=0), np.cov(real, rowvar=False))
+    except ValueError:
+        fgd = 1e10
+    feat_dist = np.mean(np.sum(np.absolute(real - gen), axis=-1))
+    return fgd, feat_dist
+
+
+def diversity_permutation(n, seed):
+    """torch.randperm(n) from a fresh generator seeded with `seed`: the permutation the reference draws from the global RNG
+    (eval_new_metrics.py:161) after torch.manual_seed(seed)."""
+    import torch
+    return torch.randperm(int(n), generator=torch.Generator().manual_seed(int(seed))).numpy()
+
+
+def diversity_score(gen_latents, seed=0):
+    """Evaluator.get_diversity_scores (eval_new_metrics.py:159-166): the first 500 generated clips against the clips at
+    randperm(n)[:500], mean over stacked rows of sum |feat1 - feat2|; np.float32."""
+    lat = list(gen_latents)
+    feat1 = _stack(lat[:500], "generated latents")
+    feat2 = _stack([lat[i] for i in diversity_permutation(len(lat), seed)[:500]], "generated latents")
+    return np.mean(np.sum(np.absolute(feat1 - feat2), axis=-1))
+
+
+def latent_mse(gen_latent, real_latent):
+    """One clip's Sync Error term (eval_old_metrics.py:90-100, mse_loss_latent): mean((gen - real)^2) over its [64, T] latent,
+    a float32 mean; np.float32."""
+    g = np.asarray(gen_latent.detach().cpu() if hasattr(gen_latent, "detach") else gen_latent, np.float32)
+    r = np.asarray(real_latent.detach().cpu() if hasattr(real_latent, "detach") else real_latent, np.float32)
+    if g.shape != r.shape:
+        raise ValueError(f"latent shapes differ: {g.shape} vs {r.shape}")
+    return np.mean((g - r) ** 2)
+
+
+def sync_error(per_clip):
+    """final_latent_mse (eval_old_metrics.py:187-197): the per-clip latent_mse values summed in clip order from 0 (float32
+    arithmetic, as the reference's accumulation of np.float32 terms), divided by the clip count."""
+    vals = list(per_clip)
+    if not vals:
+        raise ValueError("sync_error: no clips")
+    total = 0
+    for v in vals:
+        total += v
+    return total / len(vals)

@@ -25,6 +25,8 @@ EXPORTS = [
     "dc_sampler_debug_read", "dc_sampler_debug_layer", "dc_savgol_coefficients", "dc_savgol_filter",
     "dc_ddim_coefficients_ex", "dc_sampler_ddim_loop_ex", "dc_sampler_status", "dc_sampler_set_smoothing",
     "dc_sampler_set_step_noise_seed", "dc_sampler_set_step_noise_seed_at", "dc_step_noise_fill",
+    "dc_motion_encoder_create", "dc_motion_encoder_destroy", "dc_motion_encoder_set_param", "dc_motion_encoder_finalize",
+    "dc_motion_encoder_encode",
 ]
 
 UPDATE_CLIP_DENOISED, UPDATE_EPSILON = 1, 2          # flags of dc_sampler_ddim_loop_ex
@@ -40,7 +42,7 @@ class DcError(RuntimeError):
     pass
 
 
-SOURCES = ("dc_kernels.hip", "dc_api.hip", "dc_music.hip", "dc_layer16.hip")
+SOURCES = ("dc_kernels.hip", "dc_api.hip", "dc_music.hip", "dc_layer16.hip", "dc_stgcn.hip")
 HEADERS = ("dc_common.h", "dc_dev.h", "dc_launch.h", "dc_music.h")
 EXTRA_FLAGS = {}      # per-source compiler flags
 
@@ -137,6 +139,12 @@ def lib():
     L.dc_sampler_debug_read.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]
     L.dc_sampler_debug_layer.argtypes = [C.c_void_p, fp, ip, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
     L.dc_sampler_profile_loop.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, fp, fp, ip, C.c_int32, C.c_void_p]
+    L.dc_motion_encoder_create.argtypes = [C.c_int32, C.POINTER(C.c_void_p)]
+    L.dc_motion_encoder_destroy.argtypes = [C.c_void_p]
+    L.dc_motion_encoder_destroy.restype = None
+    L.dc_motion_encoder_set_param.argtypes = [C.c_void_p, C.c_char_p, fp, C.c_int64]
+    L.dc_motion_encoder_finalize.argtypes = [C.c_void_p]
+    L.dc_motion_encoder_encode.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -467,3 +475,47 @@ class NativeSampler:
 
     def workspace_bytes(self):
         return int(lib().dc_sampler_workspace_bytes(self._h))
+
+
+# ---------------------------------------------------------------------------------------
+# the motion encoder (M2SNet's ST-GCN, the evaluation metrics' latent space)
+# ---------------------------------------------------------------------------------------
+class NativeMotionEncoder:
+    """Owns one dc_motion_encoder (dc_ddim.h).  Tensors are torch CUDA(ROCm) tensors; only their data_ptr() crosses the ABI."""
+
+    def __init__(self, device=0):
+        self._h = C.c_void_p()
+        _check(lib().dc_motion_encoder_create(int(device), C.byref(self._h)))
+        self.device = int(device)
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            lib().dc_motion_encoder_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_param(self, name, a):
+        a = np.ascontiguousarray(np.asarray(a), np.float32)
+        _check(lib().dc_motion_encoder_set_param(self._h, name.encode(), _fptr(a), a.size))
+
+    def finalize(self):
+        _check(lib().dc_motion_encoder_finalize(self._h))
+
+    def encode(self, motion, out=None):
+        """motion fp32 [B, T, 13, 2] (or [B, T, 26]) on the device -> latent fp32 [B, 64, T] (`out`: a tensor to fill)."""
+        import torch
+        assert motion.is_cuda and motion.dtype == torch.float32 and motion.is_contiguous()
+        B, T = int(motion.shape[0]), int(motion.shape[1])
+        assert motion.numel() == B * T * 26, tuple(motion.shape)
+        if out is None:
+            out = torch.empty((B, 64, T), dtype=torch.float32, device=motion.device)
+        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (B, 64, T)
+        with torch.cuda.device(motion.device):
+            _check(lib().dc_motion_encoder_encode(self._h, motion.data_ptr(), B, T, out.data_ptr(),
+                                                  C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        return out

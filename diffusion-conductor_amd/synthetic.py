@@ -138,3 +138,64 @@ def batch_step_noise(S, B, T=1800, P=26, seed=4, first=0):
     """Per-iteration DDIM noise z_i ~ N(0,1) (eta > 0), [S, B, T, P]: iteration i of clip b has its own stream."""
     return np.stack([np.stack([_rng(seed, f"z{i}", first + b).standard_normal((T, P), dtype=np.float32) for b in range(B)])
                      for i in range(S)])
+
+
+def synthetic_motion_encoder_state_dict(seed: int = 0):
+    """name -> np.ndarray for every state_dict entry of MotionEncoder_STGCN (motion_encoder.py): conv weights and biases
+    ~ U(-1/sqrt(fan_in), 1/sqrt(fan_in)), BatchNorm affines and running statistics away from the identity, `st_gcn.A` the
+    skeleton's normalised adjacency and edge importances 1 + 0.3 N(0, 1) (all-ones importances would leave that path untested)."""
+    from .motion_encoder import motion_encoder_shapes, skeleton_adjacency
+    out = OrderedDict()
+    shapes = motion_encoder_shapes()
+    for name, shape in shapes.items():
+        g = _rng(seed, "stgcn:" + name)
+        leaf = name.rsplit(".", 1)[-1]
+        if leaf == "num_batches_tracked":
+            out[name] = np.asarray(1000, dtype=np.int64)
+            continue
+        if name == "st_gcn.A":
+            a = skeleton_adjacency()
+        elif ".edge_importance." in name:
+            a = 1.0 + 0.3 * g.standard_normal(shape)
+        elif leaf == "running_mean":
+            a = 0.1 * g.standard_normal(shape)
+        elif leaf == "running_var":
+            a = g.uniform(0.5, 1.5, shape)
+        elif len(shape) == 1 and ("bn." in name or ".tcn.0." in name or ".tcn.3." in name or name.startswith("fc.1.")):
+            a = (1.0 + 0.1 * g.standard_normal(shape)) if leaf == "weight" else 0.1 * g.standard_normal(shape)
+        else:
+            wshape = shapes[name if leaf == "weight" else name[:-4] + "weight"]
+            bound = 1.0 / np.sqrt(int(np.prod(wshape[1:])))
+            a = g.uniform(-bound, bound, shape)
+        out[name] = np.ascontiguousarray(a, dtype=np.float32)
+    return out
+
+
+def synthetic_motion(B, T, seed=5, first=0):
+    """[B, T, 13, 2] fp32 smooth pose-like tracks (random walks around a random rest pose, in [-1, 1]-ish units)."""
+    out = np.empty((B, T, 13, 2), np.float32)
+    for b in range(B):
+        g = _rng(seed, "motion", first + b)
+        rest = g.uniform(-0.6, 0.6, (1, 13, 2))
+        walk = np.cumsum(0.02 * g.standard_normal((T, 13, 2)), axis=0)
+        out[b] = rest + walk
+    return out
+
+
+def synthetic_generated_motion(real, seed=13):
+    """A stand-in for sampled motion beside `real` [n, T, 13, 2]: clip i plus a smooth random-walk perturbation whose size grows
+    from 0.5x to 2x over the clips (so the latent-space scores between the two sets are non-trivial and differ per clip)."""
+    n = real.shape[0]
+    scale = np.linspace(0.5, 2.0, n)
+    out = np.empty_like(real, dtype=np.float32)
+    for i in range(n):
+        walk = np.cumsum(0.03 * _rng(seed, "gen_motion", i).standard_normal(real.shape[1:]), axis=0)
+        out[i] = real[i] + walk * scale[i]
+    return out
+
+
+def array_digest(a):
+    """(sum, sum of |x|, sum of x * index) in float64 of an array's values: a compact fingerprint that pins a regenerable input
+    without storing it."""
+    x = np.asarray(a, np.float64).ravel()
+    return np.array([x.sum(), np.abs(x).sum(), (x * np.arange(x.size)).sum()])

@@ -320,6 +320,34 @@ DC_EXPORT int dc_sampler_set_smoothing(dc_sampler* s, int32_t window, int32_t or
 DC_EXPORT int dc_savgol_filter(const float* d_in, float* d_out, int32_t B, int32_t T, int32_t P, int32_t window, int32_t order,
                      void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Motion encoder: M2SNet's ST-GCN (the latent space of the evaluation metrics)
+ * ---------------------------------------------------------------------------------- */
+
+/* Opaque handle of one encoder (device-resident folded weights + activation planes).  Not thread-safe.
+ * Replaces constructing MotionEncoder_STGCN (trainers/ddpm_trainer.py:27-43; tools/eval_new_metrics.py:39-55) on the
+ * device `device`. */
+typedef struct dc_motion_encoder dc_motion_encoder;
+DC_EXPORT int dc_motion_encoder_create(int32_t device, dc_motion_encoder** out);
+DC_EXPORT void dc_motion_encoder_destroy(dc_motion_encoder* e);
+
+/* Replaces load_state_dict of MotionPretrain (trainers/ddpm_trainer.py:66-80): one call per state_dict entry with the key
+ * WITHOUT the checkpoint's "module.motion_encoder." prefix (e.g. "st_gcn.st_gcn_networks.3.tcn.2.weight", "fc.1.running_var")
+ * and its contiguous fp32 data.  Unknown key or wrong numel -> DC_ERR_PARAM.  st_gcn.fcn.* and the num_batches_tracked
+ * counters are accepted and ignored (the reference never applies them in eval mode). */
+DC_EXPORT int dc_motion_encoder_set_param(dc_motion_encoder* e, const char* name, const float* h_data, int64_t numel);
+
+/* Folds every BatchNorm (eval mode, running statistics) into the conv in front of it, A * edge_importance[l] into the graph
+ * mix, and uploads the image.  An entry the encoder computes with that was never set -> DC_ERR_PARAM.  Synchronous. */
+DC_EXPORT int dc_motion_encoder_finalize(dc_motion_encoder* e);
+
+/* MotionEncoder_STGCN.features(x)[-1] in eval mode (trainers/ddpm_trainer.py:45-63; the latent the metrics of
+ * tools/eval_old_metrics.py:89-100 and tools/eval_new_metrics.py:159-252 use): d_motion fp32 [B, T, 13, 2] -> d_out fp32
+ * [B, 64, T] (caller-allocated).  B >= 1, T >= 1.  A clip's latent is bit-identical whatever the batch around it.
+ * DC_ERR_INVALID before dc_motion_encoder_finalize. */
+DC_EXPORT int dc_motion_encoder_encode(dc_motion_encoder* e, const float* d_motion, int32_t B, int32_t T, float* d_out,
+                                       void* stream);
+
 /* Introspection used by tests: bytes of device workspace currently held; frames per clip of the sampler's internal token space
  * (the T of dc_sampler_set_conditioning, padded to whole 32-frame groups where the clip-aligned kernels run): the layout of the
  * buffers dc_sampler_debug_read returns. */

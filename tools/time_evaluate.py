@@ -27,6 +27,8 @@ ap.add_argument("--clips", type=int, default=294)       # the reference's test s
 ap.add_argument("--ddim", type=int, default=50)
 ap.add_argument("--batch_size", type=int, default=32)
 ap.add_argument("--repeat", type=int, default=2)
+ap.add_argument("--metrics", action="store_true", help="every repeat also runs with the latent scores (ST-GCN encoder on seeded "
+                                                       "synthetic weights): runs_metrics beside runs")
 args = ap.parse_args()
 
 dev = torch.device("cuda", 0)
@@ -63,11 +65,19 @@ try:
     e2e = sorted(te[2:])[2]
     line = {"serial": bool(os.environ.get("DC_EVAL_SERIAL")), "clips": args.clips, "ddim": args.ddim, "batch_size": B, "end_to_end_ms_per_batch": round(1e3 * e2e, 2),
             "end_to_end_frames_per_s": round(B * 1800 / e2e, 1), "runs": []}
+    menc = None
+    if args.metrics:
+        from diffusion_conductor_amd.motion_encoder import MotionEncoder_STGCN
+        from diffusion_conductor_amd.synthetic import synthetic_motion_encoder_state_dict
+        menc = MotionEncoder_STGCN(dev).load_state_dict(synthetic_motion_encoder_state_dict())
+        line["runs_metrics"] = []
     for rep in range(args.repeat):
-        r = ev.evaluate_dataset(tr, root, 26, batch_size=B, seed=1, verbose=False)
-        line["runs"].append({"seconds": round(r["seconds"], 3), "frames_per_s": round(r["frames_per_s"], 1),
-                             "steady_frames_per_s": round(r.get("steady_frames_per_s", 0.0), 1), "final_mse": r["final_mse"],
-                             "main_thread_s": r["main_thread_s"]})
+        for enc in ([None, menc] if menc is not None else [None]):
+            r = ev.evaluate_dataset(tr, root, 26, batch_size=B, seed=1, verbose=False, motion_encoder=enc)
+            line["runs" if enc is None else "runs_metrics"].append(
+                {"seconds": round(r["seconds"], 3), "frames_per_s": round(r["frames_per_s"], 1),
+                 "steady_frames_per_s": round(r.get("steady_frames_per_s", 0.0), 1), "final_mse": r["final_mse"],
+                 "main_thread_s": r["main_thread_s"], **({"metrics_s": round(r["metrics_s"], 3), "fgd": r["fgd"]} if enc else {})})
     best = max(x["frames_per_s"] for x in line["runs"])
     line["evaluate_over_end_to_end"] = round(best / line["end_to_end_frames_per_s"], 4)
     line["steady_over_end_to_end"] = round(max(x["steady_frames_per_s"] for x in line["runs"]) / line["end_to_end_frames_per_s"], 4)
