@@ -59,6 +59,8 @@ constexpr int OFF_FCB = OFF_FCW + 2 * (SG_K / 2) * 64;     // fc bias' [64]
 constexpr int PAR_FLOATS = OFF_FCB + SG_OUT;
 
 DEV f32x16 mfma2(float a, float b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
+// torch.relu: NaN stays NaN.  (fmaxf is v_max_f32, which in the kernels' IEEE mode returns the non-NaN operand: max(NaN, 0) = 0.)
+DEV float relu(float y) { return y < 0.f ? 0.f : y; }
 
 // One st_gcn block for frames [30 blockIdx.x, +30) of clip blockIdx.y.  FIRST: `in` is the motion [B][T][13][2] and data_bn is
 // applied on load; otherwise `in` is the previous block's [B][13][32][T].  out: [B][13][32][T].
@@ -121,7 +123,8 @@ __global__ __launch_bounds__(SG_THREADS) void k_stgcn_block(const float* __restr
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
         const int c = (r & 3) + 8 * (r >> 2) + 4 * h;
-        as[w][c][j + 1] = inside ? fmaxf(acc[r] + b1[c], 0.f) : 0.f;
+        const float y = acc[r] + b1[c];
+        as[w][c][j + 1] = inside ? relu(y) : 0.f;
     }
     if (lane < 32) {
         as[w][lane][0] = 0.f;
@@ -144,7 +147,7 @@ __global__ __launch_bounds__(SG_THREADS) void k_stgcn_block(const float* __restr
             const int c = (r & 3) + 8 * (r >> 2) + 4 * h;
             float y = acc2[r] + b2[c];
             if (!FIRST) y += xs[w][c][j];
-            dst[(size_t)c * T] = fmaxf(y, 0.f);
+            dst[(size_t)c * T] = relu(y);
         }
     }
 }

@@ -171,6 +171,54 @@ def synthetic_motion_encoder_state_dict(seed: int = 0):
     return out
 
 
+MOTION_ENCODER_VARIANTS = ("seeded", "sparse_importance", "dense_adjacency", "bn_stress", "identity")
+
+
+def motion_encoder_weight_variant(kind: str, seed: int = 1):
+    """synthetic_motion_encoder_state_dict(seed) with one part of the weights moved to an edge the seeded weights never reach:
+      seeded             unchanged;
+      sparse_importance  edge importances with about a quarter of the entries zeroed and another quarter negated, plus in block l
+                         the off-diagonal entries of column l zeroed and its self link negative (odd l) or the whole column l zeroed (even l);
+      dense_adjacency    `st_gcn.A` a dense, non-symmetric random matrix (mixed signs) instead of the skeleton's;
+      bn_stress          every BatchNorm with gains of both signs, running_var log-uniform in [1e-4, 2] (so eps = 1e-5 moves the
+                         scale by up to 5 %; the gain scales with sqrt(var) so activations stay O(1)) and running_mean ~ 2 N(0, 1);
+      identity           all-ones importances and identity BatchNorms (the control)."""
+    if kind not in MOTION_ENCODER_VARIANTS:
+        raise ValueError(f"unknown motion encoder weight variant {kind!r}")
+    sd = synthetic_motion_encoder_state_dict(seed)
+    g = _rng(seed, "stgcn_variant:" + kind)
+    n = 13
+    bns = sorted({k.rsplit(".", 1)[0] + "." for k in sd if k.endswith("running_var")})
+    if kind == "sparse_importance":
+        for l in range(10):
+            e = sd[f"st_gcn.edge_importance.{l}"][0]
+            u = g.random((n, n))
+            e[u < 0.25] = 0.0
+            e[(u >= 0.25) & (u < 0.5)] *= -1.0
+            if l % 2:
+                e[np.arange(n) != l, l] = 0.0
+                e[l, l] = -0.8            # a negative self link as the column's only entry
+            else:
+                e[:, l] = 0.0
+    elif kind == "dense_adjacency":
+        sd["st_gcn.A"] = g.uniform(-0.15, 0.3, (1, n, n)).astype(np.float32)
+    elif kind == "bn_stress":
+        for p in bns:
+            c = sd[p + "running_var"].shape[0]
+            var = np.exp(g.uniform(np.log(1e-4), np.log(2.0), c))
+            sd[p + "running_var"] = var.astype(np.float32)
+            sd[p + "weight"] = (np.where(g.random(c) < 0.5, -1.0, 1.0) * g.uniform(0.7, 1.3, c) * np.sqrt(var)).astype(np.float32)
+            sd[p + "running_mean"] = (2.0 * g.standard_normal(c)).astype(np.float32)
+    elif kind == "identity":
+        for l in range(10):
+            sd[f"st_gcn.edge_importance.{l}"] = np.ones((1, n, n), np.float32)
+        for p in bns:
+            c = sd[p + "running_var"].shape[0]
+            sd[p + "weight"], sd[p + "running_var"] = np.ones(c, np.float32), np.ones(c, np.float32)
+            sd[p + "bias"], sd[p + "running_mean"] = np.zeros(c, np.float32), np.zeros(c, np.float32)
+    return sd
+
+
 def synthetic_motion(B, T, seed=5, first=0):
     """[B, T, 13, 2] fp32 smooth pose-like tracks (random walks around a random rest pose, in [-1, 1]-ish units)."""
     out = np.empty((B, T, 13, 2), np.float32)
