@@ -10,6 +10,7 @@
 #include <cstring>
 #include <map>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "../../include/dc_ddim.h"
@@ -132,8 +133,7 @@ struct Arena {
 enum KernelId { K_BEGIN = 0, K_SILU, K_FILM, K_EMBED, K_COMBINE, K_LAYER, K_NOISE, K_COUNT };
 const char* kKernelNames[K_COUNT] = {"k_begin_step", "k_silu_emb", "k_film_gemm", "k_embed_front", "k_attn_combine", "k_layer", "k_step_noise"};
 
-struct Prof {
-    bool on = false;
+struct Prof {                       // per-kernel profile (dc_sampler_profile_loop): events around every launch
     std::vector<hipEvent_t> ev;     // pairs
     std::vector<int> ids;
 };
@@ -153,7 +153,6 @@ struct dc_sampler {
     DcModel* d_model = nullptr;
     DcModel h_model{};
     int NT = 0;   // FiLM feature tiles = 3 * L * 8
-    int gran = 32;   // tokens per partial-record unit: 32 (per group) or waves-per-workgroup * 32 (T permitting)
 
     hipStream_t stream = nullptr;
     hipEvent_t ev_in = nullptr, ev_out = nullptr;
@@ -188,7 +187,6 @@ struct dc_sampler {
     unsigned long long* d_stamps = nullptr;
     float* d_film_rate = nullptr;  // FiLM GEMM: per-workgroup speeds measured by the previous launches, two buffers of 1024 (ping-pong)
     int film_rate_parity = 0;
-    bool graph_folded = false;     // the captured steps look their timestep up through *d_iter (no k_begin_step launches)
     int num_cu = 0;
     int *d_iter = nullptr, *d_t_clip = nullptr, *d_snap_cur = nullptr, *d_t_of_iter = nullptr, *d_snap_of_iter = nullptr;
     float *d_coef_cur = nullptr, *d_coef_of_t = nullptr, *d_coef_of_iter = nullptr;   // DDIM scalars by timestep / by iteration
@@ -200,20 +198,12 @@ struct dc_sampler {
     std::vector<int> tab_t, tab_snap;
     std::vector<float> tab_coef, tab_coef_iter;
 
-    // graph cache: one per (B, T, steps_per_graph, launch form, update options)
-    hipGraphExec_t graph = nullptr;
-    int graph_B = 0, graph_T = 0, graph_Tx = 0, graph_K = 0;
-    unsigned long long graph_form = 0;     // form_key() of the captured launches
-    // ... and up to three more for other batch shapes (a dataset's last, smaller batch; a service whose batch size varies): a shape
+    // graph cache, keyed by (B, T, Tx, steps per graph, form_key() of the captured launches): the current graph (the last entry) and
+    // up to three parked ones for other batch shapes (a dataset's last, smaller batch; a service whose batch size varies): a shape
     // seen before replays its graph instead of paying a capture (tens of ms) every time the shape changes.  The workspace's
     // addresses are baked into every captured graph, so whatever re-allocates a buffer drops them all (drop_graph).
-    struct GraphSlot {
-        hipGraphExec_t exec;
-        int B, T, Tx, K;
-        unsigned long long form;
-        bool folded;
-    };
-    std::vector<GraphSlot> graph_park;
+    using GraphKey = std::tuple<int, int, int, int, unsigned long long>;
+    std::vector<std::pair<GraphKey, hipGraphExec_t>> graphs;
     // DDIM update options of the loop being enqueued (dc_sampler_ddim_loop_ex) and the device status word
     int upd_flags = 0;              // DC_UPD_* of the loop being enqueued (incl. the internal NOISY / ZSTEP bits)
     const float** d_zslot = nullptr;    // device slot holding the base address of the per-iteration noise (DcUpdate::zslot)
@@ -236,9 +226,6 @@ struct dc_sampler {
     bool host_only = false;      // -DDC_HOST_SANITIZE builds without a device: the host half only (tests/test_host_sanitize.py)
 
     Prof prof;
-    int dbg_layers = -1, dbg_stage = 0;   // test hooks (dc_sampler_debug_denoise)
-    int dbg_first = -1;                   // test hook (dc_sampler_debug_layer): start at this layer from the residual stream in d_h
-    bool embedded_by_prev = false;        // enqueue_step: the step just enqueued also did the next step's front work (DC_UPD_EMBED_NEXT)
     bool diag_film_done = false;          // DC_DIAG_SKIP_FILM (diagnostic): the FiLM GEMM has been launched once on this sampler
 };
 
@@ -267,12 +254,8 @@ int dev_alloc(dc_sampler* s, P*& p, size_t bytes) {
 }
 
 void drop_graph(dc_sampler* s) {
-    for (auto& g : s->graph_park) hipGraphExecDestroy(g.exec);
-    s->graph_park.clear();
-    if (s->graph) {
-        hipGraphExecDestroy(s->graph);
-        s->graph = nullptr;
-    }
+    for (auto& g : s->graphs) hipGraphExecDestroy(g.second);
+    s->graphs.clear();
 }
 
 const std::vector<float>* find(dc_sampler* s, const std::string& n) {
@@ -813,11 +796,6 @@ int ensure_workspace(dc_sampler* s, int B, int Tx) {
     s->Tx = Tx;
     s->M = M;
     s->G = G;
-    {   // per-workgroup partial records when a workgroup (NW groups) cannot span more than two clips
-        const int nw = s->split_small ? 4 : 8;
-        (void)nw;
-        s->gran = 32;   // per-group records (a workgroup-level LDS pre-reduction was measured slower overall)
-    }
     return DC_OK;
 }
 
@@ -836,14 +814,9 @@ int ensure_steps(dc_sampler* s, int S) {
     return DC_OK;
 }
 
-struct Timed {   // RAII-less helper: wraps a launch with events when profiling
-    dc_sampler* s;
-    int id;
-};
-
 #define LAUNCH(id, expr)                                              \
     do {                                                              \
-        if (s->prof.on) {                                             \
+        if (c.profile) {                                              \
             hipEvent_t a_, b_;                                        \
             HIP_TRY(hipEventCreate(&a_));                             \
             HIP_TRY(hipEventCreate(&b_));                             \
@@ -872,32 +845,63 @@ unsigned long long form_key(const dc_sampler* s) {
     return k;
 }
 
+// Test hooks of one evaluation (dc_sampler_debug_denoise, dc_sampler_debug_layer); the defaults run the production evaluation
+struct Hooks {
+    int layers = -1, stage = 0;   // run the first `layers` layers, the last of them up to `stage` (| (first stage - 1) << 16)
+    int first = -1;               // start at this layer from the residual stream in d_h
+};
+
+// One enqueue_step call ...
+struct Step {
+    bool loop_mode = false;       // a loop's step: the last layer applies the DDIM update to x_src
+    const float* x_src = nullptr;
+    float* x_dst = nullptr;
+    int graph_step = -1;          // >= 0: step number inside a graph being captured
+    bool split = false;           // this evaluation's 128-wide GEMMs on split operands (the fp16 images' hi + lo halves)
+    bool g1_loop = false;         // a loop with a precise tail: its plain-operand evaluations read G' scale tiles
+    bool next_plain = false;      // loops: another step follows in this enqueue sequence (same graph) and it is a plain-operand evaluation
+    bool embedded = false;        // the previous step's last layer has embedded x and run layer 0's front half for this step
+    Hooks dbg;
+    bool profile = false;         // events around every launch, collected in s->prof
+};
+// ... and what it tells its caller
+struct StepDone {
+    bool embedded_next = false;   // the step also did the next step's front work (DC_UPD_EMBED_NEXT): Step::embedded of that step
+    bool folded = false;          // the step's kernels look their timestep up through *d_iter (no k_begin_step launch)
+};
+
+// The FiLM GEMM over the current geometry (pp: the fp32 emb image of the non-split formats, nullptr for the split ones)
+DcFilmArgs film_args(const dc_sampler* s, const float* pp, const int* t_clip) {
+    DcFilmArgs f{};
+    f.W = s->h_model.film_w, f.bias_ft = s->h_model.film_b, f.s_hi = s->d_s_hi, f.s_lo = s->d_s_lo, f.E = s->d_E, f.G = s->G, f.NT = s->NT;
+    f.nround = s->NT / 16, f.pp = pp, f.temb = s->h_model.temb, f.t_clip = t_clip, f.T = s->T, f.B = s->B;
+    f.W16 = s->h_model.film_w16, f.bias16 = s->h_model.film_b16, f.status = s->d_status;
+    return f;
+}
+
 // One denoiser evaluation (+ DDIM update when loop_mode) enqueued on st.
 // graph_step >= 0: step number inside a graph being captured.  On the default path (fused SiLU fill, per-layer launches) the
 // step's kernels then look the timestep / DDIM scalars up themselves - this step's slot of the per-iteration tables, offset by
 // the iteration at which the replay began (*d_iter, advanced once per replay) - and the per-step bookkeeping launch
 // (k_begin_step, 5 us + a launch gap) is dropped.
-int enqueue_step(dc_sampler* s, hipStream_t st, bool loop_mode, const float* x_src, float* x_dst, int graph_step = -1,
-                 bool split_step = false /* this evaluation's 128-wide GEMMs on split operands (the fp16 images' hi + lo halves) */,
-                 bool g1_loop = false /* a loop with a precise tail: its plain-operand evaluations read G' scale tiles */,
-                 bool next_plain = false /* loops: another step follows in this enqueue sequence (same graph) and it is a plain-operand evaluation */) {
+int enqueue_step(dc_sampler* s, hipStream_t st, const Step& c, StepDone* done = nullptr) {
     const int B = s->B, T = s->T, M = s->M, G = s->G, L = s->cfg.num_layers;
-    const bool embedded = s->embedded_by_prev;      // the previous step's last layer has embedded x and run layer 0's front half for this step
-    s->embedded_by_prev = false;
-    const bool ss = s->split_small || split_step, sf = s->split_film;
-    const DcModel* dmod = (split_step && !s->split_small) ? s->d_model_split : s->d_model;      // (the precise tail's split stage images)
+    const bool loop_mode = c.loop_mode, embedded = c.embedded;
+    const int graph_step = c.graph_step;
+    const Hooks& dbg = c.dbg;
+    const bool ss = s->split_small || c.split, sf = s->split_film;
+    const DcModel* dmod = (c.split && !s->split_small) ? s->d_model_split : s->d_model;      // (the precise tail's split stage images)
     // (bf16 precision, split evaluations: the f16 FiLM image - the step is then exactly a "mixed" evaluation)
-    const bool film_tail = split_step && !s->split_small && s->h_model.film_w16_tail != nullptr && !getenv("DC_TAIL_FILM_BF16");
+    const bool film_tail = c.split && !s->split_small && s->h_model.film_w16_tail != nullptr && !getenv("DC_TAIL_FILM_BF16");
     const int fs = s->small_fmt, ff = film_tail ? 1 : s->film_fmt;
     // non-split formats: the FiLM GEMM produces its own operand from pp + temb (no k_silu_emb pass); the separate pass
     // remains for the split formats, for the v1 kernel, and under the test hooks that read the operand image back
-    const bool fuse_silu = !sf && s->dbg_layers < 0;
-    const bool folded = loop_mode && graph_step >= 0 && fuse_silu && !s->cfg.no_eff && !getenv("DC_BEGIN_STEP") && s->dbg_stage == 0;
+    const bool fuse_silu = !sf && dbg.layers < 0;
+    const bool folded = loop_mode && graph_step >= 0 && fuse_silu && !s->cfg.no_eff && !getenv("DC_BEGIN_STEP") && dbg.stage == 0;
     const int* iter_base = folded ? s->d_iter : nullptr;
     const int* t_src = folded ? s->d_t_of_iter + graph_step : s->d_t_clip;
     const float* coef_src = folded ? s->d_coef_of_iter + DC_COEF * (size_t)graph_step : s->d_coef_cur;
     const int* snap_src = folded ? s->d_snap_of_iter + graph_step : s->d_snap_cur;
-    if (graph_step >= 0) s->graph_folded = folded;
     if (loop_mode && !folded)
         LAUNCH(K_BEGIN, dc_launch_begin_step(st, s->d_iter, s->d_t_of_iter, s->d_coef_of_t, s->d_snap_of_iter,
                                              s->d_t_clip, s->d_coef_cur, s->d_snap_cur, B));
@@ -916,8 +920,8 @@ int enqueue_step(dc_sampler* s, hipStream_t st, bool loop_mode, const float* x_s
     const bool no_wgr = getenv("DC_NO_WGREC") != nullptr;          // (read per call: the tests toggle it)
     // (split formats: on clip-aligned units only - the doubled weight images leave LDS for ONE clip's attention fragments - and in
     // the production build only: the test hooks keep the per-group form)
-    const bool wgr = T >= 256 && !no_wgr && s->dbg_first < 0 && !s->cfg.no_eff &&
-                     (!ss || (T % 32 == 0 && s->dbg_layers < 0 && s->dbg_stage == 0 && !getenv("DC_NO_ALIGN")));
+    const bool wgr = T >= 256 && !no_wgr && dbg.first < 0 && !s->cfg.no_eff &&
+                     (!ss || (T % 32 == 0 && dbg.layers < 0 && dbg.stage == 0 && !getenv("DC_NO_ALIGN")));
     static const bool want_stamps = getenv("DC_STAMPS") != nullptr;
     // Narrow workgroups (4 waves = 128-token units, one wave per SIMD) while every unit still gets a CU of its own: the layer
     // kernel is bound by instruction issue, so a wave alone on its SIMD runs a layer in about half the time (DESIGN.md
@@ -929,7 +933,7 @@ int enqueue_step(dc_sampler* s, hipStream_t st, bool loop_mode, const float* x_s
     const int upc_wide = (T + 255) / 256, upc_narrow = (T + 127) / 128;
     const bool aligned_env = can_align && getenv("DC_ALIGN") != nullptr;
     const int nwg_narrow = can_align ? B * upc_narrow : (G + 3) / 4;
-    const bool narrow = wgr && !ss && nwg_narrow <= s->num_cu && T <= 3840 && s->dbg_layers < 0 && s->dbg_stage == 0 &&
+    const bool narrow = wgr && !ss && nwg_narrow <= s->num_cu && T <= 3840 && dbg.layers < 0 && dbg.stage == 0 &&
                         !getenv("DC_NO_NARROW") && !want_stamps;
     // ... and for the wide (chip-full) form whenever the clip-aligned launch needs no more rounds of workgroups over the chip than the flat
     // one (bs = 32 x 1800: 256 workgroups instead of 228, one round either way): a clip's result is then bit-identical whatever the
@@ -945,7 +949,7 @@ int enqueue_step(dc_sampler* s, hipStream_t st, bool loop_mode, const float* x_s
     // regime the layer is bound by the LENGTH of one wave's dependency chain, and a 16-token wave's is about half as long.  The
     // embedding stays the narrow 32-token form (its 128-token unit records feed layer 0).  DC_NO_LAYER16=1 keeps the 32-token form.
     const int upc16 = (T + 63) / 64;
-    const bool layer16 = narrow && aligned && (long long)B * upc16 <= s->num_cu && upc16 <= dc_layer16_max_units() && s->dbg_first < 0 &&
+    const bool layer16 = narrow && aligned && (long long)B * upc16 <= s->num_cu && upc16 <= dc_layer16_max_units() && dbg.first < 0 &&
                          !getenv("DC_NO_LAYER16");
     const int upc = aligned ? (narrow ? upc_narrow : upc_wide) : 0;
     const int nwg = aligned ? B * upc : (narrow ? (G + 3) / 4 : (G + 7) / 8);
@@ -968,85 +972,77 @@ int enqueue_step(dc_sampler* s, hipStream_t st, bool loop_mode, const float* x_s
     // k_layer, DC_UPD_EMBED_NEXT) when that step is a plain wide step of the same enqueue sequence; its FiLM launch is then the bare GEMM
     // and it has no front launch.  DC_NO_EMBED_NEXT=1 keeps the front work in every step's own FiLM launch.
     const bool embed_next_on = !getenv("DC_NO_EMBED_NEXT");            // (read per call: a test toggles it)
-    const bool wide_plain = wgr && !narrow && !ss && fuse_silu && ff == fs && s->dbg_layers < 0 && s->dbg_stage == 0 && s->dbg_first < 0 &&
+    const bool wide_plain = wgr && !narrow && !ss && fuse_silu && ff == fs && dbg.layers < 0 && dbg.stage == 0 && dbg.first < 0 &&
                             !want_stamps && !s->cfg.no_eff;
-    const bool embed_next = embed_next_on && loop_mode && next_plain && wide_plain;
+    const bool embed_next = embed_next_on && loop_mode && c.next_plain && wide_plain;
     if (embedded && !(loop_mode && wide_plain)) return fail(DC_ERR_INVALID, "internal: a step whose front work was done by its predecessor changed its launch form");
-    const bool fuse_embed = !embedded && wgr && !narrow && (ss ? (aligned && mixed_form) : ff == fs) && fuse_silu && s->dbg_layers < 0 &&
-                            s->dbg_stage == 0 && nwg <= s->num_cu && !want_stamps && !s->prof.on && !getenv("DC_NO_FUSE_EMBED");
+    if (done) done->embedded_next = embed_next, done->folded = folded;
+    const bool fuse_embed = !embedded && wgr && !narrow && (ss ? (aligned && mixed_form) : ff == fs) && fuse_silu && dbg.layers < 0 &&
+                            dbg.stage == 0 && nwg <= s->num_cu && !want_stamps && !c.profile && !getenv("DC_NO_FUSE_EMBED");
     // small batches (narrow clip-aligned units): the embedding's workgroups ride BEHIND the GEMM's in the FiLM launch
     // (film_extra_workgroups, dc_kernels.hip): one launch (15 us at one clip) and one kernel boundary less per step.  DC_NO_FUSE_EMBED=1 keeps the two launches.
-    const bool fuse_extra = narrow && aligned && !ss && ff == fs && fuse_silu && s->h_model.film_w16 && s->dbg_first < 0 && !s->prof.on &&
+    const bool fuse_extra = narrow && aligned && !ss && ff == fs && fuse_silu && s->h_model.film_w16 && dbg.first < 0 && !c.profile &&
                             !getenv("DC_NO_FUSE_EMBED");
     DcEmbedArgs ea{};
-    if (fuse_embed) ea = DcEmbedArgs{dmod, x_src, s->d_h, s->d_recs, s->d_length, M, Tx, nwg, aligned ? upc : 0, ss ? 1 : 0, 0};
-    if (fuse_extra) ea = DcEmbedArgs{s->d_model, x_src, s->d_h, s->d_recs, s->d_length, M, Tx, nwg, upc, 0, 1};
+    if (fuse_embed) ea = DcEmbedArgs{dmod, c.x_src, s->d_h, s->d_recs, s->d_length, M, Tx, nwg, aligned ? upc : 0, ss ? 1 : 0, 0};
+    if (fuse_extra) ea = DcEmbedArgs{s->d_model, c.x_src, s->d_h, s->d_recs, s->d_length, M, Tx, nwg, upc, 0, 1};
     const DcUpdate upd{s->d_zslot, s->d_status, (loop_mode ? s->upd_flags : 0) | (getenv("DC_L16_TEST_DROP_SLICE") ? DC_UPD_TEST_DROP_SLICE : 0) |
                                                 (embed_next ? DC_UPD_EMBED_NEXT : 0),
                        folded ? graph_step : -1, nullptr};
-    const int film_rounds = s->NT / 16;
     // scale tiles: G' for the plain-operand consumers of this step, G' - 1 for the split-operand ones (dc_dev.h, film_affine)
     // (the production forms of the plain-operand kernels only: test hooks, stamps and the per-group record form keep G' - 1)
 #ifdef DC_NO_FILM_G1
     const bool g1_tiles = false;
 #else
-    const bool g1_tiles = g1_loop && !ss && wgr && !s->cfg.no_eff && s->dbg_stage == 0 && s->dbg_layers < 0 && s->dbg_first < 0 && !want_stamps;
+    const bool g1_tiles = c.g1_loop && !ss && wgr && !s->cfg.no_eff && dbg.stage == 0 && dbg.layers < 0 && dbg.first < 0 && !want_stamps;
 #endif
-    const float* film_b = g1_tiles ? s->h_model.film_b_g1 : s->h_model.film_b;
-    const float* film_b16 = g1_tiles ? s->h_model.film_b16_g1 : s->h_model.film_b16;
+    DcFilmArgs fa = film_args(s, fuse_silu ? s->d_pp : nullptr, t_src);
+    if (g1_tiles) fa.bias_ft = s->h_model.film_b_g1, fa.bias16 = s->h_model.film_b16_g1;
+    if (film_tail) fa.W16 = s->h_model.film_w16_tail;
+    fa.clk = want_stamps_film ? s->d_stamps + 252 : nullptr;
+    if (adapt) fa.rate_in = s->d_film_rate + 1024 * s->film_rate_parity, fa.rate_out = s->d_film_rate + 1024 * (s->film_rate_parity ^ 1);
+    fa.iter_base = iter_base;
+    fa.embed = (fuse_embed || fuse_extra) ? &ea : nullptr;
     // DC_DIAG_SKIP_FILM=1 (diagnostic, eager passes only, results invalid): the FiLM GEMM is launched once and never again - the layers then
     // read stale tiles and run without the GEMM's 300 us of power-limited matrix work between them (what the chip's clock management
     // does to the layer launches that follow a GEMM: tools/diag_clock_coupling.py)
     const bool diag_skip_film = getenv("DC_DIAG_SKIP_FILM") && !fuse_embed && !fuse_extra && s->diag_film_done;
     s->diag_film_done = true;
-    if (!diag_skip_film)
-    LAUNCH(K_FILM, dc_launch_film_gemm(st, ff, sf, s->h_model.film_w, film_b, s->d_s_hi, s->d_s_lo, s->d_E, G, s->NT, 0,
-                                       film_rounds, fuse_silu ? s->d_pp : nullptr, s->h_model.temb, t_src, T, B,
-                                       want_stamps_film ? s->d_stamps + 252 : nullptr,
-                                       adapt ? s->d_film_rate + 1024 * s->film_rate_parity : nullptr,
-                                       adapt ? s->d_film_rate + 1024 * (s->film_rate_parity ^ 1) : nullptr, iter_base,
-                                       film_tail ? s->h_model.film_w16_tail : s->h_model.film_w16, film_b16,
-                                       (fuse_embed || fuse_extra) ? &ea : nullptr, s->d_status));
+    if (!diag_skip_film) LAUNCH(K_FILM, dc_launch_film_gemm(st, ff, sf, fa));
     s->film_rate_parity ^= 1;
-    const int nl_run = (s->dbg_layers >= 0 && s->dbg_layers < L) ? s->dbg_layers : L;
+    const int nl_run = (dbg.layers >= 0 && dbg.layers < L) ? dbg.layers : L;
+    DcLayerArgs la{};
+    la.dm = dmod, la.hbuf = s->d_h, la.E = s->d_E, la.NT = s->NT, la.recs = s->d_recs, la.length = s->d_length, la.xin = c.x_src, la.xout = c.x_dst;
+    la.out_mode = loop_mode ? 1 : 0, la.coef_cur = coef_src, la.snap_cur = snap_src, la.snaps = s->d_snaps, la.iter_base = iter_base;
+    la.M = M, la.T = T, la.G = G, la.B = B, la.Tx = Tx, la.upd = upd;
+    DcLayerArgs la_stamps = la;      // (stage stamps of layer 3 in diagnostic builds: DcUpdate::stamps carries the buffer)
+    la_stamps.upd.stamps = s->d_stamps;
     if (s->cfg.no_eff) {
-        LAUNCH(K_EMBED, dc_launch_embed_front_full(st, fs, ss, dmod, x_src, s->d_h, s->d_kv_sa[0], M, T, B, s->KT));
-        for (int l = 0; l < nl_run; ++l) {
-            DcUpdate u = upd;              // (stage stamps of layer 3, tools/stage_stamps_full.py + a -DDC_FULL_STAMPS build: DcUpdate::stamps carries the buffer)
-            u.stamps = (want_stamps && l == 3) ? s->d_stamps : nullptr;
-            LAUNCH(K_LAYER, dc_launch_layer_full(st, fs, ss, dmod, l, s->d_h, s->d_E, s->NT, s->d_kv_sa[l & 1], s->d_kv_sa[(l + 1) & 1],
-                                                 s->d_kv_ca, s->d_length, x_src, x_dst, loop_mode ? 1 : 0, s->d_coef_cur,
-                                                 s->d_snap_cur, s->d_snaps, M, T, B, s->KT,
-                                                 (l == nl_run - 1) ? (s->dbg_stage ? s->dbg_stage : (nl_run < L ? 3 : 0)) : 0, u));
-        }
+        LAUNCH(K_EMBED, dc_launch_embed_front_full(st, fs, ss, dmod, c.x_src, s->d_h, s->d_kv_sa[0], M, T, B, s->KT));
+        for (int l = 0; l < nl_run; ++l)        // (stage stamps: tools/stage_stamps_full.py + a -DDC_FULL_STAMPS build)
+            LAUNCH(K_LAYER, dc_launch_layer_full(st, fs, ss, (want_stamps && l == 3) ? la_stamps : la, l, s->d_kv_sa[l & 1], s->d_kv_sa[(l + 1) & 1],
+                                                 s->d_kv_ca, s->KT, (l == nl_run - 1) ? (dbg.stage ? dbg.stage : (nl_run < L ? 3 : 0)) : 0));
         return DC_OK;
     }
     if (fuse_embed || fuse_extra || embedded) {
         // (embedded by the FiLM launch, or by the previous step's last layer)
-    } else if (s->dbg_first >= 0)
-        LAUNCH(K_EMBED, dc_launch_front_from_h(st, fs, ss, dmod, s->d_h, s->d_recs, s->d_length, M, T, G, B, s->dbg_first));
+    } else if (dbg.first >= 0)
+        LAUNCH(K_EMBED, dc_launch_front_from_h(st, fs, ss, dmod, s->d_h, s->d_recs, s->d_length, M, T, G, B, dbg.first));
     else
-        LAUNCH(K_EMBED, dc_launch_embed_front(st, fs, ss, wgr, dmod, x_src, s->d_h, s->d_recs, s->d_length, M, T, G, B,
+        LAUNCH(K_EMBED, dc_launch_embed_front(st, fs, ss, wgr, dmod, c.x_src, s->d_h, s->d_recs, s->d_length, M, T, G, B,
                                               want_stamps_film ? s->d_stamps + 256 : nullptr, narrow, Tx, upc));
-    for (int l = s->dbg_first >= 0 ? s->dbg_first : 0; l < nl_run; ++l) {
-        const int dbg = (l == nl_run - 1) ? s->dbg_stage : 0;
+    for (int l = dbg.first >= 0 ? dbg.first : 0; l < nl_run; ++l) {
         if (layer16) {
-            DcUpdate u16 = upd;       // (-DDC_L16_STAMPS builds: stage stamps of layer 3, tools/stage_stamps16.py)
-            static const bool stamps16 = getenv("DC_L16_STAMPS") != nullptr;
-            u16.stamps = (stamps16 && l == 3) ? s->d_stamps : nullptr;
-            LAUNCH(K_LAYER, dc_launch_layer16(st, fs, s->d_model, l, s->d_h, s->d_E, s->NT, s->d_a_ca16, s->d_recs, s->d_length, x_src, x_dst,
-                                              loop_mode ? 1 : 0, coef_src, snap_src, s->d_snaps, M, T, B, upc16, rec_stride,
-                                              l == 0 ? upc_narrow : upc16, l == 0 ? (size_t)2 * DC_REC_FLOATS : (size_t)DC_REC_FLOATS, iter_base, Tx,
-                                              u16, l16_shared ? s->d_gran : nullptr, l16_tag, g1_tiles));
+            static const bool stamps16 = getenv("DC_L16_STAMPS") != nullptr;        // (-DDC_L16_STAMPS builds: tools/stage_stamps16.py)
+            LAUNCH(K_LAYER, dc_launch_layer16(st, fs, (stamps16 && l == 3) ? la_stamps : la, l, s->d_a_ca16, upc16, rec_stride,
+                                              l == 0 ? upc_narrow : upc16, l == 0 ? (size_t)2 * DC_REC_FLOATS : (size_t)DC_REC_FLOATS,
+                                              l16_shared ? s->d_gran : nullptr, l16_tag, g1_tiles));
             continue;
         }
-        if (!wgr) LAUNCH(K_COMBINE, dc_launch_attn_combine(st, fs, s->d_recs, s->d_a_sa, T, (M + s->gran - 1) / s->gran, B, 1, s->gran));
-        LAUNCH(K_LAYER, dc_launch_layer(st, fs, ss, wgr, dmod, l, s->d_h, s->d_E, s->NT, s->d_a_sa, s->d_a_ca, s->d_recs,
-                                        s->d_length, x_src, x_dst, loop_mode ? 1 : 0, coef_src, snap_src,
-                                        s->d_snaps, M, T, G, B, dbg, ((l == 3 || l == 4) && want_stamps) ? s->d_stamps : nullptr, rec_stride,
-                                        iter_base, narrow, Tx, upc, upd, g1_tiles));
+        if (!wgr) LAUNCH(K_COMBINE, dc_launch_attn_combine(st, fs, s->d_recs, s->d_a_sa, T, G, B, 1, 32));      // (per-group records)
+        LAUNCH(K_LAYER, dc_launch_layer(st, fs, ss, wgr, la, l, s->d_a_sa, s->d_a_ca, (l == nl_run - 1) ? dbg.stage : 0,
+                                        ((l == 3 || l == 4) && want_stamps) ? s->d_stamps : nullptr, rec_stride, narrow, upc, g1_tiles));
     }
-    s->embedded_by_prev = embed_next;
     return DC_OK;
 }
 
@@ -1079,9 +1075,9 @@ int steps_per_graph(int S) {
 extern "C" DC_EXPORT int32_t dc_precise_tail_default(int32_t precision);
 namespace {
 // split-operand evaluations (the precise tail, dc_sampler_set_precise_forward) exist for: fp16 / bf16 precision, linear attention, no test hooks
-bool can_split_steps(const dc_sampler* s) {
-    return (s->cfg.precision == DC_PREC_FP16 || s->cfg.precision == DC_PREC_BF16) && s->dbg_layers < 0 && s->dbg_first < 0 &&
-           s->dbg_stage == 0 && s->d_model_split;
+bool can_split_steps(const dc_sampler* s, const Hooks& dbg) {
+    return (s->cfg.precision == DC_PREC_FP16 || s->cfg.precision == DC_PREC_BF16) && dbg.layers < 0 && dbg.first < 0 &&
+           dbg.stage == 0 && s->d_model_split;
 }
 
 int loop_common(dc_sampler* s, const float* d_noise, float* d_out, int S, const float* h_coef,
@@ -1178,20 +1174,26 @@ int loop_common(dc_sampler* s, const float* d_noise, float* d_out, int S, const 
     if (!tail_asked && s->cfg.precision == DC_PREC_BF16 && s->Tx < DC_BF16_SHORT_CLIP) tail = S;
     // (clip strides that are not whole 32-frame groups - T = 900 x 128 unpadded - and short clips run the split evaluations in the
     // per-group record form with its combine launches: no measurable cost at one evaluation per loop, 70.6 vs 70.6 ms at bs = 128 x 900)
-    if (!can_split_steps(s)) tail = 0;
+    if (!can_split_steps(s, Hooks{})) tail = 0;
     // (a tail of the whole loop splits every replay's graph; any shorter one lives in the last replay and is clipped to its steps)
     const bool tail_all = tail >= S;
     tail = std::max(0, std::min(tail, std::min(S, steps_per_graph(S))));
-    s->embedded_by_prev = false;
+    // n steps of the loop, the last split_n of them on split operands (graph: the steps of a capture)
+    bool folded = false;            // the last step enqueued looks its timestep up through *d_iter (StepDone::folded)
+    auto enqueue_steps = [&](int n, int split_n, bool graph) -> int {
+        bool embedded = false;      // (a sequence's first step does its own front work, its last step nobody else's)
+        for (int i = 0; i < n; ++i) {
+            Step c;
+            c.loop_mode = true, c.x_src = c.x_dst = s->d_x, c.graph_step = graph ? i : -1, c.split = i >= n - split_n, c.g1_loop = tail > 0;
+            c.next_plain = i + 1 < n - split_n, c.embedded = embedded, c.profile = profile;
+            StepDone d;
+            if (int rc = enqueue_step(s, st, c, &d)) return rc;
+            embedded = d.embedded_next, folded = d.folded;
+        }
+        return DC_OK;
+    };
     if (profile || no_graph) {
-        s->prof.on = profile;
-        for (int i = 0; i < S; ++i)
-            if ((rc = enqueue_step(s, st, true, s->d_x, s->d_x, -1, tail_all || i >= S - tail, tail > 0,
-                                   i + 1 < S && !(tail_all || i + 1 >= S - tail)))) {
-                s->prof.on = false;
-                return rc;
-            }
-        s->prof.on = false;
+        if ((rc = enqueue_steps(S, tail_all ? S : tail, false))) return rc;
     } else {
         const int K = steps_per_graph(S);
         const int replays = S / K;
@@ -1202,58 +1204,37 @@ int loop_common(dc_sampler* s, const float* d_noise, float* d_out, int S, const 
         // (g1 bit: the plain evaluations of a loop WITH a tail read G' scale tiles, those of a loop without one G' - 1 tiles - two
         // different captures of the same part-0 graph when S > 64)
         const unsigned long long fk = form_key(s) | ((unsigned long long)tail_here << 40) | ((tail > 0 ? 1ull : 0ull) << 39);
-        auto current = [&]() {
-            return s->graph && s->graph_B == s->B && s->graph_T == s->T && s->graph_Tx == s->Tx && s->graph_K == K && s->graph_form == fk;
-        };
-        if (!current()) {       // park the graph at hand, take this shape's from the park when it has been captured before
-            if (s->graph) {
-                if (s->graph_park.size() >= 3) {
-                    hipGraphExecDestroy(s->graph_park.front().exec);
-                    s->graph_park.erase(s->graph_park.begin());
-                }
-                s->graph_park.push_back({s->graph, s->graph_B, s->graph_T, s->graph_Tx, s->graph_K, s->graph_form, s->graph_folded});
-                s->graph = nullptr;
+        const dc_sampler::GraphKey key{s->B, s->T, s->Tx, K, fk};
+        auto& gs = s->graphs;
+        if (gs.empty() || gs.back().first != key) {
+            if (gs.size() > 3) {        // the current graph is parked: the oldest parked one makes room
+                hipGraphExecDestroy(gs.front().second);
+                gs.erase(gs.begin());
             }
-            for (size_t i = 0; i < s->graph_park.size(); ++i) {
-                const auto& g = s->graph_park[i];
-                if (g.B == s->B && g.T == s->T && g.Tx == s->Tx && g.K == K && g.form == fk) {
-                    s->graph = g.exec;
-                    s->graph_B = g.B, s->graph_T = g.T, s->graph_Tx = g.Tx, s->graph_K = g.K, s->graph_form = g.form, s->graph_folded = g.folded;
-                    s->graph_park.erase(s->graph_park.begin() + i);
-                    break;
-                }
-            }
-        }
-        if (!current()) {
-            hipGraph_t g = nullptr;
-            HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-            s->embedded_by_prev = false;      // (a graph's first step does its own front work, its last step nobody else's)
-            for (int i = 0; i < K; ++i)
-                if ((rc = enqueue_step(s, st, true, s->d_x, s->d_x, i, i >= K - tail_here, tail > 0, i + 1 < K && !(i + 1 >= K - tail_here)))) {
+            auto it = std::find_if(gs.begin(), gs.end(), [&](const auto& g) { return g.first == key; });
+            if (it != gs.end()) {
+                std::rotate(it, it + 1, gs.end());      // captured before: it becomes the current graph
+            } else {
+                hipGraph_t g = nullptr;
+                HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+                rc = enqueue_steps(K, tail_here, true);
+                // steps that indexed the iteration tables themselves did not advance the counter (see enqueue_step)
+                if (!rc && folded)
+                    if (hipError_t ea = dc_launch_advance_iter(st, s->d_iter, K)) rc = fail(DC_ERR_HIP, "k_advance_iter: %s", hipGetErrorString(ea));
+                if (rc) {
                     hipStreamEndCapture(st, &g);
                     if (g) hipGraphDestroy(g);
                     return rc;
                 }
-            // steps that indexed the iteration tables themselves did not advance the counter (see enqueue_step)
-            if (s->graph_folded) {
-                hipError_t ea = dc_launch_advance_iter(st, s->d_iter, K);
-                if (ea != hipSuccess) {
-                    hipStreamEndCapture(st, &g);
-                    if (g) hipGraphDestroy(g);
-                    return fail(DC_ERR_HIP, "k_advance_iter: %s", hipGetErrorString(ea));
-                }
+                HIP_TRY(hipStreamEndCapture(st, &g));
+                hipGraphExec_t exec = nullptr;
+                hipError_t e = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
+                hipGraphDestroy(g);
+                if (e != hipSuccess) return fail(DC_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e));
+                gs.push_back({key, exec});
             }
-            HIP_TRY(hipStreamEndCapture(st, &g));
-            hipError_t e = hipGraphInstantiate(&s->graph, g, nullptr, nullptr, 0);
-            hipGraphDestroy(g);
-            if (e != hipSuccess) return fail(DC_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e));
-            s->graph_B = s->B;
-            s->graph_T = s->T;
-            s->graph_Tx = s->Tx;
-            s->graph_K = K;
-            s->graph_form = fk;
         }
-        for (int i = 0; i < launches; ++i) HIP_TRY(hipGraphLaunch(s->graph, st));
+        for (int i = 0; i < launches; ++i) HIP_TRY(hipGraphLaunch(gs.back().second, st));
       }
     }
     // the final write x0 -> the caller's tensor: a copy, or (dc_sampler_set_smoothing) the Savitzky-Golay filter along time
@@ -1274,6 +1255,26 @@ std::vector<float> widen_coef(const float* h_coef, int S) {
     if (h_coef)
         for (int t = 0; t < S; ++t) memcpy(&c8[(size_t)DC_COEF * t], h_coef + 4 * (size_t)t, 16);
     return c8;
+}
+
+// dc_sampler_denoise; the debug entry points run it with their test hooks
+int denoise(dc_sampler* s, const float* d_x, const int32_t* h_timesteps, float* d_out, void* stream, const Hooks& dbg) {
+    if (!s || !s->finalized) return fail(DC_ERR_INVALID, "sampler not finalized");
+    if (!s->cond_set) return fail(DC_ERR_INVALID, "dc_sampler_set_conditioning must be called first");
+    if (!d_x || !h_timesteps || !d_out) return fail(DC_ERR_INVALID, "null pointer argument");
+    for (int b = 0; b < s->B; ++b)
+        if (h_timesteps[b] < 0 || h_timesteps[b] >= s->cfg.max_timesteps)
+            return fail(DC_ERR_INVALID, "timestep %d outside [0,%d)", h_timesteps[b], s->cfg.max_timesteps);
+    HIP_TRY(hipSetDevice(s->cfg.device));
+    hipStream_t user = (hipStream_t)stream, st = s->stream;
+    int rc;
+    if ((rc = sync_in(s, user))) return rc;
+    HIP_TRY(hipMemcpyAsync(s->d_t_clip, h_timesteps, (size_t)s->B * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    Step c;
+    c.x_src = d_x, c.x_dst = d_out, c.split = s->precise_forward && can_split_steps(s, dbg), c.dbg = dbg;
+    if ((rc = enqueue_step(s, st, c))) return rc;
+    return sync_out(s, user);
 }
 
 }  // namespace
@@ -1696,20 +1697,7 @@ int dc_savgol_filter(const float* d_in, float* d_out, int32_t B, int32_t T, int3
 }
 
 int dc_sampler_denoise(dc_sampler* s, const float* d_x, const int32_t* h_timesteps, float* d_out, void* stream) {
-    if (!s || !s->finalized) return fail(DC_ERR_INVALID, "sampler not finalized");
-    if (!s->cond_set) return fail(DC_ERR_INVALID, "dc_sampler_set_conditioning must be called first");
-    if (!d_x || !h_timesteps || !d_out) return fail(DC_ERR_INVALID, "null pointer argument");
-    for (int b = 0; b < s->B; ++b)
-        if (h_timesteps[b] < 0 || h_timesteps[b] >= s->cfg.max_timesteps)
-            return fail(DC_ERR_INVALID, "timestep %d outside [0,%d)", h_timesteps[b], s->cfg.max_timesteps);
-    HIP_TRY(hipSetDevice(s->cfg.device));
-    hipStream_t user = (hipStream_t)stream, st = s->stream;
-    int rc;
-    if ((rc = sync_in(s, user))) return rc;
-    HIP_TRY(hipMemcpyAsync(s->d_t_clip, h_timesteps, (size_t)s->B * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if ((rc = enqueue_step(s, st, false, d_x, d_out, -1, s->precise_forward && can_split_steps(s)))) return rc;
-    return sync_out(s, user);
+    return denoise(s, d_x, h_timesteps, d_out, stream, Hooks{});
 }
 
 int dc_sampler_ddim_loop(dc_sampler* s, const float* d_noise, float* d_out, int32_t num_steps, const float* h_coef,
@@ -1785,9 +1773,7 @@ int dc_sampler_status(dc_sampler* s, int32_t* h_status, int32_t clear) {
                 HIP_TRY(hipMemcpy(s->d_t_clip, tc.data(), tc.size() * 4, hipMemcpyHostToDevice));
                 if (s->split_film)
                     HIP_TRY(dc_launch_silu_emb(s->stream, s->film_fmt, true, s->d_pp, s->h_model.temb, s->d_t_clip, s->d_s_hi, s->d_s_lo, s->G, s->T, s->B));
-                HIP_TRY(dc_launch_film_gemm(s->stream, s->film_fmt, s->split_film, s->h_model.film_w, s->h_model.film_b, s->d_s_hi, s->d_s_lo, s->d_E,
-                                            s->G, s->NT, 0, s->NT / 16, s->split_film ? nullptr : s->d_pp, s->h_model.temb, s->d_t_clip, s->T, s->B,
-                                            nullptr, nullptr, nullptr, nullptr, s->h_model.film_w16, s->h_model.film_b16, nullptr, s->d_status));
+                HIP_TRY(dc_launch_film_gemm(s->stream, s->film_fmt, s->split_film, film_args(s, s->split_film ? nullptr : s->d_pp, s->d_t_clip)));
                 HIP_TRY(dc_launch_scan_f16(s->stream, s->d_E, ebytes, s->d_status));
                 HIP_TRY(hipStreamSynchronize(s->stream));
                 HIP_TRY(hipMemcpy(h_status, s->d_status, 4, hipMemcpyDeviceToHost));
@@ -1830,12 +1816,7 @@ int dc_sampler_profile_loop(dc_sampler* s, const float* d_noise, float* d_out, i
 int dc_sampler_debug_denoise(dc_sampler* s, const float* d_x, const int32_t* h_timesteps, float* d_out,
                              int32_t n_layers, int32_t stage, void* stream) {
     if (!s) return fail(DC_ERR_INVALID, "null sampler");
-    s->dbg_layers = n_layers;
-    s->dbg_stage = stage;
-    const int rc = dc_sampler_denoise(s, d_x, h_timesteps, d_out, stream);
-    s->dbg_layers = -1;
-    s->dbg_stage = 0;
-    return rc;
+    return denoise(s, d_x, h_timesteps, d_out, stream, Hooks{n_layers, stage, -1});
 }
 
 int dc_sampler_debug_layer(dc_sampler* s, const float* h_h, const int32_t* h_timesteps, int32_t layer, int32_t first_stage,
@@ -1862,14 +1843,8 @@ int dc_sampler_debug_layer(dc_sampler* s, const float* h_h, const int32_t* h_tim
                     }
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(s->d_h, img.data(), img.size() * 4, hipMemcpyHostToDevice));
-    s->dbg_first = layer;
-    s->dbg_layers = layer + 1;
-    s->dbg_stage = stage | ((first_stage - 1) << 16);
-    const int rc = dc_sampler_denoise(s, s->d_x, h_timesteps, s->d_x, stream);     // x is not read on this path; out_mode is never reached
-    s->dbg_first = -1;
-    s->dbg_layers = -1;
-    s->dbg_stage = 0;
-    return rc;
+    // (x is not read on this path; out_mode is never reached)
+    return denoise(s, s->d_x, h_timesteps, s->d_x, stream, Hooks{layer + 1, stage | ((first_stage - 1) << 16), layer});
 }
 
 int dc_sampler_debug_read(dc_sampler* s, const char* what, void* h_out, int64_t nbytes) {

@@ -2763,11 +2763,9 @@ hipError_t dc_launch_silu_emb(hipStream_t st, int fmt, bool split, const float* 
 }
 
 template <class T16, bool SP>
-static void launch_film_t(hipStream_t st, const void* W, const float* bias_ft,
-                          const void* s_hi, const void* s_lo, void* E, int G, int NT, int* status) {
-    k_film_gemm<T16, SP><<<dim3(NT / 8, (G + 3) / 4), dim3(256), 0, st>>>((const v8<T16>*)W, bias_ft,
-                                                                         (const v8<T16>*)s_hi, (const v8<T16>*)s_lo,
-                                                                         (f16x16*)E, G, NT, status);
+static void launch_film_t(hipStream_t st, const DcFilmArgs& a) {
+    k_film_gemm<T16, SP><<<dim3(a.NT / 8, (a.G + 3) / 4), dim3(256), 0, st>>>((const v8<T16>*)a.W, a.bias_ft, (const v8<T16>*)a.s_hi,
+                                                                             (const v8<T16>*)a.s_lo, (f16x16*)a.E, a.G, a.NT, a.status);
 }
 // GEMM workgroups of a FiLM launch that also carries `ne` embedding workgroups behind them (DcEmbedArgs::extra; small batches).  While
 // both fit the chip and the GEMM keeps its rounds, the GEMM gives up CUs (every workgroup on a CU of its own).  With the chip full the
@@ -2785,9 +2783,7 @@ static int film_extra_workgroups(long long nunit, int nblk, int ne, int ncu) {
     return (int)alone;
 }
 template <class T16>
-static hipError_t launch_film3_t(hipStream_t st, const void* W16, const float* bias16, void* E, int G, int NT, int round0, int nround,
-                                 const float* pp, const float* temb, const int* t_clip, int T, int B, unsigned long long* clk,
-                                 const float* rate_in, float* rate_out, const int* iter_base, const DcEmbedArgs* ea, int* status) {
+static hipError_t launch_film3_t(hipStream_t st, const DcFilmArgs& a) {
     const size_t shm = 4 * DC_KS_E * 1024 + 64;        // slab + the pair counter
     static unsigned long long optin_done = 0;
     if (hipError_t e = lds_optin((const void*)k_film_gemm3<T16>, (int)shm, optin_done)) return e;
@@ -2796,19 +2792,22 @@ static hipError_t launch_film3_t(hipStream_t st, const void* W16, const float* b
     // (token block x round) units are spread over more workgroups than there are token blocks, down to one unit each - several
     // workgroups then build the same slab, but a slab fill costs ~6 us and a block's 12 rounds ~60 us when one workgroup sweeps them
     // alone (B=1: 49 -> 36 us per step with one unit per workgroup instead of four).
-    const int nblk = (G + 3) / 4;
-    const long long nunit = (long long)nblk * nround;
+    const int nblk = (a.G + 3) / 4;
+    const long long nunit = (long long)nblk * a.nround;
     int nwg = (int)(nunit < ncu ? nunit : ncu);
     if (nwg < nblk) nwg = nblk < ncu ? nblk : ncu;
     if (nwg < 1) nwg = 1;
+    const v8<T16>* W16 = (const v8<T16>*)a.W16;
+    f16x16* E = (f16x16*)a.E;
+    const DcEmbedArgs* ea = a.embed;
     if (ea && ea->x && ea->extra) {              // small batches: the embedding's narrow units as extra workgroups of this launch (k_film_embed)
         if (ea->split_bf16 || ea->upc <= 0) return hipErrorInvalidValue;
         const int nf = film_extra_workgroups(nunit, nblk, ea->ne, ncu);
         if (nf <= 0) return hipErrorInvalidValue;
         static unsigned long long optin4 = 0;
         if (hipError_t e = lds_optin((const void*)k_film_embed<T16>, (int)shm, optin4)) return e;
-        k_film_embed<T16><<<dim3(nf + ea->ne), dim3(512), shm, st>>>((const v8<T16>*)W16, bias16, (f16x16*)E, G, NT, round0, nround, pp, temb, t_clip, T, B,
-                                                                     clk, rate_in, rate_out, iter_base, *ea, status);
+        k_film_embed<T16><<<dim3(nf + ea->ne), dim3(512), shm, st>>>(W16, a.bias16, E, a.G, a.NT, a.round0, a.nround, a.pp, a.temb, a.t_clip, a.T,
+                                                                     a.B, a.clk, a.rate_in, a.rate_out, a.iter_base, *ea, a.status);
         return hipGetLastError();
     }
     if (ea && ea->x && nwg >= ea->ne) {          // fused with k_embed_front (its LDS image is smaller than the slab)
@@ -2817,33 +2816,29 @@ static hipError_t launch_film3_t(hipStream_t st, const void* W16, const float* b
             const size_t shm2 = 8192 + 65 * 1024 + 9 * 4 * 32 * 4 + 65 * 1024;
             static unsigned long long optin3 = 0;
             if (hipError_t e = lds_optin((const void*)k_film_embed<T16, __bf16, true>, (int)shm2, optin3)) return e;
-            k_film_embed<T16, __bf16, true><<<dim3(nwg), dim3(512), shm2, st>>>((const v8<T16>*)W16, bias16, (f16x16*)E, G, NT, round0, nround, pp, temb,
-                                                                                t_clip, T, B, clk, rate_in, rate_out, iter_base, *ea, status);
+            k_film_embed<T16, __bf16, true><<<dim3(nwg), dim3(512), shm2, st>>>(W16, a.bias16, E, a.G, a.NT, a.round0, a.nround, a.pp, a.temb,
+                                                                                a.t_clip, a.T, a.B, a.clk, a.rate_in, a.rate_out, a.iter_base, *ea,
+                                                                                a.status);
             return hipGetLastError();
         }
         static unsigned long long optin2 = 0;
         if (hipError_t e = lds_optin((const void*)k_film_embed<T16>, (int)shm, optin2)) return e;
-        k_film_embed<T16><<<dim3(nwg), dim3(512), shm, st>>>((const v8<T16>*)W16, bias16, (f16x16*)E, G, NT, round0, nround, pp, temb, t_clip, T, B,
-                                                             clk, rate_in, rate_out, iter_base, *ea, status);
+        k_film_embed<T16><<<dim3(nwg), dim3(512), shm, st>>>(W16, a.bias16, E, a.G, a.NT, a.round0, a.nround, a.pp, a.temb, a.t_clip, a.T, a.B,
+                                                             a.clk, a.rate_in, a.rate_out, a.iter_base, *ea, a.status);
         return hipGetLastError();
     }
     if (ea && ea->x) return hipErrorInvalidValue;      // the caller skipped k_embed_front relying on the fused launch: never drop it silently
-    k_film_gemm3<T16><<<dim3(nwg), dim3(512), shm, st>>>((const v8<T16>*)W16, bias16, (f16x16*)E, G, NT, round0, nround,
-                                                                           pp, temb, t_clip, T, B, clk, rate_in, rate_out, iter_base, status);
+    k_film_gemm3<T16><<<dim3(nwg), dim3(512), shm, st>>>(W16, a.bias16, E, a.G, a.NT, a.round0, a.nround, a.pp, a.temb, a.t_clip, a.T, a.B,
+                                                         a.clk, a.rate_in, a.rate_out, a.iter_base, a.status);
     return hipGetLastError();
 }
-hipError_t dc_launch_film_gemm(hipStream_t st, int fmt, bool split, const void* W, const float* bias_ft, const void* s_hi, const void* s_lo, void* E, int G, int NT, int round0,
-                               int nround, const float* pp, const float* temb, const int* t_clip, int T, int B, unsigned long long* clk,
-                               const float* rate_in, float* rate_out, const int* iter_base, const void* W16, const float* bias16,
-                               const DcEmbedArgs* embed, int* status) {
+hipError_t dc_launch_film_gemm(hipStream_t st, int fmt, bool split, const DcFilmArgs& a) {
     // non-split formats with the fp32 emb image at hand: the S-stationary 16x16x32 kernel builds its operand itself; the split
     // formats (and the test hooks, which read the 16-bit operand image back) use the plain tiled kernel on S_hi / S_lo
-    if (!split && pp && W16)
-        return fmt == 1 ? launch_film3_t<_Float16>(st, W16, bias16, E, G, NT, round0, nround, pp, temb, t_clip, T, B, clk, rate_in, rate_out, iter_base, embed, status)
-                        : launch_film3_t<__bf16>(st, W16, bias16, E, G, NT, round0, nround, pp, temb, t_clip, T, B, clk, rate_in, rate_out, iter_base, embed, status);
-    if (embed && embed->x) return hipErrorInvalidValue;      // only the S-stationary form can carry the embedding
-    if (round0 != 0) return hipSuccess;        // the plain kernel computes all rounds in its first launch
-    DISPATCH(fmt, split, (launch_film_t<T16, SP>(st, W, bias_ft, s_hi, s_lo, E, G, NT, status)));
+    if (!split && a.pp && a.W16) return fmt == 1 ? launch_film3_t<_Float16>(st, a) : launch_film3_t<__bf16>(st, a);
+    if (a.embed && a.embed->x) return hipErrorInvalidValue;      // only the S-stationary form can carry the embedding
+    if (a.round0 != 0) return hipSuccess;        // the plain kernel computes all rounds in its first launch
+    DISPATCH(fmt, split, (launch_film_t<T16, SP>(st, a)));
     return LAUNCH_CHECK();
 }
 
@@ -2895,106 +2890,83 @@ hipError_t dc_launch_embed_front(hipStream_t st, int fmt, bool split, bool wgr, 
 }
 
 template <class T16, bool SP, bool DBG, bool STAMP, bool WGR, bool NARROW = false, bool G1 = false>
-static hipError_t launch_layer_t(hipStream_t st, const DcModel* dm, int l, float* hbuf, const void* E, int NT,
-                                 const void* a_sa, const void* a_ca, float* recs, const int* length, const float* xin,
-                                 float* xout, int out_mode, const float* coef_cur, const int* snap_cur, float* snaps,
-                                 int M, int T, int G, int B, int dbg, unsigned long long* stamps, size_t rec_stride,
-                                 const int* iter_base, int Tx, int upc, const DcUpdate& upd) {
+static hipError_t launch_layer_t(hipStream_t st, const DcLayerArgs& a, int l, const void* a_sa, const void* a_ca, int dbg,
+                                 unsigned long long* stamps, size_t rec_stride, int upc) {
     constexpr int NW = NARROW ? 4 : (SP ? DC_SPLIT_NW : 8);
     // two stage images (+1 KiB constants each); non-split adds the attention-frag region and the FiLM rings
     const size_t shm = SP ? 2 * 65 * 1024 + (WGR ? 16384 + 6144 : 0) : 2 * 33 * 1024 + 16384 + 8 * 8192 + 6144;
     static unsigned long long optin_done = 0;   // > 64 KiB of dynamic LDS needs the opt-in
     if (hipError_t e = lds_optin((const void*)k_layer<T16, SP, DBG, STAMP, WGR, NARROW, G1>, (int)shm, optin_done)) return e;
-    k_layer<T16, SP, DBG, STAMP, WGR, NARROW, G1><<<dim3((WGR && upc) ? B * upc : (G + NW - 1) / NW), dim3(NW * 64), shm, st>>>(
-        dm, l, hbuf, (const f16x16*)E, NT, (const v8<T16>*)a_sa, (const v8<T16>*)a_ca, recs, length, xin, xout, out_mode, coef_cur, snap_cur,
-        snaps, M, T, G, B, dbg, stamps, rec_stride, iter_base, Tx, WGR ? upc : 0, upd);
+    k_layer<T16, SP, DBG, STAMP, WGR, NARROW, G1><<<dim3((WGR && upc) ? a.B * upc : (a.G + NW - 1) / NW), dim3(NW * 64), shm, st>>>(
+        a.dm, l, a.hbuf, (const f16x16*)a.E, a.NT, (const v8<T16>*)a_sa, (const v8<T16>*)a_ca, a.recs, a.length, a.xin, a.xout, a.out_mode,
+        a.coef_cur, a.snap_cur, a.snaps, a.M, a.T, a.G, a.B, dbg, stamps, rec_stride, a.iter_base, a.Tx, WGR ? upc : 0, a.upd);
     return hipGetLastError();
 }
 
-hipError_t dc_launch_layer(hipStream_t st, int fmt, bool split, bool wgr, const DcModel* dm, int l, float* hbuf, const void* E, int NT,
-                           const void* a_sa, const void* a_ca, float* recs, const int* length, const float* xin,
-                           float* xout, int out_mode, const float* coef_cur, const int* snap_cur, float* snaps,
-                           int M, int T, int G, int B, int dbg, unsigned long long* stamps, size_t rec_stride, const int* iter_base,
-                           bool narrow, int Tx, int upc, const DcUpdate& upd, bool g1) {
-    hipError_t e = hipSuccess;
-#define LAYER_ARGS st, dm, l, hbuf, E, NT, a_sa, a_ca, recs, length, xin, xout, out_mode, coef_cur, snap_cur, snaps, M, T, G, B, dbg, stamps, \
-                   rec_stride, iter_base, Tx, upc, upd
+hipError_t dc_launch_layer(hipStream_t st, int fmt, bool split, bool wgr, const DcLayerArgs& a, int l, const void* a_sa, const void* a_ca,
+                           int dbg, unsigned long long* stamps, size_t rec_stride, bool narrow, int upc, bool g1) {
+    using Launch = hipError_t (*)(hipStream_t, const DcLayerArgs&, int, const void*, const void*, int, unsigned long long*, size_t, int);
+    const bool f16 = fmt == 1;
+    Launch f;
     // (g1: the FiLM scale tiles of this evaluation hold G' - the two production forms of the plain-operand kernel only)
     if (g1 && !(wgr && !split && dbg == 0 && stamps == nullptr)) return hipErrorInvalidValue;
     if (wgr && !split && narrow && dbg == 0 && stamps == nullptr) {      // narrow workgroups: production build only
         if (g1)
-            return fmt == 1 ? launch_layer_t<_Float16, false, false, false, true, true, true>(LAYER_ARGS)
-                            : launch_layer_t<__bf16, false, false, false, true, true, true>(LAYER_ARGS);
-        return fmt == 1 ? launch_layer_t<_Float16, false, false, false, true, true>(LAYER_ARGS)
-                        : launch_layer_t<__bf16, false, false, false, true, true>(LAYER_ARGS);
-    }
-    if (wgr && !split && g1)
-        return fmt == 1 ? launch_layer_t<_Float16, false, false, false, true, false, true>(LAYER_ARGS)
-                        : launch_layer_t<__bf16, false, false, false, true, false, true>(LAYER_ARGS);
-    if (wgr && !split) {        // workgroup-level records + in-kernel combine (non-split formats, T >= 256)
-        if (dbg != 0)
-            e = fmt == 1 ? launch_layer_t<_Float16, false, true, false, true>(LAYER_ARGS) : launch_layer_t<__bf16, false, true, false, true>(LAYER_ARGS);
-        else if (stamps != nullptr)
-            e = fmt == 1 ? launch_layer_t<_Float16, false, false, true, true>(LAYER_ARGS) : launch_layer_t<__bf16, false, false, true, true>(LAYER_ARGS);
+            f = f16 ? launch_layer_t<_Float16, false, false, false, true, true, true> : launch_layer_t<__bf16, false, false, false, true, true, true>;
         else
-            e = fmt == 1 ? launch_layer_t<_Float16, false, false, false, true>(LAYER_ARGS) : launch_layer_t<__bf16, false, false, false, true>(LAYER_ARGS);
-        return e;
-    }
-    if (wgr) {            // split formats: workgroup records + in-kernel combine on clip-aligned units (production build only)
+            f = f16 ? launch_layer_t<_Float16, false, false, false, true, true> : launch_layer_t<__bf16, false, false, false, true, true>;
+    } else if (wgr && !split && g1) {
+        f = f16 ? launch_layer_t<_Float16, false, false, false, true, false, true> : launch_layer_t<__bf16, false, false, false, true, false, true>;
+    } else if (wgr && !split) {        // workgroup-level records + in-kernel combine (non-split formats, T >= 256)
+        if (dbg != 0)
+            f = f16 ? launch_layer_t<_Float16, false, true, false, true> : launch_layer_t<__bf16, false, true, false, true>;
+        else if (stamps != nullptr)
+            f = f16 ? launch_layer_t<_Float16, false, false, true, true> : launch_layer_t<__bf16, false, false, true, true>;
+        else
+            f = f16 ? launch_layer_t<_Float16, false, false, false, true> : launch_layer_t<__bf16, false, false, false, true>;
+    } else if (wgr) {            // split formats: workgroup records + in-kernel combine on clip-aligned units (production build only)
         if (upc <= 0 || dbg != 0) return hipErrorInvalidValue;
         if (stamps != nullptr)
-            return fmt == 1 ? launch_layer_t<_Float16, true, false, true, true>(LAYER_ARGS) : launch_layer_t<__bf16, true, false, true, true>(LAYER_ARGS);
-        return fmt == 1 ? launch_layer_t<_Float16, true, false, false, true>(LAYER_ARGS) : launch_layer_t<__bf16, true, false, false, true>(LAYER_ARGS);
-    }
-    if (dbg != 0) {
-        DISPATCH(fmt, split, (e = launch_layer_t<T16, SP, true, false, false>(LAYER_ARGS)));
+            f = f16 ? launch_layer_t<_Float16, true, false, true, true> : launch_layer_t<__bf16, true, false, true, true>;
+        else
+            f = f16 ? launch_layer_t<_Float16, true, false, false, true> : launch_layer_t<__bf16, true, false, false, true>;
+    } else if (dbg != 0) {
+        DISPATCH(fmt, split, (f = launch_layer_t<T16, SP, true, false, false>));
     } else if (stamps != nullptr) {
-        DISPATCH(fmt, split, (e = launch_layer_t<T16, SP, false, true, false>(LAYER_ARGS)));
+        DISPATCH(fmt, split, (f = launch_layer_t<T16, SP, false, true, false>));
     } else {
-        DISPATCH(fmt, split, (e = launch_layer_t<T16, SP, false, false, false>(LAYER_ARGS)));
+        DISPATCH(fmt, split, (f = launch_layer_t<T16, SP, false, false, false>));
     }
-#undef LAYER_ARGS
-    return e;
+    return f(st, a, l, a_sa, a_ca, dbg, stamps, rec_stride, upc);
 }
 
 // ---- no_eff variant ------------------------------------------------------------------
+// (fp16 only: with bf16 scores, weights and values x0 sits 1 - 2e-3 from the reference - dc_sampler_create refuses the combination)
 template <class T16, bool SP>
-static hipError_t launch_full_t(hipStream_t st, int which, const DcModel* dm, int l, const float* x, float* hbuf, const void* E,
-                                int NT, const void* kv_cur, void* kv_next, const void* kv_ca, const int* length,
-                                const float* xin, float* xout, int out_mode, const float* coef_cur, const int* snap_cur,
-                                float* snaps, int M, int T, int B, int KT, int stop_after, const DcUpdate& upd) {
+static hipError_t launch_full_t(hipStream_t st, const DcLayerArgs& a, int l, const void* kv_cur, void* kv_next, const void* kv_ca, int KT,
+                                int stop_after) {
     const int WPC = (KT + 7) / 8;
     static unsigned long long optin_done = 0;   // key-tile double buffer (32 KiB) + per-wave query fragments (64 KiB) > 64 KiB of dynamic LDS
     if (hipError_t e = lds_optin((const void*)k_layer_full<T16, SP>, DC_FULL_LDS, optin_done)) return e;
-    if (which == 0)
-        k_embed_front_full<T16, SP><<<dim3(B * WPC), dim3(512), 0, st>>>(dm, x, hbuf, (v8<T16>*)kv_next, M, T, KT, WPC);
-    else
-        k_layer_full<T16, SP><<<dim3(B * WPC), dim3(512), DC_FULL_LDS, st>>>(dm, l, hbuf, (const f16x16*)E, NT, (const v8<T16>*)kv_cur,
-                                                                       (v8<T16>*)kv_next, (const v8<T16>*)kv_ca, length, xin, xout,
-                                                                       out_mode, coef_cur, snap_cur, snaps, M, T, B, KT, WPC,
-                                                                       stop_after, upd);
+    k_layer_full<T16, SP><<<dim3(a.B * WPC), dim3(512), DC_FULL_LDS, st>>>(
+        a.dm, l, a.hbuf, (const f16x16*)a.E, a.NT, (const v8<T16>*)kv_cur, (v8<T16>*)kv_next, (const v8<T16>*)kv_ca, a.length, a.xin, a.xout,
+        a.out_mode, a.coef_cur, a.snap_cur, a.snaps, a.M, a.T, a.B, KT, WPC, stop_after, a.upd);
     return hipGetLastError();
 }
-// (fp16 only: with bf16 scores, weights and values x0 sits 1 - 2e-3 from the reference - dc_sampler_create refuses the combination)
 hipError_t dc_launch_embed_front_full(hipStream_t st, int fmt, bool split, const DcModel* dm, const float* x, float* hbuf, void* kv_next,
                                       int M, int T, int B, int KT) {
     if (fmt != 1) return hipErrorInvalidValue;
+    const int WPC = (KT + 7) / 8;
     if (split)
-        return launch_full_t<_Float16, true>(st, 0, dm, 0, x, hbuf, nullptr, 0, nullptr, kv_next, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr,
-                                             nullptr, M, T, B, KT, 0, DcUpdate{});
-    return launch_full_t<_Float16, false>(st, 0, dm, 0, x, hbuf, nullptr, 0, nullptr, kv_next, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr,
-                                          nullptr, M, T, B, KT, 0, DcUpdate{});
+        k_embed_front_full<_Float16, true><<<dim3(B * WPC), dim3(512), 0, st>>>(dm, x, hbuf, (f16x8*)kv_next, M, T, KT, WPC);
+    else
+        k_embed_front_full<_Float16, false><<<dim3(B * WPC), dim3(512), 0, st>>>(dm, x, hbuf, (f16x8*)kv_next, M, T, KT, WPC);
+    return hipGetLastError();
 }
-hipError_t dc_launch_layer_full(hipStream_t st, int fmt, bool split, const DcModel* dm, int l, float* hbuf, const void* E, int NT,
-                                const void* kv_cur, void* kv_next, const void* kv_ca, const int* length, const float* xin,
-                                float* xout, int out_mode, const float* coef_cur, const int* snap_cur, float* snaps, int M,
-                                int T, int B, int KT, int stop_after, const DcUpdate& upd) {
+hipError_t dc_launch_layer_full(hipStream_t st, int fmt, bool split, const DcLayerArgs& a, int l, const void* kv_cur, void* kv_next,
+                                const void* kv_ca, int KT, int stop_after) {
     if (fmt != 1) return hipErrorInvalidValue;
-    if (split)
-        return launch_full_t<_Float16, true>(st, 1, dm, l, nullptr, hbuf, E, NT, kv_cur, kv_next, kv_ca, length, xin, xout, out_mode, coef_cur, snap_cur,
-                                             snaps, M, T, B, KT, stop_after, upd);
-    return launch_full_t<_Float16, false>(st, 1, dm, l, nullptr, hbuf, E, NT, kv_cur, kv_next, kv_ca, length, xin, xout, out_mode, coef_cur, snap_cur,
-                                          snaps, M, T, B, KT, stop_after, upd);
+    return (split ? launch_full_t<_Float16, true> : launch_full_t<_Float16, false>)(st, a, l, kv_cur, kv_next, kv_ca, KT, stop_after);
 }
 hipError_t dc_launch_ca_kv(hipStream_t st, int fmt, const DcModel* dm, const void* nh_hi, const void* nh_lo, void* kv_ca,
                            int M, int T, int G, int B, int KT, int L) {

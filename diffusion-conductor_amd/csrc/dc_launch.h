@@ -24,16 +24,26 @@ hipError_t dc_launch_attn_combine(hipStream_t st, int fmt, const float* recs, vo
 hipError_t dc_launch_silu_emb(hipStream_t st, int fmt, bool split, const float* pp, const float* temb, const int* t_clip,
                               void* s_hi, void* s_lo, int G, int T, int B,
                               const int* iter_base = nullptr /* captured loop: t_clip = &t_of_iter[step], indexed by *iter_base */);
-hipError_t dc_launch_film_gemm(hipStream_t st, int fmt, bool split, const void* W, const float* bias_ft, const void* s_hi, const void* s_lo, void* E, int G, int NT, int round0,
-                               int nround, const float* pp, const float* temb, const int* t_clip, int T, int B,
-                               unsigned long long* clk /* diagnostic clock stamps or nullptr */,
-                               const float* rate_in, float* rate_out /* per-workgroup speeds of the previous / this launch (num_cu floats) or nullptr */,
-                               const int* iter_base /* captured loop: t_clip = &t_of_iter[step], indexed by *iter_base; else nullptr */,
-                               const void* W16, const float* bias16 /* operands of the 16x16x32-MFMA form (used with pp, non-split) */,
-                               const DcEmbedArgs* embed = nullptr /* S-stationary form only: fuse k_embed_front into this launch;
-                                                                     an error if the launch cannot carry it */,
-                               int* status = nullptr /* device status word: DC_STATUS_F16_SAT is OR-ed in when a tile leaves the fp16 range */);
 // pp != nullptr (non-split formats): the FiLM GEMM builds its operand SiLU(temb[t_clip] + pp) itself and s_hi is not read
+struct DcFilmArgs {
+    const void* W;
+    const float* bias_ft;
+    const void *s_hi, *s_lo;
+    void* E;
+    int G, NT, round0, nround;
+    const float *pp, *temb;
+    const int* t_clip;
+    int T, B;
+    unsigned long long* clk;     // diagnostic clock stamps or nullptr
+    const float* rate_in;        // per-workgroup speeds of the previous / this launch (num_cu floats) or nullptr
+    float* rate_out;
+    const int* iter_base;        // captured loop: t_clip = &t_of_iter[step], indexed by *iter_base; else nullptr
+    const void* W16;             // operands of the 16x16x32-MFMA form (used with pp, non-split)
+    const float* bias16;
+    const DcEmbedArgs* embed;    // S-stationary form only: fuse k_embed_front into this launch; an error if the launch cannot carry it
+    int* status;                 // device status word: DC_STATUS_F16_SAT is OR-ed in when a tile leaves the fp16 range, or nullptr
+};
+hipError_t dc_launch_film_gemm(hipStream_t st, int fmt, bool split, const DcFilmArgs& a);
 // wgr: workgroup-level partial records, combined by the consuming layer kernel itself (non-split formats and T >= 256 only;
 // no dc_launch_attn_combine between the layers then)
 hipError_t dc_launch_embed_front(hipStream_t st, int fmt, bool split, bool wgr, const DcModel* dm, const float* x, float* hbuf, float* recs,
@@ -45,28 +55,40 @@ hipError_t dc_launch_embed_front(hipStream_t st, int fmt, bool split, bool wgr, 
 // test hook: front half of layer l0 from the residual stream as it stands in hbuf (per-group records)
 hipError_t dc_launch_front_from_h(hipStream_t st, int fmt, bool split, const DcModel* dm, float* hbuf, float* recs, const int* length,
                                   int M, int T, int G, int B, int l0);
-hipError_t dc_launch_layer(hipStream_t st, int fmt, bool split, bool wgr, const DcModel* dm, int l, float* hbuf, const void* E, int NT,
-                           const void* a_sa, const void* a_ca, float* recs, const int* length, const float* xin,
-                           float* xout, int out_mode, const float* coef_cur, const int* snap_cur, float* snaps,
-                           int M, int T, int G, int B, int dbg, unsigned long long* stamps, size_t rec_stride,
-                           const int* iter_base /* captured loop: coef_cur / snap_cur = this step's slots of the per-iteration tables,
-                                                   indexed by *iter_base; else nullptr (scalars prepared by k_begin_step) */,
+// What the layer launches of one step share (dc_launch_layer, dc_launch_layer16, dc_launch_layer_full)
+struct DcLayerArgs {
+    const DcModel* dm;
+    float* hbuf;
+    const void* E;
+    int NT;
+    float* recs;
+    const int* length;
+    const float* xin;
+    float* xout;
+    int out_mode;
+    const float* coef_cur;       // captured loop: coef_cur / snap_cur = this step's slots of the per-iteration tables, indexed by
+    const int* snap_cur;         // *iter_base; else iter_base = nullptr (scalars prepared by k_begin_step)
+    float* snaps;
+    const int* iter_base;
+    int M, T, G, B;
+    int Tx;                      // frames per clip of xin / xout / snaps
+    DcUpdate upd;                // options of the fused DDIM update + the status word (dc_common.h)
+};
+hipError_t dc_launch_layer(hipStream_t st, int fmt, bool split, bool wgr, const DcLayerArgs& a, int l, const void* a_sa, const void* a_ca,
+                           int dbg, unsigned long long* stamps, size_t rec_stride,
                            bool narrow /* wgr, non-split, dbg == 0: 4-wave workgroups; recs / rec_stride then count 128-token units */,
-                           int Tx /* frames per clip of xin / xout / snaps */, int upc /* as dc_launch_embed_front */,
-                           const DcUpdate& upd /* options of the fused DDIM update + the status word (dc_common.h) */,
-                           bool g1 = false /* the FiLM scale tiles hold G' (film_affine in dc_dev.h; plain-operand production forms only) */);
+                           int upc /* as dc_launch_embed_front */,
+                           bool g1 /* the FiLM scale tiles hold G' (film_affine in dc_dev.h; plain-operand production forms only) */);
 // The same layer for SMALL batches on 16-token waves (dc_layer16.hip): non-split formats, clip-aligned 64-token units (grid = B * upc,
 // upc = ceil(T / 64), T = clip stride, a multiple of 32), one unit record per workgroup.  a_ca16 = the cross-attention fragments in
 // that kernel's form (dc_launch_cond_af16, once per conditioning).  nu_in / stride_in: unit records per clip and floats per unit of
 // the records this layer combines (layer 0: k_embed_front's narrow 128-token units, 2 * DC_REC_FLOATS apart; later layers: upc
 // units DC_REC_FLOATS apart).  At most dc_layer16_max_units() records per clip.
-hipError_t dc_launch_layer16(hipStream_t st, int fmt, const DcModel* dm, int l, float* hbuf, const void* E, int NT, const void* a_ca16,
-                             float* recs, const int* length, const float* xin, float* xout, int out_mode, const float* coef_cur,
-                             const int* snap_cur, float* snaps, int M, int T, int B, int upc, size_t rec_stride, int nu_in, size_t stride_in,
-                             const int* iter_base, int Tx, const DcUpdate& upd,
+hipError_t dc_launch_layer16(hipStream_t st, int fmt, const DcLayerArgs& a, int l, const void* a_ca16, int upc, size_t rec_stride, int nu_in,
+                             size_t stride_in,
                              unsigned long long* gran /* [B][1024] granules: the clip's workgroups share the combine inside the launch (nullptr: each alone) */,
                              unsigned tag_base /* the launch's tag = tag_base + 16 * (*iter_base) + l + 1: must differ between consecutive launches */,
-                             bool g1 = false /* the FiLM scale tiles hold G' */);
+                             bool g1 /* the FiLM scale tiles hold G' */);
 hipError_t dc_launch_cond_af16(hipStream_t st, int fmt, const void* a_ca, void* a_ca16, int n_matrices);
 int dc_layer16_max_units(void);
 hipError_t dc_launch_advance_iter(hipStream_t st, int* iter, int k);
@@ -86,10 +108,8 @@ hipError_t dc_launch_ca_kv(hipStream_t st, int fmt, const DcModel* dm, const voi
                            int M, int T, int G, int B, int KT, int L);
 hipError_t dc_launch_embed_front_full(hipStream_t st, int fmt, bool split, const DcModel* dm, const float* x, float* hbuf, void* kv_next,
                                       int M, int T, int B, int KT);
-hipError_t dc_launch_layer_full(hipStream_t st, int fmt, bool split, const DcModel* dm, int l, float* hbuf, const void* E, int NT,
-                                const void* kv_cur, void* kv_next, const void* kv_ca, const int* length, const float* xin,
-                                float* xout, int out_mode, const float* coef_cur, const int* snap_cur, float* snaps, int M,
-                                int T, int B, int KT, int stop_after, const DcUpdate& upd);
+hipError_t dc_launch_layer_full(hipStream_t st, int fmt, bool split, const DcLayerArgs& a, int l, const void* kv_cur, void* kv_next,
+                                const void* kv_ca, int KT, int stop_after);
 
 // diagnostic builds (-DDC_DIAG_FULL_MOVES): visits / moves of the no_eff key loop's reference point; hipErrorNotSupported otherwise
 hipError_t dc_full_moves_read(unsigned long long* out /* [2] */, bool reset);

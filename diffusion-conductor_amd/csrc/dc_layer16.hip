@@ -954,10 +954,8 @@ int dc_layer16_max_units(void) { return L16_MAXU; }
 
 namespace {
 template <class T16, bool G1>
-hipError_t launch_layer16_t(hipStream_t st, const DcModel* dm, int l, float* hbuf, const void* E, int NT, const void* a_ca16,
-                            float* recs, const int* length, const float* xin, float* xout, int out_mode, const float* coef_cur,
-                            const int* snap_cur, float* snaps, int M, int T, int B, int upc, size_t rec_stride, int nu_in, size_t stride_in,
-                            const int* iter_base, int Tx, const DcUpdate& upd, unsigned long long* gran, unsigned tag_base) {
+hipError_t launch_layer16_t(hipStream_t st, const DcLayerArgs& a, int l, const void* a_ca16, int upc, size_t rec_stride, int nu_in,
+                            size_t stride_in, unsigned long long* gran, unsigned tag_base) {
     static unsigned long long done = 0;      // > 64 KiB of dynamic LDS needs the opt-in, per device
     int dev = 0;
     if (hipError_t e = hipGetDevice(&dev)) return e;
@@ -965,23 +963,20 @@ hipError_t launch_layer16_t(hipStream_t st, const DcModel* dm, int l, float* hbu
         if (hipError_t e = hipFuncSetAttribute((const void*)k_layer16<T16, G1>, hipFuncAttributeMaxDynamicSharedMemorySize, L16_LDS)) return e;
         if (dev < 64) done |= 1ull << dev;
     }
-    k_layer16<T16, G1><<<dim3(B * upc), dim3(256), L16_LDS, st>>>(dm, l, hbuf, (const f16x16*)E, NT, (const v8<T16>*)a_ca16, recs, length, xin, xout,
-                                                                  out_mode, coef_cur, snap_cur, snaps, M, T, B, upc, rec_stride, nu_in, stride_in,
-                                                                  iter_base, Tx, upd, gran, tag_base);
+    k_layer16<T16, G1><<<dim3(a.B * upc), dim3(256), L16_LDS, st>>>(a.dm, l, a.hbuf, (const f16x16*)a.E, a.NT, (const v8<T16>*)a_ca16, a.recs,
+                                                                    a.length, a.xin, a.xout, a.out_mode, a.coef_cur, a.snap_cur, a.snaps, a.M,
+                                                                    a.T, a.B, upc, rec_stride, nu_in, stride_in, a.iter_base, a.Tx, a.upd, gran,
+                                                                    tag_base);
     return hipGetLastError();
 }
 }  // namespace
 
-hipError_t dc_launch_layer16(hipStream_t st, int fmt, const DcModel* dm, int l, float* hbuf, const void* E, int NT, const void* a_ca16,
-                             float* recs, const int* length, const float* xin, float* xout, int out_mode, const float* coef_cur,
-                             const int* snap_cur, float* snaps, int M, int T, int B, int upc, size_t rec_stride, int nu_in, size_t stride_in,
-                             const int* iter_base, int Tx, const DcUpdate& upd, unsigned long long* gran, unsigned tag_base, bool g1) {
-    if (nu_in < 1 || nu_in > L16_MAXU || upc < 1 || (T & 31)) return hipErrorInvalidValue;
-#define L16_ARGS st, dm, l, hbuf, E, NT, a_ca16, recs, length, xin, xout, out_mode, coef_cur, snap_cur, snaps, M, T, B, upc, rec_stride, nu_in, stride_in, \
-                 iter_base, Tx, upd, gran, tag_base
-    if (fmt == 1) return g1 ? launch_layer16_t<_Float16, true>(L16_ARGS) : launch_layer16_t<_Float16, false>(L16_ARGS);
-    return g1 ? launch_layer16_t<__bf16, true>(L16_ARGS) : launch_layer16_t<__bf16, false>(L16_ARGS);
-#undef L16_ARGS
+hipError_t dc_launch_layer16(hipStream_t st, int fmt, const DcLayerArgs& a, int l, const void* a_ca16, int upc, size_t rec_stride, int nu_in,
+                             size_t stride_in, unsigned long long* gran, unsigned tag_base, bool g1) {
+    if (nu_in < 1 || nu_in > L16_MAXU || upc < 1 || (a.T & 31)) return hipErrorInvalidValue;
+    const auto f = fmt == 1 ? (g1 ? launch_layer16_t<_Float16, true> : launch_layer16_t<_Float16, false>)
+                            : (g1 ? launch_layer16_t<__bf16, true> : launch_layer16_t<__bf16, false>);
+    return f(st, a, l, a_ca16, upc, rec_stride, nu_in, stride_in, gran, tag_base);
 }
 hipError_t dc_launch_cond_af16(hipStream_t st, int fmt, const void* a_ca, void* a_ca16, int n_matrices) {
     const int n = n_matrices * 8 * 64;
