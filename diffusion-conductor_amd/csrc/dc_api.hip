@@ -17,6 +17,7 @@
 #include "dc_common.h"
 #include "dc_launch.h"
 #include "dc_music.h"
+#include "dc_pack.h"
 
 namespace {
 
@@ -38,98 +39,6 @@ int fail(int code, const char* fmt, ...) {
         if (e_ != hipSuccess) return fail(DC_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
 
-// ---- bf16 helpers (round to nearest even; inputs are finite weights) -------------------
-inline uint16_t f2bf(float f) {
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);   // NaN stays NaN
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-inline float bf2f(uint16_t h) {
-    uint32_t u = (uint32_t)h << 16;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
-
-inline uint16_t f2h(float f) {   // fp32 -> fp16 bits, round to nearest even (compiler's conversion)
-    const _Float16 h = (_Float16)f;
-    uint16_t u;
-    memcpy(&u, &h, 2);
-    return u;
-}
-inline float h2f(uint16_t u) {
-    _Float16 h;
-    memcpy(&h, &u, 2);
-    return (float)h;
-}
-
-inline int tile_row(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
-inline int cdiv(int a, int b) { return (a + b - 1) / b; }
-
-// Weight image [kt][ot][s][64][8] (kt-major).  "chained" k order: frag (ot, kt, s), lane (i = l&31, hh = l>>5), element j
-//   = W[32ot + i][32kt + 16s + 8(j>>2) + 4hh + (j&3)]
-// i.e. the k order in which an accumulator tile, converted in registers, presents its rows.
-// "natural" k order: frag (ot, ks): element j = W[32ot + i][16ks + 8hh + j].
-void pack_weight(const float* w, int n_out, int k_in, bool chained, uint16_t* hi, uint16_t* lo, bool f16 = false) {
-    const int OT = cdiv(n_out, 32), KT = cdiv(k_in, 32);
-    for (int ot = 0; ot < OT; ++ot)
-        for (int kt = 0; kt < KT; ++kt)
-            for (int s = 0; s < 2; ++s)
-                for (int l = 0; l < 64; ++l)
-                    for (int j = 0; j < 8; ++j) {
-                        const int i = l & 31, hh = l >> 5;
-                        const int row = 32 * ot + i;
-                        const int col = chained ? 32 * kt + 16 * s + 8 * (j >> 2) + 4 * hh + (j & 3)
-                                                : 32 * kt + 16 * s + 8 * hh + j;
-                        const float v = (row < n_out && col < k_in) ? w[(size_t)row * k_in + col] : 0.f;
-                        const size_t o = chained ? ((((size_t)kt * OT + ot) * 2 + s) * 64 + l) * 8 + j     // [kt][ot][s]: k-outer sweeps
-                                                 : ((((size_t)ot * KT + kt) * 2 + s) * 64 + l) * 8 + j;    // [ot][ks]: streamed per tile
-                        const uint16_t h = f16 ? f2h(v) : f2bf(v);
-                        hi[o] = h;
-                        lo[o] = f16 ? f2h(v - h2f(h)) : f2bf(v - bf2f(h));
-                    }
-}
-size_t packed_elems(int n_out, int k_in) { return (size_t)cdiv(n_out, 32) * cdiv(k_in, 32) * 2 * 64 * 8; }
-// v_mfma_f32_16x16x32 operand image of the 16-token layer kernel (DcLayer16 in dc_common.h): [m][rb][64][8]
-void pack_weight16(const float* w, int n_out, int k_in, uint16_t* hi, uint16_t* lo, bool f16) {
-    const int RB = cdiv(n_out, 16), KM = cdiv(k_in, 32);
-    for (int m = 0; m < KM; ++m)
-        for (int rb = 0; rb < RB; ++rb)
-            for (int l = 0; l < 64; ++l)
-                for (int j = 0; j < 8; ++j) {
-                    const int row = 16 * rb + (l & 15), col = 32 * m + 16 * (j >> 2) + 4 * (l >> 4) + (j & 3);
-                    const float v = (row < n_out && col < k_in) ? w[(size_t)row * k_in + col] : 0.f;
-                    const size_t o = (((size_t)m * RB + rb) * 64 + l) * 8 + j;
-                    const uint16_t h = f16 ? f2h(v) : f2bf(v);
-                    hi[o] = h;
-                    if (lo) lo[o] = f16 ? f2h(v - h2f(h)) : f2bf(v - bf2f(h));
-                }
-}
-size_t packed_elems16(int n_out, int k_in) { return (size_t)cdiv(n_out, 16) * cdiv(k_in, 32) * 64 * 8; }
-
-// per-feature vector in FT register order: out[(t*2+hh)*16 + r] = v[32t + tile_row(r,hh)]
-void pack_ftvec(const float* v, int n, int NT, float* out) {
-    for (int t = 0; t < NT; ++t)
-        for (int hh = 0; hh < 2; ++hh)
-            for (int r = 0; r < 16; ++r) {
-                const int f = 32 * t + tile_row(r, hh);
-                out[(t * 2 + hh) * 16 + r] = f < n ? v[f] : 0.f;
-            }
-}
-
-// ---- device arena builder --------------------------------------------------------------
-struct Arena {
-    std::vector<uint8_t> host;
-    size_t add(const void* p, size_t bytes) {
-        size_t off = (host.size() + 255) & ~(size_t)255;
-        host.resize(off + bytes);
-        memcpy(host.data() + off, p, bytes);
-        return off;
-    }
-};
-
 enum KernelId { K_BEGIN = 0, K_SILU, K_FILM, K_EMBED, K_COMBINE, K_LAYER, K_NOISE, K_COUNT };
 const char* kKernelNames[K_COUNT] = {"k_begin_step", "k_silu_emb", "k_film_gemm", "k_embed_front", "k_attn_combine", "k_layer", "k_step_noise"};
 
@@ -138,13 +47,22 @@ struct Prof {                       // per-kernel profile (dc_sampler_profile_lo
     std::vector<int> ids;
 };
 
-}  // namespace
-
-struct dc_sampler {
-    dc_config cfg{};
-    // operand formats (0 = bf16, 1 = f16) and split flags of the 128-wide GEMMs and of the FiLM GEMM
+// operand formats (0 = bf16, 1 = f16) and split flags of the 128-wide GEMMs and of the FiLM GEMM
+struct Formats {
     int small_fmt = 0, film_fmt = 0;
     bool split_small = false, split_film = false;
+    void set_precision(int precision) {
+        split_small = precision == DC_PREC_MIXED || precision == DC_PREC_BF16X3;
+        split_film = precision == DC_PREC_BF16X3;
+        small_fmt = precision == DC_PREC_FP16 ? 1 : 0;
+        film_fmt = (precision == DC_PREC_FP16 || precision == DC_PREC_MIXED) ? 1 : 0;
+    }
+};
+
+}  // namespace
+
+struct dc_sampler : Formats {     // (set_precision(cfg.precision))
+    dc_config cfg{};
     std::map<std::string, std::vector<float>> params;
     bool finalized = false;
 
@@ -325,378 +243,349 @@ bool music_param(const std::string& n) {
     return n.rfind("music_encoder.", 0) == 0 || n == "proj.weight" || n == "proj.bias";
 }
 
-struct Offsets {   // arena offsets mirrored into DcModel after upload
-    std::vector<std::pair<const void**, size_t>> fix;
+// ---- the model image: everything the denoiser's kernels read, prepared on the host (no HIP call from here to upload_model) ----
+// a pointer field of the model record and the same field of its split twin
+template <class T>
+struct Dst {
+    const T **model, **split;
 };
 
-int build_model(dc_sampler* s) {
-    const dc_config& c = s->cfg;
-    const int D = DC_D, L = c.num_layers, P = c.input_feats;
-    Arena A;
-    Offsets O;
-    DcModel& m = s->h_model;
-    memset(&m, 0, sizeof m);
-    auto P_ = [&](const std::string& n) -> const float* { return find(s, n)->data(); };
+// What pack_model produces: the arena, and the two model records with their pointers still to be resolved (arena.resolve).
+// `split` is the same model with the layer stage images in their split form where those are kept (dc_sampler::h_model_split).
+struct ModelImage {
+    Arena arena;
+    DcModel model{}, split{};
+    int NT = 0;                          // FiLM feature tiles = 3 * L * 8
+    size_t freqs, w0t, b0, w2t, b2;      // arena offsets of the time-embedding operands (dc_launch_temb_table)
+    ModelImage() = default;
+    ModelImage(const ModelImage&) = delete;      // (the arena's fix-ups point into this object)
+    template <class T>
+    Dst<T> top(const T* DcModel::*f) { return {&(model.*f), &(split.*f)}; }
+    template <class T>
+    Dst<T> layer(int i, const T* DcLayer::*f) { return {&(model.layer[i].*f), &(split.layer[i].*f)}; }
+    template <class T>
+    Dst<T> l16(int i, const T* DcLayer16::*f) { return {&(model.l16[i].*f), &(split.l16[i].*f)}; }
+};
 
-    const bool sf16 = s->small_fmt == 1;
-    auto add_packed = [&](const bf16x8** dst, const float* w, int n_out, int k_in, bool chained, bool f16) {
+// W' = W diag(g), c' = c + W b  (LayerNorm affine folded into the projection that consumes it)
+// `scale` additionally multiplies the whole projection: log2(e) for the query / key projections, whose
+// outputs only ever feed exp() (softmax), so the kernels can use the native exp2.
+void fold_ln(const float* w, const float* c, const float* g, const float* b, int n_out, int k, std::vector<float>& wf,
+             std::vector<float>& cf, double scale = 1.0) {
+    wf.resize((size_t)n_out * k);
+    cf.resize(n_out);
+    for (int o = 0; o < n_out; ++o) {
+        double acc = c[o];
+        for (int i = 0; i < k; ++i) {
+            wf[(size_t)o * k + i] = (float)((double)w[(size_t)o * k + i] * g[i] * scale);
+            acc += (double)w[(size_t)o * k + i] * b[i];
+        }
+        cf[o] = (float)(acc * scale);
+    }
+}
+
+// `linear` with the mean over its 512 outputs taken off (the LayerNorm in front of the cross-attention K / V projections sees
+// linear(x) - mean = Wc x + bc), and that LayerNorm's variance as a quadratic form of the 64 inputs (DcModel::lin_gram)
+struct LinearStats {
+    std::vector<double> wc, bc;      // [512][64], [512]
+    std::vector<float> gram;         // [64][64] Gc, gv[64], c
+};
+LinearStats centre_linear(const float* w /*[512][64]*/, const float* b) {
+    LinearStats s{std::vector<double>((size_t)512 * 64), std::vector<double>(512), std::vector<float>(64 * 64 + 64 + 1)};
+    double bm = 0.0;
+    for (int k = 0; k < 512; ++k) bm += b[k];
+    bm /= 512.0;
+    for (int k = 0; k < 512; ++k) s.bc[k] = (double)b[k] - bm;
+    for (int i = 0; i < 64; ++i) {
+        double wm = 0.0;
+        for (int k = 0; k < 512; ++k) wm += w[(size_t)k * 64 + i];
+        wm /= 512.0;
+        for (int k = 0; k < 512; ++k) s.wc[(size_t)k * 64 + i] = (double)w[(size_t)k * 64 + i] - wm;
+    }
+    for (int i = 0; i < 64; ++i) {
+        for (int j = 0; j < 64; ++j) {
+            double acc = 0.0;
+            for (int k = 0; k < 512; ++k) acc += s.wc[(size_t)k * 64 + i] * s.wc[(size_t)k * 64 + j];
+            s.gram[i * 64 + j] = (float)(acc / 512.0);
+        }
+        double acc = 0.0;
+        for (int k = 0; k < 512; ++k) acc += s.wc[(size_t)k * 64 + i] * s.bc[k];
+        s.gram[64 * 64 + i] = (float)(acc / 512.0);
+    }
+    double cc = 0.0;
+    for (int k = 0; k < 512; ++k) cc += s.bc[k] * s.bc[k];
+    s.gram[64 * 64 + 64] = (float)(cc / 512.0);
+    return s;
+}
+
+constexpr double LOG2E = 1.4426950408889634;
+
+// The steps of pack_model and what they share.  Every add_* appends to the arena - the order of the calls IS the arena layout -
+// and points the named field of both model records at the entry.
+struct ModelPacker {
+    const dc_config& c;
+    const Formats& fmt;
+    const DcParams& params;
+    ModelImage& I;
+    const bool sf16 = fmt.small_fmt == 1, ssp = fmt.split_small;
+    const bool want_twins = (c.precision == DC_PREC_FP16 || c.precision == DC_PREC_BF16) && !ssp;
+    // 16-token layer kernel (small batches; non-split formats, linear attention): up to two matrices + constants per stage image
+    const bool want16 = !ssp && !c.no_eff;
+    // softmax inputs: the linear-attention kernels use exp2 on log2(e)-scaled queries/keys; the full-attention
+    // (no_eff) kernels keep keys unscaled and fold log2(e) / sqrt(head_dim) into the queries (scores arrive as exp2 exponents)
+    const double QS = c.no_eff ? 0.25 * LOG2E : LOG2E, KS = c.no_eff ? 1.0 : LOG2E;
+    // the FiLM stack, filled layer by layer (film_rows)
+    std::vector<float> film_w = std::vector<float>((size_t)I.NT * 32 * DC_E), film_b = std::vector<float>((size_t)I.NT * 32), film_b_g1 = film_b;
+
+    const float* P(const std::string& n) const { return params.find(n)->second.data(); }
+    template <class T>
+    void put(Dst<T> dst, size_t off) {
+        I.arena.point(dst.model, off);
+        I.arena.point(dst.split, off);
+    }
+    void add_vec(Dst<float> dst, const float* v, size_t n) { put(dst, I.arena.add(v, n * 4)); }
+    void add_vec(Dst<float> dst, const std::vector<float>& v) { put(dst, I.arena.add(v)); }
+    // natural-k fragments, [hi][lo]
+    void add_natural(Dst<bf16x8> dst, const float* w, int n_out, int k_in, bool f16) {
         const size_t ne = packed_elems(n_out, k_in);
         std::vector<uint16_t> buf(2 * ne);
-        pack_weight(w, n_out, k_in, chained, buf.data(), buf.data() + ne, f16);
-        O.fix.push_back({(const void**)dst, A.add(buf.data(), buf.size() * 2)});
-    };
-    auto add_ft = [&](const float** dst, const float* v, int n, int NT) {
-        std::vector<float> buf((size_t)NT * 32);
-        pack_ftvec(v, n, NT, buf.data());
-        O.fix.push_back({(const void**)dst, A.add(buf.data(), buf.size() * 4)});
-    };
-    auto add_raw = [&](const float** dst, const float* v, size_t n) {
-        O.fix.push_back({(const void**)dst, A.add(v, n * 4)});
-    };
-    // stage image: [hi frags][lo frags if `with_lo`][1 KiB of fp32 constants if `consts`] (dc_common.h)
-    // fp16 precision: every layer stage image is also kept in its split form (the fp16 lo halves exist anyway): the loop's last
-    // evaluations can then run on split operands (dc_sampler_set_precise_tail) through h_model_split, a copy of the model record
-    // whose image pointers are these twins
-    const bool want_twins = (c.precision == DC_PREC_FP16 || c.precision == DC_PREC_BF16) && !s->split_small;
-    std::vector<std::pair<size_t, size_t>> twins;          // (offset of the pointer inside DcModel, arena offset of the split image)
-    auto add_image = [&](const bf16x8** dst, const float* w, int n_out, int k_in, bool with_lo, const float* consts,
-                         size_t n_consts) {
+        pack_weight(w, n_out, k_in, false, buf.data(), buf.data() + ne, f16);
+        put(dst, I.arena.add(buf));
+    }
+    // [hi frags][lo frags if `with_lo`][1 KiB of fp32 constants if `consts`]
+    static std::vector<uint8_t> blob_of(const std::vector<uint16_t>& hi, const std::vector<uint16_t>& lo, bool with_lo, const float* consts,
+                                        size_t n_consts) {
+        const size_t half = hi.size() * 2;
+        std::vector<uint8_t> blob(half * (with_lo ? 2 : 1) + (consts ? 1024 : 0), 0);
+        memcpy(blob.data(), hi.data(), half);
+        if (with_lo) memcpy(blob.data() + half, lo.data(), half);
+        if (consts) memcpy(blob.data() + half * (with_lo ? 2 : 1), consts, n_consts * 4);
+        return blob;
+    }
+    // stage image of k_layer (dc_common.h), chained k order; a plain one is followed by its split twin where the model keeps twins
+    void add_image(Dst<bf16x8> dst, const float* w, int n_out, int k_in, bool with_lo, const float* consts, size_t n_consts) {
         const size_t ne = packed_elems(n_out, k_in);
         std::vector<uint16_t> hi(ne), lo(ne);
         pack_weight(w, n_out, k_in, true, hi.data(), lo.data(), sf16);
-        auto blob_of = [&](bool lo_too) {
-            std::vector<uint8_t> blob(ne * 2 * (lo_too ? 2 : 1) + (consts ? 1024 : 0), 0);
-            memcpy(blob.data(), hi.data(), ne * 2);
-            if (lo_too) memcpy(blob.data() + ne * 2, lo.data(), ne * 2);
-            if (consts) memcpy(blob.data() + ne * 2 * (lo_too ? 2 : 1), consts, n_consts * 4);
-            return blob;
-        };
-        const std::vector<uint8_t> blob = blob_of(with_lo);
-        O.fix.push_back({(const void**)dst, A.add(blob.data(), blob.size())});
-        const size_t off = (size_t)((const char*)dst - (const char*)&m);
-        if (want_twins && !with_lo && off < sizeof(DcModel)) {
-            const std::vector<uint8_t> b2 = blob_of(true);
-            twins.push_back({off, A.add(b2.data(), b2.size())});
-        }
-    };
-    auto ftvec = [&](const float* v, int n, int NT_) {
-        std::vector<float> buf((size_t)NT_ * 32);
-        pack_ftvec(v, n, NT_, buf.data());
-        return buf;
-    };
-    const bool ssp = s->split_small;
-    // 16-token layer kernel (small batches; non-split formats, linear attention): up to two matrices + constants per stage image
-    const bool want16 = !ssp && !c.no_eff;
-    auto add_image16 = [&](const bf16x8** dst, const float* wa, int na_out, int ka, const float* wb, int nb_out, int kb, bool with_lo,
-                           const std::vector<float>& consts) {
+        const size_t off = I.arena.add(blob_of(hi, lo, with_lo, consts, n_consts));
+        I.arena.point(dst.model, off);
+        I.arena.point(dst.split, want_twins && !with_lo ? I.arena.add(blob_of(hi, lo, true, consts, n_consts)) : off);
+    }
+    // stage image of the 16-token layer kernel: one or two matrices, then the constants
+    void add_image16(Dst<bf16x8> dst, const float* wa, int na_out, int ka, const float* wb, int nb_out, int kb, bool with_lo,
+                     const std::vector<float>& consts) {
         if (!want16) return;
         const size_t ea = packed_elems16(na_out, ka), eb = wb ? packed_elems16(nb_out, kb) : 0;
         std::vector<uint16_t> hi(ea + eb), lo(ea + eb);
         pack_weight16(wa, na_out, ka, hi.data(), lo.data(), sf16);
         if (wb) pack_weight16(wb, nb_out, kb, hi.data() + ea, lo.data() + ea, sf16);
-        std::vector<uint8_t> blob((ea + eb) * 2 * (with_lo ? 2 : 1) + 1024, 0);
-        memcpy(blob.data(), hi.data(), (ea + eb) * 2);
-        if (with_lo) memcpy(blob.data() + (ea + eb) * 2, lo.data(), (ea + eb) * 2);
-        memcpy(blob.data() + (ea + eb) * 2 * (with_lo ? 2 : 1), consts.data(), consts.size() * 4);
-        O.fix.push_back({(const void**)dst, A.add(blob.data(), blob.size())});
-    };
-    auto vec = [](const float* p, size_t n) { return std::vector<float>(p, p + n); };
-    auto add_styl = [&](const bf16x8** dst, const std::string& p) -> std::vector<float> {
-        const std::vector<float> bo = ftvec(P_(p + ".out_layers.2.bias"), D, 4);
-        // the kernels hand over log2(e) * SiLU(.) (silu_l2_pair in dc_kernels.hip): ln 2 goes into the weights
-        const float* w = P_(p + ".out_layers.2.weight");
-        std::vector<float> ws((size_t)D * D);
-        for (size_t i = 0; i < ws.size(); ++i) ws[i] = (float)((double)w[i] * 0.6931471805599453);
-        add_image(dst, ws.data(), D, D, ssp, bo.data(), bo.size());
-        return ws;
-    };
-    // W' = W diag(g), c' = c + W b  (LayerNorm affine folded into the projection that consumes it)
-    // `scale` additionally multiplies the whole projection: log2(e) for the query / key projections, whose
-    // outputs only ever feed exp() (softmax), so the kernels can use the native exp2.
-    auto fold_ln = [&](const float* w, const float* c, const float* g, const float* b, int n_out, int k,
-                       std::vector<float>& wf, std::vector<float>& cf, double scale = 1.0) {
-        wf.resize((size_t)n_out * k);
-        cf.resize(n_out);
-        for (int o = 0; o < n_out; ++o) {
-            double acc = c[o];
-            for (int i = 0; i < k; ++i) {
-                wf[(size_t)o * k + i] = (float)((double)w[(size_t)o * k + i] * g[i] * scale);
-                acc += (double)w[(size_t)o * k + i] * b[i];
-            }
-            cf[o] = (float)(acc * scale);
-        }
-    };
-    // `linear` with the mean over its 512 outputs taken off (the LayerNorm in front of the cross-attention K / V projections sees
-    // linear(x) - mean = Wc x + bc), and that LayerNorm's variance as a quadratic form of the 64 inputs
-    std::vector<double> lin_wc((size_t)512 * 64), lin_bc(512);
-    std::vector<float> lin_gram(64 * 64 + 64 + 1);
-    {
-        const float* w = P_("linear.weight");   // [512][64]
-        const float* b = P_("linear.bias");
-        double bm = 0.0;
-        for (int k = 0; k < 512; ++k) bm += b[k];
-        bm /= 512.0;
-        for (int k = 0; k < 512; ++k) lin_bc[k] = (double)b[k] - bm;
-        for (int i = 0; i < 64; ++i) {
-            double wm = 0.0;
-            for (int k = 0; k < 512; ++k) wm += w[(size_t)k * 64 + i];
-            wm /= 512.0;
-            for (int k = 0; k < 512; ++k) lin_wc[(size_t)k * 64 + i] = (double)w[(size_t)k * 64 + i] - wm;
-        }
-        for (int i = 0; i < 64; ++i) {
-            for (int j = 0; j < 64; ++j) {
-                double acc = 0.0;
-                for (int k = 0; k < 512; ++k) acc += lin_wc[(size_t)k * 64 + i] * lin_wc[(size_t)k * 64 + j];
-                lin_gram[i * 64 + j] = (float)(acc / 512.0);
-            }
-            double acc = 0.0;
-            for (int k = 0; k < 512; ++k) acc += lin_wc[(size_t)k * 64 + i] * lin_bc[k];
-            lin_gram[64 * 64 + i] = (float)(acc / 512.0);
-        }
-        double cc = 0.0;
-        for (int k = 0; k < 512; ++k) cc += lin_bc[k] * lin_bc[k];
-        lin_gram[64 * 64 + 64] = (float)(cc / 512.0);
+        put(dst, I.arena.add(blob_of(hi, lo, with_lo, consts.data(), consts.size())));
     }
-    const double LOG2E = 1.4426950408889634;
-    // softmax inputs: the linear-attention kernels use exp2 on log2(e)-scaled queries/keys; the full-attention
-    // (no_eff) kernels keep keys unscaled and fold log2(e) / sqrt(head_dim) into the queries (scores arrive as exp2 exponents)
-    const bool full = c.no_eff != 0;
-    const double QS = full ? 0.25 * LOG2E : LOG2E, KS = full ? 1.0 : LOG2E;
-    // FiLM: all 3L blocks stacked along the output axis -> one [3L*256][512] GEMM operand; inside a block the
-    // 32-row tiles are interleaved (scale0, shift0, scale1, shift1, ...) so one wave holds matching pairs
-    const int NT = 3 * L * DC_FILM_TILES_PER_BLOCK;
-    s->NT = NT;
-    std::vector<float> film_w((size_t)NT * 32 * DC_E), film_b((size_t)NT * 32), film_b_g1((size_t)NT * 32);
-    for (int i = 0; i < L; ++i) {
-        const std::string p = "temporal_decoder_blocks." + std::to_string(i);
-        DcLayer& y = m.layer[i];
-        DcLayer16& y16 = m.l16[i];
+
+    // a 128 x 128 projection with the LayerNorm `norm` in front of it folded in; its bias as an FT vector (queries) or plain
+    void attn_proj(int i, const bf16x8* DcLayer::*img, const bf16x8* DcLayer16::*img16, const std::string& proj, const std::string& norm,
+                   double scale, bool ft_bias) {
         std::vector<float> wf, cf;
-        const float* sg = P_(p + ".sa_block.norm.weight");
-        const float* sb = P_(p + ".sa_block.norm.bias");
-        fold_ln(P_(p + ".sa_block.query.weight"), P_(p + ".sa_block.query.bias"), sg, sb, D, D, wf, cf, QS);
-        {
-            const std::vector<float> c = ftvec(cf.data(), D, 4);
-            add_image(&y.img_sa_q, wf.data(), D, D, ssp, c.data(), c.size());
-            add_image16(&y16.sa_q, wf.data(), D, D, nullptr, 0, 0, false, cf);
-        }
-        fold_ln(P_(p + ".sa_block.key.weight"), P_(p + ".sa_block.key.bias"), sg, sb, D, D, wf, cf, KS);
-        add_image(&y.img_sa_k, wf.data(), D, D, ssp, cf.data(), cf.size());          // plain bias[128]
-        add_image16(&y16.sa_k, wf.data(), D, D, nullptr, 0, 0, false, cf);
-        fold_ln(P_(p + ".sa_block.value.weight"), P_(p + ".sa_block.value.bias"), sg, sb, D, D, wf, cf);
-        add_image(&y.img_sa_v, wf.data(), D, D, ssp, cf.data(), cf.size());
-        add_image16(&y16.sa_v, wf.data(), D, D, nullptr, 0, 0, false, cf);
-        {
-            const std::vector<float> ws = add_styl(&y.img_sa_o, p + ".sa_block.proj_out");
-            add_image16(&y16.sa_o, ws.data(), D, D, nullptr, 0, 0, false, vec(P_(p + ".sa_block.proj_out.out_layers.2.bias"), D));
-        }
-        fold_ln(P_(p + ".ca_block.query.weight"), P_(p + ".ca_block.query.bias"), P_(p + ".ca_block.norm.weight"),
-                P_(p + ".ca_block.norm.bias"), D, D, wf, cf, QS);
-        {
-            const std::vector<float> c = ftvec(cf.data(), D, 4);
-            add_image(&y.img_ca_q, wf.data(), D, D, ssp, c.data(), c.size());
-            add_image16(&y16.ca_q, wf.data(), D, D, nullptr, 0, 0, false, cf);
-        }
-        // fold text_norm's affine (transformer.py:149,153) into the K/V projections:
-        //   W (g*n + b) + c = (W*g) n + (W b + c)
-        {
-            const float* g = P_(p + ".ca_block.text_norm.weight");
-            const float* bt = P_(p + ".ca_block.text_norm.bias");
-            for (int kv = 0; kv < 2; ++kv) {
-                const std::string nm = p + ".ca_block." + (kv ? "value" : "key");
-                const float* w = P_(nm + ".weight");
-                const float* bb = P_(nm + ".bias");
-                std::vector<float> wf((size_t)D * DC_E), bf(D);
-                const double sc = kv ? 1.0 : KS;         // keys feed exp2 in the partial records
-                for (int o = 0; o < D; ++o) {
-                    double acc = bb[o];
-                    for (int k = 0; k < DC_E; ++k) {
-                        wf[(size_t)o * DC_E + k] = (float)((double)w[(size_t)o * DC_E + k] * g[k] * sc);
-                        acc += (double)w[(size_t)o * DC_E + k] * bt[k];
-                    }
-                    bf[o] = (float)(acc * sc);
-                }
-                add_packed(kv ? &y.ca_wv : &y.ca_wk, wf.data(), D, DC_E, false, false);   // conditioning pre-pass is always split-bf16
-                add_raw(kv ? &y.ca_bv : &y.ca_bk, bf.data(), D);
-                // The same projection composed with `linear` (transformer.py:479-480; 64 -> 512, shared by all layers): with y = W x + b,
-                // n-hat = (y - mean(y)) rstd = rstd (Wc x + bc), Wc / bc = W / b with their mean over the 512 outputs taken off, so
-                //   W' n-hat + b' = rstd (A x + d) + b',   A = W' Wc [128][64],  d = W' bc
-                // - an eighth of the pre-pass GEMM's products (k_cond_ca_partials64), and no [tokens][512] image in between.
-                std::vector<float> af((size_t)D * 64), df(D);
-                for (int o = 0; o < D; ++o) {
-                    double dacc = 0.0;
-                    for (int k = 0; k < DC_E; ++k) dacc += (double)wf[(size_t)o * DC_E + k] * lin_bc[k];
-                    df[o] = (float)dacc;
-                    for (int i = 0; i < 64; ++i) {
-                        double acc = 0.0;
-                        for (int k = 0; k < DC_E; ++k) acc += (double)wf[(size_t)o * DC_E + k] * lin_wc[(size_t)k * 64 + i];
-                        af[(size_t)o * 64 + i] = (float)acc;
-                    }
-                }
-                add_packed(kv ? &y.ca_av : &y.ca_ak, af.data(), D, 64, false, false);
-                add_raw(kv ? &y.ca_dv : &y.ca_dk, df.data(), D);
+        fold_ln(P(proj + ".weight"), P(proj + ".bias"), P(norm + ".weight"), P(norm + ".bias"), DC_D, DC_D, wf, cf, scale);
+        const std::vector<float> cst = ft_bias ? ftvec(cf.data(), DC_D, 4) : cf;
+        add_image(I.layer(i, img), wf.data(), DC_D, DC_D, ssp, cst.data(), cst.size());
+        add_image16(I.l16(i, img16), wf.data(), DC_D, DC_D, nullptr, 0, 0, false, cf);
+    }
+    // a StylizationBlock's output projection
+    void styl_out(int i, const bf16x8* DcLayer::*img, const bf16x8* DcLayer16::*img16, const std::string& p) {
+        const float* b = P(p + ".out_layers.2.bias");
+        const std::vector<float> bo = ftvec(b, DC_D, 4);
+        // the kernels hand over log2(e) * SiLU(.) (silu_l2_pair in dc_kernels.hip): ln 2 goes into the weights
+        const float* w = P(p + ".out_layers.2.weight");
+        std::vector<float> ws((size_t)DC_D * DC_D);
+        for (size_t k = 0; k < ws.size(); ++k) ws[k] = (float)((double)w[k] * 0.6931471805599453);
+        add_image(I.layer(i, img), ws.data(), DC_D, DC_D, ssp, bo.data(), bo.size());
+        add_image16(I.l16(i, img16), ws.data(), DC_D, DC_D, nullptr, 0, 0, false, std::vector<float>(b, b + DC_D));
+    }
+    // Cross-attention key (kv = 0) or value (1) projection of the conditioning pre-pass, text_norm's affine folded in
+    // (transformer.py:149,153), always split-bf16 - and the same projection composed with `linear` (transformer.py:479-480;
+    // 64 -> 512, shared by all layers): with y = W x + b, n-hat = (y - mean(y)) rstd = rstd (Wc x + bc), so
+    //   W' n-hat + b' = rstd (A x + d) + b',   A = W' Wc [128][64],  d = W' bc
+    // - an eighth of the pre-pass GEMM's products (k_cond_ca_partials64), and no [tokens][512] image in between.
+    void cross_kv(int i, int kv, const std::string& ca, const LinearStats& lin) {
+        const std::string nm = ca + (kv ? ".value" : ".key");
+        std::vector<float> wf, bf;
+        fold_ln(P(nm + ".weight"), P(nm + ".bias"), P(ca + ".text_norm.weight"), P(ca + ".text_norm.bias"), DC_D, DC_E, wf, bf,
+                kv ? 1.0 : KS);                        // keys feed exp2 in the partial records
+        add_natural(I.layer(i, kv ? &DcLayer::ca_wv : &DcLayer::ca_wk), wf.data(), DC_D, DC_E, false);
+        add_vec(I.layer(i, kv ? &DcLayer::ca_bv : &DcLayer::ca_bk), bf);
+        std::vector<float> af((size_t)DC_D * 64), df(DC_D);
+        for (int o = 0; o < DC_D; ++o) {
+            double dacc = 0.0;
+            for (int k = 0; k < DC_E; ++k) dacc += (double)wf[(size_t)o * DC_E + k] * lin.bc[k];
+            df[o] = (float)dacc;
+            for (int x = 0; x < 64; ++x) {
+                double acc = 0.0;
+                for (int k = 0; k < DC_E; ++k) acc += (double)wf[(size_t)o * DC_E + k] * lin.wc[(size_t)k * 64 + x];
+                af[(size_t)o * 64 + x] = (float)acc;
             }
         }
-        {
-            const std::vector<float> ws = add_styl(&y.img_ca_o, p + ".ca_block.proj_out");
-            add_image16(&y16.ca_o, ws.data(), D, D, nullptr, 0, 0, false, vec(P_(p + ".ca_block.proj_out.out_layers.2.bias"), D));
-        }
-        add_image(&y.img_ffn_w1, P_(p + ".ffn.linear1.weight"), DC_F, D, ssp, nullptr, 0);
-        {
-            std::vector<float> c = ftvec(P_(p + ".ffn.linear1.bias"), DC_F, 2);       // 64 floats, then b2
-            const std::vector<float> c2 = ftvec(P_(p + ".ffn.linear2.bias"), D, 4);
-            c.insert(c.end(), c2.begin(), c2.end());
-            add_image(&y.img_ffn_w2, P_(p + ".ffn.linear2.weight"), D, DC_F, ssp, c.data(), c.size());
-            std::vector<float> pc = vec(P_(p + ".ffn.linear1.bias"), DC_F);
-            const std::vector<float> pb2 = vec(P_(p + ".ffn.linear2.bias"), D);
-            pc.insert(pc.end(), pb2.begin(), pb2.end());
-            add_image16(&y16.ffn_w, P_(p + ".ffn.linear1.weight"), DC_F, D, P_(p + ".ffn.linear2.weight"), D, DC_F, false, pc);
-        }
-        {
-            const std::vector<float> ws = add_styl(&y.img_ffn_o, p + ".ffn.proj_out");
-            add_image16(&y16.ffn_o, ws.data(), D, D, nullptr, 0, 0, false, vec(P_(p + ".ffn.proj_out.out_layers.2.bias"), D));
-        }
-        const char* blk[3] = {".sa_block.proj_out", ".ca_block.proj_out", ".ffn.proj_out"};
-        for (int j = 0; j < 3; ++j) {
-            const size_t row0 = (size_t)(3 * i + j) * 256;
-            const float* w = P_(p + blk[j] + ".emb_layers.1.weight");   // rows 0..127 scale, 128..255 shift
-            const float* bb = P_(p + blk[j] + ".emb_layers.1.bias");
-            const float* ng = P_(p + blk[j] + ".norm.weight");
-            const float* nb = P_(p + blk[j] + ".norm.bias");
-            // y = LN(h) (1 + scale) + shift with LN = g n + beta (transformer.py:74-78) becomes  y = n G' + H',
-            //   G' = g (1 + scale), H' = beta (1 + scale) + shift, both affine in S = SiLU(emb): fold g / beta into the rows.
-            // The H' tiles additionally carry log2(e): the kernels evaluate SiLU on log2(e)-scaled arguments (silu_l2_pair)
-            // (tile 2t = G' - 1 of features 32t.., tile 2t+1 = H' of the same features, so one wave holds matching pairs)
-            for (int t = 0; t < 4; ++t)
-                for (int f = 0; f < 32; ++f) {
-                    const int o = 32 * t + f;
-                    const float* ws = w + (size_t)o * DC_E;
-                    const float* wh = w + (size_t)(128 + o) * DC_E;
-                    float* dg = &film_w[(row0 + (size_t)(2 * t) * 32 + f) * DC_E];
-                    float* dh = &film_w[(row0 + (size_t)(2 * t + 1) * 32 + f) * DC_E];
-                    for (int k = 0; k < DC_E; ++k) {
-                        dg[k] = (float)((double)ng[o] * ws[k]);
-                        dh[k] = (float)(((double)nb[o] * ws[k] + wh[k]) * LOG2E);
-                    }
-                    film_b[row0 + (size_t)(2 * t) * 32 + f] = (float)((double)ng[o] * (1.0 + bb[o]) - 1.0);
-                    film_b[row0 + (size_t)(2 * t + 1) * 32 + f] = (float)(((double)nb[o] * (1.0 + bb[o]) + bb[128 + o]) * LOG2E);
-                    film_b_g1[row0 + (size_t)(2 * t) * 32 + f] = (float)((double)ng[o] * (1.0 + bb[o]));          // (G' itself: see below)
-                    film_b_g1[row0 + (size_t)(2 * t + 1) * 32 + f] = film_b[row0 + (size_t)(2 * t + 1) * 32 + f];
+        add_natural(I.layer(i, kv ? &DcLayer::ca_av : &DcLayer::ca_ak), af.data(), DC_D, 64, false);
+        add_vec(I.layer(i, kv ? &DcLayer::ca_dv : &DcLayer::ca_dk), df);
+    }
+    void ffn(int i, const std::string& p) {
+        const float *w1 = P(p + ".linear1.weight"), *b1 = P(p + ".linear1.bias"), *w2 = P(p + ".linear2.weight"), *b2 = P(p + ".linear2.bias");
+        add_image(I.layer(i, &DcLayer::img_ffn_w1), w1, DC_F, DC_D, ssp, nullptr, 0);
+        std::vector<float> cst = ftvec(b1, DC_F, 2);       // 64 floats, then b2
+        const std::vector<float> c2 = ftvec(b2, DC_D, 4);
+        cst.insert(cst.end(), c2.begin(), c2.end());
+        add_image(I.layer(i, &DcLayer::img_ffn_w2), w2, DC_D, DC_F, ssp, cst.data(), cst.size());
+        std::vector<float> plain(b1, b1 + DC_F);
+        plain.insert(plain.end(), b2, b2 + DC_D);
+        add_image16(I.l16(i, &DcLayer16::ffn_w), w1, DC_F, DC_D, w2, DC_D, DC_F, false, plain);
+    }
+    // Rows of the FiLM stack for StylizationBlock `blk` (0 .. 3L-1).  All blocks are stacked along the output axis -> one
+    // [3L*256][512] GEMM operand; inside a block the 32-row tiles are interleaved (tile 2t = G' - 1 of features 32t.., tile
+    // 2t+1 = H' of the same features) so one wave holds matching pairs.
+    // y = LN(h) (1 + scale) + shift with LN = g n + beta (transformer.py:74-78) becomes  y = n G' + H',
+    //   G' = g (1 + scale), H' = beta (1 + scale) + shift, both affine in S = SiLU(emb): fold g / beta into the rows.
+    // The H' tiles additionally carry log2(e): the kernels evaluate SiLU on log2(e)-scaled arguments (silu_l2_pair)
+    void film_rows(int blk, const std::string& p) {
+        const size_t row0 = (size_t)blk * 256;
+        const float* w = P(p + ".emb_layers.1.weight");   // rows 0..127 scale, 128..255 shift
+        const float* bb = P(p + ".emb_layers.1.bias");
+        const float* ng = P(p + ".norm.weight");
+        const float* nb = P(p + ".norm.bias");
+        for (int t = 0; t < 4; ++t)
+            for (int f = 0; f < 32; ++f) {
+                const int o = 32 * t + f;
+                const size_t rg = row0 + (size_t)(2 * t) * 32 + f, rh = rg + 32;
+                const float* ws = w + (size_t)o * DC_E;
+                const float* wh = w + (size_t)(128 + o) * DC_E;
+                float* dg = &film_w[rg * DC_E];
+                float* dh = &film_w[rh * DC_E];
+                for (int k = 0; k < DC_E; ++k) {
+                    dg[k] = (float)((double)ng[o] * ws[k]);
+                    dh[k] = (float)(((double)nb[o] * ws[k] + wh[k]) * LOG2E);
                 }
-        }
+                film_b[rg] = (float)((double)ng[o] * (1.0 + bb[o]) - 1.0);
+                film_b[rh] = (float)(((double)nb[o] * (1.0 + bb[o]) + bb[128 + o]) * LOG2E);
+                film_b_g1[rg] = (float)((double)ng[o] * (1.0 + bb[o]));          // (G' itself: film_stack)
+                film_b_g1[rh] = film_b[rh];
+            }
     }
-    add_packed(&m.film_w, film_w.data(), NT * 32, DC_E, false, s->film_fmt == 1);
-    add_ft(&m.film_b, film_b.data(), NT * 32, NT);
-    // ... and with the scale tiles holding G' itself: the plain-operand layer kernels then form n-hat G' + H' in ONE mixed-precision FMA
-    // instead of two (-192 vector instructions per wave and layer).  fp16 keeps 11 bits of a number near 1 there instead of 11 bits of
-    // its small part - affordable where the loop's last evaluations run on split operands and G' - 1 tiles (precise tail, dc_ddim.h)
-    add_ft(&m.film_b_g1, film_b_g1.data(), NT * 32, NT);
-    {   // 16x16x32 operand order (dc_common.h)
-        static const int pi[16] = {0, 1, 2, 3, 8, 9, 10, 11, 4, 5, 6, 7, 12, 13, 14, 15};
-        const bool f16 = s->film_fmt == 1;
-        std::vector<uint16_t> w16((size_t)NT * 32 * DC_E);
-        std::vector<float> b16((size_t)NT * 32);
-        for (int ot = 0; ot < NT; ++ot)
-            for (int ks = 0; ks < DC_E / 32; ++ks)
-                for (int fb = 0; fb < 2; ++fb)
-                    for (int l = 0; l < 64; ++l)
-                        for (int j = 0; j < 8; ++j) {
-                            const float v = film_w[(size_t)(32 * ot + 16 * fb + pi[l & 15]) * DC_E + 32 * ks + 8 * (l >> 4) + j];
-                            w16[((((size_t)ot * (DC_E / 32) + ks) * 2 + fb) * 64 + l) * 8 + j] = f16 ? f2h(v) : f2bf(v);
-                        }
-        for (int ot = 0; ot < NT; ++ot)
-            for (int fb = 0; fb < 2; ++fb)
-                for (int r = 0; r < 16; ++r) b16[((size_t)ot * 2 + fb) * 16 + r] = film_b[(size_t)32 * ot + 16 * fb + pi[r]];
-        O.fix.push_back({(const void**)&m.film_w16, A.add(w16.data(), w16.size() * 2)});
-        add_raw(&m.film_b16, b16.data(), b16.size());
-        m.film_w16_tail = nullptr;
-        if (want_twins && c.precision == DC_PREC_BF16) {
-            // bf16 precision: the evaluations of the precise tail run the "mixed" form - split-bf16 128-wide GEMMs AND an f16 FiLM GEMM
-            // (8 mantissa bits on the K = 512 operands were the tail's floor: 3.6 - 4.1e-4 with every evaluation split)
-            for (size_t i = 0; i < w16.size(); ++i) w16[i] = 0;
-            for (int ot = 0; ot < NT; ++ot)
-                for (int ks = 0; ks < DC_E / 32; ++ks)
-                    for (int fb = 0; fb < 2; ++fb)
-                        for (int l = 0; l < 64; ++l)
-                            for (int j = 0; j < 8; ++j) {
-                                const float v = film_w[(size_t)(32 * ot + 16 * fb + pi[l & 15]) * DC_E + 32 * ks + 8 * (l >> 4) + j];
-                                w16[((((size_t)ot * (DC_E / 32) + ks) * 2 + fb) * 64 + l) * 8 + j] = f2h(v);
-                            }
-            O.fix.push_back({(const void**)&m.film_w16_tail, A.add(w16.data(), w16.size() * 2)});
-        }
-        for (int ot = 0; ot < NT; ++ot)
-            for (int fb = 0; fb < 2; ++fb)
-                for (int r = 0; r < 16; ++r) b16[((size_t)ot * 2 + fb) * 16 + r] = film_b_g1[(size_t)32 * ot + 16 * fb + pi[r]];
-        add_raw(&m.film_b16_g1, b16.data(), b16.size());
+    void decoder_layer(int i, const LinearStats& lin) {
+        const std::string p = "temporal_decoder_blocks." + std::to_string(i);
+        const std::string sa = p + ".sa_block", ca = p + ".ca_block";
+        attn_proj(i, &DcLayer::img_sa_q, &DcLayer16::sa_q, sa + ".query", sa + ".norm", QS, true);
+        attn_proj(i, &DcLayer::img_sa_k, &DcLayer16::sa_k, sa + ".key", sa + ".norm", KS, false);
+        attn_proj(i, &DcLayer::img_sa_v, &DcLayer16::sa_v, sa + ".value", sa + ".norm", 1.0, false);
+        styl_out(i, &DcLayer::img_sa_o, &DcLayer16::sa_o, sa + ".proj_out");
+        attn_proj(i, &DcLayer::img_ca_q, &DcLayer16::ca_q, ca + ".query", ca + ".norm", QS, true);
+        for (int kv = 0; kv < 2; ++kv) cross_kv(i, kv, ca, lin);
+        styl_out(i, &DcLayer::img_ca_o, &DcLayer16::ca_o, ca + ".proj_out");
+        ffn(i, p + ".ffn");
+        styl_out(i, &DcLayer::img_ffn_o, &DcLayer16::ffn_o, p + ".ffn.proj_out");
+        film_rows(3 * i + 0, sa + ".proj_out");
+        film_rows(3 * i + 1, ca + ".proj_out");
+        film_rows(3 * i + 2, p + ".ffn.proj_out");
     }
-    {   // the two pose projections always run split: [hi][lo][bias]
-        const std::vector<float> jb = ftvec(P_("joint_embed.bias"), D, 4);
-        add_image(&m.img_je, P_("joint_embed.weight"), D, P, true, jb.data(), jb.size());
-        const std::vector<float> ob = ftvec(P_("out.bias"), P, 1);
-        add_image(&m.img_out, P_("out.weight"), P, D, true, ob.data(), ob.size());
+    void film_stack() {
+        const int NT = I.NT;
+        const bool f16 = fmt.film_fmt == 1;
+        add_natural(I.top(&DcModel::film_w), film_w.data(), NT * 32, DC_E, f16);
+        add_vec(I.top(&DcModel::film_b), ftvec(film_b.data(), NT * 32, NT));
+        // ... and with the scale tiles holding G' itself: the plain-operand layer kernels then form n-hat G' + H' in ONE mixed-precision FMA
+        // instead of two (-192 vector instructions per wave and layer).  fp16 keeps 11 bits of a number near 1 there instead of 11 bits of
+        // its small part - affordable where the loop's last evaluations run on split operands and G' - 1 tiles (precise tail, dc_ddim.h)
+        add_vec(I.top(&DcModel::film_b_g1), ftvec(film_b_g1.data(), NT * 32, NT));
+        // 16x16x32 operand order (dc_common.h)
+        put(I.top(&DcModel::film_w16), I.arena.add(pack_film16(film_w, NT, DC_E, f16)));
+        add_vec(I.top(&DcModel::film_b16), permute_film_bias16(film_b, NT));
+        // bf16 precision: the evaluations of the precise tail run the "mixed" form - split-bf16 128-wide GEMMs AND an f16 FiLM GEMM
+        // (8 mantissa bits on the K = 512 operands were the tail's floor: 3.6 - 4.1e-4 with every evaluation split)
+        if (want_twins && c.precision == DC_PREC_BF16) put(I.top(&DcModel::film_w16_tail), I.arena.add(pack_film16(film_w, NT, DC_E, true)));
+        add_vec(I.top(&DcModel::film_b16_g1), permute_film_bias16(film_b_g1, NT));
+    }
+    void pose_projections() {   // the two pose projections always run split: [hi][lo][bias]
+        const int P_ = c.input_feats;
+        const std::vector<float> jb = ftvec(P("joint_embed.bias"), DC_D, 4);
+        add_image(I.top(&DcModel::img_je), P("joint_embed.weight"), DC_D, P_, true, jb.data(), jb.size());
+        const std::vector<float> ob = ftvec(P("out.bias"), P_, 1);
+        add_image(I.top(&DcModel::img_out), P("out.weight"), P_, DC_D, true, ob.data(), ob.size());
         std::vector<float> ob16(32, 0.f);
-        for (int i = 0; i < P; ++i) ob16[i] = P_("out.bias")[i];
-        add_image16(&m.out16, P_("out.weight"), P, D, nullptr, 0, 0, true, ob16);
+        for (int k = 0; k < P_; ++k) ob16[k] = P("out.bias")[k];
+        add_image16(I.top(&DcModel::out16), P("out.weight"), P_, DC_D, nullptr, 0, 0, true, ob16);
     }
-    add_raw(&m.seq_emb, P_("sequence_embedding"), (size_t)c.num_frames * D);
-    {
-        const float* w = P_("linear.weight");   // [512][64] -> transposed [64][512]
+    void conditioning_front(const LinearStats& lin) {
+        const float* w = P("linear.weight");   // [512][64] -> transposed [64][512]
         std::vector<float> wt((size_t)64 * 512);
         for (int k = 0; k < 512; ++k)
-            for (int i = 0; i < 64; ++i) wt[(size_t)i * 512 + k] = w[(size_t)k * 64 + i];
-        add_raw(&m.lin_wt, wt.data(), wt.size());
-        add_raw(&m.lin_b, P_("linear.bias"), 512);
-        add_raw(&m.lin_gram, lin_gram.data(), lin_gram.size());
-        add_packed(&m.lin_pack, w, 512, 64, false, false);
+            for (int x = 0; x < 64; ++x) wt[(size_t)x * 512 + k] = w[(size_t)k * 64 + x];
+        add_vec(I.top(&DcModel::lin_wt), wt);
+        add_vec(I.top(&DcModel::lin_b), P("linear.bias"), 512);
+        add_vec(I.top(&DcModel::lin_gram), lin.gram);
+        add_natural(I.top(&DcModel::lin_pack), w, 512, 64, false);
     }
-    // timestep table storage + MLP operands (transposed for coalesced reads)
-    const int nt = c.max_timesteps;
-    std::vector<float> zeros((size_t)nt * 512, 0.f);
-    add_raw(&m.temb, zeros.data(), zeros.size());
-    const float *d_freqs = nullptr, *d_w0t = nullptr, *d_b0 = nullptr, *d_w2t = nullptr, *d_b2 = nullptr;
-    {
+    // timestep table storage (filled by dc_launch_temb_table after the upload) + the MLP's operands, transposed for coalesced reads
+    void time_embedding() {
+        add_vec(I.top(&DcModel::temb), std::vector<float>((size_t)c.max_timesteps * 512, 0.f));
         std::vector<float> fr(64);
         for (int k = 0; k < 64; ++k) fr[k] = expf((float)(-std::log(10000.0)) * (float)k / 64.f);   // transformer.py:18-20 in fp32
         std::vector<float> w0t((size_t)128 * 512), w2t((size_t)512 * 512);
-        const float* w0 = P_("time_embed.0.weight");
-        const float* w2 = P_("time_embed.2.weight");
+        const float* w0 = P("time_embed.0.weight");
+        const float* w2 = P("time_embed.2.weight");
         for (int o = 0; o < 512; ++o) {
-            for (int i = 0; i < 128; ++i) w0t[(size_t)i * 512 + o] = w0[(size_t)o * 128 + i];
-            for (int i = 0; i < 512; ++i) w2t[(size_t)i * 512 + o] = w2[(size_t)o * 512 + i];
+            for (int x = 0; x < 128; ++x) w0t[(size_t)x * 512 + o] = w0[(size_t)o * 128 + x];
+            for (int x = 0; x < 512; ++x) w2t[(size_t)x * 512 + o] = w2[(size_t)o * 512 + x];
         }
-        add_raw(&d_freqs, fr.data(), 64);
-        add_raw(&d_w0t, w0t.data(), w0t.size());
-        add_raw(&d_b0, P_("time_embed.0.bias"), 512);
-        add_raw(&d_w2t, w2t.data(), w2t.size());
-        add_raw(&d_b2, P_("time_embed.2.bias"), 512);
+        I.freqs = I.arena.add(fr);
+        I.w0t = I.arena.add(w0t);
+        I.b0 = I.arena.add(P("time_embed.0.bias"), 512 * 4);
+        I.w2t = I.arena.add(w2t);
+        I.b2 = I.arena.add(P("time_embed.2.bias"), 512 * 4);
     }
-    m.num_layers = L;
-    m.input_feats = P;
-    m.num_frames = c.num_frames;
-    m.max_timesteps = nt;
+};
 
-    if (s->host_only) {          // sanitizer build without a device: the arena stays on the host, the model's pointers point into it
+// Folds and packs the parameters (all of required_params present) into `I`.  Reads nothing but its arguments; runs on any host.
+void pack_model(const dc_config& c, const Formats& fmt, const DcParams& params, ModelImage& I) {
+    const int L = c.num_layers;
+    I.NT = 3 * L * DC_FILM_TILES_PER_BLOCK;
+    I.model.num_layers = L;
+    I.model.input_feats = c.input_feats;
+    I.model.num_frames = c.num_frames;
+    I.model.max_timesteps = c.max_timesteps;
+    I.split = I.model;
+    ModelPacker k{c, fmt, params, I};
+    const LinearStats lin = centre_linear(k.P("linear.weight"), k.P("linear.bias"));
+    for (int i = 0; i < L; ++i) k.decoder_layer(i, lin);
+    k.film_stack();
+    k.pose_projections();
+    k.add_vec(I.top(&DcModel::seq_emb), k.P("sequence_embedding"), (size_t)c.num_frames * DC_D);
+    k.conditioning_front(lin);
+    k.time_embedding();
+}
+
+// The impure half: the image goes to the device (host-only samplers: to malloc'ed memory), the pointers of both model records
+// are resolved against its address, and the time-embedding table is computed in place.
+int upload_model(dc_sampler* s, ModelImage& I) {
+    const std::vector<uint8_t>& host = I.arena.host;
+    s->NT = I.NT;
+    s->arena_bytes = host.size();
+    if (s->host_only) {
         free(s->d_arena);
-        s->arena_bytes = A.host.size();
-        s->d_arena = (uint8_t*)malloc(s->arena_bytes);
-        memcpy(s->d_arena, A.host.data(), s->arena_bytes);
-        for (auto& f : O.fix) *f.first = s->d_arena + f.second;
-        s->h_model_split = m;
-        for (auto& tw : twins) *(const void**)((char*)&s->h_model_split + tw.first) = s->d_arena + tw.second;
-        return DC_OK;
+        s->d_arena = (uint8_t*)malloc(host.size());
+        memcpy(s->d_arena, host.data(), host.size());
+    } else {
+        if (s->d_arena) hipFree(s->d_arena);
+        HIP_TRY(hipMalloc((void**)&s->d_arena, host.size()));
+        HIP_TRY(hipMemcpy(s->d_arena, host.data(), host.size(), hipMemcpyHostToDevice));
     }
-    if (s->d_arena) hipFree(s->d_arena);
-    s->arena_bytes = A.host.size();
-    HIP_TRY(hipMalloc((void**)&s->d_arena, s->arena_bytes));
-    HIP_TRY(hipMemcpy(s->d_arena, A.host.data(), s->arena_bytes, hipMemcpyHostToDevice));
-    for (auto& f : O.fix) *f.first = s->d_arena + f.second;
+    I.arena.resolve(s->d_arena);
+    s->h_model = I.model;
+    s->h_model_split = I.split;
+    if (s->host_only) return DC_OK;
     if (!s->d_model) HIP_TRY(hipMalloc((void**)&s->d_model, sizeof(DcModel)));
-    HIP_TRY(hipMemcpy(s->d_model, &m, sizeof(DcModel), hipMemcpyHostToDevice));
-    s->h_model_split = m;
-    for (auto& tw : twins) *(const void**)((char*)&s->h_model_split + tw.first) = s->d_arena + tw.second;
+    HIP_TRY(hipMemcpy(s->d_model, &s->h_model, sizeof(DcModel), hipMemcpyHostToDevice));
     if (!s->d_model_split) HIP_TRY(hipMalloc((void**)&s->d_model_split, sizeof(DcModel)));
     HIP_TRY(hipMemcpy(s->d_model_split, &s->h_model_split, sizeof(DcModel), hipMemcpyHostToDevice));
-    HIP_TRY(dc_launch_temb_table(s->stream, d_freqs, d_w0t, d_b0, d_w2t, d_b2, (float*)m.temb, nt));
+    const auto op = [&](size_t off) { return (const float*)(s->d_arena + off); };
+    HIP_TRY(dc_launch_temb_table(s->stream, op(I.freqs), op(I.w0t), op(I.b0), op(I.w2t), op(I.b2), (float*)s->h_model.temb, s->cfg.max_timesteps));
     HIP_TRY(hipStreamSynchronize(s->stream));
     return DC_OK;
 }
@@ -1364,16 +1253,13 @@ int dc_sampler_create(const dc_config* cfg, dc_sampler** out) {
 #ifdef DC_HOST_SANITIZE
     // Sanitizer build of the HOST half (address + undefined-behaviour sanitizers on the CPU; GPU sanitizers are not available on this
     // pool): without a device the sampler is created "host only" - parameter store, validation, weight folding and packing into the
-    // arena run as in production, nothing is uploaded or launched, and every entry point that needs the device fails with NO_DEVICE.
+    // arena (pack_model; the music encoder's music_pack too) run as in production, nothing is uploaded or launched, and every entry point that needs the device fails with NO_DEVICE.
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) {
         dc_sampler* h = new dc_sampler();
         h->cfg = *cfg;
         h->host_only = true;
         h->num_cu = 256;
-        h->split_small = cfg->precision == DC_PREC_MIXED || cfg->precision == DC_PREC_BF16X3;
-        h->split_film = cfg->precision == DC_PREC_BF16X3;
-        h->small_fmt = cfg->precision == DC_PREC_FP16 ? 1 : 0;
-        h->film_fmt = (cfg->precision == DC_PREC_FP16 || cfg->precision == DC_PREC_MIXED) ? 1 : 0;
+        h->set_precision(cfg->precision);
         *out = h;
         return DC_OK;
     }
@@ -1388,10 +1274,7 @@ int dc_sampler_create(const dc_config* cfg, dc_sampler** out) {
     dc_sampler* s = new dc_sampler();
     s->cfg = *cfg;
     s->num_cu = prop.multiProcessorCount;
-    s->split_small = cfg->precision == DC_PREC_MIXED || cfg->precision == DC_PREC_BF16X3;
-    s->split_film = cfg->precision == DC_PREC_BF16X3;
-    s->small_fmt = cfg->precision == DC_PREC_FP16 ? 1 : 0;
-    s->film_fmt = (cfg->precision == DC_PREC_FP16 || cfg->precision == DC_PREC_MIXED) ? 1 : 0;
+    s->set_precision(cfg->precision);
     if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreateWithFlags(&s->ev_in, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&s->ev_out, hipEventDisableTiming) != hipSuccess) {
@@ -1455,12 +1338,11 @@ int dc_sampler_finalize_params(dc_sampler* s) {
     if (!s->host_only) HIP_TRY(hipSetDevice(s->cfg.device));
     drop_graph(s);
     s->cap_G = 0;   // NT may have changed: force workspace rebuild
-    int rc = build_model(s);
-    if (rc) return rc;
-    if (s->host_only) {          // (the music encoder's weights are folded straight into device memory: not built without one)
-        s->finalized = true;
-        s->cond_set = false;
-        return DC_OK;
+    {
+        ModelImage image;
+        pack_model(s->cfg, *s, s->params, image);
+        const int rc = upload_model(s, image);
+        if (rc) return rc;
     }
     if (s->music) {
         dc_music_destroy(s->music);
@@ -1470,10 +1352,15 @@ int dc_sampler_finalize_params(dc_sampler* s) {
     for (const auto& kv : s->params) any_music = any_music || music_param(kv.first);
     if (any_music) {
         std::string err;
-        s->music = dc_music_build(s->params, DC_C, &err);
-        if (!s->music) return fail(DC_ERR_PARAM, "music encoder: %s", err.c_str());
-        // one fp16 plane where the denoiser rounds the features to 16-bit operands anyway, split planes for the split-operand precisions
-        dc_music_set_format(s->music, s->me_format >= 0 ? s->me_format : (s->split_small ? DC_ME_SPLIT : DC_ME_FP16));
+        if (s->host_only) {      // (no device to build the encoder on: its BatchNorm folding and packing run all the same, for the sanitizers)
+            if (!dc_music_check(s->params, DC_C, &err)) return fail(DC_ERR_PARAM, "music encoder: %s", err.c_str());
+            music_pack(s->params);
+        } else {
+            s->music = dc_music_build(s->params, DC_C, &err);
+            if (!s->music) return fail(DC_ERR_PARAM, "music encoder: %s", err.c_str());
+            // one fp16 plane where the denoiser rounds the features to 16-bit operands anyway, split planes for the split-operand precisions
+            dc_music_set_format(s->music, s->me_format >= 0 ? s->me_format : (s->split_small ? DC_ME_SPLIT : DC_ME_FP16));
+        }
     }
     s->finalized = true;
     s->cond_set = false;

@@ -376,7 +376,7 @@ __global__ __launch_bounds__(512, 1) void k_cond_pp64(const float* __restrict__ 
 
 // The same records from the 64 music features themselves (round 5).  `linear` (64 -> 512) is shared by all layers and the
 // LayerNorm behind it is affine in its input up to the per-token 1 / std, so
-//   K = W' n-hat + b' = rstd (A x + d) + b',   A = W' Wc [128][64], d = W' bc        (host: dc_api.hip, build_model)
+//   K = W' n-hat + b' = rstd (A x + d) + b',   A = W' Wc [128][64], d = W' bc        (host: dc_api.hip, cross_kv)
 // - 4 k-steps of 16 per layer instead of 32, no [tokens][512] image written and read back: the pre-pass GEMM does an eighth of the
 // products.  rstd comes from k_cond_rstd: the variance of linear(x) over its 512 outputs as a quadratic form of x,
 //   var = x^T Gc x + 2 gv^T x + c      (Gc = Wc^T Wc / 512 is positive semi-definite: no cancellation beyond the sum's own)
@@ -645,7 +645,7 @@ __global__ void k_silu_emb(const float* __restrict__ pp /*frag-major fp32*/, con
 
 // ------------------------------------------------------------------------------------
 // FiLM GEMM: all 3*L StylizationBlocks at once (StylizationBlock.emb_layers + norm, transformer.py:57-60,74-78).
-// The host folds the block's LayerNorm affine and the emb_layers bias into the operands (dc_api.hip build_model), so the
+// The host folds the block's LayerNorm affine and the emb_layers bias into the operands (dc_api.hip film_rows), so the
 // GEMM yields the modulation tiles directly: G'-1 = g*(1+scale)-1 and H' = beta*(1+scale)+shift, stored as fp16 FT
 // tiles (the "-1" keeps the fp16 rounding on the small modulation, not on the ~1 multiplier),
 // E[g][blk][G'0..3, H'0..3][64][16].  The weight image interleaves each block's tiles as

@@ -3,19 +3,22 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <map>
 #include <string>
+#include <utility>
 #include <vector>
+
+#include "dc_pack.h"   // DcParams; music_pack: the encoder's folding and packing, host only
 
 struct dc_music;   // device-resident folded weights + ping-pong activation planes
 
-// Builds the encoder from reference state_dict entries (`music_encoder.*`, `proj.*`); returns nullptr and sets
-// *err when a key is missing or has the wrong size.  BatchNorm (eval mode, running statistics) is folded into the
-// convolution in front of it.
-dc_music* dc_music_build(const std::map<std::string, std::vector<float>>& params, int music_dim, std::string* err);
-void dc_music_destroy(dc_music* m);
-// names/sizes of the entries dc_music_build consumes
+// names/sizes of the reference state_dict entries the encoder consumes (`music_encoder.*`, `proj.*`)
 std::vector<std::pair<std::string, size_t>> dc_music_required(int music_dim);
+// false, with *err set, when one of them is missing or has the wrong size
+bool dc_music_check(const DcParams& params, int music_dim, std::string* err);
+// Builds the encoder on the current device: dc_music_check, music_pack (BatchNorm in eval mode, running statistics, is folded
+// into the convolution in front of it), upload.  Returns nullptr and sets *err on failure.
+dc_music* dc_music_build(const DcParams& params, int music_dim, std::string* err);
+void dc_music_destroy(dc_music* m);
 
 // mel [B][Tm][128] fp32 (device) -> xf_out [B][T][64], xf_proj [B][T][64] fp32 (device), T = (Tm - 1) / 3 + 1.
 // Work is enqueued on `st`; clips are processed in chunks so the activation planes stay bounded.

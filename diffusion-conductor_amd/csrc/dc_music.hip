@@ -22,6 +22,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <type_traits>
 
 #include "dc_common.h"
 
@@ -872,61 +873,6 @@ __global__ __launch_bounds__(256) void k_me_proj(const float* __restrict__ xf, c
 }
 
 // ---- host side ------------------------------------------------------------------------------------------
-inline uint16_t f2bf(float f) {
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-inline float bf2f(uint16_t h) {
-    uint32_t u = (uint32_t)h << 16;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
-inline int tile_row(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
-inline uint16_t f2h(float f) {   // fp32 -> fp16 bits, round to nearest even (the compiler's conversion)
-    const _Float16 h = (_Float16)f;
-    uint16_t u;
-    memcpy(&u, &h, 2);
-    return u;
-}
-inline float h2f(uint16_t u) {
-    _Float16 h;
-    memcpy(&h, &u, 2);
-    return (float)h;
-}
-
-// natural-k A fragments of Wm [n_out][k_in] (row-major): frag (ot, ks), lane (i = l & 31, hh = l >> 5), element j
-//   = Wm[32 ot + i][16 ks + 8 hh + j]; order [hi: ot][ks] then [lo: ot][ks]; fmt 0: bf16 hi + lo, 1: fp16 hi only, 2: fp16 hi + lo
-std::vector<uint16_t> pack_nat(const std::vector<float>& Wm, int n_out, int k_in, int OT, int KS, int fmt = 0) {
-    const size_t ne = (size_t)OT * KS * 512;
-    std::vector<uint16_t> out((fmt == 1 ? 1 : 2) * ne, 0);
-    for (int ot = 0; ot < OT; ++ot)
-        for (int ks = 0; ks < KS; ++ks)
-            for (int l = 0; l < 64; ++l)
-                for (int j = 0; j < 8; ++j) {
-                    const int row = 32 * ot + (l & 31), col = 16 * ks + 8 * (l >> 5) + j;
-                    const float v = (row < n_out && col < k_in) ? Wm[(size_t)row * k_in + col] : 0.f;
-                    const size_t o = (((size_t)ot * KS + ks) * 64 + l) * 8 + j;
-                    const uint16_t h = fmt ? f2h(v) : f2bf(v);
-                    out[o] = h;
-                    if (fmt != 1) out[ne + o] = fmt ? f2h(v - h2f(h)) : f2bf(v - bf2f(h));
-                }
-    return out;
-}
-std::vector<float> ftvec(const std::vector<float>& v, int NT) {
-    std::vector<float> out((size_t)NT * 32, 0.f);
-    for (int t = 0; t < NT; ++t)
-        for (int hh = 0; hh < 2; ++hh)
-            for (int r = 0; r < 16; ++r) {
-                const int f = 32 * t + tile_row(r, hh);
-                out[(t * 2 + hh) * 16 + r] = f < (int)v.size() ? v[f] : 0.f;
-            }
-    return out;
-}
-
 struct ConvDev {
     const bf16x8* w = nullptr;            // split planes: bf16 hi + lo fragments
     const f16x8* w16 = nullptr;           // single plane: fp16 fragments (conv1.1 ... conv3.1)
@@ -952,24 +898,10 @@ struct dc_music {
     int format = 0;                       // 0: split bf16 planes, 1: one fp16 plane (dc_music_set_format)
 };
 
-namespace {
-
-struct ConvSpec {
-    const char* name;
-    int cin, cout;
-    bool res_conv;
-};
-const ConvSpec kConvs[7] = {{"conv1.0", 1, 16, false},  {"conv1.1", 16, 16, false}, {"conv1.2", 16, 16, false},
-                            {"conv2.0", 16, 32, true},  {"conv2.1", 32, 32, false}, {"conv3.0", 32, 32, false},
-                            {"conv3.1", 32, 32, false}};
-constexpr float kBnEps = 1e-5f;   // nn.BatchNorm default
-
-}  // namespace
-
 std::vector<std::pair<std::string, size_t>> dc_music_required(int music_dim) {
     std::vector<std::pair<std::string, size_t>> r;
     const std::string me = "music_encoder.";
-    for (const ConvSpec& c : kConvs) {
+    for (const MusicConvSpec& c : kMusicConvs) {
         const std::string p = me + c.name;
         r.push_back({p + ".conv2d_layer.0.weight", (size_t)c.cout * c.cin * 9});
         r.push_back({p + ".conv2d_layer.0.bias", (size_t)c.cout});
@@ -988,142 +920,30 @@ std::vector<std::pair<std::string, size_t>> dc_music_required(int music_dim) {
     return r;
 }
 
-dc_music* dc_music_build(const std::map<std::string, std::vector<float>>& params, int music_dim, std::string* err) {
+bool dc_music_check(const DcParams& params, int music_dim, std::string* err) {
     if (music_dim != DC_C) {
         *err = "music encoder kernels are built for 64 output channels";
-        return nullptr;
+        return false;
     }
     for (const auto& rq : dc_music_required(music_dim)) {
         auto it = params.find(rq.first);
         if (it == params.end()) {
             *err = "missing parameter '" + rq.first + "'";
-            return nullptr;
+            return false;
         }
         if (it->second.size() != rq.second) {
             *err = "parameter '" + rq.first + "' has the wrong size";
-            return nullptr;
+            return false;
         }
     }
-    auto P = [&](const std::string& n) -> const std::vector<float>& { return params.find(n)->second; };
-    std::vector<uint8_t> host;
-    auto add = [&](const void* p, size_t bytes) {
-        const size_t off = (host.size() + 255) & ~(size_t)255;
-        host.resize(off + bytes);
-        memcpy(host.data() + off, p, bytes);
-        return off;
-    };
-    // eval-mode BatchNorm folded into the convolution in front of it: s = gamma / sqrt(var + eps)
-    auto bn_fold = [&](const std::string& bn, const std::vector<float>& cb, std::vector<float>& scale, std::vector<float>& bias) {
-        const auto &g = P(bn + ".weight"), &be = P(bn + ".bias"), &mu = P(bn + ".running_mean"), &var = P(bn + ".running_var");
-        const size_t n = g.size();
-        scale.resize(n);
-        bias.resize(n);
-        for (size_t c = 0; c < n; ++c) {
-            scale[c] = g[c] / std::sqrt(var[c] + kBnEps);
-            bias[c] = (cb[c] - mu[c]) * scale[c] + be[c];
-        }
-    };
-    struct Off {
-        size_t w, w16, bias, rbias;
-    } off[7];
-    // v_mfma_f32_16x16x32 A fragments of the fused conv1 kernel: lane (co = l & 15, q4 = l >> 4), element j
-    std::vector<uint16_t> stem_hi[3], stem_lo[3], stem_16;
-    std::vector<float> stem_bias, stem_wa32;
-    auto stem_pack = [&](int layer, const std::vector<float>& Wm, int K, int cin) {
-        const int nks = cin == 1 ? 1 : 5;
-        stem_hi[layer].assign((size_t)nks * 512, 0);
-        stem_lo[layer].assign((size_t)nks * 512, 0);
-        for (int ks = 0; ks < nks; ++ks)
-            for (int l = 0; l < 64; ++l)
-                for (int j = 0; j < 8; ++j) {
-                    const int co = l & 15, q4 = l >> 4;
-                    float v = 0.f;
-                    if (cin == 1) {
-                        const int k = 8 * q4 + j;
-                        if (k < 9) v = Wm[(size_t)co * K + k];
-                    } else {
-                        const int tap = 2 * ks + (q4 >> 1), ci = 8 * (q4 & 1) + j;
-                        if (tap < 9) v = Wm[(size_t)co * K + tap * 16 + ci];
-                    }
-                    const uint16_t h = f2bf(v);
-                    stem_hi[layer][((size_t)ks * 64 + l) * 8 + j] = h;
-                    stem_lo[layer][((size_t)ks * 64 + l) * 8 + j] = f2bf(v - bf2f(h));
-                    if (cin != 1) stem_16.push_back(f2h(v));          // (layers 1, 2 in order: [layer][ks][lane][j])
-                }
-    };
-    const std::string me = "music_encoder.";
-    for (int i = 0; i < 7; ++i) {
-        const ConvSpec& c = kConvs[i];
-        const std::string p = me + c.name;
-        std::vector<float> sc, bi;
-        bn_fold(p + ".conv2d_layer.1", P(p + ".conv2d_layer.0.bias"), sc, bi);
-        const auto& w = P(p + ".conv2d_layer.0.weight");                 // [cout][cin][3][3]
-        const int K = c.cin >= 16 ? 9 * c.cin : 16, KS = K / 16;
-        std::vector<float> Wm((size_t)c.cout * K, 0.f);
-        for (int co = 0; co < c.cout; ++co)
-            for (int ci = 0; ci < c.cin; ++ci)
-                for (int tap = 0; tap < 9; ++tap)
-                    Wm[(size_t)co * K + tap * c.cin + ci] = w[((size_t)co * c.cin + ci) * 9 + tap] * sc[co];
-        std::vector<uint16_t> frags = pack_nat(Wm, c.cout, K, 1, KS);
-        std::vector<uint16_t> frags16 = pack_nat(Wm, c.cout, K, 1, KS, 1);
-        if (i == 0) {
-            stem_wa32.resize(16 * 9);
-            for (int co = 0; co < 16; ++co)
-                for (int tap = 0; tap < 9; ++tap) stem_wa32[co * 9 + tap] = Wm[(size_t)co * K + tap];
-        }
-        if (i < 3) {
-            stem_pack(i, Wm, K, c.cin);
-            stem_bias.insert(stem_bias.end(), bi.begin(), bi.end());
-        }
-        off[i].rbias = (size_t)-1;
-        std::vector<float> rb_ft;
-        if (c.res_conv) {
-            std::vector<float> rs, rb;
-            bn_fold(p + ".residual.1", P(p + ".residual.0.bias"), rs, rb);
-            const auto& rw = P(p + ".residual.0.weight");                // [cout][cin][1][1]
-            std::vector<float> Rm((size_t)c.cout * c.cin);
-            for (int co = 0; co < c.cout; ++co)
-                for (int ci = 0; ci < c.cin; ++ci) Rm[(size_t)co * c.cin + ci] = rw[(size_t)co * c.cin + ci] * rs[co];
-            const std::vector<uint16_t> rf = pack_nat(Rm, c.cout, c.cin, 1, c.cin / 16);
-            frags.insert(frags.end(), rf.begin(), rf.end());
-            const std::vector<uint16_t> rf16 = pack_nat(Rm, c.cout, c.cin, 1, c.cin / 16, 1);
-            frags16.insert(frags16.end(), rf16.begin(), rf16.end());
-            rb_ft = ftvec(rb, 1);
-        }
-        off[i].w = add(frags.data(), frags.size() * 2);
-        off[i].w16 = add(frags16.data(), frags16.size() * 2);
-        const std::vector<float> b_ft = ftvec(bi, 1);
-        off[i].bias = add(b_ft.data(), b_ft.size() * 4);
-        if (c.res_conv) off[i].rbias = add(rb_ft.data(), rb_ft.size() * 4);
-    }
-    // conv4 + BatchNorm1d; reference feature index c*16 + bin  ->  plane order bin*32 + c
-    std::vector<float> s4, b4;
-    bn_fold(me + "conv4.1", P(me + "conv4.0.bias"), s4, b4);
-    const auto& w4 = P(me + "conv4.0.weight");
-    std::vector<float> W4((size_t)64 * 512);
-    for (int o = 0; o < 64; ++o)
-        for (int c = 0; c < 32; ++c)
-            for (int bin = 0; bin < 16; ++bin) W4[(size_t)o * 512 + bin * 32 + c] = w4[(size_t)o * 512 + c * 16 + bin] * s4[o];
-    const std::vector<uint16_t> f4 = pack_nat(W4, 64, 512, 2, 32);
-    const size_t o_w4 = add(f4.data(), f4.size() * 2);
-    const std::vector<uint16_t> f4h = pack_nat(W4, 64, 512, 2, 32, 2);
-    const size_t o_w4h = add(f4h.data(), f4h.size() * 2);
-    const std::vector<float> b4_ft = ftvec(b4, 2);
-    const size_t o_b4 = add(b4_ft.data(), b4_ft.size() * 4);
-    std::vector<uint16_t> stem_frags;
-    for (int i = 0; i < 3; ++i) {
-        stem_frags.insert(stem_frags.end(), stem_hi[i].begin(), stem_hi[i].end());
-        stem_frags.insert(stem_frags.end(), stem_lo[i].begin(), stem_lo[i].end());
-    }
-    const size_t o_stem_w = add(stem_frags.data(), stem_frags.size() * 2);
-    const size_t o_stem_w16 = add(stem_16.data(), stem_16.size() * 2);
-    const size_t o_stem_b = add(stem_bias.data(), stem_bias.size() * 4);
-    const size_t o_stem_wa = add(stem_wa32.data(), stem_wa32.size() * 4);
-    const std::vector<uint16_t> fp = pack_nat(P("proj.weight"), 64, 64, 2, 4);
-    const size_t o_wp = add(fp.data(), fp.size() * 2);
-    const std::vector<float> bp_ft = ftvec(P("proj.bias"), 2);
-    const size_t o_bp = add(bp_ft.data(), bp_ft.size() * 4);
+    return true;
+}
 
+// Folding and packing are music_pack (dc_pack.h, no HIP call); here the image is uploaded and the pointers into it are resolved.
+dc_music* dc_music_build(const DcParams& params, int music_dim, std::string* err) {
+    if (!dc_music_check(params, music_dim, err)) return nullptr;
+    const MusicImage I = music_pack(params);
+    const std::vector<uint8_t>& host = I.arena.host;
     dc_music* m = new dc_music();
     if (hipMalloc((void**)&m->arena, host.size()) != hipSuccess ||
         hipMemcpy(m->arena, host.data(), host.size(), hipMemcpyHostToDevice) != hipSuccess) {
@@ -1132,21 +952,22 @@ dc_music* dc_music_build(const std::map<std::string, std::vector<float>>& params
         return nullptr;
     }
     m->ws_bytes = (long long)host.size();
+    const auto at = [&](auto& dst, size_t off) { dst = reinterpret_cast<std::remove_reference_t<decltype(dst)>>(m->arena + off); };
     for (int i = 0; i < 7; ++i) {
-        m->conv[i].w = reinterpret_cast<const bf16x8*>(m->arena + off[i].w);
-        m->conv[i].w16 = reinterpret_cast<const f16x8*>(m->arena + off[i].w16);
-        m->conv[i].bias = reinterpret_cast<const float*>(m->arena + off[i].bias);
-        m->conv[i].rbias = off[i].rbias == (size_t)-1 ? nullptr : reinterpret_cast<const float*>(m->arena + off[i].rbias);
+        at(m->conv[i].w, I.conv[i].w);
+        at(m->conv[i].w16, I.conv[i].w16);
+        at(m->conv[i].bias, I.conv[i].bias);
+        if (I.conv[i].rbias != MusicImage::kNone) at(m->conv[i].rbias, I.conv[i].rbias);
     }
-    m->stem_w = reinterpret_cast<const bf16x8*>(m->arena + o_stem_w);
-    m->stem_w16 = reinterpret_cast<const f16x8*>(m->arena + o_stem_w16);
-    m->w4_16 = reinterpret_cast<const f16x8*>(m->arena + o_w4h);
-    m->stem_b = reinterpret_cast<const float*>(m->arena + o_stem_b);
-    m->stem_wa = reinterpret_cast<const float*>(m->arena + o_stem_wa);
-    m->w4 = reinterpret_cast<const bf16x8*>(m->arena + o_w4);
-    m->b4 = reinterpret_cast<const float*>(m->arena + o_b4);
-    m->wp = reinterpret_cast<const bf16x8*>(m->arena + o_wp);
-    m->bp = reinterpret_cast<const float*>(m->arena + o_bp);
+    at(m->stem_w, I.stem_w);
+    at(m->stem_w16, I.stem_w16);
+    at(m->stem_b, I.stem_b);
+    at(m->stem_wa, I.stem_wa);
+    at(m->w4, I.w4);
+    at(m->w4_16, I.w4_16);
+    at(m->b4, I.b4);
+    at(m->wp, I.wp);
+    at(m->bp, I.bp);
     return m;
 }
 

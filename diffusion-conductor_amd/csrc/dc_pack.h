@@ -1,0 +1,287 @@
+// dc_pack.h - host-only half of the weight preparation (no kernels, no HIP call): 16-bit conversions, the MFMA fragment
+// packers, the 256-byte-aligned host arena, and the MusicEncoder's folded image.  Included by dc_api.hip (denoiser image,
+// dc_pack_weight) and dc_music.hip; the single copy of every rounding routine both must agree on bit for bit.
+#pragma once
+#include <stdint.h>
+
+#include <cmath>
+#include <cstring>
+#include <map>
+#include <string>
+#include <utility>
+#include <vector>
+
+// ---- 16-bit conversions (round to nearest even; inputs are finite weights) --------------------------------------------
+inline uint16_t f2bf(float f) {
+    uint32_t u;
+    memcpy(&u, &f, 4);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40);   // NaN stays NaN
+    u += 0x7fffu + ((u >> 16) & 1u);
+    return (uint16_t)(u >> 16);
+}
+inline float bf2f(uint16_t h) {
+    uint32_t u = (uint32_t)h << 16;
+    float f;
+    memcpy(&f, &u, 4);
+    return f;
+}
+inline uint16_t f2h(float f) {   // fp32 -> fp16 bits, round to nearest even (compiler's conversion)
+    const _Float16 h = (_Float16)f;
+    uint16_t u;
+    memcpy(&u, &h, 2);
+    return u;
+}
+inline float h2f(uint16_t u) {
+    _Float16 h;
+    memcpy(&h, &u, 2);
+    return (float)h;
+}
+inline uint16_t to16(float v, bool f16) { return f16 ? f2h(v) : f2bf(v); }
+
+inline int tile_row(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
+inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+
+// ---- fragment packers ---------------------------------------------------------------------------------------------
+// One MFMA operand fragment - 64 lanes x 8 elements, lane-major (1 KiB per half) - of w [n_out][k_in] (row-major, 0 outside):
+// element (l, j) = w[row][col] with (row, col) = at(l, j), split into v ~ hi + lo in the 16-bit format (fp16 or bf16):
+// hi = round(v), lo = round(v - hi).  A null `lo` keeps the hi halves only.  Every packer below goes through here.
+template <class At>
+inline void pack_frag(const float* w, int n_out, int k_in, bool f16, uint16_t* hi, uint16_t* lo, At at) {
+    for (int l = 0; l < 64; ++l)
+        for (int j = 0; j < 8; ++j) {
+            const std::pair<int, int> rc = at(l, j);
+            const float v = (rc.first < n_out && rc.second < k_in) ? w[(size_t)rc.first * k_in + rc.second] : 0.f;
+            const uint16_t h = hi[l * 8 + j] = to16(v, f16);
+            if (lo) lo[l * 8 + j] = to16(v - (f16 ? h2f(h) : bf2f(h)), f16);
+        }
+}
+
+// Weight image of v_mfma_f32_32x32x16 operands, lane (i = l&31, hh = l>>5).  "chained" k order: frag (ot, kt, s), element j
+//   = W[32ot + i][32kt + 16s + 8(j>>2) + 4hh + (j&3)]
+// i.e. the k order in which an accumulator tile, converted in registers, presents its rows; frags [kt][ot][s] (k-outer sweeps).
+// "natural" k order: frag (ot, ks): element j = W[32ot + i][16ks + 8hh + j]; frags [ot][ks] (streamed per tile).
+inline void pack_weight(const float* w, int n_out, int k_in, bool chained, uint16_t* hi, uint16_t* lo, bool f16 = false) {
+    const int OT = cdiv(n_out, 32), KT = cdiv(k_in, 32);
+    for (int ot = 0; ot < OT; ++ot)
+        for (int kt = 0; kt < KT; ++kt)
+            for (int s = 0; s < 2; ++s) {
+                const size_t o = 512 * ((chained ? (size_t)kt * OT + ot : (size_t)ot * KT + kt) * 2 + s);
+                pack_frag(w, n_out, k_in, f16, hi + o, lo + o, [&](int l, int j) {
+                    const int hh = l >> 5, k = chained ? 8 * (j >> 2) + 4 * hh + (j & 3) : 8 * hh + j;
+                    return std::make_pair(32 * ot + (l & 31), 32 * kt + 16 * s + k);
+                });
+            }
+}
+inline size_t packed_elems(int n_out, int k_in) { return (size_t)cdiv(n_out, 32) * cdiv(k_in, 32) * 2 * 64 * 8; }
+// v_mfma_f32_16x16x32 operand image of the 16-token layer kernel (DcLayer16 in dc_common.h): [m][rb][64][8]
+inline void pack_weight16(const float* w, int n_out, int k_in, uint16_t* hi, uint16_t* lo, bool f16) {
+    const int RB = cdiv(n_out, 16), KM = cdiv(k_in, 32);
+    for (int m = 0; m < KM; ++m)
+        for (int rb = 0; rb < RB; ++rb) {
+            const size_t o = 512 * ((size_t)m * RB + rb);
+            pack_frag(w, n_out, k_in, f16, hi + o, lo + o, [&](int l, int j) {
+                return std::make_pair(16 * rb + (l & 15), 32 * m + 16 * (j >> 2) + 4 * (l >> 4) + (j & 3));
+            });
+        }
+}
+inline size_t packed_elems16(int n_out, int k_in) { return (size_t)cdiv(n_out, 16) * cdiv(k_in, 32) * 64 * 8; }
+
+// The MusicEncoder's natural-k A fragments of Wm [n_out][k_in]: [hi: ot][ks], then [lo: ot][ks] when `with_lo`.  The element
+// order is pack_weight's natural one, but the image is sized by k-steps of 16: an odd KS (K = 16, 144) has no padding
+// half-tile, so this stays its own function.
+inline std::vector<uint16_t> pack_nat(const std::vector<float>& Wm, int n_out, int k_in, int OT, int KS, bool f16, bool with_lo) {
+    const size_t ne = (size_t)OT * KS * 512;
+    std::vector<uint16_t> out((with_lo ? 2 : 1) * ne, 0);
+    for (int ot = 0; ot < OT; ++ot)
+        for (int ks = 0; ks < KS; ++ks) {
+            uint16_t* hi = out.data() + 512 * ((size_t)ot * KS + ks);
+            pack_frag(Wm.data(), n_out, k_in, f16, hi, with_lo ? hi + ne : nullptr,
+                      [&](int l, int j) { return std::make_pair(32 * ot + (l & 31), 16 * ks + 8 * (l >> 5) + j); });
+        }
+    return out;
+}
+
+// per-feature vector in FT register order: out[(t*2+hh)*16 + r] = v[32t + tile_row(r,hh)]
+inline std::vector<float> ftvec(const float* v, int n, int NT) {
+    std::vector<float> out((size_t)NT * 32);
+    for (int t = 0; t < NT; ++t)
+        for (int hh = 0; hh < 2; ++hh)
+            for (int r = 0; r < 16; ++r) {
+                const int f = 32 * t + tile_row(r, hh);
+                out[(t * 2 + hh) * 16 + r] = f < n ? v[f] : 0.f;
+            }
+    return out;
+}
+
+// FiLM GEMM operands in v_mfma_f32_16x16x32 order (DcModel::film_w16 in dc_common.h): w [32 NT][k] row-major -> [tile][ks32][fb][64][8],
+// lane l = row 16 fb + pi(l & 15), element j = column 32 ks32 + 8 (l >> 4) + j; hi halves only
+constexpr int kFilmPi[16] = {0, 1, 2, 3, 8, 9, 10, 11, 4, 5, 6, 7, 12, 13, 14, 15};
+inline std::vector<uint16_t> pack_film16(const std::vector<float>& w, int NT, int k, bool f16) {
+    std::vector<uint16_t> out((size_t)NT * 32 * k);
+    for (int ot = 0; ot < NT; ++ot)
+        for (int ks = 0; ks < k / 32; ++ks)
+            for (int fb = 0; fb < 2; ++fb)
+                pack_frag(w.data(), NT * 32, k, f16, out.data() + 512 * (((size_t)ot * (k / 32) + ks) * 2 + fb), nullptr, [&](int l, int j) {
+                    return std::make_pair(32 * ot + 16 * fb + kFilmPi[l & 15], 32 * ks + 8 * (l >> 4) + j);
+                });
+    return out;
+}
+// ... and their constants in the same row order: [tile][fb][16]
+inline std::vector<float> permute_film_bias16(const std::vector<float>& b, int NT) {
+    std::vector<float> out((size_t)NT * 32);
+    for (int ot = 0; ot < NT; ++ot)
+        for (int fb = 0; fb < 2; ++fb)
+            for (int r = 0; r < 16; ++r) out[((size_t)ot * 2 + fb) * 16 + r] = b[(size_t)32 * ot + 16 * fb + kFilmPi[r]];
+    return out;
+}
+
+// ---- host arena ---------------------------------------------------------------------------------------------------
+// Everything a model keeps on the device, appended at 256-byte alignment.  Pointers into it are known only after the upload:
+// point() notes a destination and the arena offset it will hold, resolve() fills every destination in for a base address.
+struct Arena {
+    std::vector<uint8_t> host;
+    std::vector<std::pair<const void**, size_t>> fix;
+    size_t add(const void* p, size_t bytes) {
+        const size_t off = (host.size() + 255) & ~(size_t)255;
+        host.resize(off + bytes);
+        memcpy(host.data() + off, p, bytes);
+        return off;
+    }
+    template <class T>
+    size_t add(const std::vector<T>& v) { return add(v.data(), v.size() * sizeof(T)); }
+    template <class T>
+    void point(const T** dst, size_t off) { fix.push_back({(const void**)dst, off}); }
+    void resolve(const uint8_t* base) const {
+        for (const auto& f : fix) *f.first = base + f.second;
+    }
+};
+
+using DcParams = std::map<std::string, std::vector<float>>;
+
+// ---- MusicEncoder image (kernels: dc_music.hip) -------------------------------------------------------------------
+struct MusicConvSpec {
+    const char* name;
+    int cin, cout;
+    bool res_conv;
+};
+constexpr MusicConvSpec kMusicConvs[7] = {{"conv1.0", 1, 16, false},  {"conv1.1", 16, 16, false}, {"conv1.2", 16, 16, false},
+                                          {"conv2.0", 16, 32, true},  {"conv2.1", 32, 32, false}, {"conv3.0", 32, 32, false},
+                                          {"conv3.1", 32, 32, false}};
+constexpr float kBnEps = 1e-5f;   // nn.BatchNorm default
+
+// the folded weights as one arena plus the offsets of its entries (kNone: the layer has no such entry)
+struct MusicImage {
+    static constexpr size_t kNone = (size_t)-1;
+    Arena arena;
+    struct Conv {
+        size_t w, w16, bias, rbias;       // bf16 hi + lo fragments, fp16 fragments, folded bias, residual branch's bias
+    } conv[7];
+    size_t w4, w4_16, b4;                 // conv4: bf16 hi + lo, fp16 hi + lo, bias
+    size_t stem_w, stem_w16, stem_b, stem_wa;
+    size_t wp, bp;                        // proj
+};
+
+// v_mfma_f32_16x16x32 A fragments of the fused conv1 kernel (k_me_stem) for one of its three layers, Wm [16][K]: lane (co = l & 15,
+// q4 = l >> 4), element j; bf16 hi and lo, and for the 16-channel layers the fp16 fragments appended to `f16` ([layer][ks][lane][j])
+inline void music_pack_stem(const std::vector<float>& Wm, int K, int cin, std::vector<uint16_t>& hi, std::vector<uint16_t>& lo,
+                            std::vector<uint16_t>& f16) {
+    const int nks = cin == 1 ? 1 : 5;
+    hi.assign((size_t)nks * 512, 0);
+    lo.assign((size_t)nks * 512, 0);
+    for (int ks = 0; ks < nks; ++ks) {
+        const auto at = [&](int l, int j) {      // conv1.0: k = tap (9 of 16); else tap-major, 16 channels per tap (tap 9 of k-step 4: past K)
+            const int q4 = l >> 4;
+            return std::make_pair(l & 15, cin == 1 ? 8 * q4 + j : (2 * ks + (q4 >> 1)) * 16 + 8 * (q4 & 1) + j);
+        };
+        pack_frag(Wm.data(), 16, K, false, &hi[(size_t)ks * 512], &lo[(size_t)ks * 512], at);
+        if (cin == 1) continue;
+        f16.resize(f16.size() + 512);
+        pack_frag(Wm.data(), 16, K, true, &f16[f16.size() - 512], nullptr, at);
+    }
+}
+
+// Folds and packs the reference state_dict entries `music_encoder.*` / `proj.*` (all present, with the sizes of
+// dc_music_required: dc_music_check).
+inline MusicImage music_pack(const DcParams& params) {
+    const auto P = [&](const std::string& n) -> const std::vector<float>& { return params.find(n)->second; };
+    // eval-mode BatchNorm `bn` folded into the convolution in front of it (bias cb): s = gamma / sqrt(var + eps)
+    const auto bn_fold = [&](const std::string& bn, const std::vector<float>& cb, std::vector<float>& scale, std::vector<float>& bias) {
+        const auto &g = P(bn + ".weight"), &be = P(bn + ".bias"), &mu = P(bn + ".running_mean"), &var = P(bn + ".running_var");
+        scale.resize(g.size());
+        bias.resize(g.size());
+        for (size_t c = 0; c < g.size(); ++c) {
+            scale[c] = g[c] / std::sqrt(var[c] + kBnEps);
+            bias[c] = (cb[c] - mu[c]) * scale[c] + be[c];
+        }
+    };
+    MusicImage I;
+    Arena& A = I.arena;
+    std::vector<uint16_t> stem_hi[3], stem_lo[3], stem_16;
+    std::vector<float> stem_bias, stem_wa32;
+    const std::string me = "music_encoder.";
+    for (int i = 0; i < 7; ++i) {
+        const MusicConvSpec& c = kMusicConvs[i];
+        const std::string p = me + c.name;
+        std::vector<float> sc, bi;
+        bn_fold(p + ".conv2d_layer.1", P(p + ".conv2d_layer.0.bias"), sc, bi);
+        const auto& w = P(p + ".conv2d_layer.0.weight");                 // [cout][cin][3][3]
+        const int K = c.cin >= 16 ? 9 * c.cin : 16, KS = K / 16;
+        std::vector<float> Wm((size_t)c.cout * K, 0.f);
+        for (int co = 0; co < c.cout; ++co)
+            for (int ci = 0; ci < c.cin; ++ci)
+                for (int tap = 0; tap < 9; ++tap)
+                    Wm[(size_t)co * K + tap * c.cin + ci] = w[((size_t)co * c.cin + ci) * 9 + tap] * sc[co];
+        std::vector<uint16_t> frags = pack_nat(Wm, c.cout, K, 1, KS, false, true);
+        std::vector<uint16_t> frags16 = pack_nat(Wm, c.cout, K, 1, KS, true, false);
+        if (i == 0) {                                                    // conv1.0 runs on the vector ALU: [16][9] fp32
+            stem_wa32.resize(16 * 9);
+            for (int co = 0; co < 16; ++co)
+                for (int tap = 0; tap < 9; ++tap) stem_wa32[co * 9 + tap] = Wm[(size_t)co * K + tap];
+        }
+        if (i < 3) {
+            music_pack_stem(Wm, K, c.cin, stem_hi[i], stem_lo[i], stem_16);
+            stem_bias.insert(stem_bias.end(), bi.begin(), bi.end());
+        }
+        std::vector<float> rb;
+        if (c.res_conv) {
+            std::vector<float> rs;
+            bn_fold(p + ".residual.1", P(p + ".residual.0.bias"), rs, rb);
+            const auto& rw = P(p + ".residual.0.weight");                // [cout][cin][1][1]
+            std::vector<float> Rm((size_t)c.cout * c.cin);
+            for (int co = 0; co < c.cout; ++co)
+                for (int ci = 0; ci < c.cin; ++ci) Rm[(size_t)co * c.cin + ci] = rw[(size_t)co * c.cin + ci] * rs[co];
+            const std::vector<uint16_t> rf = pack_nat(Rm, c.cout, c.cin, 1, c.cin / 16, false, true);
+            frags.insert(frags.end(), rf.begin(), rf.end());
+            const std::vector<uint16_t> rf16 = pack_nat(Rm, c.cout, c.cin, 1, c.cin / 16, true, false);
+            frags16.insert(frags16.end(), rf16.begin(), rf16.end());
+        }
+        I.conv[i].w = A.add(frags);
+        I.conv[i].w16 = A.add(frags16);
+        I.conv[i].bias = A.add(ftvec(bi.data(), (int)bi.size(), 1));
+        I.conv[i].rbias = c.res_conv ? A.add(ftvec(rb.data(), (int)rb.size(), 1)) : MusicImage::kNone;
+    }
+    // conv4 + BatchNorm1d; reference feature index c*16 + bin  ->  plane order bin*32 + c
+    std::vector<float> s4, b4;
+    bn_fold(me + "conv4.1", P(me + "conv4.0.bias"), s4, b4);
+    const auto& w4 = P(me + "conv4.0.weight");
+    std::vector<float> W4((size_t)64 * 512);
+    for (int o = 0; o < 64; ++o)
+        for (int c = 0; c < 32; ++c)
+            for (int bin = 0; bin < 16; ++bin) W4[(size_t)o * 512 + bin * 32 + c] = w4[(size_t)o * 512 + c * 16 + bin] * s4[o];
+    I.w4 = A.add(pack_nat(W4, 64, 512, 2, 32, false, true));
+    I.w4_16 = A.add(pack_nat(W4, 64, 512, 2, 32, true, true));
+    I.b4 = A.add(ftvec(b4.data(), (int)b4.size(), 2));
+    std::vector<uint16_t> stem_frags;
+    for (int i = 0; i < 3; ++i) {
+        stem_frags.insert(stem_frags.end(), stem_hi[i].begin(), stem_hi[i].end());
+        stem_frags.insert(stem_frags.end(), stem_lo[i].begin(), stem_lo[i].end());
+    }
+    I.stem_w = A.add(stem_frags);
+    I.stem_w16 = A.add(stem_16);
+    I.stem_b = A.add(stem_bias);
+    I.stem_wa = A.add(stem_wa32);
+    const auto& bp = P("proj.bias");
+    I.wp = A.add(pack_nat(P("proj.weight"), 64, 64, 2, 4, false, true));
+    I.bp = A.add(ftvec(bp.data(), (int)bp.size(), 2));
+    return I;
+}

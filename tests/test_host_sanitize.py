@@ -1,6 +1,6 @@
 """SURVEY section 5 (race / memory checking): GPU AddressSanitizer is not available on this pool, so the HOST half of the C-ABI
-library - parameter store, validation, LayerNorm / FiLM folding, weight packing into the arena, schedule and filter tables - is
-built with AddressSanitizer + UBSan on the host side only (-Xarch_host on the compile, -fno-gpu-sanitize on the link;
+library - parameter store, validation, LayerNorm / FiLM folding, weight packing into the arena, the music encoder's BatchNorm
+folding and its stem / conv / conv4 / proj packers (csrc/dc_pack.h), schedule and filter tables - is built with AddressSanitizer + UBSan on the host side only (-Xarch_host on the compile, -fno-gpu-sanitize on the link;
 -DDC_HOST_SANITIZE: a sampler can be created without a device) and driven through its entry points by tests/san_child.py, run
 by a Python launcher that carries the sanitizer runtime itself (linked statically), in a process with no device visible."""
 import os
