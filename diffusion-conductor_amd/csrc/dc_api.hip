@@ -15,6 +15,7 @@
 
 #include "../../include/dc_ddim.h"
 #include "dc_common.h"
+#include "dc_form.h"
 #include "dc_launch.h"
 #include "dc_music.h"
 #include "dc_pack.h"
@@ -45,18 +46,6 @@ const char* kKernelNames[K_COUNT] = {"k_begin_step", "k_silu_emb", "k_film_gemm"
 struct Prof {                       // per-kernel profile (dc_sampler_profile_loop): events around every launch
     std::vector<hipEvent_t> ev;     // pairs
     std::vector<int> ids;
-};
-
-// operand formats (0 = bf16, 1 = f16) and split flags of the 128-wide GEMMs and of the FiLM GEMM
-struct Formats {
-    int small_fmt = 0, film_fmt = 0;
-    bool split_small = false, split_film = false;
-    void set_precision(int precision) {
-        split_small = precision == DC_PREC_MIXED || precision == DC_PREC_BF16X3;
-        split_film = precision == DC_PREC_BF16X3;
-        small_fmt = precision == DC_PREC_FP16 ? 1 : 0;
-        film_fmt = (precision == DC_PREC_FP16 || precision == DC_PREC_MIXED) ? 1 : 0;
-    }
 };
 
 }  // namespace
@@ -140,7 +129,7 @@ struct dc_sampler : Formats {     // (set_precision(cfg.precision))
     int me_format = -1;          // dc_sampler_set_encoder_format (-1: by precision)
     int clip_aligned = -1;         // dc_sampler_set_clip_aligned: 1 clip-aligned units in the wide form too, 0 flat units, -1 the library's rule
     bool precise_forward = false;  // dc_sampler_set_precise_forward: dc_sampler_denoise on split operands (the precise tail's evaluation form)
-    int tail_split = -1;         // dc_sampler_set_precise_tail: the loop's last evaluations with split operands (-1: by precision - fp16 1, bf16 8)
+    int tail_split = -1;         // dc_sampler_set_precise_tail: the loop's last evaluations with split operands (-1: by precision - fp16 1, bf16 DC_BF16_TAIL_DEFAULT = 6)
     bool host_only = false;      // -DDC_HOST_SANITIZE builds without a device: the host half only (tests/test_host_sanitize.py)
 
     Prof prof;
@@ -590,23 +579,15 @@ int upload_model(dc_sampler* s, ModelImage& I) {
     return DC_OK;
 }
 
-// Clip stride of the internal token space.  Where the workgroup-record kernels can run (non-split formats, linear attention,
-// Tx >= 256) a clip may be padded to whole 32-token groups, so that no group spans two clips (the padding frames behave like
-// frames past `length`).  Measured (same box): bs=32 x 1800 (+1.3 % tokens) -1.6 % per loop; bs=128 x 900
-// (+3.1 %) +0.2 %; small batches, which then also run clip-aligned units (enqueue_step), -9 % at bs=4 x 1800.
-int clip_stride(const dc_sampler* s, int B, int Tx) {
-    // clips shorter than one 32-token group: one group per clip (a group's records name at most two clips)
-    if (Tx < 32 && !s->cfg.no_eff && !getenv("DC_NO_PAD")) return 32;
-    if (s->cfg.no_eff || Tx < 256 || Tx % 32 == 0 || getenv("DC_NO_PAD")) return Tx;
-    const int Tp = (Tx + 31) / 32 * 32;
-    if (s->split_small) return Tp;         // split formats: workgroup records exist on clip-aligned units only (one clip per workgroup)
-    const bool small_batch = (long long)B * ((Tp + 127) / 128) <= s->num_cu;       // narrow, clip-aligned workgroups
-    // ... unless the padding frames cost the layer launches a whole extra round of workgroups (256 tokens each, one per CU): 36 clips of
-    // 1800 frames are 254 workgroups, of 1824 frames 257 - 38 vs 51 ms per loop (profiles/r05_big_batches.md)
-    const auto rounds = [&](int T) { return (((long long)B * T + 255) / 256 + s->num_cu - 1) / s->num_cu; };
-    if (!small_batch && rounds(Tp) > rounds(Tx)) return Tx;
-    return (small_batch || (Tp - Tx) * 50 <= Tx) ? Tp : Tx;
+// what the launch rule (dc_form.h) reads of a sampler
+Settings settings_of(const dc_sampler* s) {
+    Settings r;
+    r.precision = s->cfg.precision, r.fmt = *s, r.no_eff = s->cfg.no_eff != 0, r.clip_aligned = s->clip_aligned, r.l16_own = s->l16_own;
+    r.num_layers = s->cfg.num_layers, r.split_model = s->d_model_split != nullptr, r.film_w16 = s->h_model.film_w16 != nullptr;
+    r.film_w16_tail = s->h_model.film_w16_tail != nullptr, r.l16_max_units = dc_layer16_max_units();
+    return r;
 }
+int clip_stride(const dc_sampler* s, int B, int Tx) { return clip_stride(settings_of(s), Switches::read(), B, Tx, s->num_cu); }
 int ensure_workspace(dc_sampler* s, int B, int Tx) {
     const int T = clip_stride(s, B, Tx);
     const int M = B * T, G = cdiv(M, 32), L = s->cfg.num_layers, P = s->cfg.input_feats;
@@ -621,10 +602,7 @@ int ensure_workspace(dc_sampler* s, int B, int Tx) {
         if ((rc = dev_alloc(s, s->d_E, g * s->NT * 64 * 32))) return rc;
         if ((rc = dev_alloc(s, s->d_h, g * 4 * 64 * 64))) return rc;
         HIP_TRY(hipMemset(s->d_h, 0, g * 4 * 64 * 64));     // rows past M are read (never written) by the full-attention front half
-        // unit records: per-group form 2 slots per group; workgroup-record forms two alternating buffers of 2 slots per workgroup,
-        // i.e. 4 * nwg records with nwg <= ceil(g / 4) (narrow flat units) or B * ceil(T / 128) (clip-aligned): both <= g for the
-        // T >= 256 those forms need - sized for the larger of the two explicitly, and checked against the launch form in enqueue_step
-        s->cap_rec_floats = std::max(g * 2, 4 * ((g + 3) / 4) + 8) * DC_REC_FLOATS;
+        s->cap_rec_floats = rec_capacity(g);      // unit records (dc_form.h)
         if ((rc = dev_alloc(s, s->d_recs, s->cap_rec_floats * 4))) return rc;
         if ((rc = dev_alloc(s, s->d_nh_hi, g * 32 * 64 * 16))) return rc;
         if ((rc = dev_alloc(s, s->d_nh_lo, g * 32 * 64 * 16))) return rc;
@@ -720,38 +698,20 @@ int ensure_steps(dc_sampler* s, int S) {
         }                                                             \
     } while (0)
 
-// Everything a captured graph bakes in besides (B, T, K): the environment switches that pick the launch form (read per call, so
-// that one process can A/B them: a change re-captures) and the update options of the loop.
-unsigned long long form_key(const dc_sampler* s) {
-    static const char* sw[] = {"DC_NO_WGREC", "DC_NO_NARROW", "DC_NO_ALIGN", "DC_ALIGN", "DC_NO_FUSE_EMBED", "DC_FILM_STATIC",
-                               "DC_BEGIN_STEP", "DC_NO_PAD", "DC_NO_LAYER16", "DC_L16_OWN_COMBINE", "DC_L16_TEST_DROP_SLICE", "DC_TAIL_FILM_BF16", "DC_FLAT_UNITS",
-                               "DC_NO_EMBED_NEXT"};
-    unsigned long long k = 0;
-    for (size_t i = 0; i < sizeof sw / sizeof *sw; ++i) k |= (getenv(sw[i]) ? 1ull : 0ull) << i;
+// Everything a captured graph bakes in besides (B, T, K): the environment switches that pick the launch form (every switch step_form
+// can see: Switches::bits) and the update options of the loop.
+unsigned long long form_key(const dc_sampler* s, const Switches& w) {
+    unsigned long long k = w.bits();
     k |= (unsigned long long)(s->upd_flags & 0xff) << 16;     // (the noise tensor's address is not baked in: the kernels read it from d_zslot)
     k |= (s->l16_own ? 1ull : 0ull) << 24;
     k |= (unsigned long long)((s->clip_aligned + 1) & 3) << 25;
     return k;
 }
 
-// Test hooks of one evaluation (dc_sampler_debug_denoise, dc_sampler_debug_layer); the defaults run the production evaluation
-struct Hooks {
-    int layers = -1, stage = 0;   // run the first `layers` layers, the last of them up to `stage` (| (first stage - 1) << 16)
-    int first = -1;               // start at this layer from the residual stream in d_h
-};
-
-// One enqueue_step call ...
-struct Step {
-    bool loop_mode = false;       // a loop's step: the last layer applies the DDIM update to x_src
+// One enqueue_step call: the options that decide its form (dc_form.h) and its tensors ...
+struct Step : StepOpts {
     const float* x_src = nullptr;
     float* x_dst = nullptr;
-    int graph_step = -1;          // >= 0: step number inside a graph being captured
-    bool split = false;           // this evaluation's 128-wide GEMMs on split operands (the fp16 images' hi + lo halves)
-    bool g1_loop = false;         // a loop with a precise tail: its plain-operand evaluations read G' scale tiles
-    bool next_plain = false;      // loops: another step follows in this enqueue sequence (same graph) and it is a plain-operand evaluation
-    bool embedded = false;        // the previous step's last layer has embedded x and run layer 0's front half for this step
-    Hooks dbg;
-    bool profile = false;         // events around every launch, collected in s->prof
 };
 // ... and what it tells its caller
 struct StepDone {
@@ -768,169 +728,85 @@ DcFilmArgs film_args(const dc_sampler* s, const float* pp, const int* t_clip) {
     return f;
 }
 
-// One denoiser evaluation (+ DDIM update when loop_mode) enqueued on st.
-// graph_step >= 0: step number inside a graph being captured.  On the default path (fused SiLU fill, per-layer launches) the
-// step's kernels then look the timestep / DDIM scalars up themselves - this step's slot of the per-iteration tables, offset by
-// the iteration at which the replay began (*d_iter, advanced once per replay) - and the per-step bookkeeping launch
-// (k_begin_step, 5 us + a launch gap) is dropped.
-int enqueue_step(dc_sampler* s, hipStream_t st, const Step& c, StepDone* done = nullptr) {
-    const int B = s->B, T = s->T, M = s->M, G = s->G, L = s->cfg.num_layers;
-    const bool loop_mode = c.loop_mode, embedded = c.embedded;
-    const int graph_step = c.graph_step;
-    const Hooks& dbg = c.dbg;
-    const bool ss = s->split_small || c.split, sf = s->split_film;
+// One denoiser evaluation (+ DDIM update when loop_mode) enqueued on st, in the form step_form (dc_form.h) decides: this function
+// fills the launch arguments and launches.  `w`: the caller's Switches::read() of this API call.
+int enqueue_step(dc_sampler* s, hipStream_t st, const Step& c, const Switches& w, StepDone* done = nullptr) {
+    static const bool want_stamps = getenv("DC_STAMPS") != nullptr;       // (the FiLM GEMM's clock stamps land in stamp slots 28..31 of wave 7)
+    const int B = s->B, T = s->T, M = s->M, G = s->G, Tx = s->Tx;
+    const StepForm f = step_form(Geometry{B, T, Tx, G, s->num_cu, s->cap_rec_floats}, settings_of(s), w, c, want_stamps);
+    const bool folded = f.folded;
+    const int fs = f.fs, ff = f.ff, graph_step = c.graph_step;
+    const bool ss = f.ss, sf = s->split_film;
+    // k_layer16's tags: captured steps 16 * (graph step + *d_iter) + layer + 1, eager launches from a sequence of their own above them -
+    // consecutive launches never share a tag (the sequence advances on every step that is not folded, whichever kernel runs)
+    const unsigned l16_tag = folded ? 16u * (unsigned)graph_step : (0x40000000u | (16u * (s->l16_seq++ & 0x3ffffffu)));
+    if (!f.error.empty()) return fail(DC_ERR_INVALID, "%s", f.error.c_str());
+    if (done) done->embedded_next = f.embed_next, done->folded = folded;
     const DcModel* dmod = (c.split && !s->split_small) ? s->d_model_split : s->d_model;      // (the precise tail's split stage images)
-    // (bf16 precision, split evaluations: the f16 FiLM image - the step is then exactly a "mixed" evaluation)
-    const bool film_tail = c.split && !s->split_small && s->h_model.film_w16_tail != nullptr && !getenv("DC_TAIL_FILM_BF16");
-    const int fs = s->small_fmt, ff = film_tail ? 1 : s->film_fmt;
-    // non-split formats: the FiLM GEMM produces its own operand from pp + temb (no k_silu_emb pass); the separate pass
-    // remains for the split formats, for the v1 kernel, and under the test hooks that read the operand image back
-    const bool fuse_silu = !sf && dbg.layers < 0;
-    const bool folded = loop_mode && graph_step >= 0 && fuse_silu && !s->cfg.no_eff && !getenv("DC_BEGIN_STEP") && dbg.stage == 0;
     const int* iter_base = folded ? s->d_iter : nullptr;
     const int* t_src = folded ? s->d_t_of_iter + graph_step : s->d_t_clip;
     const float* coef_src = folded ? s->d_coef_of_iter + DC_COEF * (size_t)graph_step : s->d_coef_cur;
     const int* snap_src = folded ? s->d_snap_of_iter + graph_step : s->d_snap_cur;
-    if (loop_mode && !folded)
+    if (c.loop_mode && !folded)
         LAUNCH(K_BEGIN, dc_launch_begin_step(st, s->d_iter, s->d_t_of_iter, s->d_coef_of_t, s->d_snap_of_iter,
                                              s->d_t_clip, s->d_coef_cur, s->d_snap_cur, B));
-    if (loop_mode && (s->upd_flags & DC_UPD_ZSTEP))       // this iteration's draws (eta > 0, library-generated): consumed by the last layer's epilogue
-        LAUNCH(K_NOISE, dc_launch_step_noise(st, s->d_zstep, (size_t)B * s->Tx * s->cfg.input_feats, 0, reinterpret_cast<const unsigned long long*>(s->d_zslot) + 1,
+    if (c.loop_mode && (s->upd_flags & DC_UPD_ZSTEP))       // this iteration's draws (eta > 0, library-generated): consumed by the last layer's epilogue
+        LAUNCH(K_NOISE, dc_launch_step_noise(st, s->d_zstep, (size_t)B * Tx * s->cfg.input_feats, 0, reinterpret_cast<const unsigned long long*>(s->d_zslot) + 1,
                                              iter_base, folded ? graph_step : 0,
                                              folded ? nullptr : s->d_snap_cur, 0));
-    if (!fuse_silu)
+    if (!f.fuse_silu)
         LAUNCH(K_SILU, dc_launch_silu_emb(st, ff, sf, s->d_pp, s->h_model.temb, s->d_t_clip, s->d_s_hi, s->d_s_lo, G, T, B));
-    static const bool want_stamps_film = getenv("DC_STAMPS") != nullptr;       // clock stamps land in stamp slots 28..31 of wave 7
-    // adaptive work shares of the persistent FiLM GEMM (dc_kernels.hip, film_shares); DC_FILM_STATIC=1 keeps equal shares
-    const bool film_static = getenv("DC_FILM_STATIC") != nullptr;           // (read per call: the tests toggle it)
-    const bool adapt = !film_static && s->num_cu <= 1024;
-    // ---- form of the layer launches (linear attention) --------------------------------------------------------------------
-    // workgroup-level records (no combine launches) whenever a workgroup's 256 tokens cannot touch more than two clips
-    const bool no_wgr = getenv("DC_NO_WGREC") != nullptr;          // (read per call: the tests toggle it)
-    // (split formats: on clip-aligned units only - the doubled weight images leave LDS for ONE clip's attention fragments - and in
-    // the production build only: the test hooks keep the per-group form)
-    const bool wgr = T >= 256 && !no_wgr && dbg.first < 0 && !s->cfg.no_eff &&
-                     (!ss || (T % 32 == 0 && dbg.layers < 0 && dbg.stage == 0 && !getenv("DC_NO_ALIGN")));
-    static const bool want_stamps = getenv("DC_STAMPS") != nullptr;
-    // Narrow workgroups (4 waves = 128-token units, one wave per SIMD) while every unit still gets a CU of its own: the layer
-    // kernel is bound by instruction issue, so a wave alone on its SIMD runs a layer in about half the time (DESIGN.md
-    // section 4).  T <= 3840: the narrow combine holds 32 units per clip.  DC_NO_NARROW=1 keeps the 8-wave form (read per call).
-    // Clip-aligned units (WgMap in dc_dev.h; needs a clip stride of whole groups): upc workgroups per clip, no workgroup spans two
-    // clips.  Default for the narrow (small-batch) form; with the chip full (bs=32 x 1800: 256 workgroups instead of 228 flat
-    // units) it measured 1.2 % slower than flat units - DC_ALIGN=1 forces it there.
-    const bool can_align = wgr && T % 32 == 0 && !getenv("DC_NO_ALIGN");
-    const int upc_wide = (T + 255) / 256, upc_narrow = (T + 127) / 128;
-    const bool aligned_env = can_align && getenv("DC_ALIGN") != nullptr;
-    const int nwg_narrow = can_align ? B * upc_narrow : (G + 3) / 4;
-    const bool narrow = wgr && !ss && nwg_narrow <= s->num_cu && T <= 3840 && dbg.layers < 0 && dbg.stage == 0 &&
-                        !getenv("DC_NO_NARROW") && !want_stamps;
-    // ... and for the wide (chip-full) form whenever the clip-aligned launch needs no more rounds of workgroups over the chip than the flat
-    // one (bs = 32 x 1800: 256 workgroups instead of 228, one round either way): a clip's result is then bit-identical whatever the
-    // batch around it - the reference's semantics (transformer.py:111: the key softmax is per clip) - for +1.6 ... +2.1 % per loop
-    // (profiles/r06_ab_align.txt).  Where it would cost a round (bs = 35 x 1800: 280 against 250 workgroups on 256 CUs) flat units stay -
-    // a clip then depends on its neighbours at the rounding level (4e-4).  dc_sampler_set_clip_aligned: 1 forces
-    // aligned units, 0 flat ones; DC_ALIGN=1 / DC_FLAT_UNITS=1 in the environment do the same per process.
-    const int nwg_flat = (G + 7) / 8, ncu = s->num_cu > 0 ? s->num_cu : 256;
-    const bool same_rounds = ((long long)B * upc_wide + ncu - 1) / ncu == ((long long)nwg_flat + ncu - 1) / ncu;
-    const bool aligned_wide = s->clip_aligned > 0 || aligned_env || (s->clip_aligned < 0 && same_rounds && !getenv("DC_FLAT_UNITS"));
-    const bool aligned = can_align && (narrow || ss || aligned_wide);
-    // 16-token waves (dc_layer16.hip) while every clip-aligned 64-token unit still gets a CU of its own (bs <= 8 at T = 1800): in that
-    // regime the layer is bound by the LENGTH of one wave's dependency chain, and a 16-token wave's is about half as long.  The
-    // embedding stays the narrow 32-token form (its 128-token unit records feed layer 0).  DC_NO_LAYER16=1 keeps the 32-token form.
-    const int upc16 = (T + 63) / 64;
-    const bool layer16 = narrow && aligned && (long long)B * upc16 <= s->num_cu && upc16 <= dc_layer16_max_units() && dbg.first < 0 &&
-                         !getenv("DC_NO_LAYER16");
-    const int upc = aligned ? (narrow ? upc_narrow : upc_wide) : 0;
-    const int nwg = aligned ? B * upc : (narrow ? (G + 3) / 4 : (G + 7) / 8);
-    // k_layer16: the clip's workgroups share the combine of the previous layer's unit records inside the launch (dc_layer16.hip;
-    // DC_L16_OWN_COMBINE=1: every workgroup combines alone, round 4's form).  Tags: captured steps 16 * (graph step + *d_iter) + layer + 1,
-    // eager launches from a sequence of their own above them - consecutive launches never share a tag.
-    const bool l16_shared = layer16 && !s->l16_own && !getenv("DC_L16_OWN_COMBINE");
-    const unsigned l16_tag = folded ? 16u * (unsigned)graph_step : (0x40000000u | (16u * (s->l16_seq++ & 0x3ffffffu)));
-    const size_t rec_stride = wgr ? (size_t)nwg * 2 * DC_REC_FLOATS : 0;
-    // (the kernels write records at recs + rec_stride + wg * 2 * DC_REC_FLOATS: both alternating buffers must lie inside d_recs)
-    if ((wgr ? 2 * rec_stride : (size_t)G * 2 * DC_REC_FLOATS) > s->cap_rec_floats)
-        return fail(DC_ERR_INVALID, "unit records of this launch form (%zu floats) exceed the workspace (%zu)",
-                    wgr ? 2 * rec_stride : (size_t)G * 2 * DC_REC_FLOATS, s->cap_rec_floats);
-    const int Tx = s->Tx;
-    // k_embed_front rides in the FiLM GEMM's launch (wide flat units, non-split formats, no test hooks; DC_NO_FUSE_EMBED=1 and the
-    // per-kernel profile pass keep the two launches): one kernel boundary less per step, -1.3 % per loop at bs=32
-    // (flat units in the non-split formats; the "mixed" mode - f16 GEMM, split-bf16 embedding - on its clip-aligned units)
-    const bool mixed_form = ss && !sf && ff == 1 && fs == 0;
-    // The last layer of a plain wide step does the NEXT step's front work (embedding of x_{t-1} + layer 0's self-attention front half:
-    // k_layer, DC_UPD_EMBED_NEXT) when that step is a plain wide step of the same enqueue sequence; its FiLM launch is then the bare GEMM
-    // and it has no front launch.  DC_NO_EMBED_NEXT=1 keeps the front work in every step's own FiLM launch.
-    const bool embed_next_on = !getenv("DC_NO_EMBED_NEXT");            // (read per call: a test toggles it)
-    const bool wide_plain = wgr && !narrow && !ss && fuse_silu && ff == fs && dbg.layers < 0 && dbg.stage == 0 && dbg.first < 0 &&
-                            !want_stamps && !s->cfg.no_eff;
-    const bool embed_next = embed_next_on && loop_mode && c.next_plain && wide_plain;
-    if (embedded && !(loop_mode && wide_plain)) return fail(DC_ERR_INVALID, "internal: a step whose front work was done by its predecessor changed its launch form");
-    if (done) done->embedded_next = embed_next, done->folded = folded;
-    const bool fuse_embed = !embedded && wgr && !narrow && (ss ? (aligned && mixed_form) : ff == fs) && fuse_silu && dbg.layers < 0 &&
-                            dbg.stage == 0 && nwg <= s->num_cu && !want_stamps && !c.profile && !getenv("DC_NO_FUSE_EMBED");
-    // small batches (narrow clip-aligned units): the embedding's workgroups ride BEHIND the GEMM's in the FiLM launch
-    // (film_extra_workgroups, dc_kernels.hip): one launch (15 us at one clip) and one kernel boundary less per step.  DC_NO_FUSE_EMBED=1 keeps the two launches.
-    const bool fuse_extra = narrow && aligned && !ss && ff == fs && fuse_silu && s->h_model.film_w16 && dbg.first < 0 && !c.profile &&
-                            !getenv("DC_NO_FUSE_EMBED");
     DcEmbedArgs ea{};
-    if (fuse_embed) ea = DcEmbedArgs{dmod, c.x_src, s->d_h, s->d_recs, s->d_length, M, Tx, nwg, aligned ? upc : 0, ss ? 1 : 0, 0};
-    if (fuse_extra) ea = DcEmbedArgs{s->d_model, c.x_src, s->d_h, s->d_recs, s->d_length, M, Tx, nwg, upc, 0, 1};
-    const DcUpdate upd{s->d_zslot, s->d_status, (loop_mode ? s->upd_flags : 0) | (getenv("DC_L16_TEST_DROP_SLICE") ? DC_UPD_TEST_DROP_SLICE : 0) |
-                                                (embed_next ? DC_UPD_EMBED_NEXT : 0),
-                       folded ? graph_step : -1, nullptr};
-    // scale tiles: G' for the plain-operand consumers of this step, G' - 1 for the split-operand ones (dc_dev.h, film_affine)
-    // (the production forms of the plain-operand kernels only: test hooks, stamps and the per-group record form keep G' - 1)
-#ifdef DC_NO_FILM_G1
-    const bool g1_tiles = false;
-#else
-    const bool g1_tiles = c.g1_loop && !ss && wgr && !s->cfg.no_eff && dbg.stage == 0 && dbg.layers < 0 && dbg.first < 0 && !want_stamps;
-#endif
-    DcFilmArgs fa = film_args(s, fuse_silu ? s->d_pp : nullptr, t_src);
-    if (g1_tiles) fa.bias_ft = s->h_model.film_b_g1, fa.bias16 = s->h_model.film_b16_g1;
-    if (film_tail) fa.W16 = s->h_model.film_w16_tail;
-    fa.clk = want_stamps_film ? s->d_stamps + 252 : nullptr;
-    if (adapt) fa.rate_in = s->d_film_rate + 1024 * s->film_rate_parity, fa.rate_out = s->d_film_rate + 1024 * (s->film_rate_parity ^ 1);
+    if (f.fuse_embed) ea = DcEmbedArgs{dmod, c.x_src, s->d_h, s->d_recs, s->d_length, M, Tx, f.nwg, f.upc, ss ? 1 : 0, 0};
+    if (f.fuse_extra) ea = DcEmbedArgs{s->d_model, c.x_src, s->d_h, s->d_recs, s->d_length, M, Tx, f.nwg, f.upc, 0, 1};
+    DcFilmArgs fa = film_args(s, f.fuse_silu ? s->d_pp : nullptr, t_src);
+    if (f.g1_tiles) fa.bias_ft = s->h_model.film_b_g1, fa.bias16 = s->h_model.film_b16_g1;
+    if (f.film_tail) fa.W16 = s->h_model.film_w16_tail;
+    fa.clk = want_stamps ? s->d_stamps + 252 : nullptr;
+    if (f.adapt) fa.rate_in = s->d_film_rate + 1024 * s->film_rate_parity, fa.rate_out = s->d_film_rate + 1024 * (s->film_rate_parity ^ 1);
     fa.iter_base = iter_base;
-    fa.embed = (fuse_embed || fuse_extra) ? &ea : nullptr;
+    fa.embed = (f.fuse_embed || f.fuse_extra) ? &ea : nullptr;
     // DC_DIAG_SKIP_FILM=1 (diagnostic, eager passes only, results invalid): the FiLM GEMM is launched once and never again - the layers then
     // read stale tiles and run without the GEMM's 300 us of power-limited matrix work between them (what the chip's clock management
     // does to the layer launches that follow a GEMM: tools/diag_clock_coupling.py)
-    const bool diag_skip_film = getenv("DC_DIAG_SKIP_FILM") && !fuse_embed && !fuse_extra && s->diag_film_done;
+    const bool diag_skip_film = getenv("DC_DIAG_SKIP_FILM") && !f.fuse_embed && !f.fuse_extra && s->diag_film_done;
     s->diag_film_done = true;
     if (!diag_skip_film) LAUNCH(K_FILM, dc_launch_film_gemm(st, ff, sf, fa));
     s->film_rate_parity ^= 1;
-    const int nl_run = (dbg.layers >= 0 && dbg.layers < L) ? dbg.layers : L;
+    const int nl_run = f.nl_run;
     DcLayerArgs la{};
     la.dm = dmod, la.hbuf = s->d_h, la.E = s->d_E, la.NT = s->NT, la.recs = s->d_recs, la.length = s->d_length, la.xin = c.x_src, la.xout = c.x_dst;
-    la.out_mode = loop_mode ? 1 : 0, la.coef_cur = coef_src, la.snap_cur = snap_src, la.snaps = s->d_snaps, la.iter_base = iter_base;
-    la.M = M, la.T = T, la.G = G, la.B = B, la.Tx = Tx, la.upd = upd;
+    la.out_mode = c.loop_mode ? 1 : 0, la.coef_cur = coef_src, la.snap_cur = snap_src, la.snaps = s->d_snaps, la.iter_base = iter_base;
+    la.M = M, la.T = T, la.G = G, la.B = B, la.Tx = Tx;
+    la.upd = DcUpdate{s->d_zslot, s->d_status, (c.loop_mode ? s->upd_flags : 0) | f.upd_flags, folded ? graph_step : -1, nullptr};
     DcLayerArgs la_stamps = la;      // (stage stamps of layer 3 in diagnostic builds: DcUpdate::stamps carries the buffer)
     la_stamps.upd.stamps = s->d_stamps;
     if (s->cfg.no_eff) {
         LAUNCH(K_EMBED, dc_launch_embed_front_full(st, fs, ss, dmod, c.x_src, s->d_h, s->d_kv_sa[0], M, T, B, s->KT));
         for (int l = 0; l < nl_run; ++l)        // (stage stamps: tools/stage_stamps_full.py + a -DDC_FULL_STAMPS build)
             LAUNCH(K_LAYER, dc_launch_layer_full(st, fs, ss, (want_stamps && l == 3) ? la_stamps : la, l, s->d_kv_sa[l & 1], s->d_kv_sa[(l + 1) & 1],
-                                                 s->d_kv_ca, s->KT, (l == nl_run - 1) ? (dbg.stage ? dbg.stage : (nl_run < L ? 3 : 0)) : 0));
+                                                 s->d_kv_ca, s->KT, (l == nl_run - 1) ? f.stop_stage : 0));
         return DC_OK;
     }
-    if (fuse_embed || fuse_extra || embedded) {
+    const DcLayerForm lf{fs, ss, f.wgr, f.narrow, f.g1_tiles, f.upc, f.rec_stride};
+    if (f.fuse_embed || f.fuse_extra || c.embedded) {
         // (embedded by the FiLM launch, or by the previous step's last layer)
-    } else if (dbg.first >= 0)
-        LAUNCH(K_EMBED, dc_launch_front_from_h(st, fs, ss, dmod, s->d_h, s->d_recs, s->d_length, M, T, G, B, dbg.first));
+    } else if (c.dbg.first >= 0)
+        LAUNCH(K_EMBED, dc_launch_front_from_h(st, fs, ss, dmod, s->d_h, s->d_recs, s->d_length, M, T, G, B, c.dbg.first));
     else
-        LAUNCH(K_EMBED, dc_launch_embed_front(st, fs, ss, wgr, dmod, c.x_src, s->d_h, s->d_recs, s->d_length, M, T, G, B,
-                                              want_stamps_film ? s->d_stamps + 256 : nullptr, narrow, Tx, upc));
-    for (int l = dbg.first >= 0 ? dbg.first : 0; l < nl_run; ++l) {
-        if (layer16) {
+        LAUNCH(K_EMBED, dc_launch_embed_front(st, lf, dmod, c.x_src, s->d_h, s->d_recs, s->d_length, M, T, G, B,
+                                              want_stamps ? s->d_stamps + 256 : nullptr, Tx));
+    for (int l = c.dbg.first >= 0 ? c.dbg.first : 0; l < nl_run; ++l) {
+        if (f.layer16) {
             static const bool stamps16 = getenv("DC_L16_STAMPS") != nullptr;        // (-DDC_L16_STAMPS builds: tools/stage_stamps16.py)
-            LAUNCH(K_LAYER, dc_launch_layer16(st, fs, (stamps16 && l == 3) ? la_stamps : la, l, s->d_a_ca16, upc16, rec_stride,
-                                              l == 0 ? upc_narrow : upc16, l == 0 ? (size_t)2 * DC_REC_FLOATS : (size_t)DC_REC_FLOATS,
-                                              l16_shared ? s->d_gran : nullptr, l16_tag, g1_tiles));
+            LAUNCH(K_LAYER, dc_launch_layer16(st, fs, (stamps16 && l == 3) ? la_stamps : la, l, s->d_a_ca16, f.upc16, f.rec_stride,
+                                              l == 0 ? f.upc_narrow : f.upc16, l == 0 ? (size_t)2 * DC_REC_FLOATS : (size_t)DC_REC_FLOATS,
+                                              f.l16_shared ? s->d_gran : nullptr, l16_tag, f.g1_tiles));
             continue;
         }
-        if (!wgr) LAUNCH(K_COMBINE, dc_launch_attn_combine(st, fs, s->d_recs, s->d_a_sa, T, G, B, 1, 32));      // (per-group records)
-        LAUNCH(K_LAYER, dc_launch_layer(st, fs, ss, wgr, la, l, s->d_a_sa, s->d_a_ca, (l == nl_run - 1) ? dbg.stage : 0,
-                                        ((l == 3 || l == 4) && want_stamps) ? s->d_stamps : nullptr, rec_stride, narrow, upc, g1_tiles));
+        if (!f.wgr) LAUNCH(K_COMBINE, dc_launch_attn_combine(st, fs, s->d_recs, s->d_a_sa, T, G, B, 1, 32));      // (per-group records)
+        LAUNCH(K_LAYER, dc_launch_layer(st, lf, la, l, s->d_a_sa, s->d_a_ca, (l == nl_run - 1) ? f.stop_stage : 0,
+                                        ((l == 3 || l == 4) && want_stamps) ? s->d_stamps : nullptr));
     }
     return DC_OK;
 }
@@ -946,29 +822,7 @@ int sync_out(dc_sampler* s, hipStream_t user) {
     return DC_OK;
 }
 
-int steps_per_graph(int S) {
-    if (S <= 64) return S;
-    for (int k = 64; k >= 1; --k)
-        if (S % k == 0) return k;
-    return 1;
-}
-
 // h_coef: [S][DC_COEF] per-timestep scalars (dc_common.h); flags: DC_UPD_*; d_step_noise: [S][B][Tx][P] or nullptr
-#ifndef DC_BF16_TAIL_DEFAULT
-#define DC_BF16_TAIL_DEFAULT 6
-#endif
-#ifndef DC_BF16_SHORT_CLIP
-#define DC_BF16_SHORT_CLIP 100     // bf16 precision: loops over clips of fewer frames run every evaluation split (loop_common)
-#endif
-}  // namespace
-extern "C" DC_EXPORT int32_t dc_precise_tail_default(int32_t precision);
-namespace {
-// split-operand evaluations (the precise tail, dc_sampler_set_precise_forward) exist for: fp16 / bf16 precision, linear attention, no test hooks
-bool can_split_steps(const dc_sampler* s, const Hooks& dbg) {
-    return (s->cfg.precision == DC_PREC_FP16 || s->cfg.precision == DC_PREC_BF16) && dbg.layers < 0 && dbg.first < 0 &&
-           dbg.stage == 0 && s->d_model_split;
-}
-
 int loop_common(dc_sampler* s, const float* d_noise, float* d_out, int S, const float* h_coef,
                 const int32_t* h_snap_iters, int n_snap, float* d_snaps_user, hipStream_t user, bool profile,
                 int flags = 0, const float* d_step_noise = nullptr) {
@@ -1047,26 +901,12 @@ int loop_common(dc_sampler* s, const float* d_noise, float* d_out, int S, const 
     HIP_TRY(hipMemsetAsync(s->d_iter, 0, 16, st));
     HIP_TRY(hipMemcpyAsync(s->d_x, d_noise, MP * 4, hipMemcpyDeviceToDevice, st));
     const bool no_graph = getenv("DC_DISABLE_GRAPH") != nullptr;
-    // precise tail: the loop's last `tail` model evaluations on split operands (dc_sampler_set_precise_tail; DC_PRECISE_TAIL=k overrides):
-    // fp16 / bf16 precision, linear attention, no test hooks
-    int tail = s->tail_split >= 0 ? s->tail_split : dc_precise_tail_default(s->cfg.precision);
-    bool tail_asked = s->tail_split >= 0;
-    if (const char* e = getenv("DC_PRECISE_TAIL")) tail = atoi(e), tail_asked = true;
-    // An EPSILON model's final sample is sqrt(1 / abar) x_t - sqrt(1 / abar - 1) eps, not the last evaluations' prediction: what the plain
-    // 16-bit evaluations left in x_t stays (eta = 0: fp16 1.4 - 1.8e-3 whatever the tail, tools/fuzz_sampler.py).  Parity first: unless a
-    // tail was asked for, such a loop runs EVERY evaluation on split operands (2.1e-4, at the split precisions' speed).
-    if (!tail_asked && (flags & DC_UPD_EPS)) tail = S;
-    // Clips of fewer than 100 frames in the bf16 precision: a clip's error is a norm over a few hundred numbers (26 per frame), and the worst of
-    // a batch of dozens of such clips reached 1.27e-3 with the default tail (39 clips of 36 frames, lengths down to 1: tools/fuzz_shapes.py,
-    // profiles/r06_fuzz_final.txt; 8.6e-4 at 39 frames, <= 7.2e-4 from 100 frames up).  Such loops are bound by launch latency, not by the
-    // kernels: they run every evaluation in the split form (the `mixed` precision's evaluations, 9e-5) unless a tail was asked for.
-    if (!tail_asked && s->cfg.precision == DC_PREC_BF16 && s->Tx < DC_BF16_SHORT_CLIP) tail = S;
-    // (clip strides that are not whole 32-frame groups - T = 900 x 128 unpadded - and short clips run the split evaluations in the
-    // per-group record form with its combine launches: no measurable cost at one evaluation per loop, 70.6 vs 70.6 ms at bs = 128 x 900)
-    if (!can_split_steps(s, Hooks{})) tail = 0;
-    // (a tail of the whole loop splits every replay's graph; any shorter one lives in the last replay and is clipped to its steps)
-    const bool tail_all = tail >= S;
-    tail = std::max(0, std::min(tail, std::min(S, steps_per_graph(S))));
+    // precise tail: the loop's last `tail` model evaluations on split operands (loop_tail, dc_form.h; DC_PRECISE_TAIL=k overrides)
+    const char* env_tail = getenv("DC_PRECISE_TAIL");
+    const LoopTail lt = loop_tail(settings_of(s), s->tail_split, env_tail ? std::optional<int>(atoi(env_tail)) : std::nullopt, flags, s->Tx, S);
+    const int tail = lt.tail;
+    const bool tail_all = lt.tail_all;
+    const Switches sw = Switches::read();
     // n steps of the loop, the last split_n of them on split operands (graph: the steps of a capture)
     bool folded = false;            // the last step enqueued looks its timestep up through *d_iter (StepDone::folded)
     auto enqueue_steps = [&](int n, int split_n, bool graph) -> int {
@@ -1076,7 +916,7 @@ int loop_common(dc_sampler* s, const float* d_noise, float* d_out, int S, const 
             c.loop_mode = true, c.x_src = c.x_dst = s->d_x, c.graph_step = graph ? i : -1, c.split = i >= n - split_n, c.g1_loop = tail > 0;
             c.next_plain = i + 1 < n - split_n, c.embedded = embedded, c.profile = profile;
             StepDone d;
-            if (int rc = enqueue_step(s, st, c, &d)) return rc;
+            if (int rc = enqueue_step(s, st, c, sw, &d)) return rc;
             embedded = d.embedded_next, folded = d.folded;
         }
         return DC_OK;
@@ -1092,7 +932,7 @@ int loop_common(dc_sampler* s, const float* d_noise, float* d_out, int S, const 
         const int launches = (tail && replays > 1) ? (part == 0 ? replays - 1 : 1) : replays;
         // (g1 bit: the plain evaluations of a loop WITH a tail read G' scale tiles, those of a loop without one G' - 1 tiles - two
         // different captures of the same part-0 graph when S > 64)
-        const unsigned long long fk = form_key(s) | ((unsigned long long)tail_here << 40) | ((tail > 0 ? 1ull : 0ull) << 39);
+        const unsigned long long fk = form_key(s, sw) | ((unsigned long long)tail_here << 40) | ((tail > 0 ? 1ull : 0ull) << 39);
         const dc_sampler::GraphKey key{s->B, s->T, s->Tx, K, fk};
         auto& gs = s->graphs;
         if (gs.empty() || gs.back().first != key) {
@@ -1161,8 +1001,8 @@ int denoise(dc_sampler* s, const float* d_x, const int32_t* h_timesteps, float* 
     HIP_TRY(hipMemcpyAsync(s->d_t_clip, h_timesteps, (size_t)s->B * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipStreamSynchronize(st));
     Step c;
-    c.x_src = d_x, c.x_dst = d_out, c.split = s->precise_forward && can_split_steps(s, dbg), c.dbg = dbg;
-    if ((rc = enqueue_step(s, st, c))) return rc;
+    c.x_src = d_x, c.x_dst = d_out, c.split = s->precise_forward && can_split_steps(settings_of(s), dbg), c.dbg = dbg;
+    if ((rc = enqueue_step(s, st, c, Switches::read()))) return rc;
     return sync_out(s, user);
 }
 
@@ -1179,6 +1019,8 @@ extern "C" {
 static_assert(DC_UPDATE_CLIP_DENOISED == DC_UPD_CLIP && DC_UPDATE_EPSILON == DC_UPD_EPS && DC_STATUS_F16_SATURATED == DC_STATUS_F16_SAT &&
                   DC_STATUS_TIMEOUT == DC_STATUS_SYNC_TIMEOUT,
               "include/dc_ddim.h and dc_common.h disagree");
+static_assert(DC_PREC_BF16 == DCF_BF16 && DC_PREC_MIXED == DCF_MIXED && DC_PREC_BF16X3 == DCF_BF16X3 && DC_PREC_FP16 == DCF_FP16,
+              "include/dc_ddim.h and dc_form.h disagree");
 
 const char* dc_last_error(void) { return g_err.c_str(); }
 const char* dc_version(void) { return "dc_ddim 0.1 (gfx950)"; }
@@ -1439,7 +1281,7 @@ int dc_sampler_set_precise_tail(dc_sampler* s, int32_t steps) {
 }
 
 int32_t dc_precise_tail_default(int32_t precision) {
-    return precision == DC_PREC_FP16 ? 1 : precision == DC_PREC_BF16 ? DC_BF16_TAIL_DEFAULT : 0;
+    return precise_tail_default(precision);
 }
 
 int dc_sampler_set_clip_aligned(dc_sampler* s, int32_t mode) {

@@ -1,0 +1,283 @@
+// dc_form.h - host-only: which form a denoiser evaluation takes (no kernels, no HIP call, no side effect).  step_form decides the
+// launch form of one evaluation from the geometry, the sampler's settings, the environment switches and the step's options;
+// clip_stride, steps_per_graph and loop_tail decide the workspace stride, the graph size and the precise tail of a loop.  dc_api.hip
+// launches what they say; tests/form_probe.cpp checks the rule on the CPU (tests/test_host_form.py).
+#pragma once
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <optional>
+#include <string>
+
+#include "dc_common.h"
+
+// dc_precision of include/dc_ddim.h (dc_api.hip asserts that the two agree)
+constexpr int DCF_BF16 = 0, DCF_MIXED = 1, DCF_BF16X3 = 2, DCF_FP16 = 3;
+
+// operand formats (0 = bf16, 1 = f16) and split flags of the 128-wide GEMMs and of the FiLM GEMM
+struct Formats {
+    int small_fmt = 0, film_fmt = 0;
+    bool split_small = false, split_film = false;
+    void set_precision(int precision) {
+        split_small = precision == DCF_MIXED || precision == DCF_BF16X3;
+        split_film = precision == DCF_BF16X3;
+        small_fmt = precision == DCF_FP16 ? 1 : 0;
+        film_fmt = (precision == DCF_FP16 || precision == DCF_MIXED) ? 1 : 0;
+    }
+};
+
+// The environment switches that select a launch form or a stride.  One list: the fields, read() and bits() are made from it, so a
+// switch step_form can see is in the graph key (form_key, dc_api.hip) by construction.  read() is called once per API call that
+// enqueues or sizes the workspace and is never cached: one process can A/B the switches between calls (a change re-captures).
+#define DC_FORM_SWITCHES(X)                                                                                                            \
+    X(no_wgrec, "DC_NO_WGREC") X(no_narrow, "DC_NO_NARROW") X(no_align, "DC_NO_ALIGN") X(align, "DC_ALIGN")                          \
+    X(no_fuse_embed, "DC_NO_FUSE_EMBED") X(film_static, "DC_FILM_STATIC") X(begin_step, "DC_BEGIN_STEP") X(no_pad, "DC_NO_PAD")      \
+    X(no_layer16, "DC_NO_LAYER16") X(l16_own_combine, "DC_L16_OWN_COMBINE") X(l16_test_drop_slice, "DC_L16_TEST_DROP_SLICE")         \
+    X(tail_film_bf16, "DC_TAIL_FILM_BF16") X(flat_units, "DC_FLAT_UNITS") X(no_embed_next, "DC_NO_EMBED_NEXT")
+struct Switches {
+#define X(field, name) bool field = false;
+    DC_FORM_SWITCHES(X)
+#undef X
+    static Switches read() {
+        Switches w;
+#define X(field, name) w.field = getenv(name) != nullptr;
+        DC_FORM_SWITCHES(X)
+#undef X
+        return w;
+    }
+    unsigned long long bits() const {      // one bit per switch, in the list's order (< 16 bits)
+        unsigned long long k = 0;
+        int i = 0;
+#define X(field, name) k |= (field ? 1ull : 0ull) << i++;
+        DC_FORM_SWITCHES(X)
+#undef X
+        return k;
+    }
+};
+
+// unit records (floats) the workspace holds for `g` token groups: per-group form 2 slots per group; workgroup-record forms two
+// alternating buffers of 2 slots per workgroup, i.e. 4 * nwg records with nwg <= ceil(g / 4) (narrow flat units) or B * ceil(T / 128)
+// (clip-aligned): both <= g for the T >= 256 those forms need - sized for the larger of the two explicitly, and checked against the
+// launch form in step_form
+inline size_t rec_capacity(size_t g) { return std::max(g * 2, 4 * ((g + 3) / 4) + 8) * DC_REC_FLOATS; }
+
+struct Geometry {
+    int B = 0, T = 0, Tx = 0, G = 0;      // clips, clip stride (clip_stride), the caller's frames per clip, 32-token groups
+    int num_cu = 0;
+    size_t cap_rec_floats = 0;            // rec_capacity of the workspace
+};
+
+// what the rule reads of a sampler
+struct Settings {
+    int precision = DCF_FP16;
+    Formats fmt;
+    bool no_eff = false;
+    int clip_aligned = -1;                // dc_sampler_set_clip_aligned
+    bool l16_own = false;                 // dc_sampler_set_combine_exchange(s, 0), or latched after a timeout
+    int num_layers = 0;
+    bool split_model = false;             // the model record with the split stage images exists (fp16 / bf16 precision, on a device)
+    bool film_w16 = false, film_w16_tail = false;      // DcModel::film_w16 / film_w16_tail exist
+    int l16_max_units = 0;                // dc_layer16_max_units()
+};
+
+// Test hooks of one evaluation (dc_sampler_debug_denoise, dc_sampler_debug_layer); the defaults run the production evaluation
+struct Hooks {
+    int layers = -1, stage = 0;   // run the first `layers` layers, the last of them up to `stage` (| (first stage - 1) << 16)
+    int first = -1;               // start at this layer from the residual stream in d_h
+    bool production() const { return layers < 0 && stage == 0 && first < 0; }
+};
+
+// The part of one enqueue_step call that decides its form (dc_api.hip's Step adds the tensors)
+struct StepOpts {
+    bool loop_mode = false;       // a loop's step: the last layer applies the DDIM update to x_src
+    int graph_step = -1;          // >= 0: step number inside a graph being captured
+    bool split = false;           // this evaluation's 128-wide GEMMs on split operands (the fp16 images' hi + lo halves)
+    bool g1_loop = false;         // a loop with a precise tail: its plain-operand evaluations read G' scale tiles
+    bool next_plain = false;      // loops: another step follows in this enqueue sequence (same graph) and it is a plain-operand evaluation
+    bool embedded = false;        // the previous step's last layer has embedded x and run layer 0's front half for this step
+    bool profile = false;         // events around every launch
+    Hooks dbg;
+};
+
+struct StepForm {
+    std::string error;            // not empty: the step is refused (DC_ERR_INVALID) and nothing below `rec_stride` is decided
+    bool ss = false;              // the 128-wide GEMMs run on split operands (a split format, or a split evaluation of the precise tail)
+    bool film_tail = false;       // bf16 precision, split evaluations: the f16 FiLM image - the step is then exactly a "mixed" evaluation
+    int fs = 0, ff = 0;           // operand formats of the 128-wide GEMMs and of the FiLM GEMM
+    bool fuse_silu = false;       // the FiLM GEMM produces its own operand from pp + temb (no k_silu_emb pass)
+    bool folded = false;          // the step's kernels look their timestep up through *d_iter (no k_begin_step launch)
+    bool adapt = false;           // adaptive work shares of the persistent FiLM GEMM
+    bool wgr = false, narrow = false, aligned = false, layer16 = false, l16_shared = false;
+    int upc = 0, upc16 = 0, upc_narrow = 0, nwg = 0;
+    size_t rec_stride = 0;        // floats between the two alternating unit-record buffers (0 = single buffer, per-group records)
+    bool mixed_form = false, embed_next = false, fuse_embed = false, fuse_extra = false, g1_tiles = false;
+    int upd_flags = 0;            // DC_UPD_* bits the form adds to the loop's (TEST_DROP_SLICE, EMBED_NEXT)
+    int nl_run = 0, stop_stage = 0;      // layers to run; the stop stage handed to the last of them (0 = the whole layer)
+};
+
+// split-operand evaluations (the precise tail, dc_sampler_set_precise_forward) exist for: fp16 / bf16 precision, no test hooks
+inline bool can_split_steps(const Settings& s, const Hooks& dbg) {
+    return (s.precision == DCF_FP16 || s.precision == DCF_BF16) && dbg.production() && s.split_model;
+}
+
+// One denoiser evaluation (+ DDIM update when loop_mode).  `stamps`: the process collects clock stamps (DC_STAMPS).
+// graph_step >= 0: step number inside a graph being captured.  On the default path (fused SiLU fill, per-layer launches) the
+// step's kernels then look the timestep / DDIM scalars up themselves - this step's slot of the per-iteration tables, offset by
+// the iteration at which the replay began (*d_iter, advanced once per replay) - and the per-step bookkeeping launch
+// (k_begin_step, 5 us + a launch gap) is dropped: `folded`.
+inline StepForm step_form(const Geometry& g, const Settings& s, const Switches& w, const StepOpts& o, bool stamps) {
+    StepForm f;
+    const int B = g.B, T = g.T, G = g.G;
+    const Hooks& dbg = o.dbg;
+    // "no test hook, no stamps": what the production-only forms below ask for.  Conditions that name single hooks instead are meant
+    // as they stand, and say why.
+    const bool quiet = dbg.production() && !stamps;
+    const bool ss = f.ss = s.fmt.split_small || o.split, sf = s.fmt.split_film;
+    f.film_tail = o.split && !s.fmt.split_small && s.film_w16_tail && !w.tail_film_bf16;
+    const int fs = f.fs = s.fmt.small_fmt, ff = f.ff = f.film_tail ? 1 : s.fmt.film_fmt;
+    // non-split formats: the FiLM GEMM produces its own operand from pp + temb (no k_silu_emb pass); the separate pass
+    // remains for the split formats, for the v1 kernel, and under the test hooks that read the operand image back
+    // (`layers` alone: `stage` stops inside a layer, after the GEMM; `first` never comes without `layers`, dc_sampler_debug_layer)
+    const bool fuse_silu = f.fuse_silu = !sf && dbg.layers < 0;
+    // (`stage` beside fuse_silu's `layers`; `first` never comes without `layers`.  Captured steps are loop steps and carry no hook anyway)
+    f.folded = o.loop_mode && o.graph_step >= 0 && fuse_silu && !s.no_eff && !w.begin_step && dbg.stage == 0;
+    // adaptive work shares of the persistent FiLM GEMM (dc_kernels.hip, film_shares); DC_FILM_STATIC=1 keeps equal shares
+    f.adapt = !w.film_static && g.num_cu <= 1024;
+    f.nl_run = (dbg.layers >= 0 && dbg.layers < s.num_layers) ? dbg.layers : s.num_layers;
+    // (full attention: the last layer of a shortened run stops after its FFN block)
+    f.stop_stage = s.no_eff ? (dbg.stage ? dbg.stage : (f.nl_run < s.num_layers ? 3 : 0)) : dbg.stage;
+    // ---- form of the layer launches (linear attention) --------------------------------------------------------------------
+    // workgroup-level records (no combine launches) whenever a workgroup's 256 tokens cannot touch more than two clips
+    // (`first` alone: k_front_from_h, which starts a run at a later layer, writes per-group records only.  Split formats: on
+    // clip-aligned units only - the doubled weight images leave LDS for ONE clip's attention fragments - and in the production build
+    // only: the test hooks keep the per-group form)
+    const bool wgr = f.wgr = T >= 256 && !w.no_wgrec && dbg.first < 0 && !s.no_eff && (!ss || (T % 32 == 0 && dbg.production() && !w.no_align));
+    // Narrow workgroups (4 waves = 128-token units, one wave per SIMD) while every unit still gets a CU of its own: the layer
+    // kernel is bound by instruction issue, so a wave alone on its SIMD runs a layer in about half the time (DESIGN.md
+    // section 4).  T <= 3840: the narrow combine holds 32 units per clip.  DC_NO_NARROW=1 keeps the 8-wave form.
+    // Clip-aligned units (WgMap in dc_dev.h; needs a clip stride of whole groups): upc workgroups per clip, no workgroup spans two
+    // clips.  Default for the narrow (small-batch) form; with the chip full (bs=32 x 1800: 256 workgroups instead of 228 flat
+    // units) it measured 1.2 % slower than flat units - DC_ALIGN=1 forces it there.
+    const bool can_align = wgr && T % 32 == 0 && !w.no_align;
+    const int upc_wide = (T + 255) / 256, upc_narrow = f.upc_narrow = (T + 127) / 128;
+    const bool aligned_env = can_align && w.align;
+    const int nwg_narrow = can_align ? B * upc_narrow : (G + 3) / 4;
+    const bool narrow = f.narrow = wgr && !ss && nwg_narrow <= g.num_cu && T <= 3840 && quiet && !w.no_narrow;
+    // ... and for the wide (chip-full) form whenever the clip-aligned launch needs no more rounds of workgroups over the chip than the flat
+    // one (bs = 32 x 1800: 256 workgroups instead of 228, one round either way): a clip's result is then bit-identical whatever the
+    // batch around it - the reference's semantics (transformer.py:111: the key softmax is per clip) - for +1.6 ... +2.1 % per loop
+    // (profiles/r06_ab_align.txt).  Where it would cost a round (bs = 35 x 1800: 280 against 250 workgroups on 256 CUs) flat units stay -
+    // a clip then depends on its neighbours at the rounding level (4e-4).  dc_sampler_set_clip_aligned: 1 forces
+    // aligned units, 0 flat ones; DC_ALIGN=1 / DC_FLAT_UNITS=1 in the environment do the same per process.
+    const int nwg_flat = (G + 7) / 8, ncu = g.num_cu > 0 ? g.num_cu : 256;
+    const bool same_rounds = ((long long)B * upc_wide + ncu - 1) / ncu == ((long long)nwg_flat + ncu - 1) / ncu;
+    const bool aligned_wide = s.clip_aligned > 0 || aligned_env || (s.clip_aligned < 0 && same_rounds && !w.flat_units);
+    const bool aligned = f.aligned = can_align && (narrow || ss || aligned_wide);
+    // 16-token waves (dc_layer16.hip) while every clip-aligned 64-token unit still gets a CU of its own (bs <= 8 at T = 1800): in that
+    // regime the layer is bound by the LENGTH of one wave's dependency chain, and a 16-token wave's is about half as long.  The
+    // embedding stays the narrow 32-token form (its 128-token unit records feed layer 0).  DC_NO_LAYER16=1 keeps the 32-token form.
+    // (`first` is what k_layer16 itself cannot do - it has no stop stage either, but `narrow` has already excluded every hook)
+    const int upc16 = f.upc16 = (T + 63) / 64;
+    const bool layer16 = f.layer16 = narrow && aligned && (long long)B * upc16 <= g.num_cu && upc16 <= s.l16_max_units && dbg.first < 0 && !w.no_layer16;
+    const int upc = f.upc = aligned ? (narrow ? upc_narrow : upc_wide) : 0;
+    const int nwg = f.nwg = aligned ? B * upc : (narrow ? (G + 3) / 4 : (G + 7) / 8);
+    // k_layer16: the clip's workgroups share the combine of the previous layer's unit records inside the launch (dc_layer16.hip;
+    // DC_L16_OWN_COMBINE=1: every workgroup combines alone, round 4's form)
+    f.l16_shared = layer16 && !s.l16_own && !w.l16_own_combine;
+    f.rec_stride = wgr ? (size_t)nwg * 2 * DC_REC_FLOATS : 0;
+    // (the kernels write records at recs + rec_stride + wg * 2 * DC_REC_FLOATS: both alternating buffers must lie inside d_recs)
+    const size_t rec_floats = wgr ? 2 * f.rec_stride : (size_t)G * 2 * DC_REC_FLOATS;
+    if (rec_floats > g.cap_rec_floats) {
+        char buf[160];
+        snprintf(buf, sizeof buf, "unit records of this launch form (%zu floats) exceed the workspace (%zu)", rec_floats, g.cap_rec_floats);
+        f.error = buf;
+        return f;
+    }
+    // k_embed_front rides in the FiLM GEMM's launch (wide flat units, non-split formats, no test hooks; DC_NO_FUSE_EMBED=1 and the
+    // per-kernel profile pass keep the two launches): one kernel boundary less per step, -1.3 % per loop at bs=32
+    // (flat units in the non-split formats; the "mixed" mode - f16 GEMM, split-bf16 embedding - on its clip-aligned units)
+    const bool mixed_form = f.mixed_form = ss && !sf && ff == 1 && fs == 0;
+    // The last layer of a plain wide step does the NEXT step's front work (embedding of x_{t-1} + layer 0's self-attention front half:
+    // k_layer, DC_UPD_EMBED_NEXT) when that step is a plain wide step of the same enqueue sequence; its FiLM launch is then the bare GEMM
+    // and it has no front launch.  DC_NO_EMBED_NEXT=1 keeps the front work in every step's own FiLM launch.
+    const bool wide_plain = wgr && !narrow && !ss && fuse_silu && ff == fs && quiet && !s.no_eff;
+    f.embed_next = !w.no_embed_next && o.loop_mode && o.next_plain && wide_plain;
+    if (o.embedded && !(o.loop_mode && wide_plain)) {
+        f.error = "internal: a step whose front work was done by its predecessor changed its launch form";
+        return f;
+    }
+    f.fuse_embed = !o.embedded && wgr && !narrow && (ss ? (aligned && mixed_form) : ff == fs) && fuse_silu && quiet && nwg <= g.num_cu &&
+                   !o.profile && !w.no_fuse_embed;
+    // small batches (narrow clip-aligned units): the embedding's workgroups ride BEHIND the GEMM's in the FiLM launch
+    // (film_extra_workgroups, dc_kernels.hip): one launch (15 us at one clip) and one kernel boundary less per step.  DC_NO_FUSE_EMBED=1 keeps the two launches.
+    // (`first`: there is no embedding to fuse when the run starts from d_h; `narrow` has already excluded every hook)
+    f.fuse_extra = narrow && aligned && !ss && ff == fs && fuse_silu && s.film_w16 && dbg.first < 0 && !o.profile && !w.no_fuse_embed;
+    f.upd_flags = (w.l16_test_drop_slice ? DC_UPD_TEST_DROP_SLICE : 0) | (f.embed_next ? DC_UPD_EMBED_NEXT : 0);
+    // scale tiles: G' for the plain-operand consumers of this step, G' - 1 for the split-operand ones (dc_dev.h, film_affine)
+    // (the production forms of the plain-operand kernels only: test hooks, stamps and the per-group record form keep G' - 1)
+#ifndef DC_NO_FILM_G1
+    f.g1_tiles = o.g1_loop && !ss && wgr && !s.no_eff && quiet;
+#endif
+    return f;
+}
+
+// Clip stride of the internal token space.  Where the workgroup-record kernels can run (non-split formats, linear attention,
+// Tx >= 256) a clip may be padded to whole 32-token groups, so that no group spans two clips (the padding frames behave like
+// frames past `length`).  Measured (same box): bs=32 x 1800 (+1.3 % tokens) -1.6 % per loop; bs=128 x 900
+// (+3.1 %) +0.2 %; small batches, which then also run clip-aligned units (step_form), -9 % at bs=4 x 1800.
+inline int clip_stride(const Settings& s, const Switches& w, int B, int Tx, int num_cu) {
+    // clips shorter than one 32-token group: one group per clip (a group's records name at most two clips)
+    if (Tx < 32 && !s.no_eff && !w.no_pad) return 32;
+    if (s.no_eff || Tx < 256 || Tx % 32 == 0 || w.no_pad) return Tx;
+    const int Tp = (Tx + 31) / 32 * 32;
+    if (s.fmt.split_small) return Tp;      // split formats: workgroup records exist on clip-aligned units only (one clip per workgroup)
+    const bool small_batch = (long long)B * ((Tp + 127) / 128) <= num_cu;       // narrow, clip-aligned workgroups
+    // ... unless the padding frames cost the layer launches a whole extra round of workgroups (256 tokens each, one per CU): 36 clips of
+    // 1800 frames are 254 workgroups, of 1824 frames 257 - 38 vs 51 ms per loop (profiles/r05_big_batches.md)
+    const auto rounds = [&](int T) { return (((long long)B * T + 255) / 256 + num_cu - 1) / num_cu; };
+    if (!small_batch && rounds(Tp) > rounds(Tx)) return Tx;
+    return (small_batch || (Tp - Tx) * 50 <= Tx) ? Tp : Tx;
+}
+
+// steps of a loop one captured graph holds: the whole loop up to 64 steps, else the largest divisor of S up to 64
+inline int steps_per_graph(int S) {
+    if (S <= 64) return S;
+    for (int k = 64; k >= 1; --k)
+        if (S % k == 0) return k;
+    return 1;
+}
+
+#ifndef DC_BF16_TAIL_DEFAULT
+#define DC_BF16_TAIL_DEFAULT 6
+#endif
+#ifndef DC_BF16_SHORT_CLIP
+#define DC_BF16_SHORT_CLIP 100     // bf16 precision: loops over clips of fewer frames run every evaluation split (loop_tail)
+#endif
+inline int precise_tail_default(int precision) { return precision == DCF_FP16 ? 1 : precision == DCF_BF16 ? DC_BF16_TAIL_DEFAULT : 0; }
+
+// Precise tail of a loop of S steps: its last `tail` model evaluations run on split operands (tail_split: dc_sampler_set_precise_tail,
+// -1 = by precision; env_tail: DC_PRECISE_TAIL=k, which overrides it; flags: DC_UPD_*): fp16 / bf16 precision, no test hooks.
+struct LoopTail {
+    int tail;          // split evaluations at the end of the loop's last graph (0 ... steps_per_graph(S))
+    bool tail_all;     // every evaluation of the loop is split (every replay's graph, then)
+};
+inline LoopTail loop_tail(const Settings& s, int tail_split, std::optional<int> env_tail, int flags, int Tx, int S) {
+    int tail = tail_split >= 0 ? tail_split : precise_tail_default(s.precision);
+    bool tail_asked = tail_split >= 0;
+    if (env_tail) tail = *env_tail, tail_asked = true;
+    // An EPSILON model's final sample is sqrt(1 / abar) x_t - sqrt(1 / abar - 1) eps, not the last evaluations' prediction: what the plain
+    // 16-bit evaluations left in x_t stays (eta = 0: fp16 1.4 - 1.8e-3 whatever the tail, tools/fuzz_sampler.py).  Parity first: unless a
+    // tail was asked for, such a loop runs EVERY evaluation on split operands (2.1e-4, at the split precisions' speed).
+    if (!tail_asked && (flags & DC_UPD_EPS)) tail = S;
+    // Clips of fewer than 100 frames in the bf16 precision: a clip's error is a norm over a few hundred numbers (26 per frame), and the worst of
+    // a batch of dozens of such clips reached 1.27e-3 with the default tail (39 clips of 36 frames, lengths down to 1: tools/fuzz_shapes.py,
+    // profiles/r06_fuzz_final.txt; 8.6e-4 at 39 frames, <= 7.2e-4 from 100 frames up).  Such loops are bound by launch latency, not by the
+    // kernels: they run every evaluation in the split form (the `mixed` precision's evaluations, 9e-5) unless a tail was asked for.
+    if (!tail_asked && s.precision == DCF_BF16 && Tx < DC_BF16_SHORT_CLIP) tail = S;
+    // (clip strides that are not whole 32-frame groups - T = 900 x 128 unpadded - and short clips run the split evaluations in the
+    // per-group record form with its combine launches: no measurable cost at one evaluation per loop, 70.6 vs 70.6 ms at bs = 128 x 900)
+    if (!can_split_steps(s, Hooks{})) tail = 0;
+    // (a tail of the whole loop splits every replay's graph; any shorter one lives in the last replay and is clipped to its steps)
+    const bool tail_all = tail >= S;
+    return {std::max(0, std::min(tail, std::min(S, steps_per_graph(S)))), tail_all};
+}

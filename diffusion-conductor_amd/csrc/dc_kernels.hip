@@ -2869,24 +2869,18 @@ static hipError_t launch_embed_t(hipStream_t st, const DcModel* dm, const float*
                                                                                                                          clk, 0, Tx, WGR ? upc : 0);
     return hipGetLastError();
 }
-hipError_t dc_launch_embed_front(hipStream_t st, int fmt, bool split, bool wgr, const DcModel* dm, const float* x, float* hbuf,
-                                 float* recs, const int* length, int M, int T, int G, int B, unsigned long long* clk, bool narrow, int Tx, int upc) {
-    hipError_t e = hipSuccess;
-    if (wgr && !split && narrow)
-        return fmt == 1 ? launch_embed_t<_Float16, false, true, true>(st, dm, x, hbuf, recs, length, M, T, G, B, clk, Tx, upc)
-                        : launch_embed_t<__bf16, false, true, true>(st, dm, x, hbuf, recs, length, M, T, G, B, clk, Tx, upc);
-    if (wgr && !split) {
-        e = fmt == 1 ? launch_embed_t<_Float16, false, true>(st, dm, x, hbuf, recs, length, M, T, G, B, clk, Tx, upc)
-                     : launch_embed_t<__bf16, false, true>(st, dm, x, hbuf, recs, length, M, T, G, B, clk, Tx, upc);
-        return e;
-    }
-    if (wgr) {            // split formats: workgroup records on clip-aligned units only (one clip per workgroup)
-        if (upc <= 0) return hipErrorInvalidValue;
-        return fmt == 1 ? launch_embed_t<_Float16, true, true>(st, dm, x, hbuf, recs, length, M, T, G, B, clk, Tx, upc)
-                        : launch_embed_t<__bf16, true, true>(st, dm, x, hbuf, recs, length, M, T, G, B, clk, Tx, upc);
-    }
-    DISPATCH(fmt, split, (e = launch_embed_t<T16, SP, false>(st, dm, x, hbuf, recs, length, M, T, G, B, clk, Tx, upc)));
-    return e;
+// k_embed_front as <split, wgr, narrow>: the instantiations that exist (each for both operand formats)
+#define EMBED_FORMS(X) X(false, false, false) X(true, false, false) X(false, true, false) X(false, true, true) X(true, true, false)
+hipError_t dc_launch_embed_front(hipStream_t st, const DcLayerForm& f, const DcModel* dm, const float* x, float* hbuf, float* recs,
+                                 const int* length, int M, int T, int G, int B, unsigned long long* clk, int Tx) {
+    if (f.wgr && f.split && f.upc <= 0) return hipErrorInvalidValue;      // split formats: workgroup records on clip-aligned units only
+#define X(SP, WGR, NARROW)                                                                                      \
+    if (f.split == SP && f.wgr == WGR && f.narrow == NARROW)                                                    \
+        return (f.fmt == 1 ? launch_embed_t<_Float16, SP, WGR, NARROW> : launch_embed_t<__bf16, SP, WGR, NARROW>)( \
+            st, dm, x, hbuf, recs, length, M, T, G, B, clk, Tx, f.upc);
+    EMBED_FORMS(X)
+#undef X
+    return hipErrorInvalidValue;
 }
 
 template <class T16, bool SP, bool DBG, bool STAMP, bool WGR, bool NARROW = false, bool G1 = false>
@@ -2903,41 +2897,26 @@ static hipError_t launch_layer_t(hipStream_t st, const DcLayerArgs& a, int l, co
     return hipGetLastError();
 }
 
-hipError_t dc_launch_layer(hipStream_t st, int fmt, bool split, bool wgr, const DcLayerArgs& a, int l, const void* a_sa, const void* a_ca,
-                           int dbg, unsigned long long* stamps, size_t rec_stride, bool narrow, int upc, bool g1) {
-    using Launch = hipError_t (*)(hipStream_t, const DcLayerArgs&, int, const void*, const void*, int, unsigned long long*, size_t, int);
-    const bool f16 = fmt == 1;
-    Launch f;
-    // (g1: the FiLM scale tiles of this evaluation hold G' - the two production forms of the plain-operand kernel only)
-    if (g1 && !(wgr && !split && dbg == 0 && stamps == nullptr)) return hipErrorInvalidValue;
-    if (wgr && !split && narrow && dbg == 0 && stamps == nullptr) {      // narrow workgroups: production build only
-        if (g1)
-            f = f16 ? launch_layer_t<_Float16, false, false, false, true, true, true> : launch_layer_t<__bf16, false, false, false, true, true, true>;
-        else
-            f = f16 ? launch_layer_t<_Float16, false, false, false, true, true> : launch_layer_t<__bf16, false, false, false, true, true>;
-    } else if (wgr && !split && g1) {
-        f = f16 ? launch_layer_t<_Float16, false, false, false, true, false, true> : launch_layer_t<__bf16, false, false, false, true, false, true>;
-    } else if (wgr && !split) {        // workgroup-level records + in-kernel combine (non-split formats, T >= 256)
-        if (dbg != 0)
-            f = f16 ? launch_layer_t<_Float16, false, true, false, true> : launch_layer_t<__bf16, false, true, false, true>;
-        else if (stamps != nullptr)
-            f = f16 ? launch_layer_t<_Float16, false, false, true, true> : launch_layer_t<__bf16, false, false, true, true>;
-        else
-            f = f16 ? launch_layer_t<_Float16, false, false, false, true> : launch_layer_t<__bf16, false, false, false, true>;
-    } else if (wgr) {            // split formats: workgroup records + in-kernel combine on clip-aligned units (production build only)
-        if (upc <= 0 || dbg != 0) return hipErrorInvalidValue;
-        if (stamps != nullptr)
-            f = f16 ? launch_layer_t<_Float16, true, false, true, true> : launch_layer_t<__bf16, true, false, true, true>;
-        else
-            f = f16 ? launch_layer_t<_Float16, true, false, false, true> : launch_layer_t<__bf16, true, false, false, true>;
-    } else if (dbg != 0) {
-        DISPATCH(fmt, split, (f = launch_layer_t<T16, SP, true, false, false>));
-    } else if (stamps != nullptr) {
-        DISPATCH(fmt, split, (f = launch_layer_t<T16, SP, false, true, false>));
-    } else {
-        DISPATCH(fmt, split, (f = launch_layer_t<T16, SP, false, false, false>));
-    }
-    return f(st, a, l, a_sa, a_ca, dbg, stamps, rec_stride, upc);
+// k_layer as <split, stop stage, stamps, wgr, narrow, g1>: the instantiations that exist (each for both operand formats).
+// Narrow workgroups and G' scale tiles: the production forms of the plain-operand kernel only; no stop stage with the split
+// formats' workgroup records.
+#define LAYER_FORMS(X)                                                                                          \
+    X(false, false, false, false, false, false) X(false, true, false, false, false, false) X(false, false, true, false, false, false) \
+    X(true, false, false, false, false, false) X(true, true, false, false, false, false) X(true, false, true, false, false, false)    \
+    X(false, false, false, true, false, false) X(false, true, false, true, false, false) X(false, false, true, true, false, false)    \
+    X(false, false, false, true, false, true) X(false, false, false, true, true, false) X(false, false, false, true, true, true)      \
+    X(true, false, false, true, false, false) X(true, false, true, true, false, false)
+hipError_t dc_launch_layer(hipStream_t st, const DcLayerForm& f, const DcLayerArgs& a, int l, const void* a_sa, const void* a_ca, int dbg,
+                           unsigned long long* stamps) {
+    if (f.wgr && f.split && f.upc <= 0) return hipErrorInvalidValue;      // split formats: workgroup records on clip-aligned units only
+    const bool stop = dbg != 0, stamp = stamps != nullptr && !stop;       // (a stopped layer takes no stamps)
+#define X(SP, DBG, STAMP, WGR, NARROW, G1)                                                                      \
+    if (f.split == SP && stop == DBG && stamp == STAMP && f.wgr == WGR && f.narrow == NARROW && f.g1 == G1)     \
+        return (f.fmt == 1 ? launch_layer_t<_Float16, SP, DBG, STAMP, WGR, NARROW, G1> : launch_layer_t<__bf16, SP, DBG, STAMP, WGR, NARROW, G1>)( \
+            st, a, l, a_sa, a_ca, dbg, stamps, f.rec_stride, f.upc);
+    LAYER_FORMS(X)
+#undef X
+    return hipErrorInvalidValue;
 }
 
 // ---- no_eff variant ------------------------------------------------------------------

@@ -44,14 +44,22 @@ struct DcFilmArgs {
     int* status;                 // device status word: DC_STATUS_F16_SAT is OR-ed in when a tile leaves the fp16 range, or nullptr
 };
 hipError_t dc_launch_film_gemm(hipStream_t st, int fmt, bool split, const DcFilmArgs& a);
-// wgr: workgroup-level partial records, combined by the consuming layer kernel itself (non-split formats and T >= 256 only;
-// no dc_launch_attn_combine between the layers then)
-hipError_t dc_launch_embed_front(hipStream_t st, int fmt, bool split, bool wgr, const DcModel* dm, const float* x, float* hbuf, float* recs,
+// The form of one step's k_embed_front / k_layer launches, as step_form decided it (dc_form.h).  The launchers pick the kernel
+// instantiation from a table of the forms that exist; any other combination is hipErrorInvalidValue.
+struct DcLayerForm {
+    int fmt;
+    bool split;
+    bool wgr;            // workgroup-level partial records, combined by the consuming layer kernel itself (T >= 256 only; no
+                         // dc_launch_attn_combine between the layers then).  Split formats: on clip-aligned units only (upc > 0)
+    bool narrow;         // wgr, non-split, no stop stage, no stamps: 4-wave workgroups = 128-token units (small batches)
+    bool g1;             // the FiLM scale tiles hold G' (film_affine in dc_dev.h; plain-operand production forms of k_layer only)
+    int upc;             // wgr: workgroups per clip (clip-aligned units, WgMap in dc_dev.h), grid = B * upc; else 0
+    size_t rec_stride;   // floats between the two alternating unit-record buffers, in units of the form (0 = single buffer, non-wgr)
+};
+hipError_t dc_launch_embed_front(hipStream_t st, const DcLayerForm& f, const DcModel* dm, const float* x, float* hbuf, float* recs,
                                  const int* length, int M, int T, int G, int B,
                                  unsigned long long* clk /* diagnostic stamps (8 slots) or nullptr */,
-                                 bool narrow /* wgr, non-split: 4-wave workgroups = 128-token units (small batches) */,
-                                 int Tx /* frames per clip of x (<= the clip stride T) */,
-                                 int upc /* wgr: workgroups per clip (clip-aligned units, WgMap in dc_dev.h), grid = B * upc; else 0 */);
+                                 int Tx /* frames per clip of x (<= the clip stride T) */);
 // test hook: front half of layer l0 from the residual stream as it stands in hbuf (per-group records)
 hipError_t dc_launch_front_from_h(hipStream_t st, int fmt, bool split, const DcModel* dm, float* hbuf, float* recs, const int* length,
                                   int M, int T, int G, int B, int l0);
@@ -74,11 +82,9 @@ struct DcLayerArgs {
     int Tx;                      // frames per clip of xin / xout / snaps
     DcUpdate upd;                // options of the fused DDIM update + the status word (dc_common.h)
 };
-hipError_t dc_launch_layer(hipStream_t st, int fmt, bool split, bool wgr, const DcLayerArgs& a, int l, const void* a_sa, const void* a_ca,
-                           int dbg, unsigned long long* stamps, size_t rec_stride,
-                           bool narrow /* wgr, non-split, dbg == 0: 4-wave workgroups; recs / rec_stride then count 128-token units */,
-                           int upc /* as dc_launch_embed_front */,
-                           bool g1 /* the FiLM scale tiles hold G' (film_affine in dc_dev.h; plain-operand production forms only) */);
+hipError_t dc_launch_layer(hipStream_t st, const DcLayerForm& f, const DcLayerArgs& a, int l, const void* a_sa, const void* a_ca,
+                           int dbg /* stop stage of this layer (test hook), 0 = the whole layer */,
+                           unsigned long long* stamps /* diagnostic stage stamps or nullptr */);
 // The same layer for SMALL batches on 16-token waves (dc_layer16.hip): non-split formats, clip-aligned 64-token units (grid = B * upc,
 // upc = ceil(T / 64), T = clip stride, a multiple of 32), one unit record per workgroup.  a_ca16 = the cross-attention fragments in
 // that kernel's form (dc_launch_cond_af16, once per conditioning).  nu_in / stride_in: unit records per clip and floats per unit of
@@ -100,7 +106,6 @@ hipError_t dc_launch_step_noise(hipStream_t st, float* z, size_t n, unsigned lon
                                 int step, const int* snap_cur, unsigned long long first);
 // diagnosis: OR DC_STATUS_F16_SAT into *status when the fp16 buffer e holds an inf / nan
 hipError_t dc_launch_scan_f16(hipStream_t st, const void* e, size_t bytes, int* status);
-// rec_stride: floats between the two alternating unit-record buffers (0 = single buffer, non-wgr)
 
 // ---- no_eff variant (full T x T attention).  KT = key tiles per clip array.  split: the 128-wide GEMMs on split operands (`dm` is then
 // the model record with the split stage images); the attention's own operands stay plain 16-bit.

@@ -43,7 +43,7 @@ class DcError(RuntimeError):
 
 
 SOURCES = ("dc_kernels.hip", "dc_api.hip", "dc_music.hip", "dc_layer16.hip", "dc_stgcn.hip")
-HEADERS = ("dc_common.h", "dc_dev.h", "dc_launch.h", "dc_music.h", "dc_pack.h")
+HEADERS = ("dc_common.h", "dc_dev.h", "dc_form.h", "dc_launch.h", "dc_music.h", "dc_pack.h")
 EXTRA_FLAGS = {}      # per-source compiler flags
 
 
