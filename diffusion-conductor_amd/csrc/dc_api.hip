@@ -274,13 +274,19 @@ void fold_ln(const float* w, const float* c, const float* g, const float* b, int
 }
 
 // `linear` with the mean over its 512 outputs taken off (the LayerNorm in front of the cross-attention K / V projections sees
-// linear(x) - mean = Wc x + bc), and that LayerNorm's variance as a quadratic form of the 64 inputs (DcModel::lin_gram)
+// linear(x) - mean = Wc x + bc), and that LayerNorm's variance as a quadratic form of the 64 inputs (DcModel::lin_gram).
+// The inputs are shifted first: with u the least-squares solution of Wc u = bc, rounded to fp32, and r = bc - Wc u,
+//   Wc x + bc = Wc (x + u) + r      exactly, for any u,
+// and r is orthogonal to Wc's columns but for u's rounding.  The part of bc that lies in the column space of Wc - the part an x near
+// -u cancels against, term by term, in every sum over the 64 features - is taken off in ONE fp32 addition per feature, exact where
+// it cancels most (x_i within a factor 2 of -u_i); the sums then run over x + u and their constants come from r: d = W' r,
+// gv = Wc^T r / 512 ~ 0, c = |r|^2 / 512, so that var = (x + u)^T Gc (x + u) + c is a sum of two non-negative terms.
 struct LinearStats {
-    std::vector<double> wc, bc;      // [512][64], [512]
-    std::vector<float> gram;         // [64][64] Gc, gv[64], c
+    std::vector<double> wc, bc;      // [512][64], [512] r = bc - Wc shift
+    std::vector<float> gram;         // [64][64] Gc, gv[64], c, (3 unused), shift[64]: DC_GRAM_FLOATS
 };
 LinearStats centre_linear(const float* w /*[512][64]*/, const float* b) {
-    LinearStats s{std::vector<double>((size_t)512 * 64), std::vector<double>(512), std::vector<float>(64 * 64 + 64 + 1)};
+    LinearStats s{std::vector<double>((size_t)512 * 64), std::vector<double>(512), std::vector<float>(DC_GRAM_FLOATS, 0.f)};
     double bm = 0.0;
     for (int k = 0; k < 512; ++k) bm += b[k];
     bm /= 512.0;
@@ -291,12 +297,53 @@ LinearStats centre_linear(const float* w /*[512][64]*/, const float* b) {
         wm /= 512.0;
         for (int k = 0; k < 512; ++k) s.wc[(size_t)k * 64 + i] = (double)w[(size_t)k * 64 + i] - wm;
     }
+    std::vector<double> n((size_t)64 * 64), rhs(64);      // normal equations Wc^T Wc u = Wc^T bc
     for (int i = 0; i < 64; ++i) {
         for (int j = 0; j < 64; ++j) {
             double acc = 0.0;
             for (int k = 0; k < 512; ++k) acc += s.wc[(size_t)k * 64 + i] * s.wc[(size_t)k * 64 + j];
+            n[i * 64 + j] = acc;
             s.gram[i * 64 + j] = (float)(acc / 512.0);
         }
+        double acc = 0.0;
+        for (int k = 0; k < 512; ++k) acc += s.wc[(size_t)k * 64 + i] * s.bc[k];
+        rhs[i] = acc;
+    }
+    // Cholesky; a `linear.weight` without full column rank (to 1e-10 of its largest diagonal entry) keeps shift = 0, the unshifted form
+    double dmax = 0.0;
+    for (int i = 0; i < 64; ++i) dmax = std::max(dmax, n[i * 64 + i]);
+    bool full_rank = dmax > 0.0;
+    for (int j = 0; j < 64 && full_rank; ++j) {
+        double d = n[j * 64 + j];
+        for (int k = 0; k < j; ++k) d -= n[j * 64 + k] * n[j * 64 + k];
+        if (!(d > 1e-10 * dmax)) {
+            full_rank = false;
+            break;
+        }
+        n[j * 64 + j] = std::sqrt(d);
+        for (int i = j + 1; i < 64; ++i) {
+            double v = n[i * 64 + j];
+            for (int k = 0; k < j; ++k) v -= n[i * 64 + k] * n[j * 64 + k];
+            n[i * 64 + j] = v / n[j * 64 + j];
+        }
+    }
+    float* shift = s.gram.data() + DC_GRAM_SHIFT;
+    if (full_rank) {
+        for (int i = 0; i < 64; ++i) {                    // L z = rhs
+            double v = rhs[i];
+            for (int k = 0; k < i; ++k) v -= n[i * 64 + k] * rhs[k];
+            rhs[i] = v / n[i * 64 + i];
+        }
+        for (int i = 63; i >= 0; --i) {                   // L^T u = z
+            double v = rhs[i];
+            for (int k = i + 1; k < 64; ++k) v -= n[k * 64 + i] * rhs[k];
+            rhs[i] = v / n[i * 64 + i];
+            shift[i] = (float)rhs[i];
+        }
+        for (int k = 0; k < 512; ++k)                     // r, from the shift as the device adds it
+            for (int i = 0; i < 64; ++i) s.bc[k] -= s.wc[(size_t)k * 64 + i] * (double)shift[i];
+    }
+    for (int i = 0; i < 64; ++i) {
         double acc = 0.0;
         for (int k = 0; k < 512; ++k) acc += s.wc[(size_t)k * 64 + i] * s.bc[k];
         s.gram[64 * 64 + i] = (float)(acc / 512.0);
@@ -394,7 +441,8 @@ struct ModelPacker {
     // Cross-attention key (kv = 0) or value (1) projection of the conditioning pre-pass, text_norm's affine folded in
     // (transformer.py:149,153), always split-bf16 - and the same projection composed with `linear` (transformer.py:479-480;
     // 64 -> 512, shared by all layers): with y = W x + b, n-hat = (y - mean(y)) rstd = rstd (Wc x + bc), so
-    //   W' n-hat + b' = rstd (A x + d) + b',   A = W' Wc [128][64],  d = W' bc
+    //   W' n-hat + b' = rstd (A x + d) + b',   A = W' Wc [128][64],  d = W' bc;   on the shifted features (centre_linear):
+    //                 = rstd (A (x + u) + d) + b' with d = W' r
     // - an eighth of the pre-pass GEMM's products (k_cond_ca_partials64), and no [tokens][512] image in between.
     void cross_kv(int i, int kv, const std::string& ca, const LinearStats& lin) {
         const std::string nm = ca + (kv ? ".value" : ".key");
@@ -515,7 +563,9 @@ struct ModelPacker {
     void time_embedding() {
         add_vec(I.top(&DcModel::temb), std::vector<float>((size_t)c.max_timesteps * 512, 0.f));
         std::vector<float> fr(64);
-        for (int k = 0; k < 64; ++k) fr[k] = expf((float)(-std::log(10000.0)) * (float)k / 64.f);   // transformer.py:18-20 in fp32
+        // transformer.py:18-20 in fp32: the fp32 argument, and the correctly rounded fp32 exp of it (through double, so that it does not
+        // depend on the C library's expf; torch's own exp is one ulp off at k = 22 on some CPUs)
+        for (int k = 0; k < 64; ++k) fr[k] = (float)std::exp((double)((float)(-std::log(10000.0)) * (float)k / 64.f));
         std::vector<float> w0t((size_t)128 * 512), w2t((size_t)512 * 512);
         const float* w0 = P("time_embed.0.weight");
         const float* w2 = P("time_embed.2.weight");
@@ -1592,6 +1642,10 @@ int dc_sampler_debug_read(dc_sampler* s, const char* what, void* h_out, int64_t 
     else if (w == "recs") { src = s->d_recs; have = g * 2 * DC_REC_FLOATS * 4; }
     else if (w == "a_sa") { src = s->d_a_sa; have = (size_t)s->B * 16 * 1024; }
     else if (w == "a_ca") { src = s->d_a_ca; have = (size_t)s->cfg.num_layers * s->B * 16 * 1024; }
+    else if (w == "a_ca16") {          // filled for the 16-token layer kernel only: non-split formats, linear attention
+        if (s->split_small || s->cfg.no_eff) return fail(DC_ERR_INVALID, "buffer 'a_ca16' not filled: this sampler never runs the 16-token layer kernel");
+        src = s->d_a_ca16; have = (size_t)s->cfg.num_layers * s->B * 8 * 1024;
+    }
     else if (w == "stamps") { src = s->d_stamps; have = (8 * 32 + 8 + 1024 + 1024 + 256 + 8 + 512) * 8; }
     else if (w == "temb") { src = s->h_model.temb; have = (size_t)s->cfg.max_timesteps * 512 * 4; }
     else if (w == "full_moves") {      // diagnostic builds only: {visits, moves} of the no_eff key loop's reference point, reset by the read

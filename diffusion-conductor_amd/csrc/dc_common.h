@@ -27,6 +27,9 @@
 // tiles the two diagonal 16x16 head blocks of exp(K-m)^T V: lane (c, hh) keeps the 8 accumulator registers
 // 8*(c>>4) .. +7 of the 32x32 tile (the other 8 are cross-head products nobody reads).
 #define DC_REC_FLOATS (128 + 128 + 4 * 64 * 8)
+// DcModel::lin_gram: [64][64] Gc, gv[64], c, 3 unused, then at DC_GRAM_SHIFT the 64 shifts the features take first
+#define DC_GRAM_SHIFT (64 * 64 + 68)
+#define DC_GRAM_FLOATS (DC_GRAM_SHIFT + 64)
 
 #ifdef __HIPCC__
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
@@ -53,9 +56,10 @@ struct DcLayer {
     const bf16x8 *img_ffn_w1, *img_ffn_w2;     // 16 frags/half each; consts (b1 | b2) follow img_ffn_w2
     const bf16x8 *ca_wk, *ca_wv;               // conditioning pre-pass: natural-k pack [ot][ks], bf16 hi+lo (text_norm folded in)
     const float *ca_bk, *ca_bv;                // plain [128]
-    // ... and the same projections composed with `linear` (k_cond_ca_partials64): K = rstd (A x + d) + b on the 64 music features x
+    // ... and the same projections composed with `linear` (k_cond_ca_partials64): K = rstd (A (x + u) + d) + b on the 64 music features x,
+    // shifted by u = DcModel::lin_gram[DC_GRAM_SHIFT ..] (centre_linear, dc_api.hip)
     const bf16x8 *ca_ak, *ca_av;               // A = W' Wc  [128][64], natural-k pack [ot 4][ks 4], bf16 hi + lo
-    const float *ca_dk, *ca_dv;                // d = W' bc  [128]
+    const float *ca_dk, *ca_dv;                // d = W' r  [128], r = bc - Wc u
 };
 
 // Stage images of the 16-token layer kernel for small batches (dc_layer16.hip; non-split formats, linear attention): fragments
@@ -87,7 +91,7 @@ struct DcModel {
     const float *film_b_g1, *film_b16_g1;     // the same constants with the scale tiles holding G' instead of G' - 1 (plain-operand consumers)
     const float* lin_wt;     // `linear` weight transposed [64][512]
     const bf16x8* lin_pack;  // `linear` weight [512][64] as natural-k fragments [ot 16][ks 4], bf16 hi + lo (k_cond_pp64)
-    const float* lin_gram;   // LayerNorm variance of linear(x) as a quadratic form of x: [64][64] Gc = Wc^T Wc / 512, then gv[64] = Wc^T bc / 512, then c = |bc|^2 / 512
+    const float* lin_gram;   // LayerNorm variance of linear(x) as a quadratic form of z = x + u: [64][64] Gc = Wc^T Wc / 512, then gv[64] = Wc^T r / 512, then c = |r|^2 / 512 (r = bc - Wc u), and u[64] at DC_GRAM_SHIFT
     const float* lin_b;      // [512]
     const float* temb;       // [max_timesteps][512]
     int num_layers;

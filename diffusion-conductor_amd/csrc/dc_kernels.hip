@@ -376,16 +376,25 @@ __global__ __launch_bounds__(512, 1) void k_cond_pp64(const float* __restrict__ 
 
 // The same records from the 64 music features themselves (round 5).  `linear` (64 -> 512) is shared by all layers and the
 // LayerNorm behind it is affine in its input up to the per-token 1 / std, so
-//   K = W' n-hat + b' = rstd (A x + d) + b',   A = W' Wc [128][64], d = W' bc        (host: dc_api.hip, cross_kv)
+//   K = W' n-hat + b' = rstd (A z + d) + b',   z = x + u,  A = W' Wc [128][64],  d = W' r        (host: dc_api.hip, cross_kv)
 // - 4 k-steps of 16 per layer instead of 32, no [tokens][512] image written and read back: the pre-pass GEMM does an eighth of the
-// products.  rstd comes from k_cond_rstd: the variance of linear(x) over its 512 outputs as a quadratic form of x,
-//   var = x^T Gc x + 2 gv^T x + c      (Gc = Wc^T Wc / 512 is positive semi-definite: no cancellation beyond the sum's own)
+// products.  The features are shifted first, z = x + u, by the least-squares solution u of Wc u = bc (centre_linear; r = bc - Wc u is
+// orthogonal to Wc's columns): where linear(x) is nearly constant over its outputs (bc in the column space of Wc, x near -u), every
+// sum over the features, A x + d here and the variance below, would cancel term by term at the precision of its split-bf16 or fp32
+// operands - K and V off by 1e-3 ... 4e-3 at |x + u| = 1e-2 ... 1e-3 |u| - and the one fp32 addition takes that cancellation
+// exactly instead.  rstd comes from k_cond_rstd: the variance of linear(x) over its 512 outputs as a quadratic form of z,
+//   var = z^T Gc z + 2 gv^T z + c,     gv = Wc^T r / 512 (zero but for u's rounding),  c = |r|^2 / 512
+// Gc = Wc^T Wc / 512 is positive semi-definite, and with the shift var is a sum of two non-negative terms: no term cancels against
+// another.  What the shift does not cover is a `linear.weight` without full column rank: there linear(x) is constant on an affine
+// subspace, not at one point, no single u takes the cancellation off, and centre_linear keeps u = 0 - the sums over the features
+// then cancel for an x near that subspace as they did before the shift (tests/study_cond_rstd.py, column "quadratic").  DC_COND_512=1
+// normalises directly (k_cond_embed<1>) and has no such limit.
 // Same record format and masking as above; grid (ceil(G/8), L), one wave per (group, layer); the layer's 64 weight fragments
 // (K hi, K lo, V hi, V lo x 4 tiles x 4 k-steps, 64 KiB) are copied to LDS once per workgroup.
 __global__ __launch_bounds__(256) void k_cond_rstd(const float* __restrict__ xf /*[B][Tx][64]*/, const float* __restrict__ gram, float* __restrict__ rstd /*[G * 32]*/,
                                                    int M, int T, int Tx, int ntok) {
-    __shared__ __attribute__((aligned(16))) float gs[64 * 64 + 64 + 4];
-    for (int i = threadIdx.x; i < 64 * 64 + 64 + 1; i += 256) gs[i] = gram[i];
+    __shared__ __attribute__((aligned(16))) float gs[DC_GRAM_FLOATS];
+    for (int i = threadIdx.x; i < DC_GRAM_FLOATS; i += 256) gs[i] = gram[i];
     __syncthreads();
     const int tok = blockIdx.x * 256 + threadIdx.x;
     if (tok >= ntok) return;
@@ -393,8 +402,9 @@ __global__ __launch_bounds__(256) void k_cond_rstd(const float* __restrict__ xf 
     float r = 0.f;                                      // rows of the padding and past M: K = b', masked by the records' row ranges anyway
     if (tok < M && nn < Tx) {
         f32x4 x[16];
+        const f32x4* xrow = reinterpret_cast<const f32x4*>(xf) + ((size_t)bb * Tx + nn) * 16;
 #pragma unroll
-        for (int i = 0; i < 16; ++i) x[i] = reinterpret_cast<const f32x4*>(xf)[((size_t)bb * Tx + nn) * 16 + i];
+        for (int i = 0; i < 16; ++i) x[i] = xrow[i] + reinterpret_cast<const f32x4*>(gs + DC_GRAM_SHIFT)[i];      // z = x + u
         float var = gs[64 * 64 + 64];
 #pragma unroll      // (fully: x must stay in registers - a partly unrolled loop indexes it dynamically and it moves to scratch: 157 us instead of ~15)
         for (int i = 0; i < 64; ++i) {
@@ -414,6 +424,7 @@ __global__ __launch_bounds__(256) void k_cond_rstd(const float* __restrict__ xf 
     rstd[tok] = r;
 }
 __global__ __launch_bounds__(512, 1) void k_cond_ca_partials64(const DcModel* __restrict__ dm, const float* __restrict__ xf /*[B][Tx][64]*/,
+                                                               const float* __restrict__ shift /*[64] u: DcModel::lin_gram + DC_GRAM_SHIFT, as an argument so that no load waits for the pointer's*/,
                                                                const float* __restrict__ rstd, float* __restrict__ recs, int M, int T, int G,
                                                                int Tx /* frames per clip (<= the clip stride T) */) {
     extern __shared__ __attribute__((aligned(16))) char wbuf[];          // 64 fragments: [which: K hi, K lo, V hi, V lo][oc 4][ks 4]
@@ -440,8 +451,9 @@ __global__ __launch_bounds__(512, 1) void k_cond_ca_partials64(const DcModel* __
         f32x4 v0 = {0.f, 0.f, 0.f, 0.f}, v1 = v0;
         if (live) {
             const f32x4* px = reinterpret_cast<const f32x4*>(xf) + ((size_t)bb * Tx + nn) * 16 + 4 * ks + 2 * cx.hh;
-            v0 = px[0];
-            v1 = px[1];
+            const f32x4* pu = reinterpret_cast<const f32x4*>(shift) + 4 * ks + 2 * cx.hh;
+            v0 = px[0] + pu[0];                      // z = x + u (centre_linear): exact where x cancels against the bias most
+            v1 = px[1] + pu[1];
         }
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -2733,7 +2745,7 @@ hipError_t dc_launch_ca_partials64(hipStream_t st, const DcModel* dm, const floa
     if (hipError_t e = hipGetLastError()) return e;
     static unsigned long long optin_done = 0;
     if (hipError_t e = lds_optin((const void*)k_cond_ca_partials64, 65536, optin_done)) return e;
-    hipLaunchKernelGGL(k_cond_ca_partials64, dim3((G + 7) / 8, L), dim3(512), 65536, st, dm, xf, rstd, recs, M, T, G, Tx);
+    hipLaunchKernelGGL(k_cond_ca_partials64, dim3((G + 7) / 8, L), dim3(512), 65536, st, dm, xf, gram + DC_GRAM_SHIFT, rstd, recs, M, T, G, Tx);
     return LAUNCH_CHECK();
 }
 

@@ -295,7 +295,8 @@ DC_EXPORT int32_t dc_kernel_count(void);
  * `n_layers` decoder layers, the last one cut after stage 1 = self-attention, 2 = cross-attention,
  * 3 = FFN (0 = whole layer), leaving the residual stream in the internal buffer "h".
  * dc_sampler_debug_read copies an internal device buffer to the host (synchronous); names:
- * "h" "pp" "s_hi" "s_lo" "E" "recs" "a_sa" "a_ca" "temb" (layouts: DESIGN.md). */
+ * "h" "pp" "s_hi" "s_lo" "E" "recs" "a_sa" "a_ca" "a_ca16" "temb" (layouts: DESIGN.md; "a_ca16", the 16-token layer
+ * kernel's copy of "a_ca", is filled for non-split formats with linear attention only: DC_ERR_INVALID elsewhere). */
 DC_EXPORT int dc_sampler_debug_denoise(dc_sampler* s, const float* d_x, const int32_t* h_timesteps, float* d_out,
                              int32_t n_layers, int32_t stage, void* stream);
 DC_EXPORT int dc_sampler_debug_read(dc_sampler* s, const char* what, void* h_out, int64_t nbytes);
