@@ -119,6 +119,11 @@ struct dc_sampler : Formats {     // (set_precision(cfg.precision))
     unsigned long long noise_seed = 0, noise_first = 0;      // Philox key; index of this sampler's first element in the whole batch's draw
     bool noise_seed_set = false;                             // a seed is consumed by the loop that uses it
     int* d_status = nullptr;
+    // known values (dc_sampler_set_known): the caller's three [B][Tx][P] tensors, valid for clips of (known_B, known_Tx); the kernels read
+    // their addresses from d_kslot
+    const float *known_val = nullptr, *known_mask = nullptr, *known_noise = nullptr;
+    int known_B = 0, known_Tx = 0;
+    const float** d_kslot = nullptr;
     // Savitzky-Golay smoothing applied by the loop's final write (dc_sampler_set_smoothing; window 0 = off)
     int smooth_window = 0, smooth_order = 0, smooth_table_window = 0;     // (table_window: the hat matrix d_smooth_coef holds)
     float* d_smooth_coef = nullptr;
@@ -702,6 +707,8 @@ int ensure_workspace(dc_sampler* s, int B, int Tx) {
         HIP_TRY(hipMemset(s->d_status, 0, 16));
         if ((rc = dev_alloc(s, s->d_zslot, 32))) return rc;
         HIP_TRY(hipMemset(s->d_zslot, 0, 32));
+        if ((rc = dev_alloc(s, s->d_kslot, 32))) return rc;
+        HIP_TRY(hipMemset(s->d_kslot, 0, 32));
         if ((rc = dev_alloc(s, s->d_iter, 16))) return rc;
         if ((rc = dev_alloc(s, s->d_snap_cur, 16))) return rc;
         if ((rc = dev_alloc(s, s->d_coef_cur, DC_COEF * 4))) return rc;
@@ -752,7 +759,7 @@ int ensure_steps(dc_sampler* s, int S) {
 // can see: Switches::bits) and the update options of the loop.
 unsigned long long form_key(const dc_sampler* s, const Switches& w) {
     unsigned long long k = w.bits();
-    k |= (unsigned long long)(s->upd_flags & 0xff) << 16;     // (the noise tensor's address is not baked in: the kernels read it from d_zslot)
+    k |= (unsigned long long)(s->upd_flags & 0xff) << 16;     // (the noise / known tensors' addresses are not baked in: the kernels read them from d_zslot / d_kslot)
     k |= (s->l16_own ? 1ull : 0ull) << 24;
     k |= (unsigned long long)((s->clip_aligned + 1) & 3) << 25;
     return k;
@@ -828,7 +835,7 @@ int enqueue_step(dc_sampler* s, hipStream_t st, const Step& c, const Switches& w
     la.dm = dmod, la.hbuf = s->d_h, la.E = s->d_E, la.NT = s->NT, la.recs = s->d_recs, la.length = s->d_length, la.xin = c.x_src, la.xout = c.x_dst;
     la.out_mode = c.loop_mode ? 1 : 0, la.coef_cur = coef_src, la.snap_cur = snap_src, la.snaps = s->d_snaps, la.iter_base = iter_base;
     la.M = M, la.T = T, la.G = G, la.B = B, la.Tx = Tx;
-    la.upd = DcUpdate{s->d_zslot, s->d_status, (c.loop_mode ? s->upd_flags : 0) | f.upd_flags, folded ? graph_step : -1, nullptr};
+    la.upd = DcUpdate{s->d_zslot, s->d_status, (c.loop_mode ? s->upd_flags : 0) | f.upd_flags, folded ? graph_step : -1, nullptr, s->d_kslot};
     DcLayerArgs la_stamps = la;      // (stage stamps of layer 3 in diagnostic builds: DcUpdate::stamps carries the buffer)
     la_stamps.upd.stamps = s->d_stamps;
     if (s->cfg.no_eff) {
@@ -887,6 +894,13 @@ int loop_common(dc_sampler* s, const float* d_noise, float* d_out, int S, const 
     if ((flags & DC_UPD_EPS) && s->cfg.no_eff && !(flags & DC_UPD_NOISY) && !getenv("DC_ALLOW_EPSILON_NO_EFF_ETA0"))
         return fail(DC_ERR_UNSUPPORTED, "EPSILON model with full attention (no_eff) at eta = 0 is outside the 1e-3 parity bound (up to 1.3e-3); "
                                         "use linear attention, or eta > 0");
+    // known values (dc_sampler_set_known) serve the loops of the geometry they were set for; another (B, T) clears them
+    if (s->known_mask && (s->known_B != s->B || s->known_Tx != s->Tx)) s->known_val = s->known_mask = s->known_noise = nullptr;
+    const bool known = s->known_mask != nullptr;
+    if (known && S > 1 && !(h_coef[(size_t)DC_COEF * (S - 1) + 5] > 0.f))
+        return fail(DC_ERR_INVALID, "known values are set: the loop needs the [S][8] table of dc_ddim_coefficients_known (slot 5 = sqrt(1 - abar_prev))");
+    if (known && profile) return fail(DC_ERR_UNSUPPORTED, "dc_sampler_profile_loop does not run with known values set");
+    if (known) flags |= DC_UPD_KNOWN;
     if (s->smooth_window > 0 && s->Tx < s->smooth_window)       // (before anything is enqueued: a failed call leaves no work and no half-ordered streams)
         return fail(DC_ERR_INVALID, "smoothing window %d exceeds the %d frames of a clip", s->smooth_window, s->Tx);
     int rc;
@@ -950,6 +964,11 @@ int loop_common(dc_sampler* s, const float* d_noise, float* d_out, int S, const 
     }
     HIP_TRY(hipMemsetAsync(s->d_iter, 0, 16, st));
     HIP_TRY(hipMemcpyAsync(s->d_x, d_noise, MP * 4, hipMemcpyDeviceToDevice, st));
+    if (known) {      // x_T of the known elements at the loop's starting level abar_{S-1} (slots 6, 7 of the first step's row)
+        const float* c0 = h_coef + (size_t)DC_COEF * (S - 1);
+        HIP_TRY(dc_launch_set_known(st, s->d_kslot, s->known_val, s->known_mask, s->known_noise));
+        HIP_TRY(dc_launch_known_blend(st, s->d_x, s->known_val, s->known_mask, s->known_noise, c0[6], c0[7], MP));
+    }
     const bool no_graph = getenv("DC_DISABLE_GRAPH") != nullptr;
     // precise tail: the loop's last `tail` model evaluations on split operands (loop_tail, dc_form.h; DC_PRECISE_TAIL=k overrides)
     const char* env_tail = getenv("DC_PRECISE_TAIL");
@@ -964,7 +983,7 @@ int loop_common(dc_sampler* s, const float* d_noise, float* d_out, int S, const 
         for (int i = 0; i < n; ++i) {
             Step c;
             c.loop_mode = true, c.x_src = c.x_dst = s->d_x, c.graph_step = graph ? i : -1, c.split = i >= n - split_n, c.g1_loop = tail > 0;
-            c.next_plain = i + 1 < n - split_n, c.embedded = embedded, c.profile = profile;
+            c.next_plain = i + 1 < n - split_n, c.embedded = embedded, c.profile = profile, c.known = known;
             StepDone d;
             if (int rc = enqueue_step(s, st, c, sw, &d)) return rc;
             embedded = d.embedded_next, folded = d.folded;
@@ -1122,6 +1141,19 @@ int dc_ddim_coefficients_ex(int32_t n, const double* ac, float eta, float* coef8
     return DC_OK;
 }
 
+int dc_ddim_coefficients_known(int32_t n, const double* ac, float eta, float* coef8, float* start2) {
+    if (int rc = dc_ddim_coefficients_ex(n, ac, eta, coef8)) return rc;
+    for (int t = 0; t < n; ++t) {
+        const float a = (float)ac[t], a_prev = t == 0 ? 1.0f : (float)ac[t - 1];
+        float* c = coef8 + (size_t)DC_COEF * t;
+        c[5] = sqrtf(1.0f - a_prev);      // (dc_ddim_coefficients' column 3: the same expression and rounding)
+        c[6] = sqrtf(a);
+        c[7] = sqrtf(1.0f - a);
+    }
+    if (start2) start2[0] = coef8[(size_t)DC_COEF * (n - 1) + 6], start2[1] = coef8[(size_t)DC_COEF * (n - 1) + 7];
+    return DC_OK;
+}
+
 int dc_pack_weight(const float* w, int32_t n_out, int32_t k_in, int32_t chained, uint16_t* hi, uint16_t* lo) {
     if (!w || !hi || !lo || n_out < 1 || k_in < 1) return fail(DC_ERR_INVALID, "bad pack arguments");
     pack_weight(w, n_out, k_in, chained != 0, hi, lo);
@@ -1190,7 +1222,7 @@ void dc_sampler_destroy(dc_sampler* s) {
     void* ptrs[] = {s->d_arena, s->d_model, s->d_model_split, s->d_length, s->d_pp, s->d_s_hi, s->d_s_lo, s->d_E, s->d_h, s->d_recs, s->d_a_sa,
                     s->d_a_ca, s->d_x, s->d_snaps, s->d_recs_ca, s->d_nh_hi, s->d_nh_lo, s->d_iter,
                     s->d_t_clip, s->d_snap_cur, s->d_t_of_iter, s->d_snap_of_iter, s->d_coef_cur, s->d_coef_of_t, s->d_coef_of_iter,
-                    s->d_kv_sa[0], s->d_kv_sa[1], s->d_kv_ca, s->d_stamps, s->d_film_rate, s->d_status, s->d_smooth_coef, s->d_zslot, s->d_zstep, s->d_a_ca16, s->d_gran};
+                    s->d_kv_sa[0], s->d_kv_sa[1], s->d_kv_ca, s->d_stamps, s->d_film_rate, s->d_status, s->d_smooth_coef, s->d_zslot, s->d_kslot, s->d_zstep, s->d_a_ca16, s->d_gran};
     for (void* p : ptrs)
         if (p) hipFree(p);
     dc_music_destroy(s->music);
@@ -1501,6 +1533,21 @@ int dc_sampler_ddim_loop_ex(dc_sampler* s, const float* d_noise, float* d_out, i
                     "(dc_sampler_set_step_noise_seed) for draws generated step by step");
     return loop_common(s, d_noise, d_out, num_steps, h_coef8, h_snap_iters, n_snap, d_snaps, (hipStream_t)stream, false,
                        flags | (noisy ? DC_UPD_NOISY : 0), noisy ? d_step_noise : nullptr);
+}
+
+int dc_sampler_set_known(dc_sampler* s, const float* d_known, const float* d_mask, const float* d_known_noise) {
+    if (!s) return fail(DC_ERR_INVALID, "null sampler");
+    if (!d_known && !d_mask && !d_known_noise) {
+        s->known_val = s->known_mask = s->known_noise = nullptr;
+        return DC_OK;
+    }
+    if (d_mask && !d_known) return fail(DC_ERR_INVALID, "known values: a mask without values (d_known is NULL)");
+    if (d_mask && !d_known_noise) return fail(DC_ERR_INVALID, "known values: a mask without noise (d_known_noise is NULL; the known elements need one fixed draw)");
+    if (!d_mask) return fail(DC_ERR_INVALID, "known values: values or noise without a mask (d_mask is NULL)");
+    if (!s->cond_set) return fail(DC_ERR_INVALID, "dc_sampler_set_conditioning must be called first: known values belong to its (B, T)");
+    s->known_val = d_known, s->known_mask = d_mask, s->known_noise = d_known_noise;
+    s->known_B = s->B, s->known_Tx = s->Tx;
+    return DC_OK;
 }
 
 int dc_sampler_set_step_noise_seed(dc_sampler* s, uint64_t seed) {

@@ -101,7 +101,8 @@ struct DcModel {
 };
 
 // Options of the DDIM update fused into the last layer kernel (gaussian_diffusion.py:503-521, 812-830).  The per-step scalars
-// come as 8 floats per timestep: sqrt(1/abar), sqrt(1/abar - 1), sqrt(abar_prev), sqrt(1 - abar_prev - sigma^2), sigma, 0, 0, 0.
+// come as 8 floats per timestep: sqrt(1/abar), sqrt(1/abar - 1), sqrt(abar_prev), sqrt(1 - abar_prev - sigma^2), sigma, 0, 0, 0
+// (dc_ddim_coefficients_known: slot 5 = sqrt(1 - abar_prev), slots 6, 7 = sqrt(abar), sqrt(1 - abar): the noise levels of known values).
 #define DC_COEF 8
 #define DC_UPD_CLIP 1        // clip_denoised: pred_xstart.clamp(-1, 1)  (:506-507)
 #define DC_UPD_EPS 2         // ModelMeanType.EPSILON: pred_xstart = sqrt(1/abar) x_t - sqrt(1/abar - 1) model_out  (:516-521, 539-544)
@@ -109,6 +110,7 @@ struct DcModel {
 #define DC_UPD_ZSTEP 8       // (internal) *zslot holds ONE iteration's draws [B][Tx][P], refilled by k_step_noise at the head of every step
 #define DC_UPD_TEST_DROP_SLICE 16   // (test hook, DC_L16_TEST_DROP_SLICE=1) workgroup 0 of k_layer16 publishes nothing: its neighbours' bounded wait must end in DC_STATUS_SYNC_TIMEOUT
 #define DC_UPD_EMBED_NEXT 32  // (internal) the last layer of this step also embeds x_{t-1} and runs layer 0's self-attention front half for the NEXT step (k_layer, wide non-split production form)
+#define DC_UPD_KNOWN 64       // (internal) known values (dc_sampler_set_known): where *kslot's mask is nonzero, x_{t-1} = c[2] known + c[5] noise (known_replace, dc_dev.h)
 #define DC_STATUS_NONFINITE 1    // a predicted x0 was inf / nan
 #define DC_STATUS_F16_SAT 2      // a FiLM modulation value exceeded the fp16 range when stored
 #define DC_STATUS_SYNC_TIMEOUT 4 // a workgroup of the small-batch layer kernel gave up waiting for its clip's combine slices (GPU shared?)
@@ -120,6 +122,8 @@ struct DcUpdate {
     int flags;           // DC_UPD_*
     int step;            // captured loop: step number inside the graph (iteration = step + *iter_base); eager: -1 (iteration = snap_cur[1])
     unsigned long long* stamps;   // diagnostic builds (-DDC_FULL_STAMPS, tools/stage_stamps_full.py): stage stamps of k_layer_full, else nullptr
+    const float* const* kslot;   // DC_UPD_KNOWN: device slots holding the bases of the caller's known values, mask and noise, each [B][Tx][P]
+                         // (slots like zslot: other tensors on the next call do not re-capture the graph)
 };
 
 // k_embed_front's arguments when it rides in the FiLM GEMM's launch (the first `ne` workgroups embed one 256-token unit each, flat units)

@@ -1635,3 +1635,21 @@ DEV float ddim_update(float mo, float xt, const float* __restrict__ c, int flags
     return xn;
 }
 
+// ------------------------------------------------------------------------------------
+// Known values (dc_ddim.h, dc_sampler_set_known): an element whose mask is nonzero does not take the update's result but sits at the
+// step's noise level abar_prev on the caller's fixed draw,  x_{t-1} = sqrt(abar_prev) known + sqrt(1 - abar_prev) noise  - c[2] and
+// c[5] of the step's row (dc_ddim_coefficients_known); at t = 0 these are exactly 1 and 0, so the final sample IS `known` there.
+// known_ptrs reads the three slots once per thread, in front of the element loop (all null without DC_UPD_KNOWN); known_replace is
+// called on every x_{t-1} before it is stored or embedded.
+// ------------------------------------------------------------------------------------
+struct KnownPtrs {
+    const float *val, *mask, *noise;
+};
+DEV KnownPtrs known_ptrs(const DcUpdate& upd) {
+    if (!(upd.flags & DC_UPD_KNOWN)) return KnownPtrs{nullptr, nullptr, nullptr};
+    return KnownPtrs{upd.kslot[0], upd.kslot[1], upd.kslot[2]};
+}
+DEV float known_replace(float xn, const KnownPtrs& k, size_t o, const float* __restrict__ c) {
+    if (k.mask && k.mask[o] != 0.f) xn = c[2] * k.val[o] + c[5] * k.noise[o];
+    return xn;
+}

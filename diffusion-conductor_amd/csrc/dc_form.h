@@ -96,6 +96,7 @@ struct StepOpts {
     bool next_plain = false;      // loops: another step follows in this enqueue sequence (same graph) and it is a plain-operand evaluation
     bool embedded = false;        // the previous step's last layer has embedded x and run layer 0's front half for this step
     bool profile = false;         // events around every launch
+    bool known = false;           // loops: known values are set (dc_sampler_set_known): the update replaces them (DC_UPD_KNOWN); no form is given up
     Hooks dbg;
 };
 
@@ -111,7 +112,7 @@ struct StepForm {
     int upc = 0, upc16 = 0, upc_narrow = 0, nwg = 0;
     size_t rec_stride = 0;        // floats between the two alternating unit-record buffers (0 = single buffer, per-group records)
     bool mixed_form = false, embed_next = false, fuse_embed = false, fuse_extra = false, g1_tiles = false;
-    int upd_flags = 0;            // DC_UPD_* bits the form adds to the loop's (TEST_DROP_SLICE, EMBED_NEXT)
+    int upd_flags = 0;            // DC_UPD_* bits the form adds to the loop's (TEST_DROP_SLICE, EMBED_NEXT, KNOWN)
     int nl_run = 0, stop_stage = 0;      // layers to run; the stop stage handed to the last of them (0 = the whole layer)
 };
 
@@ -212,7 +213,8 @@ inline StepForm step_form(const Geometry& g, const Settings& s, const Switches& 
     // (film_extra_workgroups, dc_kernels.hip): one launch (15 us at one clip) and one kernel boundary less per step.  DC_NO_FUSE_EMBED=1 keeps the two launches.
     // (`first`: there is no embedding to fuse when the run starts from d_h; `narrow` has already excluded every hook)
     f.fuse_extra = narrow && aligned && !ss && ff == fs && fuse_silu && s.film_w16 && dbg.first < 0 && !o.profile && !w.no_fuse_embed;
-    f.upd_flags = (w.l16_test_drop_slice ? DC_UPD_TEST_DROP_SLICE : 0) | (f.embed_next ? DC_UPD_EMBED_NEXT : 0);
+    f.upd_flags = (w.l16_test_drop_slice ? DC_UPD_TEST_DROP_SLICE : 0) | (f.embed_next ? DC_UPD_EMBED_NEXT : 0) |
+                  ((o.known && o.loop_mode) ? DC_UPD_KNOWN : 0);
     // scale tiles: G' for the plain-operand consumers of this step, G' - 1 for the split-operand ones (dc_dev.h, film_affine)
     // (the production forms of the plain-operand kernels only: test hooks, stamps and the per-group record form keep G' - 1)
 #ifndef DC_NO_FILM_G1

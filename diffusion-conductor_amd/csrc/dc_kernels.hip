@@ -45,6 +45,18 @@ __global__ void k_set_ptr(const float** slot, const float* p, unsigned long long
     reinterpret_cast<unsigned long long*>(slot)[2] = first;        // [2]: index of z[0] in the whole batch's [B][T][P] draw (clip shards)
 }
 
+// Known values (dc_sampler_set_known): the three tensors' bases into their device slots, and x_T of the known elements at the loop's
+// starting noise level,  x[known] = ca known + cb noise  (ca, cb = sqrt(abar_{S-1}), sqrt(1 - abar_{S-1}); the steps do the same at
+// their own levels: known_replace, dc_dev.h)
+__global__ void k_set_known(const float** slot, const float* val, const float* mask, const float* noise) {
+    slot[0] = val, slot[1] = mask, slot[2] = noise;
+}
+__global__ __launch_bounds__(256) void k_known_blend(float* __restrict__ x, const float* __restrict__ val, const float* __restrict__ mask,
+                                                     const float* __restrict__ noise, float ca, float cb, size_t n) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n && mask[i] != 0.f) x[i] = ca * val[i] + cb * noise[i];
+}
+
 // ------------------------------------------------------------------------------------
 // eta > 0 without a caller-supplied noise tensor: the N(0, 1) draws of ONE iteration (the reference's th.randn_like(x),
 // gaussian_diffusion.py:822), generated at the head of the step that consumes them - a [B][Tx][P] buffer instead of the
@@ -1635,13 +1647,15 @@ void k_layer(const DcModel* __restrict__ dm, int l, float* __restrict__ hbuf, co
                 const bool noisy = (upd.flags & DC_UPD_NOISY) != 0;
                 const float* zrow = nullptr;
                 if (noisy) zrow = *upd.zslot + ((upd.flags & DC_UPD_ZSTEP) ? (size_t)0 : (size_t)(iter_base ? upd.step + ib : snap_cur[1]) * B * Tx * P);
+                const KnownPtrs kn = known_ptrs(upd);
                 bool bad = false;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int f = tile_row(r, cx.hh);
                     if (f < P) {
                         const size_t o = xrow * P + f;
-                        const float xnew = ddim_update(x0[0][r], xtv[r], cc, upd.flags, noisy, noisy ? zrow[o] : 0.f, bad);
+                        // (known values go in BEFORE xv takes the element: the next step's embedding below reads the registers, not xout)
+                        const float xnew = known_replace(ddim_update(x0[0][r], xtv[r], cc, upd.flags, noisy, noisy ? zrow[o] : 0.f, bad), kn, o, cc);
                         xout[o] = xnew;
                         if (snap >= 0) snaps[(size_t)snap * B * Tx * P + o] = xnew;
                         xv[r] = xnew;
@@ -1691,13 +1705,14 @@ void k_layer(const DcModel* __restrict__ dm, int l, float* __restrict__ hbuf, co
         const bool noisy = (upd.flags & DC_UPD_NOISY) != 0;
         const float* zrow = nullptr;
         if (noisy) zrow = *upd.zslot + ((upd.flags & DC_UPD_ZSTEP) ? (size_t)0 : (size_t)(iter_base ? upd.step + ib : snap_cur[1]) * B * Tx * P);
+        const KnownPtrs kn = known_ptrs(upd);
         bool bad = false;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int f = tile_row(r, cx.hh);
             if (f < P) {
                 const size_t o = xrow * P + f;
-                const float xnew = ddim_update(x0[0][r], xin[o], coef_cur, upd.flags, noisy, noisy ? zrow[o] : 0.f, bad);
+                const float xnew = known_replace(ddim_update(x0[0][r], xin[o], coef_cur, upd.flags, noisy, noisy ? zrow[o] : 0.f, bad), kn, o, coef_cur);
                 xout[o] = xnew;
                 if (snap >= 0) snaps[(size_t)snap * B * Tx * P + o] = xnew;
             }
@@ -2567,12 +2582,13 @@ __global__ __launch_bounds__(512, 2) void k_layer_full(const DcModel* __restrict
         const bool noisy = (upd.flags & DC_UPD_NOISY) != 0;
         const float* zrow = nullptr;                                                      // (k_begin_step runs every step on this path)
         if (noisy) zrow = *upd.zslot + ((upd.flags & DC_UPD_ZSTEP) ? (size_t)0 : (size_t)snap_cur[1] * M * P);
+        const KnownPtrs kn = known_ptrs(upd);
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int f = tile_row(r, cx.hh);
             if (f < P) {
                 const size_t o = (size_t)cx.tok * P + f;
-                const float xn = ddim_update(x0[0][r], xin[o], coef_cur, upd.flags, noisy, noisy ? zrow[o] : 0.f, bad);
+                const float xn = known_replace(ddim_update(x0[0][r], xin[o], coef_cur, upd.flags, noisy, noisy ? zrow[o] : 0.f, bad), kn, o, coef_cur);
                 xout[o] = xn;
                 if (snap >= 0) snaps[(size_t)snap * M * P + o] = xn;
             }
@@ -2688,6 +2704,14 @@ hipError_t dc_launch_scan_f16(hipStream_t st, const void* e, size_t bytes, int* 
 
 hipError_t dc_launch_advance_iter(hipStream_t st, int* iter, int k) {
     k_advance_iter<<<1, 1, 0, st>>>(iter, k);
+    return hipGetLastError();
+}
+hipError_t dc_launch_set_known(hipStream_t st, const float** slot, const float* val, const float* mask, const float* noise) {
+    k_set_known<<<1, 1, 0, st>>>(slot, val, mask, noise);
+    return hipGetLastError();
+}
+hipError_t dc_launch_known_blend(hipStream_t st, float* x, const float* val, const float* mask, const float* noise, float ca, float cb, size_t n) {
+    k_known_blend<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>(x, val, mask, noise, ca, cb, n);
     return hipGetLastError();
 }
 hipError_t dc_launch_set_ptr(hipStream_t st, const float** slot, const float* p, unsigned long long seed, unsigned long long first) {

@@ -100,6 +100,9 @@ int dc_layer16_max_units(void);
 hipError_t dc_launch_advance_iter(hipStream_t st, int* iter, int k);
 hipError_t dc_launch_set_ptr(hipStream_t st, const float** slot /* 24 bytes: base, seed, first element */, const float* p, unsigned long long seed,
                              unsigned long long first);
+// known values (dc_sampler_set_known): the tensors' bases into the 24-byte slot DcUpdate::kslot names; x[known] = ca val + cb noise over n elements
+hipError_t dc_launch_set_known(hipStream_t st, const float** slot, const float* val, const float* mask, const float* noise);
+hipError_t dc_launch_known_blend(hipStream_t st, float* x, const float* val, const float* mask, const float* noise, float ca, float cb, size_t n);
 // N(0, 1) draws of one DDIM iteration (Philox keyed by *seed_slot when given, else seed; iteration = step + *iter_base, else snap_cur[1],
 // else step) into z[0..n); z[0] is element `first` (seed_slot[1] when a slot is given) of the whole batch's draw
 hipError_t dc_launch_step_noise(hipStream_t st, float* z, size_t n, unsigned long long seed, const unsigned long long* seed_slot, const int* iter_base,

@@ -916,6 +916,7 @@ void k_layer16(const DcModel* __restrict__ dm, int l, float* __restrict__ hbuf, 
         const bool noisy = (upd.flags & DC_UPD_NOISY) != 0;
         const float* zrow = nullptr;
         if (noisy) zrow = *upd.zslot + ((upd.flags & DC_UPD_ZSTEP) ? (size_t)0 : (size_t)(iter_base ? upd.step + ib : snap_cur[1]) * B * Tx * P);
+        const KnownPtrs kn = known_ptrs(upd);
 #pragma unroll
         for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
@@ -923,7 +924,7 @@ void k_layer16(const DcModel* __restrict__ dm, int l, float* __restrict__ hbuf, 
                 const int ft = 16 * rb + 4 * c.q4 + i;
                 if (ft < P) {
                     const size_t o = xrow * P + ft;
-                    const float xnew = ddim_update(x0[rb][i], xin[o], coef_cur, upd.flags, noisy, noisy ? zrow[o] : 0.f, bad);
+                    const float xnew = known_replace(ddim_update(x0[rb][i], xin[o], coef_cur, upd.flags, noisy, noisy ? zrow[o] : 0.f, bad), kn, o, coef_cur);
                     xout[o] = xnew;
                     if (snap >= 0) snaps[(size_t)snap * B * Tx * P + o] = xnew;
                 }

@@ -4,7 +4,9 @@ Mirrors Diffusion_Stage/trainers/ddpm_trainer.py: constructor (:82-108, minus th
 MotionPretrain/ST-GCN and mmcv imports), ``load`` (:303-319), ``eval_mode``, ``to`` and
 ``generate_music_motion`` (:183-201).  Extensions over the reference: ``music_mel`` may be a
 batch ``[B,5400,128]``; ``noise=`` / ``seed=`` make sampling reproducible; under an initialised
-``torch.distributed`` group the clips are sharded over ranks (sharding.py).
+``torch.distributed`` group the clips are sharded over ranks (sharding.py);
+``generate_long_music_motion`` conducts music longer than one window by chaining windows around
+the frames already generated (``plan_windows``).
 """
 from __future__ import annotations
 
@@ -13,6 +15,25 @@ import torch
 
 from .sampler import GaussianDiffusion, LossType, ModelMeanType, ModelVarType, get_named_beta_schedule
 from .sharding import dist_info, sharded_sample
+
+
+LONG_OVERLAP = 300       # frames (10 s at 30 fps) a window of generate_long_music_motion shares with its predecessor by default
+
+
+def plan_windows(L, T, overlap):
+    """The windows of a piece of L frames sampled T frames at a time: [(start, known)] in sampling order.  Window k starts at
+    k * (T - overlap); the LAST window is aligned to the end of the piece (start L - T), so every window has T frames.  `known` is
+    the number of leading frames of the window that earlier windows have produced (0 for the first; `overlap` for the regular
+    ones; whatever is already there for the last).  Pure; raises ValueError for L < T or an overlap outside [0, T)."""
+    L, T, overlap = int(L), int(T), int(overlap)
+    if T < 1 or not 0 <= overlap < T:
+        raise ValueError(f"overlap must be in [0, {T}) frames, got {overlap}")
+    if L < T:
+        raise ValueError(f"a piece of {L} frames is shorter than one window of {T}")
+    starts = [0]
+    while starts[-1] + T < L:
+        starts.append(min(starts[-1] + T - overlap, L - T))
+    return [(s, 0 if k == 0 else starts[k - 1] + T - s) for k, s in enumerate(starts)]
 
 
 class DDPMTrainer(object):
@@ -99,3 +120,65 @@ class DDPMTrainer(object):
                 return self._sample_local(mel, noise, dim_pose, idxs, sm)
             return sharded_sample(lambda m, n: self._sample_local(m, n, dim_pose, [], sm), mel, noise, out_shape=(T, dim_pose),
                                   device=self.device)
+
+    def generate_long_music_motion(self, music_mel, dim_pose, overlap=LONG_OVERLAP, noise=None, seed=None, smooth=None, window=None):
+        """Conduct music LONGER than one window: music_mel [Tm,128] or [B,Tm,128] (pieces of one length), Tm at least one window
+        (3 * window mel frames; ValueError below that - generate_music_motion serves those) -> tensor [B, L, dim_pose] with
+        L = (Tm-1)//3 + 1.
+
+        The piece is sampled in windows of `window` frames (default: the model's num_frames, 1800 = 5400 mel frames) laid out by
+        plan_windows: window k starts at frame k * (window - overlap), the last one at L - window.  The mel slices of all windows of
+        all pieces go through ONE encode_music call (window k reads mel frames [3 start, 3 start + 3 window), the last window the
+        piece's last 3 window frames); sampling is sequential over the windows and batched over the pieces.  Each window is a
+        ddim_sample_loop AROUND KNOWN VALUES: its first `known` frames are the frames the earlier windows produced, every other
+        frame is generated.  The output is the plain concatenation - no cross-fade: the loop returns known elements bit for bit,
+        so the frames two windows share are identical in both.
+
+        Noise: ONE tensor [B, L, dim_pose] for the whole piece (`noise=`, or drawn from `seed`, or from torch's default generator).
+        Window k at frame s takes rows [s, s + window) of it both as its x_T and as its known_noise: a frame's fixed draw is the
+        row of its ABSOLUTE position in the piece, which is the x_T row the previous window started that frame from.
+
+        `overlap` (frames, default LONG_OVERLAP = 300: 10 s); `smooth`: the Savitzky-Golay kernel size (order 5), applied ONCE
+        over the whole piece with dc_savgol_filter (per window it would break the seams).  Every window runs the same captured
+        graph (the first with an all-zero mask).  Not built: sharding pieces over the ranks of a torch.distributed group."""
+        from . import native
+        _, world = dist_info()
+        if world > 1:
+            raise NotImplementedError("generate_long_music_motion does not shard pieces over the ranks of a torch.distributed group yet")
+        mel = torch.as_tensor(np.asarray(music_mel) if not torch.is_tensor(music_mel) else music_mel)
+        if mel.dim() == 2:
+            mel = mel.unsqueeze(0)
+        mel = mel.to(self.device, dtype=torch.float32)
+        B, Tm = mel.shape[0], mel.shape[1]
+        T = int(window) if window else int(self.encoder.cfg.num_frames)
+        Tw, L = 3 * T, (Tm - 1) // 3 + 1
+        if Tm < Tw:
+            raise ValueError(f"music of {Tm} mel frames is shorter than one window of {Tw}: use generate_music_motion")
+        plan = plan_windows(L, T, overlap)
+        W = len(plan)
+        if noise is None:
+            g = None
+            if seed is not None:
+                g = torch.Generator()
+                g.manual_seed(int(seed))
+            noise = torch.randn(B, L, dim_pose, generator=g)
+        noise = torch.as_tensor(noise).to(self.device, dtype=torch.float32)
+        if tuple(noise.shape) != (B, L, dim_pose):
+            raise ValueError(f"noise must be {(B, L, dim_pose)} (one row per frame of the piece), got {tuple(noise.shape)}")
+        with torch.no_grad():
+            mel_w = torch.stack([mel[:, min(3 * s, Tm - Tw):min(3 * s, Tm - Tw) + Tw] for s, _ in plan]).reshape(W * B, Tw, mel.shape[2])
+            xf_proj, xf_out = self.encoder.encode_music(mel_w, self.device)
+            xf_proj, xf_out = xf_proj.view(W, B, T, -1), xf_out.view(W, B, T, -1)
+            out = torch.zeros(B, L, dim_pose, dtype=torch.float32, device=self.device)
+            length = torch.LongTensor([T] * B)
+            for k, (s, kn) in enumerate(plan):
+                x_T = noise[:, s:s + T].contiguous()
+                mask = torch.zeros(B, T, device=self.device)
+                mask[:, :kn] = 1
+                out[:, s:s + T] = self.diffusion.ddim_sample_loop(
+                    self.encoder, (B, T, dim_pose), noise=x_T, clip_denoised=False, progress=False,
+                    model_kwargs={"xf_proj": xf_proj[k], "xf_out": xf_out[k], "length": length},
+                    known=out[:, s:s + T].contiguous(), known_mask=mask, known_noise=x_T)
+            if smooth:
+                out = native.savgol_filter(out, int(smooth), 5)
+        return out

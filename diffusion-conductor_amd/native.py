@@ -27,6 +27,7 @@ EXPORTS = [
     "dc_sampler_set_step_noise_seed", "dc_sampler_set_step_noise_seed_at", "dc_step_noise_fill",
     "dc_motion_encoder_create", "dc_motion_encoder_destroy", "dc_motion_encoder_set_param", "dc_motion_encoder_finalize",
     "dc_motion_encoder_encode",
+    "dc_ddim_coefficients_known", "dc_sampler_set_known",
 ]
 
 UPDATE_CLIP_DENOISED, UPDATE_EPSILON = 1, 2          # flags of dc_sampler_ddim_loop_ex
@@ -130,6 +131,8 @@ def lib():
     L.dc_ddim_coefficients_ex.argtypes = [C.c_int32, dp, C.c_float, fp]
     L.dc_sampler_ddim_loop_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, fp, C.c_int32, C.c_void_p, ip, C.c_int32,
                                           C.c_void_p, C.c_void_p]
+    L.dc_ddim_coefficients_known.argtypes = [C.c_int32, dp, C.c_float, fp, fp]
+    L.dc_sampler_set_known.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.dc_sampler_set_step_noise_seed.argtypes = [C.c_void_p, C.c_uint64]
     L.dc_sampler_set_step_noise_seed_at.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64]
     L.dc_step_noise_fill.argtypes = [C.c_void_p, C.c_int64, C.c_uint64, C.c_int32, C.c_void_p]
@@ -186,6 +189,16 @@ def ddim_coefficients(alphas_cumprod: np.ndarray, eta=None) -> np.ndarray:
         out = np.empty((ac.shape[0], 8), np.float32)
         _check(lib().dc_ddim_coefficients_ex(ac.shape[0], dp, C.c_float(float(eta)), _fptr(out)))
     return out
+
+
+def ddim_coefficients_known(alphas_cumprod: np.ndarray, eta=0.0):
+    """dc_ddim_coefficients_known: ([S, 8] table of a loop around known values - dc_ddim_coefficients_ex's plus slot 5 =
+    sqrt(1 - abar_prev) and slots 6, 7 = sqrt(abar), sqrt(1 - abar) -, the loop's starting pair [2])."""
+    ac = np.ascontiguousarray(alphas_cumprod, np.float64)
+    out, start = np.empty((ac.shape[0], 8), np.float32), np.empty(2, np.float32)
+    _check(lib().dc_ddim_coefficients_known(ac.shape[0], ac.ctypes.data_as(C.POINTER(C.c_double)), C.c_float(float(eta)), _fptr(out),
+                                            _fptr(start)))
+    return out, start
 
 
 def savgol_coefficients(window: int, order: int) -> np.ndarray:
@@ -413,6 +426,20 @@ class NativeSampler:
             _check(lib().dc_sampler_ddim_loop_ex(self._h, noise.data_ptr(), out.data_ptr(), S, _fptr(coef), int(flags), zp, sip,
                                                  len(si), snp, self._stream()))
         return out, snaps
+
+    def set_known(self, known=None, mask=None, noise=None):
+        """dc_sampler_set_known: the following loops hold the elements whose `mask` is nonzero at sqrt(abar) known + sqrt(1 - abar) noise
+        at every noise level (the final sample equals `known` there); fp32 device tensors [B, T, P] each, for the conditioning set
+        last.  The loops then take the table of ddim_coefficients_known.  All None: cleared.  The sampler keeps the tensors alive."""
+        import torch
+        ts = (known, mask, noise)
+        for t in ts:
+            if t is not None:
+                assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+                if tuple(t.shape) != (self.B, self.T, self.cfg.input_feats):
+                    raise ValueError(f"known values must be {(self.B, self.T, self.cfg.input_feats)}, got {tuple(t.shape)}")
+        _check(lib().dc_sampler_set_known(self._h, *[None if t is None else t.data_ptr() for t in ts]))
+        self._known = ts if mask is not None else None
 
     def set_smoothing(self, window=19, order=5):
         """dc_sampler_set_smoothing: the loops write Savitzky-Golay-smoothed poses from now on (window 0: off)."""

@@ -262,7 +262,48 @@ class GaussianDiffusion:
             self._native_coef[key] = native.ddim_coefficients(self.alphas_cumprod, key)
         return self._native_coef[key]
 
-    def _native_loop(self, model, img, mk, clip_denoised, eta, snap, step_noise, smooth=None, step_noise_seed=None):
+    def native_coefficients_known(self, eta=0.0):
+        """The [S, 8] table of dc_ddim_coefficients_known (loops around known values)."""
+        key = ("known", float(eta))
+        if self._native_coef is None:
+            self._native_coef = {}
+        if key not in self._native_coef:
+            self._native_coef[key] = native.ddim_coefficients_known(self.alphas_cumprod, float(eta))[0]
+        return self._native_coef[key]
+
+    @staticmethod
+    def _known_tensors(img, known, known_mask, known_noise, known_noise_seed):
+        """The three fp32 [B, T, P] device tensors of NativeSampler.set_known from the keywords of ddim_sample_loop, or None."""
+        if known is None and known_mask is None:
+            if known_noise is not None:
+                raise ValueError("known_noise= without known= and known_mask=")
+            return None
+        if known is None:
+            raise ValueError("known_mask= without known=: a mask needs the values it marks")
+        if known_mask is None:
+            raise ValueError("known= without known_mask=: say which elements are known")
+        shape = tuple(img.shape)
+
+        def full(t, name):
+            t = th.as_tensor(t).to(device=img.device, dtype=th.float32)
+            if tuple(t.shape) != shape:
+                raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
+            return t.contiguous()
+        m = th.as_tensor(known_mask).to(device=img.device)
+        if m.dim() == 2:
+            m = m.unsqueeze(-1)
+        if m.dim() != 3 or tuple(m.shape[:2]) != shape[:2] or m.shape[2] not in (1, shape[2]):
+            raise ValueError(f"known_mask must be {shape[:2]}, {shape[:2] + (1,)} or {shape}, got {tuple(th.as_tensor(known_mask).shape)}")
+        m = (m != 0).to(th.float32).expand(shape).contiguous()
+        if known_noise is None:
+            g = None
+            if known_noise_seed is not None:
+                g = th.Generator()
+                g.manual_seed(int(known_noise_seed))
+            known_noise = th.randn(shape, generator=g)
+        return full(known, "known"), m, full(known_noise, "known_noise")
+
+    def _native_loop(self, model, img, mk, clip_denoised, eta, snap, step_noise, smooth=None, step_noise_seed=None, known=None):
         """The captured loop on `model`'s sampler; returns (out, snaps).  Numeric health is checked once per call
         (`model.check_numerics`): a non-finite x0 under precision="auto" falls back to the bf16-range mode in a fresh sampler."""
         flags = (native.UPDATE_CLIP_DENOISED if clip_denoised else 0) | \
@@ -285,11 +326,12 @@ class GaussianDiffusion:
         # (An EPSILON model's final sample carries what the evaluations left in x_t: the library runs EVERY evaluation of such a loop on
         # split operands - in the fp16 and bf16 precisions, linear and (fp16) full attention alike (dc_ddim.h, dc_sampler_set_precise_tail; the bf16
         # precision's split evaluations take the FiLM GEMM's operands in fp16).)
-        coef = self.native_coefficients(None if plain else eta)
+        coef = self.native_coefficients(None if plain else eta) if known is None else self.native_coefficients_known(eta)
         retried = False
         while True:
             nat = model.set_conditioning(mk["xf_proj"], mk["xf_out"], mk.get("length"))
             nat.set_smoothing(*(smooth if smooth else (0, 0)))
+            nat.set_known(*(known if known is not None else (None, None, None)))
             out, snaps = nat.ddim_loop(img, coef, snap, flags, z, zseed)
             if not getattr(model, "check_numerics", True):
                 return out, snaps
@@ -308,14 +350,20 @@ class GaussianDiffusion:
 
     def ddim_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                          model_kwargs=None, device=None, progress=False, eta=0.0, idxs=[], step_noise=None, smooth=None,
-                         step_noise_seed=None):
+                         step_noise_seed=None, known=None, known_mask=None, known_noise=None, known_noise_seed=None):
         """gaussian_diffusion.py:871-915.  Returns the final sample, or when `idxs` is non-empty a
         dict {iteration: sample} for the listed iterations plus {num_timesteps: final}.
         `step_noise` (extension, eta > 0): [S, B, T, P], the draw for iteration i in place of th.randn_like.
         `step_noise_seed` (extension, eta > 0, native loop only): seed of the library's own per-step draws, or (seed, first_element)
         for a shard that holds clips [lo, hi) of a larger batch (first_element = lo*T*P: the rows the whole batch's draw gives them).
         `smooth` (extension): (window, order) of the Savitzky-Golay filter tools/visualization.py:126 applies to the result,
-        folded into the loop's final write (native loop only)."""
+        folded into the loop's final write (native loop only).
+        `known`, `known_mask`, `known_noise` (extension, native loop only): sample AROUND known values.  `known` [B, T, P]; `known_mask`
+        [B, T], [B, T, 1] or [B, T, P], nonzero = this element is known; `known_noise` [B, T, P], ONE fixed draw per element (None:
+        drawn once from torch's default generator, or from `known_noise_seed`).  At every noise level abar the known elements are held
+        at sqrt(abar) known + sqrt(1 - abar) known_noise - x_T and every x_{t-1}, snapshots included - so the final sample equals
+        `known` bit for bit there (before `smooth`); eta > 0 noise, clipping and the EPSILON update act on the other elements only
+        (include/dc_ddim.h, dc_sampler_set_known)."""
         self._refuse_epsilon_full_attention(model, eta)
         if self._fast_path_ok(model, denoised_fn, cond_fn):
             if device is None:
@@ -328,12 +376,16 @@ class GaussianDiffusion:
                 mk = dict(mk)
                 mk["xf_proj"], mk["xf_out"] = model.encode_music(mk["text"], device)
             snap = sorted(int(i) for i in set(idxs) if 0 <= int(i) < self.num_timesteps)
-            out, snaps = self._native_loop(model, img, mk, bool(clip_denoised), float(eta), snap, step_noise, smooth, step_noise_seed)
+            kn = self._known_tensors(img, known, known_mask, known_noise, known_noise_seed)
+            out, snaps = self._native_loop(model, img, mk, bool(clip_denoised), float(eta), snap, step_noise, smooth, step_noise_seed, kn)
             if len(idxs) == 0:
                 return out
             result = {it: snaps[k] for k, it in enumerate(snap)}
             result[self.num_timesteps] = out
             return result
+        if known is not None or known_mask is not None or known_noise is not None:
+            raise NotImplementedError("known= / known_mask= are replaced inside the native loop's update; with host callbacks "
+                                      "(denoised_fn, cond_fn) or another model there is no step to replace them in")
         if smooth:
             raise NotImplementedError("smooth= is folded into the native loop's final write; with host callbacks apply evaluate.smooth_motion")
         final, i, result = None, 0, {}

@@ -120,6 +120,9 @@ def make_parser():
     parser.add_argument('--model', type=str, default=None, help="checkpoint; default <model_dir>/latest.tar as in the reference")
     parser.add_argument('--smooth', action='store_true', help="Savitzky-Golay smoothing (kernel 19, order 5) as vis_motion applies it")
     parser.add_argument('--seed', type=int, default=None, help="seed of x_T (reproducible sampling)")
+    parser.add_argument('--full_length', action='store_true',
+                        help="conduct mels longer than one window (5400 frames = 60 s) whole, window by window around the frames "
+                             "already generated (DDPMTrainer.generate_long_music_motion); without it only the first window is sampled")
     parser.add_argument('--precision', type=str, default="fp16", choices=["fp16", "mixed", "bf16x3", "bf16", "auto"])
     return parser
 
@@ -142,7 +145,10 @@ def main(argv=None):
     with torch.no_grad():
         mel, names = load_mels(args.music_path)
         # [B, T, 26] on the device; --smooth: smooth_motion(kernel=19) (:126) happens in the loop's final write
-        pred_motions = trainer.generate_music_motion(mel, opt.dim_pose, seed=args.seed, smooth=19 if args.smooth else None)
+        if args.full_length and mel.shape[-2] > 3 * opt.max_motion_length:
+            pred_motions = trainer.generate_long_music_motion(mel, opt.dim_pose, seed=args.seed, smooth=19 if args.smooth else None)
+        else:
+            pred_motions = trainer.generate_music_motion(mel, opt.dim_pose, seed=args.seed, smooth=19 if args.smooth else None)
         B, T = pred_motions.shape[0], pred_motions.shape[1]
         motion = pred_motions.view(B, T, 13, 2).cpu().numpy()
     out = motion[0] if mel.ndim == 2 else motion

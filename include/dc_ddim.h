@@ -99,6 +99,16 @@ DC_EXPORT int dc_ddim_coefficients(int32_t num_steps, const double* h_alphas_cum
  *   h_coef8[t*8 + 5..7] = 0 */
 DC_EXPORT int dc_ddim_coefficients_ex(int32_t num_steps, const double* h_alphas_cumprod, float eta, float* h_coef8);
 
+/* The table of a loop that samples AROUND KNOWN VALUES (dc_sampler_set_known): dc_ddim_coefficients_ex's row, plus the noise levels
+ * the known elements are held at -
+ *   h_coef8[t*8 + 0..4] as dc_ddim_coefficients_ex, bit for bit
+ *   h_coef8[t*8 + 5] = sqrtf(1 - (float)abar_{t-1})    (dc_ddim_coefficients' column 3; exactly 0 at t = 0, where slot 2 is exactly 1)
+ *   h_coef8[t*8 + 6] = sqrtf((float)abar_t),  h_coef8[t*8 + 7] = sqrtf(1 - (float)abar_t)
+ * h_start2 (may be NULL) receives the level at which the loop of num_steps steps starts, sqrt(abar_{S-1}) and sqrt(1 - abar_{S-1})
+ * (slots 6, 7 of the last row: the library blends x_T with them).  A loop without known values reads slots 0..4 only: the table
+ * serves it as well. */
+DC_EXPORT int dc_ddim_coefficients_known(int32_t num_steps, const double* h_alphas_cumprod, float eta, float* h_coef8, float* h_start2);
+
 /* Test hook: pack a row-major Linear weight W[n_out][k_in] (torch layout) into the
  * MFMA fragment-major bf16 image the kernels read (see DESIGN.md "weight image").
  * `chained` != 0 uses the accumulator-as-operand k order, 0 the natural k order.
@@ -222,6 +232,21 @@ DC_EXPORT int dc_sampler_ddim_loop(dc_sampler* s, const float* d_noise, float* d
 DC_EXPORT int dc_sampler_ddim_loop_ex(dc_sampler* s, const float* d_noise, float* d_out, int32_t num_steps, const float* h_coef8,
                             int32_t flags, const float* d_step_noise, const int32_t* h_snap_iters, int32_t n_snap,
                             float* d_snaps, void* stream);
+
+/* Sampling around known values (no counterpart in the reference's DDIM loop; its ancestral p_sample has a pre_seq hook,
+ * gaussian_diffusion.py:634-646, with fresh noise per step - not this).  d_known, d_mask, d_known_noise: fp32 [B,T,P] each, for the
+ * (B, T) of the last dc_sampler_set_conditioning.  An element whose mask is nonzero is KNOWN: at every noise level abar the loops hold it at
+ *   x = sqrt(abar) known + sqrt(1 - abar) known_noise
+ * - x_T at abar_{S-1} before the first evaluation (the library blends it; d_noise is not written), every x_{t-1} a step writes at
+ * abar_{t-1}, snapshots included.  ONE fixed draw per element puts the known region on a deterministic DDIM trajectory; at t = 0,
+ * abar_prev = 1 and the final sample equals d_known bit for bit there (before smoothing, which runs after the replacement).  eta > 0
+ * noise, clipping and the EPSILON parameterisation act on the unknown elements only; DC_STATUS_NONFINITE still reports on the model's
+ * prediction of every element.  An all-zero mask gives the bits of a loop without known values.  The loops then need the table of
+ * dc_ddim_coefficients_known (DC_ERR_INVALID with any other).  The tensors are read while a loop runs and their addresses go through
+ * device slots: other tensors on the next call do not re-capture the hipGraph.  The setting serves the following loops until it is
+ * cleared - three NULLs - or dc_sampler_set_conditioning changes (B, T).  DC_ERR_INVALID: a mask without values, a mask without noise,
+ * values or noise without a mask. */
+DC_EXPORT int dc_sampler_set_known(dc_sampler* s, const float* d_known, const float* d_mask, const float* d_known_noise);
 
 /* eta > 0 without a noise tensor.  After this call a dc_sampler_ddim_loop_ex with sigma != 0 and d_step_noise == NULL
  * generates the draws of each iteration itself at the head of the step that consumes them (one [B,T,P] buffer instead of the
