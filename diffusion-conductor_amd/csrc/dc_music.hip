@@ -896,9 +896,10 @@ struct dc_music {
     int cap = 0, cap_tm = 0;
     long long ws_bytes = 0;
     int format = 0;                       // 0: split bf16 planes, 1: one fp16 plane (dc_music_set_format)
+    bool pinned = false;                  // dc_music_pin_format: `format` holds whatever DC_ME_PREC says
 };
 
-std::vector<std::pair<std::string, size_t>> dc_music_required(int music_dim) {
+std::vector<std::pair<std::string, size_t>> dc_music_required(int music_dim, bool with_proj) {
     std::vector<std::pair<std::string, size_t>> r;
     const std::string me = "music_encoder.";
     for (const MusicConvSpec& c : kMusicConvs) {
@@ -915,17 +916,19 @@ std::vector<std::pair<std::string, size_t>> dc_music_required(int music_dim) {
     r.push_back({me + "conv4.0.weight", (size_t)music_dim * 512});
     r.push_back({me + "conv4.0.bias", (size_t)music_dim});
     for (const char* s : {"weight", "bias", "running_mean", "running_var"}) r.push_back({me + "conv4.1." + s, (size_t)music_dim});
-    r.push_back({"proj.weight", (size_t)music_dim * music_dim});
-    r.push_back({"proj.bias", (size_t)music_dim});
+    if (with_proj) {
+        r.push_back({"proj.weight", (size_t)music_dim * music_dim});
+        r.push_back({"proj.bias", (size_t)music_dim});
+    }
     return r;
 }
 
-bool dc_music_check(const DcParams& params, int music_dim, std::string* err) {
+bool dc_music_check(const DcParams& params, int music_dim, std::string* err, bool with_proj) {
     if (music_dim != DC_C) {
         *err = "music encoder kernels are built for 64 output channels";
         return false;
     }
-    for (const auto& rq : dc_music_required(music_dim)) {
+    for (const auto& rq : dc_music_required(music_dim, with_proj)) {
         auto it = params.find(rq.first);
         if (it == params.end()) {
             *err = "missing parameter '" + rq.first + "'";
@@ -940,9 +943,9 @@ bool dc_music_check(const DcParams& params, int music_dim, std::string* err) {
 }
 
 // Folding and packing are music_pack (dc_pack.h, no HIP call); here the image is uploaded and the pointers into it are resolved.
-dc_music* dc_music_build(const DcParams& params, int music_dim, std::string* err) {
-    if (!dc_music_check(params, music_dim, err)) return nullptr;
-    const MusicImage I = music_pack(params);
+dc_music* dc_music_build(const DcParams& params, int music_dim, std::string* err, bool with_proj) {
+    if (!dc_music_check(params, music_dim, err, with_proj)) return nullptr;
+    const MusicImage I = music_pack(params, with_proj);
     const std::vector<uint8_t>& host = I.arena.host;
     dc_music* m = new dc_music();
     if (hipMalloc((void**)&m->arena, host.size()) != hipSuccess ||
@@ -966,8 +969,10 @@ dc_music* dc_music_build(const DcParams& params, int music_dim, std::string* err
     at(m->w4, I.w4);
     at(m->w4_16, I.w4_16);
     at(m->b4, I.b4);
-    at(m->wp, I.wp);
-    at(m->bp, I.bp);
+    if (with_proj) {
+        at(m->wp, I.wp);
+        at(m->bp, I.bp);
+    }
     return m;
 }
 
@@ -1121,7 +1126,13 @@ hipError_t launch_pool16(hipStream_t st, const f16x8* in, f16x8* out, int Bc, in
 void dc_music_set_format(dc_music* m, int single_fp16) {
     if (m) m->format = single_fp16 ? 1 : 0;
 }
+void dc_music_pin_format(dc_music* m, int single_fp16) {
+    if (!m) return;
+    m->format = single_fp16 ? 1 : 0;
+    m->pinned = true;
+}
 int dc_music_format(const dc_music* m) {
+    if (m && m->pinned) return m->format;
     if (const char* e = getenv("DC_ME_PREC")) return (!strcmp(e, "f16") || !strcmp(e, "fp16")) ? 1 : 0;
     return m ? m->format : 0;
 }
@@ -1129,6 +1140,10 @@ int dc_music_format(const dc_music* m) {
 hipError_t dc_music_encode(dc_music* m, const float* d_mel, int B, int Tm, float* d_xf_proj, float* d_xf_out, hipStream_t st,
                            std::string* err) {
     const int T = dc_music_frames(Tm);
+    if (d_xf_proj && !m->wp) {
+        *err = "this music encoder was built without proj";
+        return hipErrorInvalidValue;
+    }
     // chunk of clips whose largest activation (16 channels x Tm x 128 bins, two bf16 planes) stays under ~1.4 GB per buffer (32 clips of 60 s in one pass: 4.5 ms; 16 per pass: 4.7 ms, 8: 5.0 ms)
     int chunk = std::max(1, std::min(B, 32 * 5400 / std::max(Tm, 1)));
     if (const char* e = getenv("DC_ME_CHUNK")) chunk = std::max(1, std::min(B, atoi(e)));
@@ -1171,11 +1186,12 @@ hipError_t dc_music_encode(dc_music* m, const float* d_mel, int B, int Tm, float
             const int M = Bc * T;
             const unsigned grid = (unsigned)((M + 127) / 128);
             float* xo = d_xf_out + (size_t)b0 * T * 64;
-            float* xp = d_xf_proj + (size_t)b0 * T * 64;
             k_me_head<false><<<dim3(grid), dim3(256), 0, st>>>(pa, nullptr, m->w4_16, m->b4, xo, M);
             ME_TRY(hipGetLastError());
-            k_me_proj<<<dim3(grid), dim3(256), 0, st>>>(xo, m->wp, m->bp, xp, M);
-            ME_TRY(hipGetLastError());
+            if (d_xf_proj) {
+                k_me_proj<<<dim3(grid), dim3(256), 0, st>>>(xo, m->wp, m->bp, d_xf_proj + (size_t)b0 * T * 64, M);
+                ME_TRY(hipGetLastError());
+            }
         }
         return hipSuccess;
     }
@@ -1205,11 +1221,12 @@ hipError_t dc_music_encode(dc_music* m, const float* d_mel, int B, int Tm, float
         const int M = Bc * T;
         const unsigned grid = (unsigned)((M + 127) / 128);
         float* xo = d_xf_out + (size_t)b0 * T * 64;
-        float* xp = d_xf_proj + (size_t)b0 * T * 64;
         k_me_head<true><<<dim3(grid), dim3(256), 0, st>>>(bh, bl, m->w4, m->b4, xo, M);
         ME_TRY(hipGetLastError());
-        k_me_proj<<<dim3(grid), dim3(256), 0, st>>>(xo, m->wp, m->bp, xp, M);
-        ME_TRY(hipGetLastError());
+        if (d_xf_proj) {
+            k_me_proj<<<dim3(grid), dim3(256), 0, st>>>(xo, m->wp, m->bp, d_xf_proj + (size_t)b0 * T * 64, M);
+            ME_TRY(hipGetLastError());
+        }
     }
 #undef ME_TRY
     return hipSuccess;

@@ -178,7 +178,7 @@ struct MusicImage {
     } conv[7];
     size_t w4, w4_16, b4;                 // conv4: bf16 hi + lo, fp16 hi + lo, bias
     size_t stem_w, stem_w16, stem_b, stem_wa;
-    size_t wp, bp;                        // proj
+    size_t wp, bp;                        // proj (kNone when the image was packed without it)
 };
 
 // v_mfma_f32_16x16x32 A fragments of the fused conv1 kernel (k_me_stem) for one of its three layers, Wm [16][K]: lane (co = l & 15,
@@ -201,8 +201,9 @@ inline void music_pack_stem(const std::vector<float>& Wm, int K, int cin, std::v
 }
 
 // Folds and packs the reference state_dict entries `music_encoder.*` / `proj.*` (all present, with the sizes of
-// dc_music_required: dc_music_check).
-inline MusicImage music_pack(const DcParams& params) {
+// dc_music_required: dc_music_check).  with_proj = false: the `music_encoder.*` entries alone (M2SNet's encoder has no proj); the
+// image is the same up to where proj would be appended.
+inline MusicImage music_pack(const DcParams& params, bool with_proj = true) {
     const auto P = [&](const std::string& n) -> const std::vector<float>& { return params.find(n)->second; };
     // eval-mode BatchNorm `bn` folded into the convolution in front of it (bias cb): s = gamma / sqrt(var + eps)
     const auto bn_fold = [&](const std::string& bn, const std::vector<float>& cb, std::vector<float>& scale, std::vector<float>& bias) {
@@ -280,8 +281,47 @@ inline MusicImage music_pack(const DcParams& params) {
     I.stem_w16 = A.add(stem_16);
     I.stem_b = A.add(stem_bias);
     I.stem_wa = A.add(stem_wa32);
-    const auto& bp = P("proj.bias");
-    I.wp = A.add(pack_nat(P("proj.weight"), 64, 64, 2, 4, false, true));
-    I.bp = A.add(ftvec(bp.data(), (int)bp.size(), 2));
+    I.wp = I.bp = MusicImage::kNone;
+    if (with_proj) {
+        const auto& bp = P("proj.bias");
+        I.wp = A.add(pack_nat(P("proj.weight"), 64, 64, 2, 4, false, true));
+        I.bp = A.add(ftvec(bp.data(), (int)bp.size(), 2));
+    }
     return I;
+}
+
+// ---- M2SNet fuse head image (kernel: dc_m2snet.hip) ---------------------------------------------------------------
+// fuse_layer of Contrastive_Stage/models/M2SNet.py:14-18: Conv1d(128 -> 64, k = 1), ReLU, Conv1d(64 -> 64, k = 1), ReLU,
+// Conv1d(64 -> 1, k = 1), Sigmoid.  The weights are copied unchanged (nothing to fold) into v_mfma_f32_32x32x2_f32 A fragments,
+// lane-major, one float per lane and k-step: lane l of fragment (mt, ks) = W[32 mt + (l & 31)][2 ks + (l >> 5)].  The last conv
+// has one output row: its fragments carry w2 in row 0 (lanes 0 and 32) and zeros elsewhere.
+constexpr int kHeadIn = 128, kHeadHid = 64;
+constexpr int kHeadW0 = 0;                                         // [2 mt][64 ks][64 lanes]
+constexpr int kHeadB0 = kHeadW0 + 2 * (kHeadIn / 2) * 64;           // [64]
+constexpr int kHeadW1 = kHeadB0 + kHeadHid;                         // [2 mt][32 ks][64 lanes]
+constexpr int kHeadB1 = kHeadW1 + 2 * (kHeadHid / 2) * 64;          // [64]
+constexpr int kHeadW2 = kHeadB1 + kHeadHid;                         // [32 ks][64 lanes]
+constexpr int kHeadB2 = kHeadW2 + (kHeadHid / 2) * 64;              // [1] (+ padding)
+constexpr int kHeadFloats = kHeadB2 + 64;
+
+inline void head_pack_frags(const float* W, int n_out, int k_in, float* dst) {
+    for (int mt = 0; mt < cdiv(n_out, 32); ++mt)
+        for (int ks = 0; ks < k_in / 2; ++ks)
+            for (int l = 0; l < 64; ++l) {
+                const int o = 32 * mt + (l & 31), k = 2 * ks + (l >> 5);
+                dst[((size_t)mt * (k_in / 2) + ks) * 64 + l] = o < n_out ? W[(size_t)o * k_in + k] : 0.f;
+            }
+}
+
+// params: `fuse_layer.{0,2,4}.{weight,bias}` (all present, sizes 64*128, 64, 64*64, 64, 64, 1)
+inline std::vector<float> m2s_head_pack(const DcParams& params) {
+    const auto P = [&](const char* n) -> const std::vector<float>& { return params.find(n)->second; };
+    std::vector<float> img(kHeadFloats, 0.f);
+    head_pack_frags(P("fuse_layer.0.weight").data(), kHeadHid, kHeadIn, img.data() + kHeadW0);
+    head_pack_frags(P("fuse_layer.2.weight").data(), kHeadHid, kHeadHid, img.data() + kHeadW1);
+    head_pack_frags(P("fuse_layer.4.weight").data(), 1, kHeadHid, img.data() + kHeadW2);
+    memcpy(img.data() + kHeadB0, P("fuse_layer.0.bias").data(), kHeadHid * sizeof(float));
+    memcpy(img.data() + kHeadB1, P("fuse_layer.2.bias").data(), kHeadHid * sizeof(float));
+    img[kHeadB2] = P("fuse_layer.4.bias")[0];
+    return img;
 }

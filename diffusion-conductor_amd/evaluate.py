@@ -156,6 +156,24 @@ def _encode_pair(motion_encoder, pred, gts, dim_pose, ids):
     return gen_lat, real_lat
 
 
+def _sync_predictions(m2snet, mel, pred, gts, dim_pose):
+    """M2SNet's per-frame predictions [B, T] for a batch, the music encoded once and fused with three motions: the ground truth,
+    the sampled poses, and the sampled poses of the NEXT clip of the batch (rolled by one: the mismatched control; None for a batch
+    of one clip).  Enqueued on the current stream; the tensors stay on the poses' device."""
+    B, T = pred.shape[0], pred.shape[1]
+    gt = torch.from_numpy(np.ascontiguousarray(np.stack(gts), np.float32))
+    mel = torch.as_tensor(mel)
+    if pred.is_cuda:
+        gt = gt.pin_memory().to(pred.device, non_blocking=True)
+        mel = mel.to(pred.device, non_blocking=True)
+    mus = m2snet.music_latent(mel)
+    real = m2snet.fuse(mus, m2snet.motion_latent(gt))
+    gen_lat = m2snet.motion_latent(pred.reshape(B, T, dim_pose // 2, 2))
+    gen = m2snet.fuse(mus, gen_lat)
+    mis = m2snet.fuse(mus, torch.roll(gen_lat, -1, 0).contiguous()) if B > 1 else None
+    return real, gen, mis
+
+
 def _latent_scores(results, nb, diversity_seed):
     """FGD, feat_dist and diversity (metrics.py) over every clip's latents in clip order."""
     from .metrics import diversity_score, frechet_gesture_distance
@@ -225,7 +243,7 @@ class _Scorer:
 
 
 def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed=0, smooth=False, verbose=True, motion_encoder=None,
-                     diversity_seed=0):
+                     diversity_seed=0, m2snet=None):
     """Samples every clip under `root` and returns {"per_clip": {id: mse}, "total_loss", "final_mse", "clips",
     "seconds", "frames_per_s"}.  Clip i (in sorted order) starts from noise seeded with (seed, i), so the result
     does not depend on batch_size or on the number of ranks.
@@ -238,6 +256,13 @@ def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed
     same stream, and the latents come back with the poses.  Every clip must have the poses' T frames (ValueError otherwise).
     With `smooth` the latents are those of the SMOOTHED poses - the reference scores the unsmoothed output.  Without an encoder
     the result is exactly what it was before these scores existed.
+
+    `m2snet` (an m2snet.M2SNet, or anything with its `music_latent`, `motion_latent` and `fuse`): the learned synchronisation
+    score as well - the one number here that looks at the music.  Each batch's music is encoded once and scored against the
+    ground truth, the sampled poses and, as the mismatched control, the sampled poses of the next clip of the batch (left out for a
+    batch of one clip, so the control depends on `batch_size`).  Adds "m2s_sync_real", "m2s_sync_gen", "m2s_sync_mismatched" (mean
+    per-frame predictions over all clips; nan when no batch had two clips) and "m2s_accuracy_gen" (metrics.sync_stats: matched =
+    generated, mismatched = rolled).  Without it the result is unchanged.
 
     The host stays out of the GPU's way: batch k + 1's files and noise are prepared, and batch k - 1's MSEs computed, on
     background threads while batch k is sampled; the poses come back through a pinned double buffer behind an event, not a stream
@@ -264,6 +289,7 @@ def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed
     lat_buf = [None, None]               # pinned [2 (generated, real), batch_size, 64, T] latent slots (motion_encoder only)
     slot_free = [None, None]             # event: the GPU has consumed the slot's pinned mel / noise buffers
     results = {}
+    sync = {}                            # batch -> (real, generated, mismatched | None) predictions [B, T] on the device (m2snet only)
     exchange_before = getattr(enc, "combine_exchange", None)
     ev_first = ev_last = None            # completion events of the first and the last batch: the GPU's own steady-state period
     n_after_first = 0
@@ -303,6 +329,8 @@ def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed
                 lat_h = lat_buf[s][:, :pred.shape[0]]
                 lat_h[0].copy_(lats[0], non_blocking=True)
                 lat_h[1].copy_(lats[1], non_blocking=True)
+            if m2snet is not None:
+                sync[k] = _sync_predictions(m2snet, mel, pred, gts, dim_pose)
             ph.copy_(pred, non_blocking=True)
             ev = None
             if pred.is_cuda:
@@ -327,6 +355,8 @@ def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed
                 bid, mel, gts = pf2.result
                 pred_d = trainer.generate_music_motion(mel, dim_pose, noise=pf2.noise, smooth=19 if smooth else None)
                 lats = _encode_pair(motion_encoder, pred_d, gts, dim_pose, bid) if motion_encoder is not None else None
+                if m2snet is not None:
+                    sync[k] = _sync_predictions(m2snet, mel, pred_d, gts, dim_pose)
                 pred = pred_d.cpu().numpy()
                 results[k] = [(cid, mse_loss(gts[i], pred[i].reshape([pred[i].shape[0], dim_pose // 2, 2]))) for i, cid in enumerate(bid)]
                 if lats is not None:
@@ -367,6 +397,15 @@ def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed
         if verbose:
             print("final_latent_mse: ", out["final_latent_mse"])
             print(f"fgd: {out['fgd']}  feat_dist: {out['feat_dist']}  diversity: {out['diversity']}")
+    if m2snet is not None:
+        from .metrics import sync_stats
+        real, gen, mis = ([torch.as_tensor(sync[k][i]).cpu().reshape(-1) for k in range(nb) if sync[k][i] is not None] for i in range(3))
+        st = sync_stats(torch.cat(gen), torch.cat(mis) if mis else None)
+        out["m2s_sync_real"] = sync_stats(torch.cat(real))["sync"]
+        out["m2s_sync_gen"], out["m2s_sync_mismatched"], out["m2s_accuracy_gen"] = st["sync"], st["non_sync"], st["accuracy"]
+        if verbose:
+            print(f"m2s_sync_real: {out['m2s_sync_real']}  m2s_sync_gen: {out['m2s_sync_gen']}  "
+                  f"m2s_sync_mismatched: {out['m2s_sync_mismatched']}  m2s_accuracy_gen: {out['m2s_accuracy_gen']}")
     return out
 
 
@@ -387,8 +426,10 @@ def main(argv=None):
     ap.add_argument("--no_eff", action="store_true")
     ap.add_argument("--metrics", action="store_true", help="also SE, FGD, feat_dist and diversity on the ST-GCN latents (metrics.py)")
     ap.add_argument("--m2snet", default=None, help="M2SNet checkpoint for --metrics (DataParallel state_dict, keys "
-                                                   "module.motion_encoder.*); omitted = seeded synthetic weights")
+                                                   "module.motion_encoder.*) and --sync (every key); omitted = seeded synthetic weights")
     ap.add_argument("--diversity_seed", type=int, default=0)
+    ap.add_argument("--sync", action="store_true", help="also M2SNet's synchronisation score of the sampled poses against the music "
+                                                        "(m2snet.py; every entry of --m2snet, or seeded synthetic weights)")
     args = ap.parse_args(argv)
     from . import DDPMTrainer, MotionTransformer
     dev = torch.device("cuda", args.gpu_id)
@@ -413,8 +454,17 @@ def main(argv=None):
             menc = MotionEncoder_STGCN(dev).load_state_dict(synthetic_motion_encoder_state_dict())
             print("--metrics without --m2snet: the motion encoder has seeded synthetic weights, so SE / FGD / feat_dist / diversity "
                   "only check the pipeline, they say nothing about the motions")
+    m2s = None
+    if args.sync:
+        from .m2snet import M2SNet, load_m2snet_full
+        if args.m2snet:
+            m2s = load_m2snet_full(args.m2snet, dev)
+        else:
+            from .synthetic import synthetic_m2snet_state_dict
+            m2s = M2SNet(dev).load_state_dict(synthetic_m2snet_state_dict())
+            print("--sync without --m2snet: M2SNet has seeded synthetic weights, so the m2s_* scores only check the pipeline")
     r = evaluate_dataset(tr, args.data_root, 26, args.batch_size, args.limit, args.seed, args.smooth, motion_encoder=menc,
-                         diversity_seed=args.diversity_seed)
+                         diversity_seed=args.diversity_seed, m2snet=m2s)
     print(f"{r['clips']} clips in {r['seconds']:.2f} s = {r['frames_per_s']:.0f} frames/s")
     return 0
 

@@ -12,6 +12,9 @@ Host numpy / scipy over the ST-GCN latents of motion_encoder.py (``latent(x)`` =
 * means are float32 (numpy's mean of float32 data), ``np.cov`` and ``scipy.linalg.sqrtm`` run in float64; feature distance,
   diversity and SE are float32 reductions and come back as ``np.float32``, as in the reference.
 
+``sync_stats`` is the one score that looks at the music: the mean predictions and the 0.5-threshold accuracy of M2SNet
+(m2snet.py) over matched and mismatched music / motion pairs, as Contrastive_Stage/M2SNet_eval.py:58-107 reports them.
+
 Beat consistency (BC) is not here: its music side is librosa's onset / beat tracker.
 """
 from __future__ import annotations
@@ -104,3 +107,25 @@ def sync_error(per_clip):
     for v in vals:
         total += v
     return total / len(vals)
+
+
+def sync_stats(pred_matched, pred_mismatched=None):
+    """{"sync", "non_sync", "accuracy"} of M2SNet's per-frame predictions on matched pairs and on mismatched pairs (any shapes;
+    tensors or arrays), as Contrastive_Stage/M2SNet_eval.py:60-67 computes them per batch: the two means are float32 means
+    (`torch.mean(pred).item()`), accuracy = (count(matched > 0.5) + count(mismatched < 0.5)) / the number of predictions - a
+    prediction of exactly 0.5 counts for neither side.  Without mismatched pairs "non_sync" is nan and the accuracy is the matched
+    pairs' alone."""
+    import torch
+
+    def flat(p):
+        t = p.detach().cpu() if torch.is_tensor(p) else torch.from_numpy(np.ascontiguousarray(np.asarray(p)))
+        return t.to(torch.float32).reshape(-1)
+
+    m = flat(pred_matched)
+    n = flat(pred_mismatched) if pred_mismatched is not None else torch.empty(0)
+    if m.numel() == 0:
+        raise ValueError("sync_stats: no matched predictions")
+    tp = np.sum(m.numpy() > 0.5)
+    tf = np.sum(n.numpy() < 0.5)
+    return {"sync": torch.mean(m).item(), "non_sync": torch.mean(n).item() if n.numel() else float("nan"),
+            "accuracy": ((tp + tf) / (m.numel() + n.numel())).item()}

@@ -28,6 +28,8 @@ EXPORTS = [
     "dc_motion_encoder_create", "dc_motion_encoder_destroy", "dc_motion_encoder_set_param", "dc_motion_encoder_finalize",
     "dc_motion_encoder_encode",
     "dc_ddim_coefficients_known", "dc_sampler_set_known",
+    "dc_m2snet_create", "dc_m2snet_destroy", "dc_m2snet_set_param", "dc_m2snet_finalize", "dc_m2snet_encode_music", "dc_m2snet_fuse",
+    "dc_m2snet_score",
 ]
 
 UPDATE_CLIP_DENOISED, UPDATE_EPSILON = 1, 2          # flags of dc_sampler_ddim_loop_ex
@@ -43,7 +45,7 @@ class DcError(RuntimeError):
     pass
 
 
-SOURCES = ("dc_kernels.hip", "dc_api.hip", "dc_music.hip", "dc_layer16.hip", "dc_stgcn.hip")
+SOURCES = ("dc_kernels.hip", "dc_api.hip", "dc_music.hip", "dc_layer16.hip", "dc_stgcn.hip", "dc_m2snet.hip")
 HEADERS = ("dc_common.h", "dc_dev.h", "dc_form.h", "dc_launch.h", "dc_music.h", "dc_pack.h")
 EXTRA_FLAGS = {}      # per-source compiler flags
 
@@ -148,6 +150,15 @@ def lib():
     L.dc_motion_encoder_set_param.argtypes = [C.c_void_p, C.c_char_p, fp, C.c_int64]
     L.dc_motion_encoder_finalize.argtypes = [C.c_void_p]
     L.dc_motion_encoder_encode.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    L.dc_m2snet_create.argtypes = [C.c_int32, C.POINTER(C.c_void_p)]
+    L.dc_m2snet_destroy.argtypes = [C.c_void_p]
+    L.dc_m2snet_destroy.restype = None
+    L.dc_m2snet_set_param.argtypes = [C.c_void_p, C.c_char_p, fp, C.c_int64]
+    L.dc_m2snet_finalize.argtypes = [C.c_void_p]
+    L.dc_m2snet_encode_music.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    L.dc_m2snet_fuse.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.dc_m2snet_score.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                  C.c_void_p]
     _lib = L
     return L
 
@@ -546,3 +557,88 @@ class NativeMotionEncoder:
             _check(lib().dc_motion_encoder_encode(self._h, motion.data_ptr(), B, T, out.data_ptr(),
                                                   C.c_void_p(torch.cuda.current_stream().cuda_stream)))
         return out
+
+
+# ---------------------------------------------------------------------------------------
+# M2SNet (the learned music-motion synchronisation score)
+# ---------------------------------------------------------------------------------------
+class NativeM2SNet:
+    """Owns one dc_m2snet (dc_ddim.h).  Tensors are torch CUDA(ROCm) tensors; only their data_ptr() crosses the ABI."""
+
+    def __init__(self, device=0):
+        self._h = C.c_void_p()
+        _check(lib().dc_m2snet_create(int(device), C.byref(self._h)))
+        self.device = int(device)
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            lib().dc_m2snet_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_param(self, name, a):
+        a = np.ascontiguousarray(np.asarray(a), np.float32)
+        _check(lib().dc_m2snet_set_param(self._h, name.encode(), _fptr(a), a.size))
+
+    def finalize(self):
+        _check(lib().dc_m2snet_finalize(self._h))
+
+    @staticmethod
+    def _ok(t, shape=None):
+        import torch
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+        assert shape is None or tuple(t.shape) == tuple(shape), (tuple(t.shape), shape)
+
+    @staticmethod
+    def _stream():
+        import torch
+        return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    def encode_music(self, mel, out=None):
+        """mel fp32 [B, Tm, 128] on the device -> music latent fp32 [B, (Tm-1)//3+1, 64] (`out`: a tensor to fill)."""
+        import torch
+        self._ok(mel)
+        assert mel.dim() == 3 and mel.shape[2] == 128, tuple(mel.shape)
+        B, Tm = int(mel.shape[0]), int(mel.shape[1])
+        T = (Tm - 1) // 3 + 1
+        if out is None:
+            out = torch.empty((B, T, 64), dtype=torch.float32, device=mel.device)
+        self._ok(out, (B, T, 64))
+        with torch.cuda.device(mel.device):
+            _check(lib().dc_m2snet_encode_music(self._h, mel.data_ptr(), B, Tm, out.data_ptr(), self._stream()))
+        return out
+
+    def fuse(self, music_latent, motion_latent, logits=False):
+        """music latent [B, T, 64] and motion latent [B, 64, T] (fp32, on the device) -> probability [B, T], or the pair
+        (probability, logit) with `logits`."""
+        import torch
+        self._ok(music_latent)
+        B, T = int(music_latent.shape[0]), int(music_latent.shape[1])
+        self._ok(music_latent, (B, T, 64))
+        self._ok(motion_latent, (B, 64, T))
+        prob = torch.empty((B, T), dtype=torch.float32, device=music_latent.device)
+        logit = torch.empty_like(prob) if logits else None
+        with torch.cuda.device(prob.device):
+            _check(lib().dc_m2snet_fuse(self._h, music_latent.data_ptr(), motion_latent.data_ptr(), B, T, prob.data_ptr(),
+                                        logit.data_ptr() if logits else None, self._stream()))
+        return (prob, logit) if logits else prob
+
+    def score(self, mel, motion, logits=False):
+        """mel [B, Tm, 128] and motion [B, T, 13, 2] (or [B, T, 26]) -> probability [B, T] (or (probability, logit))."""
+        import torch
+        self._ok(mel)
+        self._ok(motion)
+        assert mel.dim() == 3 and mel.shape[2] == 128, tuple(mel.shape)
+        B, Tm, T = int(mel.shape[0]), int(mel.shape[1]), int(motion.shape[1])
+        assert motion.shape[0] == B and motion.numel() == B * T * 26, (tuple(mel.shape), tuple(motion.shape))
+        prob = torch.empty((B, T), dtype=torch.float32, device=mel.device)
+        logit = torch.empty_like(prob) if logits else None
+        with torch.cuda.device(prob.device):
+            _check(lib().dc_m2snet_score(self._h, mel.data_ptr(), motion.data_ptr(), B, Tm, T, prob.data_ptr(),
+                                         logit.data_ptr() if logits else None, self._stream()))
+        return (prob, logit) if logits else prob

@@ -247,3 +247,35 @@ def array_digest(a):
     without storing it."""
     x = np.asarray(a, np.float64).ravel()
     return np.array([x.sum(), np.abs(x).sum(), (x * np.arange(x.size)).sum()])
+
+
+# gains of the seeded fuse head over PyTorch's default initialiser bound, and its last bias (see synthetic_m2snet_state_dict)
+M2SNET_FUSE_GAIN = (6.0, 4.0, 8.0)
+M2SNET_FUSE_LAST_BIAS = -1.0
+
+
+def synthetic_m2snet_state_dict(seed: int = 0):
+    """name -> np.ndarray for every state_dict entry of M2SNet (m2snet.py), in the reference module's order: the `music_encoder.*`
+    entries of synthetic_state_dict(seed), synthetic_motion_encoder_state_dict(seed) under `motion_encoder.`, and a seeded fuse
+    head.  With weights at the initialiser's scale every logit of the head lands in a narrow positive band - every frame "in
+    sync", which tests nothing about the 0.5 threshold - so the head's weights are U(-1/sqrt(fan_in), 1/sqrt(fan_in)) times
+    M2SNET_FUSE_GAIN per layer and the last bias is M2SNET_FUSE_LAST_BIAS: on the fixture's inputs (tools/make_golden_m2snet.py
+    asserts it) the logits span more than [-2, 2] with at least 20 % of the frames on each side of 0, and both hidden layers have
+    dead and live ReLU units."""
+    from .m2snet import m2snet_shapes
+    den = synthetic_state_dict(seed=seed)
+    mot = synthetic_motion_encoder_state_dict(seed)
+    out = OrderedDict()
+    for name, shape in m2snet_shapes().items():
+        if name.startswith("music_encoder."):
+            out[name] = den[name]
+        elif name.startswith("motion_encoder."):
+            out[name] = mot[name[len("motion_encoder."):]]
+        else:
+            layer = int(name.split(".")[1]) // 2
+            fan_in = 128 if layer == 0 else 64
+            a = _rng(seed, "m2snet:" + name).uniform(-1.0, 1.0, shape) * (M2SNET_FUSE_GAIN[layer] / np.sqrt(fan_in))
+            if name == "fuse_layer.4.bias":
+                a = np.full(shape, M2SNET_FUSE_LAST_BIAS)
+            out[name] = np.ascontiguousarray(a, dtype=np.float32)
+    return out

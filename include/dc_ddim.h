@@ -374,6 +374,44 @@ DC_EXPORT int dc_motion_encoder_finalize(dc_motion_encoder* e);
 DC_EXPORT int dc_motion_encoder_encode(dc_motion_encoder* e, const float* d_motion, int32_t B, int32_t T, float* d_out,
                                        void* stream);
 
+/* ---- M2SNet: the learned music-motion synchronisation score ------------------------------------------------------------------
+ * Replaces constructing M2SNet (Contrastive_Stage/models/M2SNet.py:7-18: a MusicEncoder, a MotionEncoder_STGCN and fuse_layer) on
+ * the device `device`.  The handle owns its own music encoder - M2SNet's `music_encoder.*` weights are not the diffusion
+ * checkpoint's - and its own motion encoder. */
+typedef struct dc_m2snet dc_m2snet;
+DC_EXPORT int dc_m2snet_create(int32_t device, dc_m2snet** out);
+DC_EXPORT void dc_m2snet_destroy(dc_m2snet* n);
+
+/* Replaces M2SNet.load_state_dict (Contrastive_Stage/M2SNet_train.py loads the DataParallel state_dict): one call per entry with
+ * the key WITHOUT the "module." prefix - "music_encoder.*" (MusicEncoder.py:30-53), "motion_encoder.*" (MotionEncoder.py:6-15) and
+ * "fuse_layer.{0,2,4}.{weight,bias}" (M2SNet.py:14-18), 234 entries - and its contiguous fp32 data.  Unknown key or wrong numel
+ * -> DC_ERR_PARAM.  The num_batches_tracked counters and motion_encoder.st_gcn.fcn.* are accepted and ignored. */
+DC_EXPORT int dc_m2snet_set_param(dc_m2snet* n, const char* name, const float* h_data, int64_t numel);
+
+/* Replaces M2SNet.eval() + .to(device): folds every BatchNorm (running statistics) into the conv in front of it and uploads the
+ * three weight images.  An entry that was never set -> DC_ERR_PARAM.  Synchronous.  Every entry point below returns
+ * DC_ERR_INVALID before it. */
+DC_EXPORT int dc_m2snet_finalize(dc_m2snet* n);
+
+/* Replaces hx = self.music_encoder(x) (M2SNet.py:32; MusicEncoder.forward, MusicEncoder.py:46-53): d_mel fp32 [B, Tm, 128] ->
+ * d_music_latent fp32 [B, T, 64], T = (Tm-1)/3+1, caller-allocated; Tm >= 4 (the reference's reflection padding raises below).
+ * Always the DC_ME_SPLIT format (6e-6 at the encoder's output); DC_ME_PREC does not apply to this encoder. */
+DC_EXPORT int dc_m2snet_encode_music(dc_m2snet* n, const float* d_mel, int32_t B, int32_t Tm, float* d_music_latent, void* stream);
+
+/* Replaces torch.cat([hx, hy], dim=2) and fuse_layer (M2SNet.py:34-35, 14-18) on latents the caller holds: d_music_latent fp32
+ * [B, T, 64] (as dc_m2snet_encode_music writes it, 16-byte aligned) and d_motion_latent fp32 [B, 64, T] (as
+ * dc_motion_encoder_encode writes it), read as they are -> d_prob fp32 [B, T], the per-frame probability that the motion is in
+ * sync with the music, and, unless NULL, d_logit fp32 [B, T], the value in front of the sigmoid.  B >= 1, T >= 1.  Exact-fp32
+ * products in k order; a frame's result depends on that frame alone and is bit-identical whatever the batch around it. */
+DC_EXPORT int dc_m2snet_fuse(dc_m2snet* n, const float* d_music_latent, const float* d_motion_latent, int32_t B, int32_t T,
+                             float* d_prob, float* d_logit, void* stream);
+
+/* Replaces M2SNet.forward (M2SNet.py:31-36), the quantity Contrastive_Stage/M2SNet_eval.py:58-107 averages: d_mel fp32
+ * [B, Tm, 128] and d_motion fp32 [B, T, 13, 2] -> d_prob / d_logit as above.  T must equal (Tm-1)/3+1 and Tm >= 4, DC_ERR_INVALID
+ * otherwise, before anything is enqueued.  The latents live in the handle's workspace (grown on demand; 64 clips per pass). */
+DC_EXPORT int dc_m2snet_score(dc_m2snet* n, const float* d_mel, const float* d_motion, int32_t B, int32_t Tm, int32_t T,
+                              float* d_prob, float* d_logit, void* stream);
+
 /* Introspection used by tests: bytes of device workspace currently held; frames per clip of the sampler's internal token space
  * (the T of dc_sampler_set_conditioning, padded to whole 32-frame groups where the clip-aligned kernels run): the layout of the
  * buffers dc_sampler_debug_read returns. */
