@@ -40,8 +40,9 @@ int fail(int code, const char* fmt, ...) {
         if (e_ != hipSuccess) return fail(DC_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
 
-enum KernelId { K_BEGIN = 0, K_SILU, K_FILM, K_EMBED, K_COMBINE, K_LAYER, K_NOISE, K_COUNT };
-const char* kKernelNames[K_COUNT] = {"k_begin_step", "k_silu_emb", "k_film_gemm", "k_embed_front", "k_attn_combine", "k_layer", "k_step_noise"};
+enum KernelId { K_BEGIN = 0, K_SILU, K_FILM, K_EMBED, K_COMBINE, K_LAYER, K_NOISE, K_GUIDE, K_COUNT };
+const char* kKernelNames[K_COUNT] = {"k_begin_step", "k_silu_emb", "k_film_gemm", "k_embed_front", "k_attn_combine", "k_layer", "k_step_noise",
+                                     "k_guided_update"};
 
 struct Prof {                       // per-kernel profile (dc_sampler_profile_loop): events around every launch
     std::vector<hipEvent_t> ev;     // pairs
@@ -122,11 +123,23 @@ struct dc_sampler : Formats {     // (set_precision(cfg.precision))
     // known values (dc_sampler_set_known): the caller's three [B][Tx][P] tensors, valid for clips of (known_B, known_Tx); the kernels read
     // their addresses from d_kslot
     const float *known_val = nullptr, *known_mask = nullptr, *known_noise = nullptr;
-    int known_B = 0, known_Tx = 0;
+    int known_B = 0, known_Tx = 0;            // the CALLER's clips (user_B()) and frames the tensors were set for ...
+    bool known_guided = false;                // ... and whether that conditioning was guided: any other (B, T, guided) clears them
     const float** d_kslot = nullptr;
     // Savitzky-Golay smoothing applied by the loop's final write (dc_sampler_set_smoothing; window 0 = off)
     int smooth_window = 0, smooth_order = 0, smooth_table_window = 0;     // (table_window: the hat matrix d_smooth_coef holds)
     float* d_smooth_coef = nullptr;
+    // Classifier-free guidance (dc_sampler_set_conditioning_guided): B above is then the INTERNAL batch, the caller's B / 2 clips followed by
+    // their unconditional shadows; the caller's tensors (noise, out, snapshots, step noise, known values) stay [B / 2][Tx][P]
+    bool guided = false;
+    float guide_w = 1.f;            // guidance scale; travels through d_wslot, so another scale replays the same graph
+    float* d_wslot = nullptr;
+    float* d_raw = nullptr;         // the last layer's raw model output of all internal clips [B][Tx][P]
+    size_t cap_raw = 0;
+    float *d_xf2_proj = nullptr, *d_xf2_out = nullptr;      // feature images [B][Tx][64] of the internal batch (second half: the null pair)
+    size_t cap_xf2 = 0;
+    int user_B() const { return guided ? B / 2 : B; }       // clips of the caller's tensors
+    int last_film_groups = 0;       // groups of d_E the last enqueued step's FiLM GEMM wrote (dc_sampler_status scans no others)
 
     DcModel h_model_split{};     // fp16 precision: the same model with the layer stage images in their split form ([hi][lo][consts]): the loop's precise tail
     DcModel* d_model_split = nullptr;
@@ -762,6 +775,8 @@ unsigned long long form_key(const dc_sampler* s, const Switches& w) {
     k |= (unsigned long long)(s->upd_flags & 0xff) << 16;     // (the noise / known tensors' addresses are not baked in: the kernels read them from d_zslot / d_kslot)
     k |= (s->l16_own ? 1ull : 0ull) << 24;
     k |= (unsigned long long)((s->clip_aligned + 1) & 3) << 25;
+    // guided loops: another last-layer store, k_guided_update, and - bit 28 - the FiLM GEMM over the shared column's groups
+    k |= guided_key_bits(s->guided, s->guided && guided_film_groups(s->B, s->T, s->G, !s->split_film, w) < s->G);
     return k;
 }
 
@@ -808,7 +823,7 @@ int enqueue_step(dc_sampler* s, hipStream_t st, const Step& c, const Switches& w
         LAUNCH(K_BEGIN, dc_launch_begin_step(st, s->d_iter, s->d_t_of_iter, s->d_coef_of_t, s->d_snap_of_iter,
                                              s->d_t_clip, s->d_coef_cur, s->d_snap_cur, B));
     if (c.loop_mode && (s->upd_flags & DC_UPD_ZSTEP))       // this iteration's draws (eta > 0, library-generated): consumed by the last layer's epilogue
-        LAUNCH(K_NOISE, dc_launch_step_noise(st, s->d_zstep, (size_t)B * Tx * s->cfg.input_feats, 0, reinterpret_cast<const unsigned long long*>(s->d_zslot) + 1,
+        LAUNCH(K_NOISE, dc_launch_step_noise(st, s->d_zstep, (size_t)s->user_B() * Tx * s->cfg.input_feats, 0, reinterpret_cast<const unsigned long long*>(s->d_zslot) + 1,
                                              iter_base, folded ? graph_step : 0,
                                              folded ? nullptr : s->d_snap_cur, 0));
     if (!f.fuse_silu)
@@ -819,6 +834,8 @@ int enqueue_step(dc_sampler* s, hipStream_t st, const Step& c, const Switches& w
     DcFilmArgs fa = film_args(s, f.fuse_silu ? s->d_pp : nullptr, t_src);
     if (f.g1_tiles) fa.bias_ft = s->h_model.film_b_g1, fa.bias16 = s->h_model.film_b16_g1;
     if (f.film_tail) fa.W16 = s->h_model.film_w16_tail;
+    s->last_film_groups = f.film_groups;
+    fa.G = f.film_groups;       // (guided, shared column: the conditional half's groups + one for every shadow group; else G)
     fa.clk = want_stamps ? s->d_stamps + 252 : nullptr;
     if (f.adapt) fa.rate_in = s->d_film_rate + 1024 * s->film_rate_parity, fa.rate_out = s->d_film_rate + 1024 * (s->film_rate_parity ^ 1);
     fa.iter_base = iter_base;
@@ -833,8 +850,9 @@ int enqueue_step(dc_sampler* s, hipStream_t st, const Step& c, const Switches& w
     const int nl_run = f.nl_run;
     DcLayerArgs la{};
     la.dm = dmod, la.hbuf = s->d_h, la.E = s->d_E, la.NT = s->NT, la.recs = s->d_recs, la.length = s->d_length, la.xin = c.x_src, la.xout = c.x_dst;
-    la.out_mode = c.loop_mode ? 1 : 0, la.coef_cur = coef_src, la.snap_cur = snap_src, la.snaps = s->d_snaps, la.iter_base = iter_base;
-    la.M = M, la.T = T, la.G = G, la.B = B, la.Tx = Tx;
+    la.out_mode = (c.loop_mode && !f.guided) ? 1 : 0, la.coef_cur = coef_src, la.snap_cur = snap_src, la.snaps = s->d_snaps, la.iter_base = iter_base;
+    la.M = M, la.T = T, la.G = G, la.B = B, la.Tx = Tx, la.e_groups = f.film_groups;
+    if (f.guided) la.xout = s->d_raw;      // the raw output of all 2 B clips; k_guided_update (below) combines the halves and updates x
     la.upd = DcUpdate{s->d_zslot, s->d_status, (c.loop_mode ? s->upd_flags : 0) | f.upd_flags, folded ? graph_step : -1, nullptr, s->d_kslot};
     DcLayerArgs la_stamps = la;      // (stage stamps of layer 3 in diagnostic builds: DcUpdate::stamps carries the buffer)
     la_stamps.upd.stamps = s->d_stamps;
@@ -843,6 +861,9 @@ int enqueue_step(dc_sampler* s, hipStream_t st, const Step& c, const Switches& w
         for (int l = 0; l < nl_run; ++l)        // (stage stamps: tools/stage_stamps_full.py + a -DDC_FULL_STAMPS build)
             LAUNCH(K_LAYER, dc_launch_layer_full(st, fs, ss, (want_stamps && l == 3) ? la_stamps : la, l, s->d_kv_sa[l & 1], s->d_kv_sa[(l + 1) & 1],
                                                  s->d_kv_ca, s->KT, (l == nl_run - 1) ? f.stop_stage : 0));
+        if (f.guided)
+            LAUNCH(K_GUIDE, dc_launch_guided_update(st, s->d_raw, c.x_dst, (size_t)s->user_B() * Tx * s->cfg.input_feats, coef_src, snap_src,
+                                                    s->d_snaps, iter_base, s->d_wslot, la.upd));
         return DC_OK;
     }
     const DcLayerForm lf{fs, ss, f.wgr, f.narrow, f.g1_tiles, f.upc, f.rec_stride};
@@ -865,6 +886,9 @@ int enqueue_step(dc_sampler* s, hipStream_t st, const Step& c, const Switches& w
         LAUNCH(K_LAYER, dc_launch_layer(st, lf, la, l, s->d_a_sa, s->d_a_ca, (l == nl_run - 1) ? f.stop_stage : 0,
                                         ((l == 3 || l == 4) && want_stamps) ? s->d_stamps : nullptr));
     }
+    if (f.guided)
+        LAUNCH(K_GUIDE, dc_launch_guided_update(st, s->d_raw, c.x_dst, (size_t)s->user_B() * Tx * s->cfg.input_feats, coef_src, snap_src,
+                                                s->d_snaps, iter_base, s->d_wslot, la.upd));
     return DC_OK;
 }
 
@@ -895,7 +919,9 @@ int loop_common(dc_sampler* s, const float* d_noise, float* d_out, int S, const 
         return fail(DC_ERR_UNSUPPORTED, "EPSILON model with full attention (no_eff) at eta = 0 is outside the 1e-3 parity bound (up to 1.3e-3); "
                                         "use linear attention, or eta > 0");
     // known values (dc_sampler_set_known) serve the loops of the geometry they were set for; another (B, T) clears them
-    if (s->known_mask && (s->known_B != s->B || s->known_Tx != s->Tx)) s->known_val = s->known_mask = s->known_noise = nullptr;
+    // (the caller's geometry: on a guided conditioning B is the internal batch, twice the clips the known tensors hold)
+    if (s->known_mask && (s->known_B != s->user_B() || s->known_Tx != s->Tx || s->known_guided != s->guided))
+        s->known_val = s->known_mask = s->known_noise = nullptr;
     const bool known = s->known_mask != nullptr;
     if (known && S > 1 && !(h_coef[(size_t)DC_COEF * (S - 1) + 5] > 0.f))
         return fail(DC_ERR_INVALID, "known values are set: the loop needs the [S][8] table of dc_ddim_coefficients_known (slot 5 = sqrt(1 - abar_prev))");
@@ -905,7 +931,7 @@ int loop_common(dc_sampler* s, const float* d_noise, float* d_out, int S, const 
         return fail(DC_ERR_INVALID, "smoothing window %d exceeds the %d frames of a clip", s->smooth_window, s->Tx);
     int rc;
     if ((rc = ensure_steps(s, S))) return rc;
-    const size_t MP = (size_t)s->B * s->Tx * s->cfg.input_feats;          // x, snapshots: the caller's layout
+    const size_t MP = (size_t)s->user_B() * s->Tx * s->cfg.input_feats;          // x, snapshots: the caller's layout (guided: its B clips, half the internal batch)
     if ((size_t)n_snap * MP > s->cap_snap) {          // (capacity in elements: the batch may have grown since the last call)
         drop_graph(s);
         s->cap_snap = 0;
@@ -969,6 +995,10 @@ int loop_common(dc_sampler* s, const float* d_noise, float* d_out, int S, const 
         HIP_TRY(dc_launch_set_known(st, s->d_kslot, s->known_val, s->known_mask, s->known_noise));
         HIP_TRY(dc_launch_known_blend(st, s->d_x, s->known_val, s->known_mask, s->known_noise, c0[6], c0[7], MP));
     }
+    if (s->guided) {      // both halves of x start equal (behind the blend), and the scale goes into its slot
+        HIP_TRY(hipMemcpyAsync(s->d_x + MP, s->d_x, MP * 4, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(dc_launch_set_scale(st, s->d_wslot, s->guide_w));
+    }
     const bool no_graph = getenv("DC_DISABLE_GRAPH") != nullptr;
     // precise tail: the loop's last `tail` model evaluations on split operands (loop_tail, dc_form.h; DC_PRECISE_TAIL=k overrides)
     const char* env_tail = getenv("DC_PRECISE_TAIL");
@@ -983,7 +1013,7 @@ int loop_common(dc_sampler* s, const float* d_noise, float* d_out, int S, const 
         for (int i = 0; i < n; ++i) {
             Step c;
             c.loop_mode = true, c.x_src = c.x_dst = s->d_x, c.graph_step = graph ? i : -1, c.split = i >= n - split_n, c.g1_loop = tail > 0;
-            c.next_plain = i + 1 < n - split_n, c.embedded = embedded, c.profile = profile, c.known = known;
+            c.next_plain = i + 1 < n - split_n, c.embedded = embedded, c.profile = profile, c.known = known, c.guided = s->guided;
             StepDone d;
             if (int rc = enqueue_step(s, st, c, sw, &d)) return rc;
             embedded = d.embedded_next, folded = d.folded;
@@ -1038,7 +1068,7 @@ int loop_common(dc_sampler* s, const float* d_noise, float* d_out, int S, const 
     // the final write x0 -> the caller's tensor: a copy, or (dc_sampler_set_smoothing) the Savitzky-Golay filter along time
     // (tools/visualization.py:20-26,126) reading the loop's x0 and writing the caller's tensor directly - no pass of its own
     if (s->smooth_window > 0) {
-        HIP_TRY(dc_launch_savgol(st, s->d_x, d_out, s->d_smooth_coef, s->B, s->Tx, s->cfg.input_feats, s->smooth_window));
+        HIP_TRY(dc_launch_savgol(st, s->d_x, d_out, s->d_smooth_coef, s->user_B(), s->Tx, s->cfg.input_feats, s->smooth_window));      // (guided: the first half)
     } else {
         HIP_TRY(hipMemcpyAsync(d_out, s->d_x, MP * 4, hipMemcpyDeviceToDevice, st));
     }
@@ -1060,6 +1090,9 @@ int denoise(dc_sampler* s, const float* d_x, const int32_t* h_timesteps, float* 
     if (!s || !s->finalized) return fail(DC_ERR_INVALID, "sampler not finalized");
     if (!s->cond_set) return fail(DC_ERR_INVALID, "dc_sampler_set_conditioning must be called first");
     if (!d_x || !h_timesteps || !d_out) return fail(DC_ERR_INVALID, "null pointer argument");
+    if (s->guided)
+        return fail(DC_ERR_INVALID, "the conditioning is guided (dc_sampler_set_conditioning_guided): single evaluations are not guided - per-clip "
+                                    "timesteps break the unconditional half's shared FiLM column; call dc_sampler_set_conditioning and combine on your side");
     for (int b = 0; b < s->B; ++b)
         if (h_timesteps[b] < 0 || h_timesteps[b] >= s->cfg.max_timesteps)
             return fail(DC_ERR_INVALID, "timestep %d outside [0,%d)", h_timesteps[b], s->cfg.max_timesteps);
@@ -1222,7 +1255,8 @@ void dc_sampler_destroy(dc_sampler* s) {
     void* ptrs[] = {s->d_arena, s->d_model, s->d_model_split, s->d_length, s->d_pp, s->d_s_hi, s->d_s_lo, s->d_E, s->d_h, s->d_recs, s->d_a_sa,
                     s->d_a_ca, s->d_x, s->d_snaps, s->d_recs_ca, s->d_nh_hi, s->d_nh_lo, s->d_iter,
                     s->d_t_clip, s->d_snap_cur, s->d_t_of_iter, s->d_snap_of_iter, s->d_coef_cur, s->d_coef_of_t, s->d_coef_of_iter,
-                    s->d_kv_sa[0], s->d_kv_sa[1], s->d_kv_ca, s->d_stamps, s->d_film_rate, s->d_status, s->d_smooth_coef, s->d_zslot, s->d_kslot, s->d_zstep, s->d_a_ca16, s->d_gran};
+                    s->d_kv_sa[0], s->d_kv_sa[1], s->d_kv_ca, s->d_stamps, s->d_film_rate, s->d_status, s->d_smooth_coef, s->d_zslot, s->d_kslot, s->d_zstep, s->d_a_ca16, s->d_gran,
+                    s->d_wslot, s->d_raw, s->d_xf2_proj, s->d_xf2_out};
     for (void* p : ptrs)
         if (p) hipFree(p);
     dc_music_destroy(s->music);
@@ -1291,8 +1325,9 @@ int dc_sampler_finalize_params(dc_sampler* s) {
     return DC_OK;
 }
 
-int dc_sampler_set_conditioning(dc_sampler* s, const float* d_xf_proj, const float* d_xf_out, const int32_t* h_length,
-                                int32_t B, int32_t T, void* stream) {
+// dc_sampler_set_conditioning over B clips; the guided entry point calls it with its 2 B internal clips
+static int set_conditioning(dc_sampler* s, const float* d_xf_proj, const float* d_xf_out, const int32_t* h_length, int32_t B, int32_t T,
+                            void* stream) {
     if (!s || !s->finalized) return fail(DC_ERR_INVALID, "sampler not finalized");
     if (!d_xf_proj || !d_xf_out || B < 1 || T < 1) return fail(DC_ERR_INVALID, "bad conditioning arguments (need B >= 1, T >= 1)");
     if (T < 32 && clip_stride(s, B, T) < 32)
@@ -1353,6 +1388,72 @@ int dc_sampler_set_conditioning(dc_sampler* s, const float* d_xf_proj, const flo
     }
     s->cond_set = true;
     return sync_out(s, user);
+}
+
+int dc_sampler_set_conditioning(dc_sampler* s, const float* d_xf_proj, const float* d_xf_out, const int32_t* h_length,
+                                int32_t B, int32_t T, void* stream) {
+    const int rc = set_conditioning(s, d_xf_proj, d_xf_out, h_length, B, T, stream);
+    // a plain conditioning switches guidance off (a failed call on a guided sampler leaves no conditioning set: the internal batch
+    // may be half rebuilt)
+    if (s && s->guided) s->guided = false, s->cond_set = rc == DC_OK;
+    return rc;      // (known values set on the guided conditioning are dropped by the next loop: known_guided)
+}
+
+// Classifier-free guidance.  The reference trains its denoiser for it - MotionTransformer.encode_music (models/transformer.py:389,451-459)
+// zeroes a token's music features with probability cond_mask_prob = 0.1 before `proj` - and has no sampling counterpart.
+int dc_sampler_set_conditioning_guided(dc_sampler* s, const float* d_xf_proj, const float* d_xf_out, const int32_t* h_length, int32_t B,
+                                       int32_t T, const float* h_null_proj, const float* h_null_out, void* stream) {
+    if (!s || !s->finalized) return fail(DC_ERR_INVALID, "sampler not finalized");
+    if (!h_null_proj || !h_null_out) return fail(DC_ERR_INVALID, "guided conditioning: the null pair (h_null_proj[64], h_null_out[64]) is NULL");
+    if (!d_xf_proj || !d_xf_out || B < 1 || T < 1) return fail(DC_ERR_INVALID, "bad conditioning arguments (need B >= 1, T >= 1)");
+    if (B > (1 << 29)) return fail(DC_ERR_INVALID, "B=%d: the guided batch holds 2 B clips", B);
+    if (s->host_only) return fail(DC_ERR_NO_DEVICE, "host-only sampler (sanitizer build without a device)");
+    HIP_TRY(hipSetDevice(s->cfg.device));
+    s->guided = false, s->cond_set = false;
+    // the feature images of the 2 B internal clips: the caller's B, then every frame of B shadows carrying the null pair
+    const size_t rows = (size_t)B * T;
+    int rc;
+    if (2 * rows * 64 > s->cap_xf2) {
+        s->cap_xf2 = 0;
+        if ((rc = dev_alloc(s, s->d_xf2_proj, 2 * rows * 64 * 4))) return rc;
+        if ((rc = dev_alloc(s, s->d_xf2_out, 2 * rows * 64 * 4))) return rc;
+        s->cap_xf2 = 2 * rows * 64;
+    }
+    DcNull64 np{}, no{};
+    memcpy(np.v, h_null_proj, sizeof np.v);
+    memcpy(no.v, h_null_out, sizeof no.v);
+    hipStream_t user = (hipStream_t)stream;
+    HIP_TRY(hipMemcpyAsync(s->d_xf2_proj, d_xf_proj, rows * 64 * 4, hipMemcpyDeviceToDevice, user));
+    HIP_TRY(hipMemcpyAsync(s->d_xf2_out, d_xf_out, rows * 64 * 4, hipMemcpyDeviceToDevice, user));
+    HIP_TRY(dc_launch_fill_rows64(user, s->d_xf2_proj + rows * 64, rows, np));
+    HIP_TRY(dc_launch_fill_rows64(user, s->d_xf2_out + rows * 64, rows, no));
+    std::vector<int32_t> len2;
+    if (h_length) {
+        len2.assign(h_length, h_length + B);
+        len2.insert(len2.end(), h_length, h_length + B);
+    }
+    if ((rc = set_conditioning(s, s->d_xf2_proj, s->d_xf2_out, h_length ? len2.data() : nullptr, 2 * B, T, stream))) return rc;
+    s->cond_set = false;
+    const size_t raw = 2 * rows * s->cfg.input_feats;
+    if (raw > s->cap_raw) {
+        drop_graph(s);          // (the buffer's address is an argument of the captured launches)
+        s->cap_raw = 0;
+        if ((rc = dev_alloc(s, s->d_raw, raw * 4))) return rc;
+        s->cap_raw = raw;
+    }
+    if (!s->d_wslot && (rc = dev_alloc(s, s->d_wslot, 16))) return rc;
+    s->guide_w = 1.f;
+    s->guided = true;
+    s->cond_set = true;
+    return DC_OK;
+}
+
+int dc_sampler_set_guidance_scale(dc_sampler* s, float w) {
+    if (!s) return fail(DC_ERR_INVALID, "null sampler");
+    if (!std::isfinite(w)) return fail(DC_ERR_INVALID, "guidance scale must be finite");
+    if (!s->guided) return fail(DC_ERR_INVALID, "dc_sampler_set_conditioning_guided must be called first: the scale belongs to a guided conditioning");
+    s->guide_w = w;
+    return DC_OK;
 }
 
 int dc_sampler_set_precise_tail(dc_sampler* s, int32_t steps) {
@@ -1546,7 +1647,7 @@ int dc_sampler_set_known(dc_sampler* s, const float* d_known, const float* d_mas
     if (!d_mask) return fail(DC_ERR_INVALID, "known values: values or noise without a mask (d_mask is NULL)");
     if (!s->cond_set) return fail(DC_ERR_INVALID, "dc_sampler_set_conditioning must be called first: known values belong to its (B, T)");
     s->known_val = d_known, s->known_mask = d_mask, s->known_noise = d_known_noise;
-    s->known_B = s->B, s->known_Tx = s->Tx;
+    s->known_B = s->user_B(), s->known_Tx = s->Tx, s->known_guided = s->guided;
     return DC_OK;
 }
 
@@ -1588,7 +1689,10 @@ int dc_sampler_status(dc_sampler* s, int32_t* h_status, int32_t clear) {
         // epilogue (it measured at 4 % of that kernel); the tiles are scanned here instead - the last step's as they stand, then,
         // while nothing was found, the tiles of every other timestep of the last loop (the GEMM re-run per timestep: the modulation
         // depends on t, and a value that saturates only early in the loop would otherwise read as an operand overflow)
-        const size_t ebytes = (size_t)s->G * s->NT * 64 * 32;
+        // (the groups the last loop's GEMM wrote: behind a guided loop with a shared column the tiles past them are stale or were never
+        // written; the re-runs below cover the same groups)
+        const int eg = s->last_film_groups > 0 ? std::min(s->last_film_groups, s->G) : s->G;
+        const size_t ebytes = (size_t)eg * s->NT * 64 * 32;
         HIP_TRY(dc_launch_scan_f16(s->stream, s->d_E, ebytes, s->d_status));
         HIP_TRY(hipStreamSynchronize(s->stream));
         HIP_TRY(hipMemcpy(h_status, s->d_status, 4, hipMemcpyDeviceToHost));
@@ -1599,7 +1703,9 @@ int dc_sampler_status(dc_sampler* s, int32_t* h_status, int32_t clear) {
                 HIP_TRY(hipMemcpy(s->d_t_clip, tc.data(), tc.size() * 4, hipMemcpyHostToDevice));
                 if (s->split_film)
                     HIP_TRY(dc_launch_silu_emb(s->stream, s->film_fmt, true, s->d_pp, s->h_model.temb, s->d_t_clip, s->d_s_hi, s->d_s_lo, s->G, s->T, s->B));
-                HIP_TRY(dc_launch_film_gemm(s->stream, s->film_fmt, s->split_film, film_args(s, s->split_film ? nullptr : s->d_pp, s->d_t_clip)));
+                DcFilmArgs fa = film_args(s, s->split_film ? nullptr : s->d_pp, s->d_t_clip);
+                fa.G = eg;
+                HIP_TRY(dc_launch_film_gemm(s->stream, s->film_fmt, s->split_film, fa));
                 HIP_TRY(dc_launch_scan_f16(s->stream, s->d_E, ebytes, s->d_status));
                 HIP_TRY(hipStreamSynchronize(s->stream));
                 HIP_TRY(hipMemcpy(h_status, s->d_status, 4, hipMemcpyDeviceToHost));
@@ -1649,6 +1755,7 @@ int dc_sampler_debug_layer(dc_sampler* s, const float* h_h, const int32_t* h_tim
                            int32_t stage, void* stream) {
     if (!s || !s->finalized || !s->cond_set) return fail(DC_ERR_INVALID, "sampler not ready (finalize + set_conditioning first)");
     if (!h_h || !h_timesteps) return fail(DC_ERR_INVALID, "null pointer argument");
+    if (s->guided) return fail(DC_ERR_INVALID, "the conditioning is guided (dc_sampler_set_conditioning_guided): the debug entry points run plain conditionings");
     if (layer < 0 || layer >= s->cfg.num_layers || first_stage < 1 || stage > 3 || first_stage > stage)
         return fail(DC_ERR_INVALID, "layer / stage out of range (need 1 <= first_stage <= last_stage <= 3)");
     if (s->cfg.no_eff) return fail(DC_ERR_UNSUPPORTED, "dc_sampler_debug_layer covers the linear-attention layers");

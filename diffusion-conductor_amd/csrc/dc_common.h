@@ -126,6 +126,11 @@ struct DcUpdate {
                          // (slots like zslot: other tensors on the next call do not re-capture the graph)
 };
 
+// one 64-vector of the null pair of a guided conditioning, by value (k_fill_rows64)
+struct DcNull64 {
+    float v[64];
+};
+
 // k_embed_front's arguments when it rides in the FiLM GEMM's launch (the first `ne` workgroups embed one 256-token unit each, flat units)
 struct DcEmbedArgs {
     const DcModel* dm;

@@ -33,7 +33,8 @@ struct Formats {
     X(no_wgrec, "DC_NO_WGREC") X(no_narrow, "DC_NO_NARROW") X(no_align, "DC_NO_ALIGN") X(align, "DC_ALIGN")                          \
     X(no_fuse_embed, "DC_NO_FUSE_EMBED") X(film_static, "DC_FILM_STATIC") X(begin_step, "DC_BEGIN_STEP") X(no_pad, "DC_NO_PAD")      \
     X(no_layer16, "DC_NO_LAYER16") X(l16_own_combine, "DC_L16_OWN_COMBINE") X(l16_test_drop_slice, "DC_L16_TEST_DROP_SLICE")         \
-    X(tail_film_bf16, "DC_TAIL_FILM_BF16") X(flat_units, "DC_FLAT_UNITS") X(no_embed_next, "DC_NO_EMBED_NEXT")
+    X(tail_film_bf16, "DC_TAIL_FILM_BF16") X(flat_units, "DC_FLAT_UNITS") X(no_embed_next, "DC_NO_EMBED_NEXT")                  \
+    X(guide_full_film, "DC_GUIDE_FULL_FILM")
 struct Switches {
 #define X(field, name) bool field = false;
     DC_FORM_SWITCHES(X)
@@ -67,6 +68,12 @@ struct Geometry {
     size_t cap_rec_floats = 0;            // rec_capacity of the workspace
 };
 
+// what a guided loop adds to the key of its captured graph (form_key, dc_api.hip; bits 27 and 28): the guided bit - another store in the
+// last layer, k_guided_update behind it - and the shared-column bit - the FiLM GEMM's group count and the clamp of the tile reads
+inline unsigned long long guided_key_bits(bool guided, bool shared_film) {
+    return (guided ? 1ull << 27 : 0ull) | ((guided && shared_film) ? 1ull << 28 : 0ull);
+}
+
 // what the rule reads of a sampler
 struct Settings {
     int precision = DCF_FP16;
@@ -97,6 +104,9 @@ struct StepOpts {
     bool embedded = false;        // the previous step's last layer has embedded x and run layer 0's front half for this step
     bool profile = false;         // events around every launch
     bool known = false;           // loops: known values are set (dc_sampler_set_known): the update replaces them (DC_UPD_KNOWN); no form is given up
+    bool guided = false;          // loops: classifier-free guidance (dc_sampler_set_conditioning_guided): the geometry's B clips are B / 2 conditional
+                                  // clips followed by their B / 2 unconditional shadows; the last layer stores the raw model output and
+                                  // k_guided_update combines the halves and updates x (no embed_next: x_{t-1} is not in the last layer's registers)
     Hooks dbg;
 };
 
@@ -114,7 +124,28 @@ struct StepForm {
     bool mixed_form = false, embed_next = false, fuse_embed = false, fuse_extra = false, g1_tiles = false;
     int upd_flags = 0;            // DC_UPD_* bits the form adds to the loop's (TEST_DROP_SLICE, EMBED_NEXT, KNOWN)
     int nl_run = 0, stop_stage = 0;      // layers to run; the stop stage handed to the last of them (0 = the whole layer)
+    bool guided = false;          // the last layer writes the raw output of all clips; k_guided_update follows it
+    bool shared_film = false;     // guided: the FiLM GEMM covers film_groups < G groups and the shadow half reads group film_groups - 1
+    int film_groups = 0;          // groups the FiLM GEMM computes = the e_groups the layer kernels clamp their tile reads to (unguided: G)
 };
+
+// Guided loops: the token groups the FiLM GEMM has to compute.  Every frame of every unconditional shadow clip carries the same
+// conditioning (the null pair) and a loop's step has one timestep, so emb - and with it every FiLM tile column - is one vector for the
+// whole shadow half.  When the conditional half is a whole number Gc of 32-token groups, group Gc is the first 32 tokens of the token
+// space's shadow half, and lane n of it serves lane n of every shadow group:
+//   - clip stride == frames per clip (no padding): every lane of every shadow group is a frame of a shadow clip, all with null pp;
+//   - clip stride 32 for clips shorter than 32 frames: one group per clip, lane n is frame n of its clip in every group (null pp below
+//     the frame count, the padding rows' value above it - zeros from k_cond_pp64, linear(0) from k_cond_embed: by position alone either way);
+//   - clip stride padded to whole groups (>= 256 frames): group Gc holds frames 0 .. 31 of shadow clip 0, all null pp; the padding lanes
+//     of later groups then read the null column instead of the padding rows' own - rows that no record, no output and no other token reads.
+// The GEMM then runs over Gc + 1 groups and the layer kernels read group min(g, Gc).  Needs the GEMM that builds its operand from
+// pp + temb (non-split FiLM formats); DC_GUIDE_FULL_FILM=1 keeps all 2 Gc groups.  Returns G when nothing is shared.
+inline int guided_film_groups(int B, int T, int G, bool film_from_pp, const Switches& w) {
+    const long long mc = (long long)(B / 2) * T;
+    if (B % 2 || !film_from_pp || w.guide_full_film || mc % 32 != 0) return G;
+    const int gc = (int)(mc / 32);
+    return (2 * gc == G && gc + 1 < G) ? gc + 1 : G;
+}
 
 // split-operand evaluations (the precise tail, dc_sampler_set_precise_forward) exist for: fp16 / bf16 precision, no test hooks
 inline bool can_split_steps(const Settings& s, const Hooks& dbg) {
@@ -130,6 +161,11 @@ inline StepForm step_form(const Geometry& g, const Settings& s, const Switches& 
     StepForm f;
     const int B = g.B, T = g.T, G = g.G;
     const Hooks& dbg = o.dbg;
+    if (o.guided && !(o.loop_mode && B % 2 == 0 && dbg.production())) {
+        f.error = "internal: a guided evaluation is a loop step over an even number of internal clips";
+        return f;
+    }
+    const bool guided = f.guided = o.guided;
     // "no test hook, no stamps": what the production-only forms below ask for.  Conditions that name single hooks instead are meant
     // as they stand, and say why.
     const bool quiet = dbg.production() && !stamps;
@@ -144,6 +180,8 @@ inline StepForm step_form(const Geometry& g, const Settings& s, const Switches& 
     f.folded = o.loop_mode && o.graph_step >= 0 && fuse_silu && !s.no_eff && !w.begin_step && dbg.stage == 0;
     // adaptive work shares of the persistent FiLM GEMM (dc_kernels.hip, film_shares); DC_FILM_STATIC=1 keeps equal shares
     f.adapt = !w.film_static && g.num_cu <= 1024;
+    f.film_groups = guided ? guided_film_groups(B, T, G, fuse_silu, w) : G;
+    f.shared_film = f.film_groups < G;
     f.nl_run = (dbg.layers >= 0 && dbg.layers < s.num_layers) ? dbg.layers : s.num_layers;
     // (full attention: the last layer of a shortened run stops after its FFN block)
     f.stop_stage = s.no_eff ? (dbg.stage ? dbg.stage : (f.nl_run < s.num_layers ? 3 : 0)) : dbg.stage;
@@ -202,17 +240,21 @@ inline StepForm step_form(const Geometry& g, const Settings& s, const Switches& 
     // k_layer, DC_UPD_EMBED_NEXT) when that step is a plain wide step of the same enqueue sequence; its FiLM launch is then the bare GEMM
     // and it has no front launch.  DC_NO_EMBED_NEXT=1 keeps the front work in every step's own FiLM launch.
     const bool wide_plain = wgr && !narrow && !ss && fuse_silu && ff == fs && quiet && !s.no_eff;
-    f.embed_next = !w.no_embed_next && o.loop_mode && o.next_plain && wide_plain;
+    // (a guided step's update runs in k_guided_update, behind the last layer: there is no x_{t-1} in that layer's registers to embed)
+    f.embed_next = !w.no_embed_next && o.loop_mode && o.next_plain && wide_plain && !guided;
     if (o.embedded && !(o.loop_mode && wide_plain)) {
         f.error = "internal: a step whose front work was done by its predecessor changed its launch form";
         return f;
     }
+    // (a FiLM launch that carries the embedding hands it its own group count: with the shadow half's shared column the GEMM covers
+    // fewer groups than the embedding, and the two launches stay apart - the form the profile pass runs)
     f.fuse_embed = !o.embedded && wgr && !narrow && (ss ? (aligned && mixed_form) : ff == fs) && fuse_silu && quiet && nwg <= g.num_cu &&
-                   !o.profile && !w.no_fuse_embed;
+                   !o.profile && !w.no_fuse_embed && !f.shared_film;
     // small batches (narrow clip-aligned units): the embedding's workgroups ride BEHIND the GEMM's in the FiLM launch
     // (film_extra_workgroups, dc_kernels.hip): one launch (15 us at one clip) and one kernel boundary less per step.  DC_NO_FUSE_EMBED=1 keeps the two launches.
     // (`first`: there is no embedding to fuse when the run starts from d_h; `narrow` has already excluded every hook)
-    f.fuse_extra = narrow && aligned && !ss && ff == fs && fuse_silu && s.film_w16 && dbg.first < 0 && !o.profile && !w.no_fuse_embed;
+    f.fuse_extra = narrow && aligned && !ss && ff == fs && fuse_silu && s.film_w16 && dbg.first < 0 && !o.profile && !w.no_fuse_embed &&
+                   !f.shared_film;
     f.upd_flags = (w.l16_test_drop_slice ? DC_UPD_TEST_DROP_SLICE : 0) | (f.embed_next ? DC_UPD_EMBED_NEXT : 0) |
                   ((o.known && o.loop_mode) ? DC_UPD_KNOWN : 0);
     // scale tiles: G' for the plain-operand consumers of this step, G' - 1 for the split-operand ones (dc_dev.h, film_affine)

@@ -58,6 +58,86 @@ __global__ __launch_bounds__(256) void k_known_blend(float* __restrict__ x, cons
 }
 
 // ------------------------------------------------------------------------------------
+// Classifier-free guidance (dc_sampler_set_conditioning_guided; the reference trains for it - transformer.py:389,451-459 zeroes a token's
+// music features with probability cond_mask_prob - and has no sampling counterpart).  The internal batch is the caller's B clips
+// followed by their B unconditional shadows, both reading the same x_t.  k_fill_rows64 broadcasts one 64-vector of the null pair over the
+// shadows' rows of a feature image; k_guided_update runs behind the step's last layer, which has stored the raw model output of all 2 B
+// clips (out_mode 0):   out = c + (w - 1) (c - u)   in fp32, in this order and without contraction, so that w = 1 returns c bit for bit
+// whenever u is finite; then ddim_update and known_replace exactly as the layer epilogue applies them, the step's scalars read the
+// same way (folded: through *iter_base; else k_begin_step's).  x_{t-1} goes to BOTH halves of x.  One thread per 4 consecutive
+// elements, 16-byte accesses where n and every base allow.
+// ------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_fill_rows64(float* __restrict__ dst, size_t rows, const DcNull64 v) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;           // one f32x4 per thread
+    if (i >= rows * 16) return;
+    const int q = (int)(i & 15);
+    reinterpret_cast<f32x4*>(dst)[i] = f32x4{v.v[4 * q], v.v[4 * q + 1], v.v[4 * q + 2], v.v[4 * q + 3]};
+}
+__global__ void k_set_scale(float* slot, float w) { *slot = w; }
+DEV float guide_combine(float c, float u, float wm1) {
+#pragma clang fp contract(off)
+    const float d = c - u;
+    const float p = wm1 * d;
+    return c + p;
+}
+DEV void guide_ld4(float (&o)[4], const float* __restrict__ p, size_t i, int cnt, bool vec) {
+    if (vec) {
+        const f32x4 t = *reinterpret_cast<const f32x4*>(p + i);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = t[j];
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = j < cnt ? p[i + j] : 0.f;
+    }
+}
+DEV void guide_st4(float* __restrict__ p, size_t i, const float (&v)[4], int cnt, bool vec) {
+    if (vec) {
+        *reinterpret_cast<f32x4*>(p + i) = f32x4{v[0], v[1], v[2], v[3]};
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (j < cnt) p[i + j] = v[j];
+    }
+}
+__global__ __launch_bounds__(256) void k_guided_update(const float* __restrict__ raw /*[2][n]*/, float* __restrict__ x /*[2][n]*/, size_t n,
+                                                       const float* __restrict__ coef_cur, const int* __restrict__ snap_cur,
+                                                       float* __restrict__ snaps, const int* __restrict__ iter_base,
+                                                       const float* __restrict__ wslot, const DcUpdate upd) {
+    const size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i >= n) return;
+    const int cnt = (int)(n - i < 4 ? n - i : 4);
+    const int ib = iter_base ? *iter_base : 0;
+    const float* cc = coef_cur + DC_COEF * ib;
+    const int snap = snap_cur[ib];
+    const bool noisy = (upd.flags & DC_UPD_NOISY) != 0;
+    const float* zrow = nullptr;
+    if (noisy) zrow = *upd.zslot + ((upd.flags & DC_UPD_ZSTEP) ? (size_t)0 : (size_t)(iter_base ? upd.step + ib : snap_cur[1]) * n);
+    const KnownPtrs kn = known_ptrs(upd);
+    const float wm1 = *wslot - 1.f;
+    // (x, raw and snaps are workspace buffers: their halves and slots are 16-byte aligned whenever n is a multiple of 4)
+    const auto a16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    const bool vec = (n & 3) == 0 && a16(raw) && a16(x) && a16(snaps) && a16(zrow);
+    float c[4], u[4], xt[4], z[4] = {0.f, 0.f, 0.f, 0.f}, xn[4];
+    guide_ld4(c, raw, i, cnt, vec);
+    guide_ld4(u, raw + n, i, cnt, vec);
+    guide_ld4(xt, x, i, cnt, vec);
+    if (noisy) guide_ld4(z, zrow, i, cnt, vec);
+    bool bad = false;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        bad = bad || (j < cnt && !(fabsf(c[j]) <= 3.0e38f && fabsf(u[j]) <= 3.0e38f));
+        bool badj = false;
+        xn[j] = ddim_update(guide_combine(c[j], u[j], wm1), xt[j], cc, upd.flags, noisy, z[j], badj);
+        bad = bad || (j < cnt && badj);
+        if (j < cnt) xn[j] = known_replace(xn[j], kn, i + j, cc);
+    }
+    guide_st4(x, i, xn, cnt, vec);
+    guide_st4(x + n, i, xn, cnt, vec);
+    if (snap >= 0) guide_st4(snaps + (size_t)snap * n, i, xn, cnt, vec);
+    if (bad && upd.status) atomicOr(upd.status, DC_STATUS_NONFINITE);
+}
+
+// ------------------------------------------------------------------------------------
 // eta > 0 without a caller-supplied noise tensor: the N(0, 1) draws of ONE iteration (the reference's th.randn_like(x),
 // gaussian_diffusion.py:822), generated at the head of the step that consumes them - a [B][Tx][P] buffer instead of the
 // [S][B][Tx][P] tensor (6 GB at S = 1000, bs = 32).  Philox4x32-10 keyed by the seed, counter = (element quad, iteration);
@@ -1284,7 +1364,7 @@ void k_layer(const DcModel* __restrict__ dm, int l, float* __restrict__ hbuf, co
              float* __restrict__ snaps, int M, int T, int G, int B, int dbg,
              unsigned long long* __restrict__ stamps, size_t rec_stride, const int* __restrict__ iter_base,
              int Tx /* frames per clip of xin / xout / snaps (<= the clip stride T) */, int upc /* workgroups per clip (WgMap) or 0 */,
-             const DcUpdate upd) {
+             int e_groups /* groups of FiLM tiles behind E (DcLayerArgs) */, const DcUpdate upd) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     static_assert(!NARROW || (WGR && !SPLIT && !DBG), "narrow workgroups: workgroup-record form, non-split formats, no test hooks");
     constexpr int NW = NARROW ? 4 : (SPLIT ? DC_SPLIT_NW : 8);
@@ -1362,7 +1442,7 @@ void k_layer(const DcModel* __restrict__ dm, int l, float* __restrict__ hbuf, co
     const W* af = reinterpret_cast<const W*>(lds + OFF_AF);
     const DcLayer& L = dm->layer[l];
     const bool last = l + 1 >= nl;
-    const f16x8* Eg = reinterpret_cast<const f16x8*>(E) + ((size_t)g * NT + (size_t)l * 24) * 128;   // 3 blocks x 8 tiles
+    const f16x8* Eg = reinterpret_cast<const f16x8*>(E) + ((size_t)min(g, e_groups - 1) * NT + (size_t)l * 24) * 128;   // 3 blocks x 8 tiles
     const W* acl = a_ca + (size_t)l * B * 16 * 64;
     const float* recs_in = recs + (size_t)(l & 1) * rec_stride;
     float* recs_out = recs + (size_t)((l + 1) & 1) * rec_stride;
@@ -2465,7 +2545,7 @@ __global__ __launch_bounds__(512, 2) void k_layer_full(const DcModel* __restrict
                                                        const int* __restrict__ length, const float* __restrict__ xin,
                                                        float* __restrict__ xout, int out_mode, const float* __restrict__ coef_cur,
                                                        const int* __restrict__ snap_cur, float* __restrict__ snaps, int M, int T,
-                                                       int B, int KT, int WPC, int stop_after, const DcUpdate upd) {
+                                                       int B, int KT, int WPC, int stop_after, int e_groups, const DcUpdate upd) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     using W = v8<T16>;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -2477,7 +2557,7 @@ __global__ __launch_bounds__(512, 2) void k_layer_full(const DcModel* __restrict
     const bool any_pad = len < T;
     const bool q_pad = cx.n >= len;
     const int key_lo = cx.b * T, key_hi = min((cx.b + 1) * T, M);
-    const f16x8* Eg = reinterpret_cast<const f16x8*>(E) + ((size_t)cx.g * NT + (size_t)l * 24) * 128;
+    const f16x8* Eg = reinterpret_cast<const f16x8*>(E) + ((size_t)min(cx.g, e_groups - 1) * NT + (size_t)l * 24) * 128;
     constexpr int HL = SPLIT ? 2 : 1;
     auto consts = [](const bf16x8* img) { return reinterpret_cast<const float*>(reinterpret_cast<const W*>(img) + 32 * 64 * HL); };
     f32x16 h[4];
@@ -2714,6 +2794,21 @@ hipError_t dc_launch_known_blend(hipStream_t st, float* x, const float* val, con
     k_known_blend<<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>(x, val, mask, noise, ca, cb, n);
     return hipGetLastError();
 }
+hipError_t dc_launch_fill_rows64(hipStream_t st, float* dst, size_t rows, const DcNull64& v) {
+    if (rows == 0) return hipSuccess;
+    k_fill_rows64<<<dim3((unsigned)((rows * 16 + 255) / 256)), dim3(256), 0, st>>>(dst, rows, v);
+    return hipGetLastError();
+}
+hipError_t dc_launch_set_scale(hipStream_t st, float* slot, float w) {
+    k_set_scale<<<1, 1, 0, st>>>(slot, w);
+    return hipGetLastError();
+}
+hipError_t dc_launch_guided_update(hipStream_t st, const float* raw, float* x, size_t n, const float* coef_cur, const int* snap_cur, float* snaps,
+                                   const int* iter_base, const float* wslot, const DcUpdate& upd) {
+    const size_t threads = (n + 3) / 4;
+    k_guided_update<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st>>>(raw, x, n, coef_cur, snap_cur, snaps, iter_base, wslot, upd);
+    return hipGetLastError();
+}
 hipError_t dc_launch_set_ptr(hipStream_t st, const float** slot, const float* p, unsigned long long seed, unsigned long long first) {
     k_set_ptr<<<1, 1, 0, st>>>(slot, p, seed, first);
     return hipGetLastError();
@@ -2929,7 +3024,7 @@ static hipError_t launch_layer_t(hipStream_t st, const DcLayerArgs& a, int l, co
     if (hipError_t e = lds_optin((const void*)k_layer<T16, SP, DBG, STAMP, WGR, NARROW, G1>, (int)shm, optin_done)) return e;
     k_layer<T16, SP, DBG, STAMP, WGR, NARROW, G1><<<dim3((WGR && upc) ? a.B * upc : (a.G + NW - 1) / NW), dim3(NW * 64), shm, st>>>(
         a.dm, l, a.hbuf, (const f16x16*)a.E, a.NT, (const v8<T16>*)a_sa, (const v8<T16>*)a_ca, a.recs, a.length, a.xin, a.xout, a.out_mode,
-        a.coef_cur, a.snap_cur, a.snaps, a.M, a.T, a.G, a.B, dbg, stamps, rec_stride, a.iter_base, a.Tx, WGR ? upc : 0, a.upd);
+        a.coef_cur, a.snap_cur, a.snaps, a.M, a.T, a.G, a.B, dbg, stamps, rec_stride, a.iter_base, a.Tx, WGR ? upc : 0, a.e_groups, a.upd);
     return hipGetLastError();
 }
 
@@ -2965,7 +3060,7 @@ static hipError_t launch_full_t(hipStream_t st, const DcLayerArgs& a, int l, con
     if (hipError_t e = lds_optin((const void*)k_layer_full<T16, SP>, DC_FULL_LDS, optin_done)) return e;
     k_layer_full<T16, SP><<<dim3(a.B * WPC), dim3(512), DC_FULL_LDS, st>>>(
         a.dm, l, a.hbuf, (const f16x16*)a.E, a.NT, (const v8<T16>*)kv_cur, (v8<T16>*)kv_next, (const v8<T16>*)kv_ca, a.length, a.xin, a.xout,
-        a.out_mode, a.coef_cur, a.snap_cur, a.snaps, a.M, a.T, a.B, KT, WPC, stop_after, a.upd);
+        a.out_mode, a.coef_cur, a.snap_cur, a.snaps, a.M, a.T, a.B, KT, WPC, stop_after, a.e_groups, a.upd);
     return hipGetLastError();
 }
 hipError_t dc_launch_embed_front_full(hipStream_t st, int fmt, bool split, const DcModel* dm, const float* x, float* hbuf, void* kv_next,

@@ -80,6 +80,8 @@ struct DcLayerArgs {
     const int* iter_base;
     int M, T, G, B;
     int Tx;                      // frames per clip of xin / xout / snaps
+    int e_groups;                // groups of FiLM tiles behind E: group g reads the tiles of group min(g, e_groups - 1) (G; a guided step whose
+                                 // unconditional half shares one column: the conditional half's groups + 1, dc_form.h)
     DcUpdate upd;                // options of the fused DDIM update + the status word (dc_common.h)
 };
 hipError_t dc_launch_layer(hipStream_t st, const DcLayerForm& f, const DcLayerArgs& a, int l, const void* a_sa, const void* a_ca,
@@ -103,6 +105,15 @@ hipError_t dc_launch_set_ptr(hipStream_t st, const float** slot /* 24 bytes: bas
 // known values (dc_sampler_set_known): the tensors' bases into the 24-byte slot DcUpdate::kslot names; x[known] = ca val + cb noise over n elements
 hipError_t dc_launch_set_known(hipStream_t st, const float** slot, const float* val, const float* mask, const float* noise);
 hipError_t dc_launch_known_blend(hipStream_t st, float* x, const float* val, const float* mask, const float* noise, float ca, float cb, size_t n);
+// Classifier-free guidance (dc_sampler_set_conditioning_guided).  dc_launch_fill_rows64: `rows` rows of dst [rows][64] = v (the null pair
+// broadcast over the unconditional clips' frames).  dc_launch_set_scale: the guidance scale into its device slot.
+// dc_launch_guided_update: raw = the last layer's model output [2][n] (conditional half, unconditional half; n = B * Tx * P of the
+// caller's B clips), x = [2][n]:  x_{t-1} = known_replace(ddim_update(c + (w - 1)(c - u), x_t)) into BOTH halves of x and the due snapshot.
+// The step's scalars as the layer epilogue reads them (coef_cur / snap_cur / iter_base / upd: DcLayerArgs).
+hipError_t dc_launch_fill_rows64(hipStream_t st, float* dst, size_t rows, const DcNull64& v);
+hipError_t dc_launch_set_scale(hipStream_t st, float* slot, float w);
+hipError_t dc_launch_guided_update(hipStream_t st, const float* raw, float* x, size_t n, const float* coef_cur, const int* snap_cur, float* snaps,
+                                   const int* iter_base, const float* wslot, const DcUpdate& upd);
 // N(0, 1) draws of one DDIM iteration (Philox keyed by *seed_slot when given, else seed; iteration = step + *iter_base, else snap_cur[1],
 // else step) into z[0..n); z[0] is element `first` (seed_slot[1] when a slot is given) of the whole batch's draw
 hipError_t dc_launch_step_noise(hipStream_t st, float* z, size_t n, unsigned long long seed, const unsigned long long* seed_slot, const int* iter_base,

@@ -560,7 +560,8 @@ void k_layer16(const DcModel* __restrict__ dm, int l, float* __restrict__ hbuf, 
                int nu_in, size_t stride_in /* unit records per clip / floats per unit of the records this layer combines */,
                const int* __restrict__ iter_base, int Tx, const DcUpdate upd,
                unsigned long long* __restrict__ gran /* [B][1024] granules of the shared combine, or nullptr: every workgroup combines alone */,
-               unsigned tag_base /* + 16 * (*iter_base) + l + 1 = this launch's tag */) {
+               unsigned tag_base /* + 16 * (*iter_base) + l + 1 = this launch's tag */,
+               int e_groups /* groups of FiLM tiles behind E (DcLayerArgs) */) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     using W = v8<T16>;
     constexpr int NW = L16_NW;
@@ -602,7 +603,7 @@ void k_layer16(const DcModel* __restrict__ dm, int l, float* __restrict__ hbuf, 
     const DcLayer16& L = dm->l16[l];
     const int nl = dm->num_layers;
     const bool last = l + 1 >= nl;
-    const f16x8* Eg = reinterpret_cast<const f16x8*>(E) + ((size_t)c.g * NT + (size_t)l * 24) * 128;   // 3 blocks x 8 tiles
+    const f16x8* Eg = reinterpret_cast<const f16x8*>(E) + ((size_t)min(c.g, e_groups - 1) * NT + (size_t)l * 24) * 128;   // 3 blocks x 8 tiles
     const float* recs_in = recs + (size_t)(l & 1) * rec_stride;
     float* recs_out = recs + (size_t)((l + 1) & 1) * rec_stride;
 
@@ -967,7 +968,7 @@ hipError_t launch_layer16_t(hipStream_t st, const DcLayerArgs& a, int l, const v
     k_layer16<T16, G1><<<dim3(a.B * upc), dim3(256), L16_LDS, st>>>(a.dm, l, a.hbuf, (const f16x16*)a.E, a.NT, (const v8<T16>*)a_ca16, a.recs,
                                                                     a.length, a.xin, a.xout, a.out_mode, a.coef_cur, a.snap_cur, a.snaps, a.M,
                                                                     a.T, a.B, upc, rec_stride, nu_in, stride_in, a.iter_base, a.Tx, a.upd, gran,
-                                                                    tag_base);
+                                                                    tag_base, a.e_groups);
     return hipGetLastError();
 }
 }  // namespace

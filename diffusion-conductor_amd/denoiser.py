@@ -248,7 +248,14 @@ class MotionTransformer(nn.Module):
         sl[1].record(cur)
         return xf_proj, xf_out
 
-    def set_conditioning(self, xf_proj, xf_out, length=None):
+    def null_conditioning(self):
+        """The null pair (null_proj[64], null_out[64]) of classifier-free guidance: the all-masked limit of the reference's token
+        dropout (transformer.py:389,451-459 zeroes a token's music features before `proj`), null_out = 0 and null_proj = proj(0) =
+        proj.bias.  The reference has no sampling counterpart."""
+        return self.get_parameter("proj.bias").detach().float().cpu().reshape(64), torch.zeros(64)
+
+    def set_conditioning(self, xf_proj, xf_out, length=None, guided=False):
+        """`guided`: the conditioning of a guided loop (include/dc_ddim.h, dc_sampler_set_conditioning_guided) with null_conditioning()."""
         nat = self._ensure_native(xf_proj.device)
         T = xf_proj.shape[1]
         if length is None:
@@ -259,10 +266,12 @@ class MotionTransformer(nn.Module):
         # caching allocator hands the same address to a new tensor.
         k = self._cond_key
         same = (k is not None and k[0] is xf_proj and k[1] is xf_out and k[2] == (xf_proj._version, xf_out._version)
-                and k[3] == ln)
+                and k[3] == ln and k[4] == bool(guided))
         if not same:
-            nat.set_conditioning(xf_proj.contiguous().float(), xf_out.contiguous().float(), list(ln))
-            self._cond_key = (xf_proj, xf_out, (xf_proj._version, xf_out._version), ln)
+            self._cond_key = None
+            nat.set_conditioning(xf_proj.contiguous().float(), xf_out.contiguous().float(), list(ln),
+                                 null=self.null_conditioning() if guided else None)
+            self._cond_key = (xf_proj, xf_out, (xf_proj._version, xf_out._version), ln, bool(guided))
         return nat
 
     def forward(self, x, timesteps, length=None, text=None, xf_proj=None, xf_out=None):

@@ -243,7 +243,7 @@ class _Scorer:
 
 
 def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed=0, smooth=False, verbose=True, motion_encoder=None,
-                     diversity_seed=0, m2snet=None):
+                     diversity_seed=0, m2snet=None, guidance_scale=None):
     """Samples every clip under `root` and returns {"per_clip": {id: mse}, "total_loss", "final_mse", "clips",
     "seconds", "frames_per_s"}.  Clip i (in sorted order) starts from noise seeded with (seed, i), so the result
     does not depend on batch_size or on the number of ranks.
@@ -264,11 +264,14 @@ def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed
     per-frame predictions over all clips; nan when no batch had two clips) and "m2s_accuracy_gen" (metrics.sync_stats: matched =
     generated, mismatched = rolled).  Without it the result is unchanged.
 
+    `guidance_scale`: None, or the classifier-free guidance scale every batch is sampled with (generate_music_motion).
+
     The host stays out of the GPU's way: batch k + 1's files and noise are prepared, and batch k - 1's MSEs computed, on
     background threads while batch k is sampled; the poses come back through a pinned double buffer behind an event, not a stream
     synchronisation; the sampler's per-loop numeric check (a status read that waits for the GPU) is replaced by a finiteness check
     of the poses on the scoring thread, and a batch that fails it is sampled again the checked way (which is where
     precision="auto" falls back to the bf16-range mode).  At most two batches are in flight."""
+    gkw = {} if guidance_scale is None else {"guidance_scale": float(guidance_scale)}      # (None: the trainer is called as before)
     ids = list_clips(root)
     if limit is not None:
         ids = ids[:int(limit)]
@@ -312,7 +315,7 @@ def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed
                 noise = noise.to(dev, non_blocking=True)      # (a blocking copy on the default stream would wait for the previous batch)
             # [B, T, dim_pose] on the device; smoothing (tools/visualization.py:126) happens in the sampling loop's final write
             tw = time.perf_counter()
-            pred = trainer.generate_music_motion(mel, dim_pose, noise=noise, smooth=19 if smooth else None)
+            pred = trainer.generate_music_motion(mel, dim_pose, noise=noise, smooth=19 if smooth else None, **gkw)
             waits["enqueue"] += time.perf_counter() - tw
             tw = time.perf_counter()
             scorer.wait_for(k - 2, reraise=False)             # the pinned pose buffer of this slot has been scored (errors: collected below)
@@ -353,7 +356,7 @@ def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed
                 pf2 = _Prefetcher(root, ids, batch_size, mel_shape, noise=(seed, T, dim_pose))
                 pf2._load_batch(k, 0)
                 bid, mel, gts = pf2.result
-                pred_d = trainer.generate_music_motion(mel, dim_pose, noise=pf2.noise, smooth=19 if smooth else None)
+                pred_d = trainer.generate_music_motion(mel, dim_pose, noise=pf2.noise, smooth=19 if smooth else None, **gkw)
                 lats = _encode_pair(motion_encoder, pred_d, gts, dim_pose, bid) if motion_encoder is not None else None
                 if m2snet is not None:
                     sync[k] = _sync_predictions(m2snet, mel, pred_d, gts, dim_pose)
@@ -428,6 +431,7 @@ def main(argv=None):
     ap.add_argument("--m2snet", default=None, help="M2SNet checkpoint for --metrics (DataParallel state_dict, keys "
                                                    "module.motion_encoder.*) and --sync (every key); omitted = seeded synthetic weights")
     ap.add_argument("--diversity_seed", type=int, default=0)
+    ap.add_argument("--guidance_scale", type=float, default=None, help="classifier-free guidance scale of the sampling loops (omitted: no guidance)")
     ap.add_argument("--sync", action="store_true", help="also M2SNet's synchronisation score of the sampled poses against the music "
                                                         "(m2snet.py; every entry of --m2snet, or seeded synthetic weights)")
     args = ap.parse_args(argv)
@@ -464,7 +468,7 @@ def main(argv=None):
             m2s = M2SNet(dev).load_state_dict(synthetic_m2snet_state_dict())
             print("--sync without --m2snet: M2SNet has seeded synthetic weights, so the m2s_* scores only check the pipeline")
     r = evaluate_dataset(tr, args.data_root, 26, args.batch_size, args.limit, args.seed, args.smooth, motion_encoder=menc,
-                         diversity_seed=args.diversity_seed, m2snet=m2s)
+                         diversity_seed=args.diversity_seed, m2snet=m2s, guidance_scale=args.guidance_scale)
     print(f"{r['clips']} clips in {r['seconds']:.2f} s = {r['frames_per_s']:.0f} frames/s")
     return 0
 

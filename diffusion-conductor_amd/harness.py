@@ -61,7 +61,7 @@ class DDPMTrainer(object):
         self.encoder.load_state_dict(checkpoint["encoder"], strict=False)
         return checkpoint.get("ep", 0), checkpoint.get("total_it", 0)
 
-    def _sample_local(self, mel, noise, dim_pose, idxs, smooth=None):
+    def _sample_local(self, mel, noise, dim_pose, idxs, smooth=None, guidance_scale=None):
         xf_proj, xf_out = self.encoder.encode_music(mel, self.device)
         B, T = mel.shape[0], xf_proj.shape[1]
         try:
@@ -69,7 +69,7 @@ class DDPMTrainer(object):
                 self.encoder, (B, T, dim_pose), noise=noise, clip_denoised=False, progress=False,
                 model_kwargs={"xf_proj": xf_proj, "xf_out": xf_out,
                               "length": torch.LongTensor([T] * B)},
-                idxs=idxs, smooth=smooth)
+                idxs=idxs, smooth=smooth, guidance_scale=guidance_scale)
         except FloatingPointError:
             # The loop's numeric check failed.  If the music features themselves are not finite, the fp16-plane MusicEncoder
             # overflowed (an activation beyond 65504; the reference's mel is normalised to [0, 1], so this takes unusual input):
@@ -80,12 +80,15 @@ class DDPMTrainer(object):
             nat = getattr(self.encoder, "_native", None)
             if nat is not None:
                 nat.set_encoder_format("split")
-            return self._sample_local(mel, noise, dim_pose, idxs, smooth)
+            return self._sample_local(mel, noise, dim_pose, idxs, smooth, guidance_scale)
 
-    def generate_music_motion(self, music_mel, dim_pose, batch_size=1024, idxs=[], noise=None, seed=None, smooth=None):
+    def generate_music_motion(self, music_mel, dim_pose, batch_size=1024, idxs=[], noise=None, seed=None, smooth=None,
+                              guidance_scale=None):
         """music_mel: np.ndarray/tensor [5400,128] (reference) or [B,5400,128] -> tensor [B,1800,dim_pose].
         smooth: None, or the Savitzky-Golay kernel size (order 5) tools/visualization.py:126 smooths the keypoints with - applied
-        by the sampling loop's final write."""
+        by the sampling loop's final write.
+        guidance_scale: None, or the classifier-free guidance scale of the loop (GaussianDiffusion.ddim_sample_loop; each rank of a
+        sharded run builds the unconditional shadows of its own clips)."""
         mel = torch.as_tensor(np.asarray(music_mel) if not torch.is_tensor(music_mel) else music_mel)
         if mel.dim() == 2:
             mel = mel.unsqueeze(0)
@@ -117,11 +120,12 @@ class DDPMTrainer(object):
         sm = (int(smooth), 5) if smooth else None
         with torch.no_grad():
             if not grouped or len(idxs):
-                return self._sample_local(mel, noise, dim_pose, idxs, sm)
-            return sharded_sample(lambda m, n: self._sample_local(m, n, dim_pose, [], sm), mel, noise, out_shape=(T, dim_pose),
+                return self._sample_local(mel, noise, dim_pose, idxs, sm, guidance_scale)
+            return sharded_sample(lambda m, n: self._sample_local(m, n, dim_pose, [], sm, guidance_scale), mel, noise, out_shape=(T, dim_pose),
                                   device=self.device)
 
-    def generate_long_music_motion(self, music_mel, dim_pose, overlap=LONG_OVERLAP, noise=None, seed=None, smooth=None, window=None):
+    def generate_long_music_motion(self, music_mel, dim_pose, overlap=LONG_OVERLAP, noise=None, seed=None, smooth=None, window=None,
+                                   guidance_scale=None):
         """Conduct music LONGER than one window: music_mel [Tm,128] or [B,Tm,128] (pieces of one length), Tm at least one window
         (3 * window mel frames; ValueError below that - generate_music_motion serves those) -> tensor [B, L, dim_pose] with
         L = (Tm-1)//3 + 1.
@@ -140,7 +144,7 @@ class DDPMTrainer(object):
 
         `overlap` (frames, default LONG_OVERLAP = 300: 10 s); `smooth`: the Savitzky-Golay kernel size (order 5), applied ONCE
         over the whole piece with dc_savgol_filter (per window it would break the seams).  Every window runs the same captured
-        graph (the first with an all-zero mask).  Not built: sharding pieces over the ranks of a torch.distributed group."""
+        graph (the first with an all-zero mask) - also with `guidance_scale` (classifier-free guidance of every window's loop).  Not built: sharding pieces over the ranks of a torch.distributed group."""
         from . import native
         _, world = dist_info()
         if world > 1:
@@ -178,7 +182,7 @@ class DDPMTrainer(object):
                 out[:, s:s + T] = self.diffusion.ddim_sample_loop(
                     self.encoder, (B, T, dim_pose), noise=x_T, clip_denoised=False, progress=False,
                     model_kwargs={"xf_proj": xf_proj[k], "xf_out": xf_out[k], "length": length},
-                    known=out[:, s:s + T].contiguous(), known_mask=mask, known_noise=x_T)
+                    known=out[:, s:s + T].contiguous(), known_mask=mask, known_noise=x_T, guidance_scale=guidance_scale)
             if smooth:
                 out = native.savgol_filter(out, int(smooth), 5)
         return out

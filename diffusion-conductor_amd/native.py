@@ -28,6 +28,7 @@ EXPORTS = [
     "dc_motion_encoder_create", "dc_motion_encoder_destroy", "dc_motion_encoder_set_param", "dc_motion_encoder_finalize",
     "dc_motion_encoder_encode",
     "dc_ddim_coefficients_known", "dc_sampler_set_known",
+    "dc_sampler_set_conditioning_guided", "dc_sampler_set_guidance_scale",
     "dc_m2snet_create", "dc_m2snet_destroy", "dc_m2snet_set_param", "dc_m2snet_finalize", "dc_m2snet_encode_music", "dc_m2snet_fuse",
     "dc_m2snet_score",
 ]
@@ -135,6 +136,8 @@ def lib():
                                           C.c_void_p, C.c_void_p]
     L.dc_ddim_coefficients_known.argtypes = [C.c_int32, dp, C.c_float, fp, fp]
     L.dc_sampler_set_known.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.dc_sampler_set_conditioning_guided.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, ip, C.c_int32, C.c_int32, fp, fp, C.c_void_p]
+    L.dc_sampler_set_guidance_scale.argtypes = [C.c_void_p, C.c_float]
     L.dc_sampler_set_step_noise_seed.argtypes = [C.c_void_p, C.c_uint64]
     L.dc_sampler_set_step_noise_seed_at.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64]
     L.dc_step_noise_fill.argtypes = [C.c_void_p, C.c_int64, C.c_uint64, C.c_int32, C.c_void_p]
@@ -314,6 +317,7 @@ class NativeSampler:
         _check(lib().dc_sampler_create(C.byref(c), C.byref(self._h)))
         self.cfg, self.precision, self.device, self.max_timesteps = cfg, precision, int(device), int(max_timesteps)
         self.B = self.T = 0
+        self.guided = False
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
@@ -341,7 +345,10 @@ class NativeSampler:
         import torch
         return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
-    def set_conditioning(self, xf_proj, xf_out, length=None):
+    def set_conditioning(self, xf_proj, xf_out, length=None, null=None):
+        """dc_sampler_set_conditioning, or - `null` = the pair (null_proj[64], null_out[64]) - dc_sampler_set_conditioning_guided: the
+        loops then run with classifier-free guidance at the scale of set_guidance_scale (1 after this call); every tensor handed to
+        them stays [B, T, P]."""
         import torch
         assert xf_proj.is_cuda and xf_proj.dtype == torch.float32 and xf_proj.is_contiguous()
         assert xf_out.is_cuda and xf_out.dtype == torch.float32 and xf_out.is_contiguous()
@@ -352,8 +359,21 @@ class NativeSampler:
             la = np.ascontiguousarray(np.asarray(length.cpu() if hasattr(length, "cpu") else length), np.int32)
             assert la.shape == (B,)
             lp = _iptr(la)
-        _check(lib().dc_sampler_set_conditioning(self._h, xf_proj.data_ptr(), xf_out.data_ptr(), lp, B, T, self._stream()))
+        if null is None:
+            _check(lib().dc_sampler_set_conditioning(self._h, xf_proj.data_ptr(), xf_out.data_ptr(), lp, B, T, self._stream()))
+        else:
+            nv = [None if v is None else
+                  np.ascontiguousarray(np.asarray(v.detach().cpu() if hasattr(v, "detach") else v), np.float32).reshape(-1) for v in null]
+            assert len(nv) == 2 and all(v is None or v.shape == (64,) for v in nv), "null = (null_proj[64], null_out[64])"
+            _check(lib().dc_sampler_set_conditioning_guided(self._h, xf_proj.data_ptr(), xf_out.data_ptr(), lp, B, T,
+                                                            *[None if v is None else _fptr(v) for v in nv], self._stream()))
         self.B, self.T = B, T
+        self.guided = null is not None
+
+    def set_guidance_scale(self, w):
+        """dc_sampler_set_guidance_scale: out = c + (w - 1)(c - u) in the loops of a guided conditioning; another scale replays the same
+        graph.  Must be finite."""
+        _check(lib().dc_sampler_set_guidance_scale(self._h, C.c_float(float(w))))
 
     def set_precise_tail(self, steps):
         """The loop's last `steps` model evaluations on split operands (fp16: golden DDIM-50 5.0e-4 -> 2.3e-4 / 1.6e-4 with 1 / 2 steps at

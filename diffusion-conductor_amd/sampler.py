@@ -303,7 +303,22 @@ class GaussianDiffusion:
             known_noise = th.randn(shape, generator=g)
         return full(known, "known"), m, full(known_noise, "known_noise")
 
-    def _native_loop(self, model, img, mk, clip_denoised, eta, snap, step_noise, smooth=None, step_noise_seed=None, known=None):
+    def _check_guidance(self, model, guidance_scale, denoised_fn, cond_fn, stepped=False):
+        """guidance_scale= runs inside the captured loop only: ValueError where the loop would step through ddim_sample."""
+        if guidance_scale is None:
+            return
+        why = ("the progressive generator" if stepped else "denoised_fn" if denoised_fn is not None else "cond_fn" if cond_fn is not None else
+               "the PREVIOUS_X parameterisation" if self.model_mean_type == ModelMeanType.PREVIOUS_X else
+               "a learned-variance model" if self.model_var_type in (ModelVarType.LEARNED, ModelVarType.LEARNED_RANGE) else
+               None if self._fast_path_ok(model, denoised_fn, cond_fn) else "this model / rescale_timesteps")
+        if why is not None:
+            raise ValueError(f"guidance_scale= is combined inside the captured loop; {why} steps through ddim_sample, where the caller "
+                             "combines the two evaluations")
+        if not math.isfinite(float(guidance_scale)):
+            raise ValueError(f"guidance_scale must be finite, got {guidance_scale!r}")
+
+    def _native_loop(self, model, img, mk, clip_denoised, eta, snap, step_noise, smooth=None, step_noise_seed=None, known=None,
+                     guidance_scale=None):
         """The captured loop on `model`'s sampler; returns (out, snaps).  Numeric health is checked once per call
         (`model.check_numerics`): a non-finite x0 under precision="auto" falls back to the bf16-range mode in a fresh sampler."""
         flags = (native.UPDATE_CLIP_DENOISED if clip_denoised else 0) | \
@@ -329,7 +344,11 @@ class GaussianDiffusion:
         coef = self.native_coefficients(None if plain else eta) if known is None else self.native_coefficients_known(eta)
         retried = False
         while True:
-            nat = model.set_conditioning(mk["xf_proj"], mk["xf_out"], mk.get("length"))
+            if guidance_scale is None:
+                nat = model.set_conditioning(mk["xf_proj"], mk["xf_out"], mk.get("length"))
+            else:        # (inside the retry loop: precision="auto"'s re-run on a fresh sampler keeps the scale)
+                nat = model.set_conditioning(mk["xf_proj"], mk["xf_out"], mk.get("length"), guided=True)
+                nat.set_guidance_scale(guidance_scale)
             nat.set_smoothing(*(smooth if smooth else (0, 0)))
             nat.set_known(*(known if known is not None else (None, None, None)))
             out, snaps = nat.ddim_loop(img, coef, snap, flags, z, zseed)
@@ -350,7 +369,8 @@ class GaussianDiffusion:
 
     def ddim_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                          model_kwargs=None, device=None, progress=False, eta=0.0, idxs=[], step_noise=None, smooth=None,
-                         step_noise_seed=None, known=None, known_mask=None, known_noise=None, known_noise_seed=None):
+                         step_noise_seed=None, known=None, known_mask=None, known_noise=None, known_noise_seed=None,
+                         guidance_scale=None):
         """gaussian_diffusion.py:871-915.  Returns the final sample, or when `idxs` is non-empty a
         dict {iteration: sample} for the listed iterations plus {num_timesteps: final}.
         `step_noise` (extension, eta > 0): [S, B, T, P], the draw for iteration i in place of th.randn_like.
@@ -363,7 +383,12 @@ class GaussianDiffusion:
         drawn once from torch's default generator, or from `known_noise_seed`).  At every noise level abar the known elements are held
         at sqrt(abar) known + sqrt(1 - abar) known_noise - x_T and every x_{t-1}, snapshots included - so the final sample equals
         `known` bit for bit there (before `smooth`); eta > 0 noise, clipping and the EPSILON update act on the other elements only
-        (include/dc_ddim.h, dc_sampler_set_known)."""
+        (include/dc_ddim.h, dc_sampler_set_known).
+        `guidance_scale` (extension, native loop only; None = no guidance, today's loop bit for bit): classifier-free guidance at
+        scale w - every step evaluates the model on the music and on the model's null_conditioning() and continues from
+        c + (w - 1)(c - u) (include/dc_ddim.h, dc_sampler_set_conditioning_guided; the reference trains for it, transformer.py:389,
+        451-459, and never samples with it).  ValueError with denoised_fn, cond_fn, PREVIOUS_X or a learned variance."""
+        self._check_guidance(model, guidance_scale, denoised_fn, cond_fn)
         self._refuse_epsilon_full_attention(model, eta)
         if self._fast_path_ok(model, denoised_fn, cond_fn):
             if device is None:
@@ -377,7 +402,8 @@ class GaussianDiffusion:
                 mk["xf_proj"], mk["xf_out"] = model.encode_music(mk["text"], device)
             snap = sorted(int(i) for i in set(idxs) if 0 <= int(i) < self.num_timesteps)
             kn = self._known_tensors(img, known, known_mask, known_noise, known_noise_seed)
-            out, snaps = self._native_loop(model, img, mk, bool(clip_denoised), float(eta), snap, step_noise, smooth, step_noise_seed, kn)
+            out, snaps = self._native_loop(model, img, mk, bool(clip_denoised), float(eta), snap, step_noise, smooth, step_noise_seed, kn,
+                                            guidance_scale)
             if len(idxs) == 0:
                 return out
             result = {it: snaps[k] for k, it in enumerate(snap)}
@@ -407,8 +433,10 @@ class GaussianDiffusion:
 
     def ddim_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None,
                                      cond_fn=None, model_kwargs=None, device=None, progress=False, eta=0.0,
-                                     step_noise=None):
-        """gaussian_diffusion.py:917-965: yields {"sample","pred_xstart"} after every step."""
+                                     step_noise=None, guidance_scale=None):
+        """gaussian_diffusion.py:917-965: yields {"sample","pred_xstart"} after every step.  `guidance_scale`: None only - this
+        generator steps through ddim_sample (ValueError otherwise; ddim_sample_loop guides inside the captured loop)."""
+        self._check_guidance(model, guidance_scale, denoised_fn, cond_fn, stepped=True)
         self._refuse_epsilon_full_attention(model, eta)
         if device is None:
             device = next(model.parameters()).device

@@ -124,6 +124,8 @@ def make_parser():
                         help="conduct mels longer than one window (5400 frames = 60 s) whole, window by window around the frames "
                              "already generated (DDPMTrainer.generate_long_music_motion); without it only the first window is sampled")
     parser.add_argument('--precision', type=str, default="fp16", choices=["fp16", "mixed", "bf16x3", "bf16", "auto"])
+    parser.add_argument('--guidance_scale', type=float, default=None,
+                        help="classifier-free guidance scale of the sampling loops (omitted: no guidance, the reference's sampling)")
     return parser
 
 
@@ -142,13 +144,14 @@ def main(argv=None):
     trainer.load(args.model if args.model else pjoin(opt.model_dir, 'latest.tar'))
     trainer.eval_mode()
     trainer.to(opt.device)
+    gkw = {} if args.guidance_scale is None else {"guidance_scale": args.guidance_scale}
     with torch.no_grad():
         mel, names = load_mels(args.music_path)
         # [B, T, 26] on the device; --smooth: smooth_motion(kernel=19) (:126) happens in the loop's final write
         if args.full_length and mel.shape[-2] > 3 * opt.max_motion_length:
-            pred_motions = trainer.generate_long_music_motion(mel, opt.dim_pose, seed=args.seed, smooth=19 if args.smooth else None)
+            pred_motions = trainer.generate_long_music_motion(mel, opt.dim_pose, seed=args.seed, smooth=19 if args.smooth else None, **gkw)
         else:
-            pred_motions = trainer.generate_music_motion(mel, opt.dim_pose, seed=args.seed, smooth=19 if args.smooth else None)
+            pred_motions = trainer.generate_music_motion(mel, opt.dim_pose, seed=args.seed, smooth=19 if args.smooth else None, **gkw)
         B, T = pred_motions.shape[0], pred_motions.shape[1]
         motion = pred_motions.view(B, T, 13, 2).cpu().numpy()
     out = motion[0] if mel.ndim == 2 else motion

@@ -244,9 +244,33 @@ DC_EXPORT int dc_sampler_ddim_loop_ex(dc_sampler* s, const float* d_noise, float
  * prediction of every element.  An all-zero mask gives the bits of a loop without known values.  The loops then need the table of
  * dc_ddim_coefficients_known (DC_ERR_INVALID with any other).  The tensors are read while a loop runs and their addresses go through
  * device slots: other tensors on the next call do not re-capture the hipGraph.  The setting serves the following loops until it is
- * cleared - three NULLs - or dc_sampler_set_conditioning changes (B, T).  DC_ERR_INVALID: a mask without values, a mask without noise,
+ * cleared - three NULLs - or dc_sampler_set_conditioning / dc_sampler_set_conditioning_guided changes the caller's (B, T) or switches
+ * guidance on or off (the tensors belong to the conditioning they were set on).  DC_ERR_INVALID: a mask without values, a mask without noise,
  * values or noise without a mask. */
 DC_EXPORT int dc_sampler_set_known(dc_sampler* s, const float* d_known, const float* d_mask, const float* d_known_noise);
+
+/* Classifier-free guidance.  The reference trains its denoiser for it - MotionTransformer.encode_music (models/transformer.py:389,
+ * 451-459) zeroes the music features of a token with probability cond_mask_prob = 0.1 before `proj` - and has NO sampling
+ * counterpart: its samplers never evaluate the unconditional branch.  This call is dc_sampler_set_conditioning for a guided loop: the
+ * sampler then evaluates 2 B internal clips per step - clip b with the caller's xf_proj[b], xf_out[b], length[b], clip B + b its
+ * unconditional shadow, every frame carrying the null pair (h_null_proj[64], h_null_out[64]; host arrays) and length[b] - both on the
+ * same x_t[b], and combines the two model outputs before anything else of the update, in fp32 and in this order:
+ *   out = c + (w - 1) (c - u)          c conditional, u unconditional output, w the guidance scale
+ * followed by the update of dc_sampler_ddim_loop_ex (START_X or EPSILON, clipping, eta noise) and the replacement of known values,
+ * unchanged.  w = 1 returns c bit for bit whenever u is finite.  DC_STATUS_NONFINITE looks at c, u and the combined prediction.
+ * The null pair of the reference's masking taken to every token is null_out = 0 and null_proj = proj.bias (proj(0)).
+ * Everything the caller passes to the loops and to dc_sampler_set_known stays [B,T,P] (d_noise, d_out, snapshots, step noise, seeded
+ * step noise and its first_element); the workspace is sized for 2 B.  dc_sampler_ddim_loop, _ex and dc_sampler_profile_loop run guided
+ * whenever the conditioning is guided; dc_sampler_denoise and the debug entry points return DC_ERR_INVALID on it (per-clip timesteps
+ * break the unconditional half's shared FiLM column; step-through callers combine on their side).  A plain
+ * dc_sampler_set_conditioning switches guidance off again.  DC_ERR_INVALID: NULL null vectors. */
+DC_EXPORT int dc_sampler_set_conditioning_guided(dc_sampler* s, const float* d_xf_proj, const float* d_xf_out, const int32_t* h_length,
+                                       int32_t B, int32_t T, const float* h_null_proj, const float* h_null_out, void* stream);
+
+/* The guidance scale w of the loops on a guided conditioning (same reference lines: transformer.py:389,451-459 train for it, no sampling
+ * counterpart).  1 after every dc_sampler_set_conditioning_guided.  Must be finite (DC_ERR_INVALID), and a guided conditioning must be
+ * set.  The scale reaches the kernels through a device slot: another scale replays the same hipGraph. */
+DC_EXPORT int dc_sampler_set_guidance_scale(dc_sampler* s, float w);
 
 /* eta > 0 without a noise tensor.  After this call a dc_sampler_ddim_loop_ex with sigma != 0 and d_step_noise == NULL
  * generates the draws of each iteration itself at the head of the step that consumes them (one [B,T,P] buffer instead of the
