@@ -97,14 +97,14 @@ struct dc_sampler : Formats {     // (set_precision(cfg.precision))
     int film_rate_parity = 0;
     int num_cu = 0;
     int *d_iter = nullptr, *d_t_clip = nullptr, *d_snap_cur = nullptr, *d_t_of_iter = nullptr, *d_snap_of_iter = nullptr;
-    float *d_coef_cur = nullptr, *d_coef_of_t = nullptr, *d_coef_of_iter = nullptr;   // DDIM scalars by timestep / by iteration
+    float *d_coef_cur = nullptr, *d_coef_of_iter = nullptr;   // the update's scalars: this step's row / every row, by ITERATION (only d_t_of_iter holds timesteps)
     bool cond_set = false;
     int64_t ws_bytes = 0;
     std::map<void*, size_t> alloc_bytes;   // live workspace allocations (ws_bytes = their sum)
     // host copies of the per-iteration tables currently on the device (tables_S == 0: none)
     int tables_S = 0;
     std::vector<int> tab_t, tab_snap;
-    std::vector<float> tab_coef, tab_coef_iter;
+    std::vector<float> tab_coef_iter;
 
     // graph cache, keyed by (B, T, Tx, steps per graph, form_key() of the captured launches): the current graph (the last entry) and
     // up to three parked ones for other batch shapes (a dataset's last, smaller batch; a service whose batch size varies): a shape
@@ -120,6 +120,8 @@ struct dc_sampler : Formats {     // (set_precision(cfg.precision))
     unsigned long long noise_seed = 0, noise_first = 0;      // Philox key; index of this sampler's first element in the whole batch's draw
     bool noise_seed_set = false;                             // a seed is consumed by the loop that uses it
     int* d_status = nullptr;
+    float* d_x0_prev = nullptr;     // DC_UPD_MULTISTEP: the previous step's predicted x0 [user_B][Tx][P], zeroed when such a loop starts
+    size_t cap_x0_prev = 0;
     // known values (dc_sampler_set_known): the caller's three [B][Tx][P] tensors, valid for clips of (known_B, known_Tx); the kernels read
     // their addresses from d_kslot
     const float *known_val = nullptr, *known_mask = nullptr, *known_noise = nullptr;
@@ -744,7 +746,6 @@ int ensure_steps(dc_sampler* s, int S) {
         int rc;
         if ((rc = dev_alloc(s, s->d_t_of_iter, (size_t)S * 4))) return rc;
         if ((rc = dev_alloc(s, s->d_snap_of_iter, (size_t)S * 4))) return rc;
-        if ((rc = dev_alloc(s, s->d_coef_of_t, (size_t)S * DC_COEF * 4))) return rc;
         if ((rc = dev_alloc(s, s->d_coef_of_iter, (size_t)S * DC_COEF * 4))) return rc;
         s->cap_steps = (size_t)S;
     }
@@ -820,7 +821,7 @@ int enqueue_step(dc_sampler* s, hipStream_t st, const Step& c, const Switches& w
     const float* coef_src = folded ? s->d_coef_of_iter + DC_COEF * (size_t)graph_step : s->d_coef_cur;
     const int* snap_src = folded ? s->d_snap_of_iter + graph_step : s->d_snap_cur;
     if (c.loop_mode && !folded)
-        LAUNCH(K_BEGIN, dc_launch_begin_step(st, s->d_iter, s->d_t_of_iter, s->d_coef_of_t, s->d_snap_of_iter,
+        LAUNCH(K_BEGIN, dc_launch_begin_step(st, s->d_iter, s->d_t_of_iter, s->d_coef_of_iter, s->d_snap_of_iter,
                                              s->d_t_clip, s->d_coef_cur, s->d_snap_cur, B));
     if (c.loop_mode && (s->upd_flags & DC_UPD_ZSTEP))       // this iteration's draws (eta > 0, library-generated): consumed by the last layer's epilogue
         LAUNCH(K_NOISE, dc_launch_step_noise(st, s->d_zstep, (size_t)s->user_B() * Tx * s->cfg.input_feats, 0, reinterpret_cast<const unsigned long long*>(s->d_zslot) + 1,
@@ -853,7 +854,7 @@ int enqueue_step(dc_sampler* s, hipStream_t st, const Step& c, const Switches& w
     la.out_mode = (c.loop_mode && !f.guided) ? 1 : 0, la.coef_cur = coef_src, la.snap_cur = snap_src, la.snaps = s->d_snaps, la.iter_base = iter_base;
     la.M = M, la.T = T, la.G = G, la.B = B, la.Tx = Tx, la.e_groups = f.film_groups;
     if (f.guided) la.xout = s->d_raw;      // the raw output of all 2 B clips; k_guided_update (below) combines the halves and updates x
-    la.upd = DcUpdate{s->d_zslot, s->d_status, (c.loop_mode ? s->upd_flags : 0) | f.upd_flags, folded ? graph_step : -1, nullptr, s->d_kslot};
+    la.upd = DcUpdate{s->d_zslot, s->d_status, (c.loop_mode ? s->upd_flags : 0) | f.upd_flags, folded ? graph_step : -1, nullptr, s->d_kslot, s->d_x0_prev};
     DcLayerArgs la_stamps = la;      // (stage stamps of layer 3 in diagnostic builds: DcUpdate::stamps carries the buffer)
     la_stamps.upd.stamps = s->d_stamps;
     if (s->cfg.no_eff) {
@@ -903,8 +904,9 @@ int sync_out(dc_sampler* s, hipStream_t user) {
     return DC_OK;
 }
 
-// h_coef: [S][DC_COEF] per-timestep scalars (dc_common.h); flags: DC_UPD_*; d_step_noise: [S][B][Tx][P] or nullptr
-int loop_common(dc_sampler* s, const float* d_noise, float* d_out, int S, const float* h_coef,
+// S iterations; h_t: the timestep the model sees at each ([S], strictly decreasing, validated by the caller; nullptr = S-1 .. 0);
+// h_coef: [S][DC_COEF] scalars of the update PER ITERATION (dc_common.h); flags: DC_UPD_*; d_step_noise: [S][B][Tx][P] or nullptr
+int loop_common(dc_sampler* s, const float* d_noise, float* d_out, int S, const int32_t* h_t, const float* h_coef,
                 const int32_t* h_snap_iters, int n_snap, float* d_snaps_user, hipStream_t user, bool profile,
                 int flags = 0, const float* d_step_noise = nullptr) {
     if (!s || !s->finalized) return fail(DC_ERR_INVALID, "sampler not finalized");
@@ -923,7 +925,7 @@ int loop_common(dc_sampler* s, const float* d_noise, float* d_out, int S, const 
     if (s->known_mask && (s->known_B != s->user_B() || s->known_Tx != s->Tx || s->known_guided != s->guided))
         s->known_val = s->known_mask = s->known_noise = nullptr;
     const bool known = s->known_mask != nullptr;
-    if (known && S > 1 && !(h_coef[(size_t)DC_COEF * (S - 1) + 5] > 0.f))
+    if (known && S > 1 && !(h_coef[5] > 0.f))      // (the first iteration's row: abar_prev < 1 there)
         return fail(DC_ERR_INVALID, "known values are set: the loop needs the [S][8] table of dc_ddim_coefficients_known (slot 5 = sqrt(1 - abar_prev))");
     if (known && profile) return fail(DC_ERR_UNSUPPORTED, "dc_sampler_profile_loop does not run with known values set");
     if (known) flags |= DC_UPD_KNOWN;
@@ -946,8 +948,18 @@ int loop_common(dc_sampler* s, const float* d_noise, float* d_out, int S, const 
         if (h_snap_iters[k] < 0 || h_snap_iters[k] >= S) return fail(DC_ERR_INVALID, "snapshot iteration %d outside [0,%d)", h_snap_iters[k], S);
         snap_of_iter[h_snap_iters[k]] = k;
     }
-    const bool same_tables = s->tables_S == S && s->tab_snap == snap_of_iter &&
-                             memcmp(s->tab_coef.data(), h_coef, (size_t)S * DC_COEF * 4) == 0;
+    std::vector<int> t_of_iter(S);
+    for (int i = 0; i < S; ++i) t_of_iter[i] = h_t ? h_t[i] : S - 1 - i;            // indices = range(num_timesteps)[::-1] (gaussian_diffusion.py:943)
+    const bool same_tables = s->tables_S == S && s->tab_snap == snap_of_iter && s->tab_t == t_of_iter &&
+                             memcmp(s->tab_coef_iter.data(), h_coef, (size_t)S * DC_COEF * 4) == 0;
+    if (flags & DC_UPD_MULTISTEP) {          // the history of the second-order update: one more [B][Tx][P] buffer, zeroed below
+        if (MP > s->cap_x0_prev) {
+            drop_graph(s);          // (its address is baked into the captured launches)
+            s->cap_x0_prev = 0;
+            if ((rc = dev_alloc(s, s->d_x0_prev, MP * 4))) return rc;
+            s->cap_x0_prev = MP;
+        }
+    }
     // eta > 0: the caller's [S][B][Tx][P] draws, or - none given, a seed set - one iteration's draws generated at the head of every step
     const float* zbase = nullptr;
     if (flags & DC_UPD_NOISY) {
@@ -975,23 +987,20 @@ int loop_common(dc_sampler* s, const float* d_noise, float* d_out, int S, const 
     if (!same_tables) {
         HIP_TRY(hipStreamSynchronize(st));          // an earlier call's copies out of the member vectors are done
         s->tables_S = 0;
-        s->tab_t.resize(S);
-        for (int i = 0; i < S; ++i) s->tab_t[i] = S - 1 - i;            // indices = range(num_timesteps)[::-1] (gaussian_diffusion.py:943)
+        s->tab_t = t_of_iter;
         s->tab_snap = snap_of_iter;
-        s->tab_coef.assign(h_coef, h_coef + (size_t)S * DC_COEF);
-        s->tab_coef_iter.resize((size_t)S * DC_COEF);
-        for (int i = 0; i < S; ++i) memcpy(&s->tab_coef_iter[DC_COEF * (size_t)i], h_coef + DC_COEF * (size_t)s->tab_t[i], DC_COEF * 4);
+        s->tab_coef_iter.assign(h_coef, h_coef + (size_t)S * DC_COEF);
         HIP_TRY(hipMemcpyAsync(s->d_t_of_iter, s->tab_t.data(), S * 4, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(s->d_snap_of_iter, s->tab_snap.data(), S * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(s->d_coef_of_t, s->tab_coef.data(), (size_t)S * DC_COEF * 4, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(s->d_coef_of_iter, s->tab_coef_iter.data(), (size_t)S * DC_COEF * 4, hipMemcpyHostToDevice, st));
         HIP_TRY(hipStreamSynchronize(st));          // pageable sources: the copies have left the host vectors
         s->tables_S = S;
     }
     HIP_TRY(hipMemsetAsync(s->d_iter, 0, 16, st));
+    if (flags & DC_UPD_MULTISTEP) HIP_TRY(hipMemsetAsync(s->d_x0_prev, 0, MP * 4, st));      // (kappa is 0 in the first step: the zeros are read, never used)
     HIP_TRY(hipMemcpyAsync(s->d_x, d_noise, MP * 4, hipMemcpyDeviceToDevice, st));
-    if (known) {      // x_T of the known elements at the loop's starting level abar_{S-1} (slots 6, 7 of the first step's row)
-        const float* c0 = h_coef + (size_t)DC_COEF * (S - 1);
+    if (known) {      // x_T of the known elements at the loop's starting level (slots 6, 7 of the first step's row)
+        const float* c0 = h_coef;
         HIP_TRY(dc_launch_set_known(st, s->d_kslot, s->known_val, s->known_mask, s->known_noise));
         HIP_TRY(dc_launch_known_blend(st, s->d_x, s->known_val, s->known_mask, s->known_noise, c0[6], c0[7], MP));
     }
@@ -1077,12 +1086,77 @@ int loop_common(dc_sampler* s, const float* d_noise, float* d_out, int S, const 
     return sync_out(s, user);
 }
 
-// the eta = 0 table [S][4] of dc_ddim_coefficients in the internal [S][DC_COEF] form (sigma = 0)
-std::vector<float> widen_coef(const float* h_coef, int S) {
-    std::vector<float> c8((size_t)(S > 0 ? S : 0) * DC_COEF, 0.f);
+// A public per-TIMESTEP table [S][width] (width 4: dc_ddim_coefficients, sigma = 0; 8: dc_ddim_coefficients_ex / _known) as the rows
+// PER ITERATION of the loop over t = S-1 .. 0, in the internal width (slots past `width` are 0: no history term)
+std::vector<float> rows_of_table(const float* h_coef, int S, int width) {
+    std::vector<float> rows((size_t)(S > 0 ? S : 0) * DC_COEF, 0.f);
     if (h_coef)
-        for (int t = 0; t < S; ++t) memcpy(&c8[(size_t)DC_COEF * t], h_coef + 4 * (size_t)t, 16);
-    return c8;
+        for (int i = 0; i < S; ++i) memcpy(&rows[(size_t)DC_COEF * i], h_coef + (size_t)width * (S - 1 - i), (size_t)width * 4);
+    return rows;
+}
+
+// One row of the update's scalars for a step from noise level abar = a64 to abar_next = an64 (`last`: to 1, the clean sample), slots 0..7
+// as dc_ddim.h lists them: fp32 arithmetic on the fp32-rounded table entries, in the order ddim_sample evaluates them
+// (gaussian_diffusion.py:812-826).  The one copy of these roundings: dc_ddim_coefficients_ex / _known call it with (abar_t, abar_{t-1}),
+// dc_solver_table with the sub-schedule's pair.
+void ddim_row8(double a64, bool last, double an64, float eta, float* c) {
+    const float a = (float)a64, a_prev = last ? 1.0f : (float)an64;
+    const float sigma = eta * sqrtf((1.0f - a_prev) / (1.0f - a)) * sqrtf(1.0f - a / a_prev);
+    c[0] = (float)std::sqrt(1.0 / a64);
+    c[1] = (float)std::sqrt(1.0 / a64 - 1.0);
+    c[2] = sqrtf(a_prev);
+    c[3] = sqrtf(1.0f - a_prev - sigma * sigma);
+    c[4] = sigma;
+    c[5] = sqrtf(1.0f - a_prev);      // (dc_ddim_coefficients' column 3: the same expression and rounding)
+    c[6] = sqrtf(a);
+    c[7] = sqrtf(1.0f - a);
+}
+
+// dc_sampler_solver_loop and its profiled twin: validation of the caller's list and rows, then loop_common
+int solver_loop(dc_sampler* s, const float* d_noise, float* d_out, int n, const int32_t* h_t, const float* h_rows, int flags,
+                const float* d_step_noise, const int32_t* h_snap_iters, int n_snap, float* d_snaps, void* stream, bool profile) {
+    if (!s) return fail(DC_ERR_INVALID, "null sampler");
+    if (n_snap < 0 || (n_snap > 0 && (!h_snap_iters || !d_snaps))) return fail(DC_ERR_INVALID, "bad snapshot arguments");
+    if (flags & ~(DC_UPD_CLIP | DC_UPD_EPS)) return fail(DC_ERR_INVALID, "unknown update flags 0x%x", flags);
+    if (!h_t || !h_rows) return fail(DC_ERR_INVALID, "null pointer argument");
+    if (n < 1 || n > s->cfg.max_timesteps) return fail(DC_ERR_INVALID, "%d timesteps outside [1, max_timesteps=%d]", n, s->cfg.max_timesteps);
+    bool noisy = false, multi = false;
+    for (int i = 0; i < n; ++i) {
+        if (h_t[i] < 0 || h_t[i] >= s->cfg.max_timesteps || (i > 0 && h_t[i] >= h_t[i - 1]))
+            return fail(DC_ERR_INVALID, "timesteps must be strictly decreasing inside [0, max_timesteps=%d): entry %d is %d", s->cfg.max_timesteps, i, h_t[i]);
+        noisy = noisy || h_rows[(size_t)DC_COEF * i + 4] != 0.f;
+        multi = multi || h_rows[(size_t)DC_COEF * i + 8] != 0.f;
+    }
+    if (multi && (h_rows[8] != 0.f || h_rows[(size_t)DC_COEF * (n - 1) + 8] != 0.f))
+        return fail(DC_ERR_INVALID, "the history coefficient (slot 8) must be 0 in the first row (no history yet) and in the last (the final sample is the model's x0)");
+    if (multi && noisy) return fail(DC_ERR_INVALID, "the second-order multistep update is deterministic: rows with a history coefficient need sigma = 0 (eta = 0)");
+    if (noisy && !d_step_noise && !s->noise_seed_set)
+        return fail(DC_ERR_INVALID, "sigma != 0 (eta > 0) needs the per-iteration noise: the tensor d_step_noise [n][B][T][P], or a seed "
+                    "(dc_sampler_set_step_noise_seed) for draws generated step by step");
+    return loop_common(s, d_noise, d_out, n, h_t, h_rows, h_snap_iters, n_snap, d_snaps, (hipStream_t)stream, profile,
+                       flags | (noisy ? DC_UPD_NOISY : 0) | (multi ? DC_UPD_MULTISTEP : 0), noisy ? d_step_noise : nullptr);
+}
+
+// the per-kernel sums of a profiled loop's events (dc_sampler_profile_loop, dc_sampler_solver_profile_loop)
+int collect_profile(dc_sampler* s, float* h_ms, int32_t* h_count, int n) {
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    for (int i = 0; i < n; ++i) {
+        h_ms[i] = 0.f;
+        h_count[i] = 0;
+    }
+    for (size_t i = 0; i < s->prof.ids.size(); ++i) {
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, s->prof.ev[2 * i], s->prof.ev[2 * i + 1]));
+        const int id = s->prof.ids[i];
+        if (id < n) {
+            h_ms[id] += ms;
+            h_count[id] += 1;
+        }
+    }
+    for (hipEvent_t e : s->prof.ev) hipEventDestroy(e);
+    s->prof.ev.clear();
+    s->prof.ids.clear();
+    return DC_OK;
 }
 
 // dc_sampler_denoise; the debug entry points run it with their test hooks
@@ -1121,6 +1195,7 @@ extern "C" {
 static_assert(DC_UPDATE_CLIP_DENOISED == DC_UPD_CLIP && DC_UPDATE_EPSILON == DC_UPD_EPS && DC_STATUS_F16_SATURATED == DC_STATUS_F16_SAT &&
                   DC_STATUS_TIMEOUT == DC_STATUS_SYNC_TIMEOUT,
               "include/dc_ddim.h and dc_common.h disagree");
+static_assert(DC_SOLVER_ROW == DC_COEF, "include/dc_ddim.h and dc_common.h disagree on the row width");
 static_assert(DC_PREC_BF16 == DCF_BF16 && DC_PREC_MIXED == DCF_MIXED && DC_PREC_BF16X3 == DCF_BF16X3 && DC_PREC_FP16 == DCF_FP16,
               "include/dc_ddim.h and dc_form.h disagree");
 
@@ -1159,31 +1234,43 @@ int dc_ddim_coefficients(int32_t n, const double* ac, float* coef) {
 
 int dc_ddim_coefficients_ex(int32_t n, const double* ac, float eta, float* coef8) {
     if (n < 1 || !ac || !coef8 || !(eta >= 0.f)) return fail(DC_ERR_INVALID, "bad coefficient arguments");
-    // fp32 arithmetic on the fp32-rounded table entries, in the order ddim_sample evaluates them (gaussian_diffusion.py:812-826)
     for (int t = 0; t < n; ++t) {
-        const float a = (float)ac[t], a_prev = t == 0 ? 1.0f : (float)ac[t - 1];
-        const float sigma = eta * sqrtf((1.0f - a_prev) / (1.0f - a)) * sqrtf(1.0f - a / a_prev);
-        float* c = coef8 + (size_t)DC_COEF * t;
-        c[0] = (float)std::sqrt(1.0 / ac[t]);
-        c[1] = (float)std::sqrt(1.0 / ac[t] - 1.0);
-        c[2] = sqrtf(a_prev);
-        c[3] = sqrtf(1.0f - a_prev - sigma * sigma);
-        c[4] = sigma;
+        float* c = coef8 + (size_t)8 * t;
+        ddim_row8(ac[t], t == 0, t == 0 ? 1.0 : ac[t - 1], eta, c);
         c[5] = c[6] = c[7] = 0.f;
     }
     return DC_OK;
 }
 
 int dc_ddim_coefficients_known(int32_t n, const double* ac, float eta, float* coef8, float* start2) {
-    if (int rc = dc_ddim_coefficients_ex(n, ac, eta, coef8)) return rc;
-    for (int t = 0; t < n; ++t) {
-        const float a = (float)ac[t], a_prev = t == 0 ? 1.0f : (float)ac[t - 1];
-        float* c = coef8 + (size_t)DC_COEF * t;
-        c[5] = sqrtf(1.0f - a_prev);      // (dc_ddim_coefficients' column 3: the same expression and rounding)
-        c[6] = sqrtf(a);
-        c[7] = sqrtf(1.0f - a);
+    if (n < 1 || !ac || !coef8 || !(eta >= 0.f)) return fail(DC_ERR_INVALID, "bad coefficient arguments");
+    for (int t = 0; t < n; ++t) ddim_row8(ac[t], t == 0, t == 0 ? 1.0 : ac[t - 1], eta, coef8 + (size_t)8 * t);
+    if (start2) start2[0] = coef8[(size_t)8 * (n - 1) + 6], start2[1] = coef8[(size_t)8 * (n - 1) + 7];
+    return DC_OK;
+}
+
+int dc_solver_table(int32_t n_train, const double* ac, const int32_t* ts, int32_t n, float eta, int32_t order, float* rows, float* start2) {
+    if (n_train < 1 || !ac || !ts || !rows || !(eta >= 0.f)) return fail(DC_ERR_INVALID, "bad solver table arguments");
+    if (n < 1) return fail(DC_ERR_INVALID, "a solver loop needs at least one timestep (n = %d)", n);
+    if (order != 1 && order != 2) return fail(DC_ERR_INVALID, "solver order %d: 1 (DDIM) and 2 (multistep, DPM-Solver++ 2M) are built", order);
+    if (order == 2 && eta != 0.f) return fail(DC_ERR_INVALID, "the second-order multistep update is deterministic: eta must be 0 (got %g)", (double)eta);
+    for (int i = 0; i < n; ++i)
+        if (ts[i] < 0 || ts[i] >= n_train || (i > 0 && ts[i] >= ts[i - 1]))
+            return fail(DC_ERR_INVALID, "timesteps must be strictly decreasing inside [0, %d): entry %d is %d", n_train, i, ts[i]);
+    // lambda = log(alpha / sigma) = 1/2 ln(abar / (1 - abar)), the half log-SNR the solver steps in
+    const auto lam = [](double a) { return 0.5 * std::log(a / (1.0 - a)); };
+    for (int i = 0; i < n; ++i) {
+        float* c = rows + (size_t)DC_SOLVER_ROW * i;
+        const bool last = i == n - 1;
+        const double a = ac[ts[i]], an = last ? 1.0 : ac[ts[i + 1]];
+        ddim_row8(a, last, an, eta, c);
+        for (int k = 8; k < DC_SOLVER_ROW; ++k) c[k] = 0.f;
+        if (order == 2 && i > 0 && !last) {
+            const double la = lam(a), h = lam(an) - la, h_before = la - lam(ac[ts[i - 1]]), r = h_before / h;
+            c[8] = (float)((std::sqrt(an) - std::sqrt(1.0 - an) * std::sqrt(a) / std::sqrt(1.0 - a)) / (2.0 * r));
+        }
     }
-    if (start2) start2[0] = coef8[(size_t)DC_COEF * (n - 1) + 6], start2[1] = coef8[(size_t)DC_COEF * (n - 1) + 7];
+    if (start2) start2[0] = rows[6], start2[1] = rows[7];      // the first iteration's level: the loop starts at abar[ts[0]]
     return DC_OK;
 }
 
@@ -1254,7 +1341,7 @@ void dc_sampler_destroy(dc_sampler* s) {
     drop_graph(s);
     void* ptrs[] = {s->d_arena, s->d_model, s->d_model_split, s->d_length, s->d_pp, s->d_s_hi, s->d_s_lo, s->d_E, s->d_h, s->d_recs, s->d_a_sa,
                     s->d_a_ca, s->d_x, s->d_snaps, s->d_recs_ca, s->d_nh_hi, s->d_nh_lo, s->d_iter,
-                    s->d_t_clip, s->d_snap_cur, s->d_t_of_iter, s->d_snap_of_iter, s->d_coef_cur, s->d_coef_of_t, s->d_coef_of_iter,
+                    s->d_t_clip, s->d_snap_cur, s->d_t_of_iter, s->d_snap_of_iter, s->d_coef_cur, s->d_x0_prev, s->d_coef_of_iter,
                     s->d_kv_sa[0], s->d_kv_sa[1], s->d_kv_ca, s->d_stamps, s->d_film_rate, s->d_status, s->d_smooth_coef, s->d_zslot, s->d_kslot, s->d_zstep, s->d_a_ca16, s->d_gran,
                     s->d_wslot, s->d_raw, s->d_xf2_proj, s->d_xf2_out};
     for (void* p : ptrs)
@@ -1616,8 +1703,8 @@ int dc_sampler_ddim_loop(dc_sampler* s, const float* d_noise, float* d_out, int3
                          const int32_t* h_snap_iters, int32_t n_snap, float* d_snaps, void* stream) {
     if (s) HIP_TRY(hipSetDevice(s->cfg.device));
     if (n_snap < 0 || (n_snap > 0 && (!h_snap_iters || !d_snaps))) return fail(DC_ERR_INVALID, "bad snapshot arguments");
-    const std::vector<float> c8 = widen_coef(h_coef, num_steps);
-    return loop_common(s, d_noise, d_out, num_steps, h_coef ? c8.data() : nullptr, h_snap_iters, n_snap, d_snaps, (hipStream_t)stream, false);
+    const std::vector<float> rows = rows_of_table(h_coef, num_steps, 4);
+    return loop_common(s, d_noise, d_out, num_steps, nullptr, h_coef ? rows.data() : nullptr, h_snap_iters, n_snap, d_snaps, (hipStream_t)stream, false);
 }
 
 int dc_sampler_ddim_loop_ex(dc_sampler* s, const float* d_noise, float* d_out, int32_t num_steps, const float* h_coef8,
@@ -1628,12 +1715,19 @@ int dc_sampler_ddim_loop_ex(dc_sampler* s, const float* d_noise, float* d_out, i
     if (flags & ~(DC_UPD_CLIP | DC_UPD_EPS)) return fail(DC_ERR_INVALID, "unknown update flags 0x%x", flags);
     bool noisy = false;
     if (h_coef8 && num_steps > 0)
-        for (int t = 0; t < num_steps; ++t) noisy = noisy || h_coef8[(size_t)DC_COEF * t + 4] != 0.f;
+        for (int t = 0; t < num_steps; ++t) noisy = noisy || h_coef8[(size_t)8 * t + 4] != 0.f;
     if (noisy && !d_step_noise && !(s && s->noise_seed_set))
         return fail(DC_ERR_INVALID, "sigma != 0 (eta > 0) needs the per-iteration noise: the tensor d_step_noise [S][B][T][P], or a seed "
                     "(dc_sampler_set_step_noise_seed) for draws generated step by step");
-    return loop_common(s, d_noise, d_out, num_steps, h_coef8, h_snap_iters, n_snap, d_snaps, (hipStream_t)stream, false,
+    const std::vector<float> rows = rows_of_table(h_coef8, num_steps, 8);
+    return loop_common(s, d_noise, d_out, num_steps, nullptr, h_coef8 ? rows.data() : nullptr, h_snap_iters, n_snap, d_snaps, (hipStream_t)stream, false,
                        flags | (noisy ? DC_UPD_NOISY : 0), noisy ? d_step_noise : nullptr);
+}
+
+int dc_sampler_solver_loop(dc_sampler* s, const float* d_noise, float* d_out, int32_t n, const int32_t* h_timesteps, const float* h_rows,
+                           int32_t flags, const float* d_step_noise, const int32_t* h_snap_iters, int32_t n_snap, float* d_snaps, void* stream) {
+    if (s) HIP_TRY(hipSetDevice(s->cfg.device));
+    return solver_loop(s, d_noise, d_out, n, h_timesteps, h_rows, flags, d_step_noise, h_snap_iters, n_snap, d_snaps, stream, false);
 }
 
 int dc_sampler_set_known(dc_sampler* s, const float* d_known, const float* d_mask, const float* d_known_noise) {
@@ -1722,27 +1816,20 @@ int dc_sampler_profile_loop(dc_sampler* s, const float* d_noise, float* d_out, i
     HIP_TRY(hipSetDevice(s->cfg.device));
     s->prof.ev.clear();
     s->prof.ids.clear();
-    const std::vector<float> c8 = widen_coef(h_coef, num_steps);
-    int rc = loop_common(s, d_noise, d_out, num_steps, h_coef ? c8.data() : nullptr, nullptr, 0, nullptr, (hipStream_t)stream, true);
+    const std::vector<float> rows = rows_of_table(h_coef, num_steps, 4);
+    int rc = loop_common(s, d_noise, d_out, num_steps, nullptr, h_coef ? rows.data() : nullptr, nullptr, 0, nullptr, (hipStream_t)stream, true);
     if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    for (int i = 0; i < n; ++i) {
-        h_ms[i] = 0.f;
-        h_count[i] = 0;
-    }
-    for (size_t i = 0; i < s->prof.ids.size(); ++i) {
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, s->prof.ev[2 * i], s->prof.ev[2 * i + 1]));
-        const int id = s->prof.ids[i];
-        if (id < n) {
-            h_ms[id] += ms;
-            h_count[id] += 1;
-        }
-    }
-    for (hipEvent_t e : s->prof.ev) hipEventDestroy(e);
+    return collect_profile(s, h_ms, h_count, n);
+}
+
+int dc_sampler_solver_profile_loop(dc_sampler* s, const float* d_noise, float* d_out, int32_t n, const int32_t* h_timesteps, const float* h_rows,
+                                   int32_t flags, float* h_ms, int32_t* h_count, int32_t n_kernels, void* stream) {
+    if (!s || !h_ms || !h_count) return fail(DC_ERR_INVALID, "null argument");
+    HIP_TRY(hipSetDevice(s->cfg.device));
     s->prof.ev.clear();
     s->prof.ids.clear();
-    return DC_OK;
+    if (int rc = solver_loop(s, d_noise, d_out, n, h_timesteps, h_rows, flags, nullptr, nullptr, 0, nullptr, stream, true)) return rc;
+    return collect_profile(s, h_ms, h_count, n_kernels);
 }
 
 int dc_sampler_debug_denoise(dc_sampler* s, const float* d_x, const int32_t* h_timesteps, float* d_out,

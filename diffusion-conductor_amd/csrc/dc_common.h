@@ -103,7 +103,10 @@ struct DcModel {
 // Options of the DDIM update fused into the last layer kernel (gaussian_diffusion.py:503-521, 812-830).  The per-step scalars
 // come as 8 floats per timestep: sqrt(1/abar), sqrt(1/abar - 1), sqrt(abar_prev), sqrt(1 - abar_prev - sigma^2), sigma, 0, 0, 0
 // (dc_ddim_coefficients_known: slot 5 = sqrt(1 - abar_prev), slots 6, 7 = sqrt(abar), sqrt(1 - abar): the noise levels of known values).
-#define DC_COEF 8
+// Slot 8 is kappa, the history coefficient of the second-order multistep update (dc_solver_table; 0 in every DDIM loop), slots 9..11
+// are 0.  Every per-step table on the device holds rows of this width, indexed by ITERATION; the public [S][4] / [S][8] tables are
+// widened on the host (dc_api.hip).
+#define DC_COEF 12
 #define DC_UPD_CLIP 1        // clip_denoised: pred_xstart.clamp(-1, 1)  (:506-507)
 #define DC_UPD_EPS 2         // ModelMeanType.EPSILON: pred_xstart = sqrt(1/abar) x_t - sqrt(1/abar - 1) model_out  (:516-521, 539-544)
 #define DC_UPD_NOISY 4       // (internal) eta > 0: sigma z is added; the draws are read from *zslot
@@ -111,6 +114,7 @@ struct DcModel {
 #define DC_UPD_TEST_DROP_SLICE 16   // (test hook, DC_L16_TEST_DROP_SLICE=1) workgroup 0 of k_layer16 publishes nothing: its neighbours' bounded wait must end in DC_STATUS_SYNC_TIMEOUT
 #define DC_UPD_EMBED_NEXT 32  // (internal) the last layer of this step also embeds x_{t-1} and runs layer 0's self-attention front half for the NEXT step (k_layer, wide non-split production form)
 #define DC_UPD_KNOWN 64       // (internal) known values (dc_sampler_set_known): where *kslot's mask is nonzero, x_{t-1} = c[2] known + c[5] noise (known_replace, dc_dev.h)
+#define DC_UPD_MULTISTEP 128   // (internal) second-order multistep update (dc_sampler_solver_loop, order 2): x_{t-1} += c[8] (pred - *x0_prev), then *x0_prev = pred (multistep_update, dc_dev.h)
 #define DC_STATUS_NONFINITE 1    // a predicted x0 was inf / nan
 #define DC_STATUS_F16_SAT 2      // a FiLM modulation value exceeded the fp16 range when stored
 #define DC_STATUS_SYNC_TIMEOUT 4 // a workgroup of the small-batch layer kernel gave up waiting for its clip's combine slices (GPU shared?)
@@ -124,6 +128,7 @@ struct DcUpdate {
     unsigned long long* stamps;   // diagnostic builds (-DDC_FULL_STAMPS, tools/stage_stamps_full.py): stage stamps of k_layer_full, else nullptr
     const float* const* kslot;   // DC_UPD_KNOWN: device slots holding the bases of the caller's known values, mask and noise, each [B][Tx][P]
                          // (slots like zslot: other tensors on the next call do not re-capture the graph)
+    float* x0_prev;      // DC_UPD_MULTISTEP: the previous step's predicted x0 [B][Tx][P] (the caller's clips), read and rewritten in place; else unused
 };
 
 // one 64-vector of the null pair of a guided conditioning, by value (k_fill_rows64)

@@ -1623,7 +1623,7 @@ DEV void styl_accumulate_ring(f32x16 (&h)[4], const ytile<SPLIT> (&y)[4], float 
 //   eps  = (sqrt(1/abar) x_t - pred) / sqrt(1/abar - 1);   x_{t-1} = sqrt(abar_prev) pred + sqrt(1 - abar_prev - sigma^2) eps + sigma z
 // (sigma is 0 at t = 0 - abar_prev = 1 there - which is the reference's nonzero_mask.)  Returns x_{t-1}; `bad` collects non-finite pred.
 // ------------------------------------------------------------------------------------
-DEV float ddim_update(float mo, float xt, const float* __restrict__ c, int flags, bool noisy, float z, bool& bad) {
+DEV float ddim_update(float mo, float xt, const float* __restrict__ c, int flags, bool noisy, float z, bool& bad, float& pred_out) {
     const float sr = c[0], srm1 = c[1], cx0 = c[2], ceps = c[3];
     float pred = mo;
     if (flags & DC_UPD_EPS) pred = sr * xt - srm1 * mo;
@@ -1632,6 +1632,27 @@ DEV float ddim_update(float mo, float xt, const float* __restrict__ c, int flags
     const float eps = (sr * xt - pred) / srm1;
     float xn = pred * cx0 + ceps * eps;
     if (noisy) xn += c[4] * z;
+    pred_out = pred;
+    return xn;
+}
+
+// ------------------------------------------------------------------------------------
+// The update every site applies to element `o` of x: ddim_update, and - DC_UPD_MULTISTEP, the second-order multistep solver
+// (DPM-Solver++ 2M in its x0-prediction form; no counterpart in the reference, whose only deterministic sampler is the first-order
+// update above) - the history term   x_{t-1} += kappa (pred - prev),   kappa = c[8] of the step's row (dc_solver_table; 0 in the first
+// and the last step), prev = the pred the previous step stored in upd.x0_prev[o], which then takes this step's pred (after the
+// EPSILON conversion and clipping: what the update itself used).  The thread that updates an element is the only one that touches its
+// slot, so one buffer serves in place.  Without the flag nothing is loaded or stored and the result is ddim_update's, bit for bit.
+// Known values are replaced behind this (known_replace).
+// ------------------------------------------------------------------------------------
+DEV float multistep_update(float mo, float xt, const float* __restrict__ c, const DcUpdate& upd, bool noisy, float z, bool& bad, size_t o) {
+    float pred;
+    float xn = ddim_update(mo, xt, c, upd.flags, noisy, z, bad, pred);
+    if (upd.flags & DC_UPD_MULTISTEP) {
+        float* hp = upd.x0_prev + o;
+        xn += c[8] * (pred - *hp);
+        *hp = pred;
+    }
     return xn;
 }
 

@@ -23,12 +23,12 @@
 // per-step bookkeeping: iteration counter -> timestep per clip, DDIM scalars, snapshot slot
 // ------------------------------------------------------------------------------------
 __global__ void k_begin_step(int* __restrict__ iter, const int* __restrict__ t_of_iter,
-                             const float* __restrict__ coef_of_t, const int* __restrict__ snap_of_iter,
+                             const float* __restrict__ coef_of_iter, const int* __restrict__ snap_of_iter,
                              int* __restrict__ t_clip, float* __restrict__ coef_cur, int* __restrict__ snap_cur, int B) {
     const int it = *iter;
     const int t = t_of_iter[it];
     for (int b = threadIdx.x; b < B; b += blockDim.x) t_clip[b] = t;
-    if (threadIdx.x < DC_COEF) coef_cur[threadIdx.x] = coef_of_t[t * DC_COEF + threadIdx.x];
+    if (threadIdx.x < DC_COEF) coef_cur[threadIdx.x] = coef_of_iter[it * DC_COEF + threadIdx.x];      // (rows are per ITERATION: t may exceed the loop's length)
     __syncthreads();
     if (threadIdx.x == 0) {
         snap_cur[0] = snap_of_iter ? snap_of_iter[it] : -1;
@@ -116,8 +116,10 @@ __global__ __launch_bounds__(256) void k_guided_update(const float* __restrict__
     const float wm1 = *wslot - 1.f;
     // (x, raw and snaps are workspace buffers: their halves and slots are 16-byte aligned whenever n is a multiple of 4)
     const auto a16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    const bool vec = (n & 3) == 0 && a16(raw) && a16(x) && a16(snaps) && a16(zrow);
-    float c[4], u[4], xt[4], z[4] = {0.f, 0.f, 0.f, 0.f}, xn[4];
+    const bool multi = (upd.flags & DC_UPD_MULTISTEP) != 0;
+    const bool vec = (n & 3) == 0 && a16(raw) && a16(x) && a16(snaps) && a16(zrow) && a16(upd.x0_prev);
+    float c[4], u[4], xt[4], z[4] = {0.f, 0.f, 0.f, 0.f}, xn[4], pred[4], prev[4] = {0.f, 0.f, 0.f, 0.f};
+    if (multi) guide_ld4(prev, upd.x0_prev, i, cnt, vec);
     guide_ld4(c, raw, i, cnt, vec);
     guide_ld4(u, raw + n, i, cnt, vec);
     guide_ld4(xt, x, i, cnt, vec);
@@ -127,12 +129,14 @@ __global__ __launch_bounds__(256) void k_guided_update(const float* __restrict__
     for (int j = 0; j < 4; ++j) {
         bad = bad || (j < cnt && !(fabsf(c[j]) <= 3.0e38f && fabsf(u[j]) <= 3.0e38f));
         bool badj = false;
-        xn[j] = ddim_update(guide_combine(c[j], u[j], wm1), xt[j], cc, upd.flags, noisy, z[j], badj);
+        xn[j] = ddim_update(guide_combine(c[j], u[j], wm1), xt[j], cc, upd.flags, noisy, z[j], badj, pred[j]);
+        if (multi) xn[j] += cc[8] * (pred[j] - prev[j]);      // (multistep_update, dc_dev.h, on this thread's four elements)
         bad = bad || (j < cnt && badj);
         if (j < cnt) xn[j] = known_replace(xn[j], kn, i + j, cc);
     }
     guide_st4(x, i, xn, cnt, vec);
     guide_st4(x + n, i, xn, cnt, vec);
+    if (multi) guide_st4(upd.x0_prev, i, pred, cnt, vec);
     if (snap >= 0) guide_st4(snaps + (size_t)snap * n, i, xn, cnt, vec);
     if (bad && upd.status) atomicOr(upd.status, DC_STATUS_NONFINITE);
 }
@@ -1735,7 +1739,7 @@ void k_layer(const DcModel* __restrict__ dm, int l, float* __restrict__ hbuf, co
                     if (f < P) {
                         const size_t o = xrow * P + f;
                         // (known values go in BEFORE xv takes the element: the next step's embedding below reads the registers, not xout)
-                        const float xnew = known_replace(ddim_update(x0[0][r], xtv[r], cc, upd.flags, noisy, noisy ? zrow[o] : 0.f, bad), kn, o, cc);
+                        const float xnew = known_replace(multistep_update(x0[0][r], xtv[r], cc, upd, noisy, noisy ? zrow[o] : 0.f, bad, o), kn, o, cc);
                         xout[o] = xnew;
                         if (snap >= 0) snaps[(size_t)snap * B * Tx * P + o] = xnew;
                         xv[r] = xnew;
@@ -1792,7 +1796,7 @@ void k_layer(const DcModel* __restrict__ dm, int l, float* __restrict__ hbuf, co
             const int f = tile_row(r, cx.hh);
             if (f < P) {
                 const size_t o = xrow * P + f;
-                const float xnew = known_replace(ddim_update(x0[0][r], xin[o], coef_cur, upd.flags, noisy, noisy ? zrow[o] : 0.f, bad), kn, o, coef_cur);
+                const float xnew = known_replace(multistep_update(x0[0][r], xin[o], coef_cur, upd, noisy, noisy ? zrow[o] : 0.f, bad, o), kn, o, coef_cur);
                 xout[o] = xnew;
                 if (snap >= 0) snaps[(size_t)snap * B * Tx * P + o] = xnew;
             }
@@ -2668,7 +2672,7 @@ __global__ __launch_bounds__(512, 2) void k_layer_full(const DcModel* __restrict
             const int f = tile_row(r, cx.hh);
             if (f < P) {
                 const size_t o = (size_t)cx.tok * P + f;
-                const float xn = known_replace(ddim_update(x0[0][r], xin[o], coef_cur, upd.flags, noisy, noisy ? zrow[o] : 0.f, bad), kn, o, coef_cur);
+                const float xn = known_replace(multistep_update(x0[0][r], xin[o], coef_cur, upd, noisy, noisy ? zrow[o] : 0.f, bad, o), kn, o, coef_cur);
                 xout[o] = xn;
                 if (snap >= 0) snaps[(size_t)snap * M * P + o] = xn;
             }
@@ -2821,9 +2825,9 @@ hipError_t dc_launch_step_noise(hipStream_t st, float* z, size_t n, unsigned lon
     k_step_noise<<<dim3(grid ? grid : 1), dim3(256), 0, st>>>(z, n, seed, seed_slot, iter_base, step, snap_cur, first);
     return hipGetLastError();
 }
-hipError_t dc_launch_begin_step(hipStream_t st, int* iter, const int* t_of_iter, const float* coef_of_t,
+hipError_t dc_launch_begin_step(hipStream_t st, int* iter, const int* t_of_iter, const float* coef_of_iter,
                                 const int* snap_of_iter, int* t_clip, float* coef_cur, int* snap_cur, int B) {
-    hipLaunchKernelGGL(k_begin_step, dim3(1), dim3(64), 0, st, iter, t_of_iter, coef_of_t, snap_of_iter, t_clip,
+    hipLaunchKernelGGL(k_begin_step, dim3(1), dim3(64), 0, st, iter, t_of_iter, coef_of_iter, snap_of_iter, t_clip,
                        coef_cur, snap_cur, B);
     return LAUNCH_CHECK();
 }

@@ -3,7 +3,7 @@
 #include <hip/hip_runtime.h>
 #include "dc_common.h"
 
-hipError_t dc_launch_begin_step(hipStream_t st, int* iter, const int* t_of_iter, const float* coef_of_t,
+hipError_t dc_launch_begin_step(hipStream_t st, int* iter, const int* t_of_iter, const float* coef_of_iter,
                                 const int* snap_of_iter, int* t_clip, float* coef_cur, int* snap_cur, int B);
 hipError_t dc_launch_temb_table(hipStream_t st, const float* freqs, const float* w0t, const float* b0,
                                 const float* w2t, const float* b2, float* temb, int nt);

@@ -925,7 +925,7 @@ void k_layer16(const DcModel* __restrict__ dm, int l, float* __restrict__ hbuf, 
                 const int ft = 16 * rb + 4 * c.q4 + i;
                 if (ft < P) {
                     const size_t o = xrow * P + ft;
-                    const float xnew = known_replace(ddim_update(x0[rb][i], xin[o], coef_cur, upd.flags, noisy, noisy ? zrow[o] : 0.f, bad), kn, o, coef_cur);
+                    const float xnew = known_replace(multistep_update(x0[rb][i], xin[o], coef_cur, upd, noisy, noisy ? zrow[o] : 0.f, bad, o), kn, o, coef_cur);
                     xout[o] = xnew;
                     if (snap >= 0) snaps[(size_t)snap * B * Tx * P + o] = xnew;
                 }

@@ -243,7 +243,7 @@ class _Scorer:
 
 
 def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed=0, smooth=False, verbose=True, motion_encoder=None,
-                     diversity_seed=0, m2snet=None, guidance_scale=None):
+                     diversity_seed=0, m2snet=None, guidance_scale=None, steps=None, spacing="uniform", solver="ddim"):
     """Samples every clip under `root` and returns {"per_clip": {id: mse}, "total_loss", "final_mse", "clips",
     "seconds", "frames_per_s"}.  Clip i (in sorted order) starts from noise seeded with (seed, i), so the result
     does not depend on batch_size or on the number of ranks.
@@ -265,6 +265,8 @@ def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed
     generated, mismatched = rolled).  Without it the result is unchanged.
 
     `guidance_scale`: None, or the classifier-free guidance scale every batch is sampled with (generate_music_motion).
+    `steps`, `spacing`, `solver`: every batch is sampled on `steps` of the schedule's timesteps (generate_music_motion; the defaults
+    walk every timestep, as before).
 
     The host stays out of the GPU's way: batch k + 1's files and noise are prepared, and batch k - 1's MSEs computed, on
     background threads while batch k is sampled; the poses come back through a pinned double buffer behind an event, not a stream
@@ -272,6 +274,8 @@ def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed
     of the poses on the scoring thread, and a batch that fails it is sampled again the checked way (which is where
     precision="auto" falls back to the bf16-range mode).  At most two batches are in flight."""
     gkw = {} if guidance_scale is None else {"guidance_scale": float(guidance_scale)}      # (None: the trainer is called as before)
+    if steps is not None or solver != "ddim":
+        gkw.update(steps=steps, spacing=spacing, solver=solver)
     ids = list_clips(root)
     if limit is not None:
         ids = ids[:int(limit)]
@@ -432,6 +436,9 @@ def main(argv=None):
                                                    "module.motion_encoder.*) and --sync (every key); omitted = seeded synthetic weights")
     ap.add_argument("--diversity_seed", type=int, default=0)
     ap.add_argument("--guidance_scale", type=float, default=None, help="classifier-free guidance scale of the sampling loops (omitted: no guidance)")
+    ap.add_argument("--steps", type=int, default=None, help="sample on this many of the schedule's timesteps (omitted: all of them)")
+    ap.add_argument("--spacing", default="uniform", choices=["uniform", "logsnr"], help="how --steps picks them (use logsnr with dpmpp2m)")
+    ap.add_argument("--solver", default="ddim", choices=["ddim", "dpmpp2m"], help="first-order DDIM or the second-order multistep update")
     ap.add_argument("--sync", action="store_true", help="also M2SNet's synchronisation score of the sampled poses against the music "
                                                         "(m2snet.py; every entry of --m2snet, or seeded synthetic weights)")
     args = ap.parse_args(argv)
@@ -468,7 +475,8 @@ def main(argv=None):
             m2s = M2SNet(dev).load_state_dict(synthetic_m2snet_state_dict())
             print("--sync without --m2snet: M2SNet has seeded synthetic weights, so the m2s_* scores only check the pipeline")
     r = evaluate_dataset(tr, args.data_root, 26, args.batch_size, args.limit, args.seed, args.smooth, motion_encoder=menc,
-                         diversity_seed=args.diversity_seed, m2snet=m2s, guidance_scale=args.guidance_scale)
+                         diversity_seed=args.diversity_seed, m2snet=m2s, guidance_scale=args.guidance_scale,
+                         steps=args.steps, spacing=args.spacing, solver=args.solver)
     print(f"{r['clips']} clips in {r['seconds']:.2f} s = {r['frames_per_s']:.0f} frames/s")
     return 0
 

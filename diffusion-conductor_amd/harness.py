@@ -61,7 +61,15 @@ class DDPMTrainer(object):
         self.encoder.load_state_dict(checkpoint["encoder"], strict=False)
         return checkpoint.get("ep", 0), checkpoint.get("total_it", 0)
 
-    def _sample_local(self, mel, noise, dim_pose, idxs, smooth=None, guidance_scale=None):
+    @staticmethod
+    def _solver_kwargs(steps, spacing, solver):
+        """The keywords of ddim_sample_loop for a loop on a sub-sequence of timesteps; none when the defaults were left (the
+        loop is then called as before)."""
+        if steps is None and solver == "ddim":
+            return {}
+        return {"steps": steps, "spacing": spacing, "solver": solver}
+
+    def _sample_local(self, mel, noise, dim_pose, idxs, smooth=None, guidance_scale=None, skw={}):
         xf_proj, xf_out = self.encoder.encode_music(mel, self.device)
         B, T = mel.shape[0], xf_proj.shape[1]
         try:
@@ -69,7 +77,7 @@ class DDPMTrainer(object):
                 self.encoder, (B, T, dim_pose), noise=noise, clip_denoised=False, progress=False,
                 model_kwargs={"xf_proj": xf_proj, "xf_out": xf_out,
                               "length": torch.LongTensor([T] * B)},
-                idxs=idxs, smooth=smooth, guidance_scale=guidance_scale)
+                idxs=idxs, smooth=smooth, guidance_scale=guidance_scale, **skw)
         except FloatingPointError:
             # The loop's numeric check failed.  If the music features themselves are not finite, the fp16-plane MusicEncoder
             # overflowed (an activation beyond 65504; the reference's mel is normalised to [0, 1], so this takes unusual input):
@@ -80,15 +88,19 @@ class DDPMTrainer(object):
             nat = getattr(self.encoder, "_native", None)
             if nat is not None:
                 nat.set_encoder_format("split")
-            return self._sample_local(mel, noise, dim_pose, idxs, smooth, guidance_scale)
+            return self._sample_local(mel, noise, dim_pose, idxs, smooth, guidance_scale, skw)
 
     def generate_music_motion(self, music_mel, dim_pose, batch_size=1024, idxs=[], noise=None, seed=None, smooth=None,
-                              guidance_scale=None):
+                              guidance_scale=None, steps=None, spacing="uniform", solver="ddim"):
         """music_mel: np.ndarray/tensor [5400,128] (reference) or [B,5400,128] -> tensor [B,1800,dim_pose].
         smooth: None, or the Savitzky-Golay kernel size (order 5) tools/visualization.py:126 smooths the keypoints with - applied
         by the sampling loop's final write.
         guidance_scale: None, or the classifier-free guidance scale of the loop (GaussianDiffusion.ddim_sample_loop; each rank of a
-        sharded run builds the unconditional shadows of its own clips)."""
+        sharded run builds the unconditional shadows of its own clips).
+        steps, spacing, solver: sample on `steps` of the schedule's timesteps picked by `spacing`, with the first-order update
+        ("ddim") or the second-order multistep one ("dpmpp2m"; GaussianDiffusion.ddim_sample_loop - `idxs` then count that loop's
+        iterations).  Left at their defaults the loop walks every timestep, as before.  Not sharded over the ranks of a group yet."""
+        skw = self._solver_kwargs(steps, spacing, solver)
         mel = torch.as_tensor(np.asarray(music_mel) if not torch.is_tensor(music_mel) else music_mel)
         if mel.dim() == 2:
             mel = mel.unsqueeze(0)
@@ -100,6 +112,8 @@ class DDPMTrainer(object):
             mel = mel.to(self.device, dtype=torch.float32)
         B, T = mel.shape[0], (mel.shape[1] - 1) // 3 + 1       # frames encode_music produces (MusicEncoder pools time by 3)
         _, world = dist_info()
+        if skw and world > 1:
+            raise NotImplementedError("steps= / solver= are not sharded over the ranks of a torch.distributed group yet")
         grouped = torch.distributed.is_available() and torch.distributed.is_initialized()     # a world-size-1 group still gathers
         if noise is None and (seed is not None or world > 1):
             # x_T for the WHOLE batch from one generator, sliced per shard: with every rank drawing from its own default
@@ -120,12 +134,12 @@ class DDPMTrainer(object):
         sm = (int(smooth), 5) if smooth else None
         with torch.no_grad():
             if not grouped or len(idxs):
-                return self._sample_local(mel, noise, dim_pose, idxs, sm, guidance_scale)
-            return sharded_sample(lambda m, n: self._sample_local(m, n, dim_pose, [], sm, guidance_scale), mel, noise, out_shape=(T, dim_pose),
+                return self._sample_local(mel, noise, dim_pose, idxs, sm, guidance_scale, skw)
+            return sharded_sample(lambda m, n: self._sample_local(m, n, dim_pose, [], sm, guidance_scale, skw), mel, noise, out_shape=(T, dim_pose),
                                   device=self.device)
 
     def generate_long_music_motion(self, music_mel, dim_pose, overlap=LONG_OVERLAP, noise=None, seed=None, smooth=None, window=None,
-                                   guidance_scale=None):
+                                   guidance_scale=None, steps=None, spacing="uniform", solver="ddim"):
         """Conduct music LONGER than one window: music_mel [Tm,128] or [B,Tm,128] (pieces of one length), Tm at least one window
         (3 * window mel frames; ValueError below that - generate_music_motion serves those) -> tensor [B, L, dim_pose] with
         L = (Tm-1)//3 + 1.
@@ -144,7 +158,7 @@ class DDPMTrainer(object):
 
         `overlap` (frames, default LONG_OVERLAP = 300: 10 s); `smooth`: the Savitzky-Golay kernel size (order 5), applied ONCE
         over the whole piece with dc_savgol_filter (per window it would break the seams).  Every window runs the same captured
-        graph (the first with an all-zero mask) - also with `guidance_scale` (classifier-free guidance of every window's loop).  Not built: sharding pieces over the ranks of a torch.distributed group."""
+        graph (the first with an all-zero mask) - also with `guidance_scale` (classifier-free guidance of every window's loop) and with `steps`, `spacing`, `solver` (every window's loop on that sub-sequence of timesteps, generate_music_motion; the solver's table carries the known slots and its last step lands on abar = 1, so the seams stay exact).  Not built: sharding pieces over the ranks of a torch.distributed group."""
         from . import native
         _, world = dist_info()
         if world > 1:
@@ -182,7 +196,8 @@ class DDPMTrainer(object):
                 out[:, s:s + T] = self.diffusion.ddim_sample_loop(
                     self.encoder, (B, T, dim_pose), noise=x_T, clip_denoised=False, progress=False,
                     model_kwargs={"xf_proj": xf_proj[k], "xf_out": xf_out[k], "length": length},
-                    known=out[:, s:s + T].contiguous(), known_mask=mask, known_noise=x_T, guidance_scale=guidance_scale)
+                    known=out[:, s:s + T].contiguous(), known_mask=mask, known_noise=x_T, guidance_scale=guidance_scale,
+                    **self._solver_kwargs(steps, spacing, solver))
             if smooth:
                 out = native.savgol_filter(out, int(smooth), 5)
         return out

@@ -31,10 +31,13 @@ EXPORTS = [
     "dc_sampler_set_conditioning_guided", "dc_sampler_set_guidance_scale",
     "dc_m2snet_create", "dc_m2snet_destroy", "dc_m2snet_set_param", "dc_m2snet_finalize", "dc_m2snet_encode_music", "dc_m2snet_fuse",
     "dc_m2snet_score",
+    "dc_solver_table", "dc_sampler_solver_loop", "dc_sampler_solver_profile_loop",
 ]
 
 UPDATE_CLIP_DENOISED, UPDATE_EPSILON = 1, 2          # flags of dc_sampler_ddim_loop_ex
 STATUS_NONFINITE, STATUS_F16_SATURATED, STATUS_TIMEOUT = 1, 2, 4        # bits of dc_sampler_status
+SOLVER_ROW = 12                                       # DC_SOLVER_ROW: floats per row of dc_solver_table
+SOLVER_ORDER = {"ddim": 1, "dpmpp2m": 2}              # solver= of the Python surfaces -> order of dc_solver_table
 
 
 class DcConfig(C.Structure):
@@ -135,6 +138,11 @@ def lib():
     L.dc_sampler_ddim_loop_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, fp, C.c_int32, C.c_void_p, ip, C.c_int32,
                                           C.c_void_p, C.c_void_p]
     L.dc_ddim_coefficients_known.argtypes = [C.c_int32, dp, C.c_float, fp, fp]
+    L.dc_solver_table.argtypes = [C.c_int32, dp, ip, C.c_int32, C.c_float, C.c_int32, fp, fp]
+    L.dc_sampler_solver_loop.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, ip, fp, C.c_int32, C.c_void_p, ip, C.c_int32,
+                                         C.c_void_p, C.c_void_p]
+    L.dc_sampler_solver_profile_loop.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, ip, fp, C.c_int32, fp, ip, C.c_int32,
+                                                 C.c_void_p]
     L.dc_sampler_set_known.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.dc_sampler_set_conditioning_guided.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, ip, C.c_int32, C.c_int32, fp, fp, C.c_void_p]
     L.dc_sampler_set_guidance_scale.argtypes = [C.c_void_p, C.c_float]
@@ -213,6 +221,18 @@ def ddim_coefficients_known(alphas_cumprod: np.ndarray, eta=0.0):
     _check(lib().dc_ddim_coefficients_known(ac.shape[0], ac.ctypes.data_as(C.POINTER(C.c_double)), C.c_float(float(eta)), _fptr(out),
                                             _fptr(start)))
     return out, start
+
+
+def solver_table(alphas_cumprod: np.ndarray, timesteps, eta=0.0, order=1):
+    """dc_solver_table: ([n, SOLVER_ROW] rows of a loop over `timesteps` - a strictly decreasing sub-sequence of the training
+    schedule `alphas_cumprod` -, the loop's starting pair [2]).  Slots 0..7 are ddim_coefficients_known's on the sub-schedule, slot 8
+    the history coefficient of the second-order multistep update (order 2; 0 at order 1).  DcError for a bad list, order or eta."""
+    ac = np.ascontiguousarray(alphas_cumprod, np.float64)
+    ts = np.ascontiguousarray(np.asarray(timesteps).reshape(-1), np.int32)
+    rows, start = np.zeros((max(ts.shape[0], 1), SOLVER_ROW), np.float32), np.empty(2, np.float32)
+    _check(lib().dc_solver_table(ac.shape[0], ac.ctypes.data_as(C.POINTER(C.c_double)), _iptr(ts), ts.shape[0], C.c_float(float(eta)),
+                                 int(order), _fptr(rows), _fptr(start)))
+    return rows, start
 
 
 def savgol_coefficients(window: int, order: int) -> np.ndarray:
@@ -457,6 +477,47 @@ class NativeSampler:
             _check(lib().dc_sampler_ddim_loop_ex(self._h, noise.data_ptr(), out.data_ptr(), S, _fptr(coef), int(flags), zp, sip,
                                                  len(si), snp, self._stream()))
         return out, snaps
+
+    def solver_loop(self, noise, timesteps, rows, snap_iters=(), flags=0, step_noise=None, noise_seed=None):
+        """dc_sampler_solver_loop: ddim_loop on the caller's `timesteps` [n] (strictly decreasing, < max_timesteps) and `rows`
+        [n, SOLVER_ROW] of solver_table; step_noise is [n, B, T, P] and snap_iters count this loop's iterations."""
+        import torch
+        assert noise.is_cuda and noise.dtype == torch.float32 and noise.is_contiguous()
+        assert tuple(noise.shape) == (self.B, self.T, self.cfg.input_feats)
+        ts, rows, si, n = self._solver_args(timesteps, rows, snap_iters)
+        out = torch.empty_like(noise)
+        snaps = torch.empty((len(si),) + tuple(noise.shape), dtype=torch.float32, device=noise.device) if len(si) else None
+        zp = None
+        if step_noise is not None:
+            assert step_noise.is_cuda and step_noise.dtype == torch.float32 and step_noise.is_contiguous()
+            assert tuple(step_noise.shape) == (n,) + tuple(noise.shape)
+            zp = step_noise.data_ptr()
+        elif noise_seed is not None:
+            seed, first = noise_seed if isinstance(noise_seed, (tuple, list)) else (noise_seed, 0)
+            _check(lib().dc_sampler_set_step_noise_seed_at(self._h, C.c_uint64(int(seed) & (2 ** 64 - 1)), C.c_uint64(int(first))))
+        _check(lib().dc_sampler_solver_loop(self._h, noise.data_ptr(), out.data_ptr(), n, _iptr(ts), _fptr(rows), int(flags), zp,
+                                            _iptr(si) if len(si) else None, len(si), snaps.data_ptr() if snaps is not None else None,
+                                            self._stream()))
+        return out, snaps
+
+    @staticmethod
+    def _solver_args(timesteps, rows, snap_iters=()):
+        ts = np.ascontiguousarray(np.asarray(timesteps).reshape(-1), np.int32)
+        rows = np.ascontiguousarray(rows, np.float32)
+        assert rows.shape == (ts.shape[0], SOLVER_ROW), f"rows must be {(ts.shape[0], SOLVER_ROW)}: native.solver_table"
+        return ts, rows, np.ascontiguousarray(np.asarray(list(snap_iters), np.int32)), int(ts.shape[0])
+
+    def solver_profile_loop(self, noise, timesteps, rows, flags=0):
+        """profile_loop for a loop over `timesteps` / `rows` (dc_sampler_solver_profile_loop)."""
+        import torch
+        ts, rows, _, n = self._solver_args(timesteps, rows)
+        nk = lib().dc_kernel_count()
+        ms, cnt = np.zeros(nk, np.float32), np.zeros(nk, np.int32)
+        out = torch.empty_like(noise)
+        _check(lib().dc_sampler_solver_profile_loop(self._h, noise.data_ptr(), out.data_ptr(), n, _iptr(ts), _fptr(rows), int(flags),
+                                                    _fptr(ms), _iptr(cnt), nk, self._stream()))
+        names = [lib().dc_kernel_name(i).decode() for i in range(nk)]
+        return {names[i]: (float(ms[i]), int(cnt[i])) for i in range(nk)}, out
 
     def set_known(self, known=None, mask=None, noise=None):
         """dc_sampler_set_known: the following loops hold the elements whose `mask` is nonzero at sqrt(abar) known + sqrt(1 - abar) noise

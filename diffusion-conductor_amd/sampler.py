@@ -55,6 +55,37 @@ def betas_for_alpha_bar(num_diffusion_timesteps, alpha_bar, max_beta=0.999):
     return np.array(betas)
 
 
+def spaced_timesteps(alphas_cumprod, n, spacing="uniform"):
+    """A decreasing list of at most `n` timesteps of the training schedule `alphas_cumprod` [S] to sample on (no counterpart in the
+    reference, whose loops walk every timestep; improved-diffusion's SpacedDiffusion picks such lists).  It always starts at S - 1.
+    `spacing`:
+      "uniform"  round(k (S - 1) / (n - 1)), k = 0 .. n-1: equal strides in the timestep number, both ends included.  On a linear
+                 beta schedule the last stride then spans most of the log-SNR range (1000 steps, n = 25: 3.6 units of lambda out
+                 of 9.6), and the second-order solver ("dpmpp2m"), whose error constants assume comparable strides in lambda, is
+                 WORSE than DDIM below about 50 steps on the closed-form model of tests/test_host_solver.py.  Use it with "ddim".
+      "logsnr"   n targets equally spaced in lambda = 1/2 ln(abar / (1 - abar)) between lambda(abar_{S-1}) and lambda(abar_0), each
+                 replaced by the nearest timestep, duplicates dropped (the list can be shorter than n).  The spacing the
+                 second-order solver is analysed for.
+    n = 1 gives [S - 1]; n = S the full sequence S-1 .. 0 with either spacing."""
+    ac = np.asarray(alphas_cumprod, np.float64).reshape(-1)
+    S, n = int(ac.shape[0]), int(n)
+    if not 1 <= n <= S:
+        raise ValueError(f"steps must be in [1, {S}], got {n}")
+    if spacing not in ("uniform", "logsnr"):
+        raise ValueError(f"spacing must be 'uniform' or 'logsnr', got {spacing!r}")
+    if n == 1:
+        return [S - 1]
+    if n == S:
+        return list(range(S - 1, -1, -1))
+    if spacing == "uniform":
+        ts = {int(math.floor(k * (S - 1) / (n - 1) + 0.5)) for k in range(n)}
+    else:
+        lam = 0.5 * np.log(ac / (1.0 - ac))
+        targets = np.linspace(lam[S - 1], lam[0], n)
+        ts = {int(t) for t in np.abs(lam[None, :] - targets[:, None]).argmin(axis=1)}
+    return sorted(ts, reverse=True)
+
+
 class ModelMeanType(enum.Enum):
     PREVIOUS_X = enum.auto()
     START_X = enum.auto()
@@ -317,16 +348,42 @@ class GaussianDiffusion:
         if not math.isfinite(float(guidance_scale)):
             raise ValueError(f"guidance_scale must be finite, got {guidance_scale!r}")
 
+    def _solver_timesteps(self, model, steps, spacing, timesteps, solver, eta, denoised_fn, cond_fn, stepped=False):
+        """The list of a loop on a sub-sequence (steps= / timesteps= / solver=), or None when none of them was given (today's loop).
+        Such a loop runs natively only: ValueError where the call would step through ddim_sample, as for guidance_scale=."""
+        if steps is None and timesteps is None and solver == "ddim":
+            return None
+        if solver not in native.SOLVER_ORDER:
+            raise ValueError(f"solver must be one of {sorted(native.SOLVER_ORDER)}, got {solver!r}")
+        why = ("the progressive generator" if stepped else "denoised_fn" if denoised_fn is not None else "cond_fn" if cond_fn is not None else
+               "the PREVIOUS_X parameterisation" if self.model_mean_type == ModelMeanType.PREVIOUS_X else
+               "a learned-variance model" if self.model_var_type in (ModelVarType.LEARNED, ModelVarType.LEARNED_RANGE) else
+               None if self._fast_path_ok(model, denoised_fn, cond_fn) else "this model / rescale_timesteps")
+        if why is not None:
+            raise ValueError(f"steps= / timesteps= / solver= run inside the native loop; {why} steps through ddim_sample, which walks "
+                             "every timestep with the first-order update")
+        if solver == "dpmpp2m" and float(eta) != 0.0:
+            raise ValueError("solver='dpmpp2m' is deterministic: eta must be 0")
+        if timesteps is None:
+            return spaced_timesteps(self.alphas_cumprod, self.num_timesteps if steps is None else steps, spacing)
+        ts = [int(t) for t in np.asarray(timesteps).reshape(-1)]
+        if steps is not None and int(steps) != len(ts):
+            raise ValueError(f"steps={steps} beside a list of {len(ts)} timesteps")
+        if not ts or any(not 0 <= t < self.num_timesteps for t in ts) or any(b >= a for a, b in zip(ts, ts[1:])):
+            raise ValueError(f"timesteps must be a strictly decreasing list inside [0, {self.num_timesteps})")
+        return ts
+
     def _native_loop(self, model, img, mk, clip_denoised, eta, snap, step_noise, smooth=None, step_noise_seed=None, known=None,
-                     guidance_scale=None):
+                     guidance_scale=None, timesteps=None, solver="ddim"):
         """The captured loop on `model`'s sampler; returns (out, snaps).  Numeric health is checked once per call
-        (`model.check_numerics`): a non-finite x0 under precision="auto" falls back to the bf16-range mode in a fresh sampler."""
+        (`model.check_numerics`): a non-finite x0 under precision="auto" falls back to the bf16-range mode in a fresh sampler.
+        `timesteps` (a list) runs dc_sampler_solver_loop on it with `solver`'s table; None the loop over every timestep."""
         flags = (native.UPDATE_CLIP_DENOISED if clip_denoised else 0) | \
             (native.UPDATE_EPSILON if self.model_mean_type == ModelMeanType.EPSILON else 0)
         z, zseed = None, None
         if eta != 0.0:
             if step_noise is not None:
-                shape = (self.num_timesteps,) + tuple(img.shape)
+                shape = (self.num_timesteps if timesteps is None else len(timesteps),) + tuple(img.shape)
                 z = step_noise.to(device=img.device, dtype=th.float32).contiguous()
                 assert tuple(z.shape) == shape, f"step_noise must be {shape}"
             elif step_noise_seed is not None:
@@ -341,7 +398,10 @@ class GaussianDiffusion:
         # (An EPSILON model's final sample carries what the evaluations left in x_t: the library runs EVERY evaluation of such a loop on
         # split operands - in the fp16 and bf16 precisions, linear and (fp16) full attention alike (dc_ddim.h, dc_sampler_set_precise_tail; the bf16
         # precision's split evaluations take the FiLM GEMM's operands in fp16).)
-        coef = self.native_coefficients(None if plain else eta) if known is None else self.native_coefficients_known(eta)
+        if timesteps is not None:      # (the rows carry the known slots: one table serves loops with and without known values)
+            coef = native.solver_table(self.alphas_cumprod, timesteps, eta, native.SOLVER_ORDER[solver])[0]
+        else:
+            coef = self.native_coefficients(None if plain else eta) if known is None else self.native_coefficients_known(eta)
         retried = False
         while True:
             if guidance_scale is None:
@@ -351,7 +411,10 @@ class GaussianDiffusion:
                 nat.set_guidance_scale(guidance_scale)
             nat.set_smoothing(*(smooth if smooth else (0, 0)))
             nat.set_known(*(known if known is not None else (None, None, None)))
-            out, snaps = nat.ddim_loop(img, coef, snap, flags, z, zseed)
+            if timesteps is not None:
+                out, snaps = nat.solver_loop(img, timesteps, coef, snap, flags, z, zseed)
+            else:
+                out, snaps = nat.ddim_loop(img, coef, snap, flags, z, zseed)
             if not getattr(model, "check_numerics", True):
                 return out, snaps
             st = nat.status()
@@ -370,9 +433,16 @@ class GaussianDiffusion:
     def ddim_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                          model_kwargs=None, device=None, progress=False, eta=0.0, idxs=[], step_noise=None, smooth=None,
                          step_noise_seed=None, known=None, known_mask=None, known_noise=None, known_noise_seed=None,
-                         guidance_scale=None):
+                         guidance_scale=None, steps=None, spacing="uniform", timesteps=None, solver="ddim"):
         """gaussian_diffusion.py:871-915.  Returns the final sample, or when `idxs` is non-empty a
         dict {iteration: sample} for the listed iterations plus {num_timesteps: final}.
+        `steps`, `spacing`, `timesteps`, `solver` (extension, native loop only; none given = today's loop over every timestep, bit for
+        bit): sample on a sub-sequence of the schedule's timesteps - `timesteps`, a strictly decreasing list, or `steps` of them picked
+        by spaced_timesteps(alphas_cumprod, steps, spacing) - with the first-order update (solver="ddim") or the second-order
+        multistep one (solver="dpmpp2m": DPM-Solver++ 2M on the predicted x0, eta = 0 only, no extra model evaluation; use
+        spacing="logsnr" with it, see spaced_timesteps).  The model sees the original timestep numbers.  `idxs` then count iterations
+        of that loop, the final key is len(timesteps), and `step_noise` is [n, B, T, P].  Neither exists in the reference.  ValueError
+        with denoised_fn, cond_fn, PREVIOUS_X or a learned variance (they step through ddim_sample), and for dpmpp2m with eta != 0.
         `step_noise` (extension, eta > 0): [S, B, T, P], the draw for iteration i in place of th.randn_like.
         `step_noise_seed` (extension, eta > 0, native loop only): seed of the library's own per-step draws, or (seed, first_element)
         for a shard that holds clips [lo, hi) of a larger batch (first_element = lo*T*P: the rows the whole batch's draw gives them).
@@ -389,6 +459,8 @@ class GaussianDiffusion:
         c + (w - 1)(c - u) (include/dc_ddim.h, dc_sampler_set_conditioning_guided; the reference trains for it, transformer.py:389,
         451-459, and never samples with it).  ValueError with denoised_fn, cond_fn, PREVIOUS_X or a learned variance."""
         self._check_guidance(model, guidance_scale, denoised_fn, cond_fn)
+        ts = self._solver_timesteps(model, steps, spacing, timesteps, solver, eta, denoised_fn, cond_fn)
+        n_iter = self.num_timesteps if ts is None else len(ts)
         self._refuse_epsilon_full_attention(model, eta)
         if self._fast_path_ok(model, denoised_fn, cond_fn):
             if device is None:
@@ -400,14 +472,14 @@ class GaussianDiffusion:
             if mk.get("xf_proj") is None or mk.get("xf_out") is None:
                 mk = dict(mk)
                 mk["xf_proj"], mk["xf_out"] = model.encode_music(mk["text"], device)
-            snap = sorted(int(i) for i in set(idxs) if 0 <= int(i) < self.num_timesteps)
+            snap = sorted(int(i) for i in set(idxs) if 0 <= int(i) < n_iter)
             kn = self._known_tensors(img, known, known_mask, known_noise, known_noise_seed)
             out, snaps = self._native_loop(model, img, mk, bool(clip_denoised), float(eta), snap, step_noise, smooth, step_noise_seed, kn,
-                                            guidance_scale)
+                                            guidance_scale, ts, solver)
             if len(idxs) == 0:
                 return out
             result = {it: snaps[k] for k, it in enumerate(snap)}
-            result[self.num_timesteps] = out
+            result[n_iter] = out
             return result
         if known is not None or known_mask is not None or known_noise is not None:
             raise NotImplementedError("known= / known_mask= are replaced inside the native loop's update; with host callbacks "
@@ -433,10 +505,12 @@ class GaussianDiffusion:
 
     def ddim_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None,
                                      cond_fn=None, model_kwargs=None, device=None, progress=False, eta=0.0,
-                                     step_noise=None, guidance_scale=None):
-        """gaussian_diffusion.py:917-965: yields {"sample","pred_xstart"} after every step.  `guidance_scale`: None only - this
-        generator steps through ddim_sample (ValueError otherwise; ddim_sample_loop guides inside the captured loop)."""
+                                     step_noise=None, guidance_scale=None, steps=None, spacing="uniform", timesteps=None, solver="ddim"):
+        """gaussian_diffusion.py:917-965: yields {"sample","pred_xstart"} after every step.  `guidance_scale`, `steps`, `timesteps`,
+        `solver`: the defaults only - this generator steps through ddim_sample (ValueError otherwise; ddim_sample_loop guides, and
+        samples on a sub-sequence, inside the captured loop)."""
         self._check_guidance(model, guidance_scale, denoised_fn, cond_fn, stepped=True)
+        self._solver_timesteps(model, steps, spacing, timesteps, solver, eta, denoised_fn, cond_fn, stepped=True)
         self._refuse_epsilon_full_attention(model, eta)
         if device is None:
             device = next(model.parameters()).device

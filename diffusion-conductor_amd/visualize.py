@@ -124,6 +124,9 @@ def make_parser():
                         help="conduct mels longer than one window (5400 frames = 60 s) whole, window by window around the frames "
                              "already generated (DDPMTrainer.generate_long_music_motion); without it only the first window is sampled")
     parser.add_argument('--precision', type=str, default="fp16", choices=["fp16", "mixed", "bf16x3", "bf16", "auto"])
+    parser.add_argument('--steps', type=int, default=None, help="sample on this many of the schedule's timesteps (omitted: all of them)")
+    parser.add_argument('--spacing', type=str, default="uniform", choices=["uniform", "logsnr"], help="how --steps picks them (use logsnr with dpmpp2m)")
+    parser.add_argument('--solver', type=str, default="ddim", choices=["ddim", "dpmpp2m"], help="first-order DDIM or the second-order multistep update")
     parser.add_argument('--guidance_scale', type=float, default=None,
                         help="classifier-free guidance scale of the sampling loops (omitted: no guidance, the reference's sampling)")
     return parser
@@ -145,6 +148,8 @@ def main(argv=None):
     trainer.eval_mode()
     trainer.to(opt.device)
     gkw = {} if args.guidance_scale is None else {"guidance_scale": args.guidance_scale}
+    if args.steps is not None or args.solver != "ddim":
+        gkw.update(steps=args.steps, spacing=args.spacing, solver=args.solver)
     with torch.no_grad():
         mel, names = load_mels(args.music_path)
         # [B, T, 26] on the device; --smooth: smooth_motion(kernel=19) (:126) happens in the loop's final write

@@ -109,6 +109,28 @@ DC_EXPORT int dc_ddim_coefficients_ex(int32_t num_steps, const double* h_alphas_
  * serves it as well. */
 DC_EXPORT int dc_ddim_coefficients_known(int32_t num_steps, const double* h_alphas_cumprod, float eta, float* h_coef8, float* h_start2);
 
+/* Sampling on a SUB-SEQUENCE of the checkpoint's timesteps, first or second order.  The reference has neither: its ddim_sample_loop
+ * walks every timestep of the schedule it was built with (models/gaussian_diffusion.py:943), and its only deterministic update is the
+ * first-order one of ddim_sample (:812-830).  h_timesteps int32 [n]: strictly decreasing, inside [0, n_train) - the numbers the model
+ * sees; h_alphas_cumprod fp64 [n_train] of the TRAINING schedule.  With a_i = abar[t_i] and a'_i = abar[t_{i+1}] (a'_{n-1} = 1: the
+ * last step lands on the clean sample), row i - DC_SOLVER_ROW floats, indexed by ITERATION - holds
+ *   h_rows[i][0..7]  dc_ddim_coefficients_known's slots with (abar_t, abar_{t-1}) replaced by (a_i, a'_i): the same fp32 roundings in
+ *                    the same order (one routine computes both), so h_timesteps = n_train-1 .. 0 gives that table's rows, reversed, bit
+ *                    for bit: the first-order update (:812-830) on the sub-schedule, what improved-diffusion calls SpacedDiffusion
+ *   h_rows[i][8]     kappa_i, the history coefficient of the second-order multistep update (DPM-Solver++ 2M, x0-prediction form):
+ *                      x_{i+1} = [first-order update] + kappa_i (x0_i - x0_{i-1}),     x0_i = the step's predicted x0;
+ *                      lambda(a) = 1/2 ln(a / (1 - a)),  h_i = lambda(a'_i) - lambda(a_i),  r_i = h_{i-1} / h_i,
+ *                      kappa_i = ( sqrt(a'_i) - sqrt(1 - a'_i) sqrt(a_i) / sqrt(1 - a_i) ) / (2 r_i)      (fp64, rounded once)
+ *                    nonzero only for order == 2 and 0 < i < n-1: the first step has no history, the last one is first order, so the
+ *                    final sample stays the model's own x0
+ *   h_rows[i][9..]   0
+ * h_start2 (may be NULL): sqrt(a_0), sqrt(1 - a_0), the level a loop around known values starts at.
+ * DC_ERR_INVALID: order outside {1, 2}; order 2 with eta != 0 (the multistep update is deterministic); n < 1; a list that is not
+ * strictly decreasing or leaves [0, n_train).  Host only. */
+#define DC_SOLVER_ROW 12
+DC_EXPORT int dc_solver_table(int32_t n_train, const double* h_alphas_cumprod, const int32_t* h_timesteps, int32_t n, float eta,
+                              int32_t order, float* h_rows, float* h_start2);
+
 /* Test hook: pack a row-major Linear weight W[n_out][k_in] (torch layout) into the
  * MFMA fragment-major bf16 image the kernels read (see DESIGN.md "weight image").
  * `chained` != 0 uses the accumulator-as-operand k order, 0 the natural k order.
@@ -232,6 +254,23 @@ DC_EXPORT int dc_sampler_ddim_loop(dc_sampler* s, const float* d_noise, float* d
 DC_EXPORT int dc_sampler_ddim_loop_ex(dc_sampler* s, const float* d_noise, float* d_out, int32_t num_steps, const float* h_coef8,
                             int32_t flags, const float* d_step_noise, const int32_t* h_snap_iters, int32_t n_snap,
                             float* d_snaps, void* stream);
+
+/* dc_sampler_ddim_loop_ex on the caller's timesteps and rows (dc_solver_table; no counterpart in the reference, see there):
+ * iteration i evaluates the model at h_timesteps[i] and updates with h_rows[i] - every per-step table of the loop is indexed by
+ * iteration, the timestep only selects the model's embedding.  n <= max_timesteps, every timestep < max_timesteps, strictly
+ * decreasing (DC_ERR_INVALID otherwise, before anything is enqueued).  Rows with a history coefficient (slot 8) run the second-order
+ * multistep update: the previous step's predicted x0 - after guidance, the EPSILON conversion and clipping - is kept in one more
+ * [B,T,P] fp32 buffer of the workspace, zeroed when the loop starts, read and rewritten in place by the update in the last layer's
+ * kernels, and carried across the graph replays of a long loop; the history term is added before known values are replaced.  Such rows need
+ * sigma = 0.  d_step_noise is [n,B,T,P]; snapshot iterations count iterations of this loop.  Known values, guidance, smoothing, the
+ * precise tail and DC_DISABLE_GRAPH apply as in dc_sampler_ddim_loop_ex; the hipGraph is keyed by (B, T, n, form) - another list of
+ * the same length replays it.  dc_sampler_solver_profile_loop is dc_sampler_profile_loop for such a loop. */
+DC_EXPORT int dc_sampler_solver_loop(dc_sampler* s, const float* d_noise, float* d_out, int32_t n, const int32_t* h_timesteps,
+                                     const float* h_rows, int32_t flags, const float* d_step_noise, const int32_t* h_snap_iters,
+                                     int32_t n_snap, float* d_snaps, void* stream);
+DC_EXPORT int dc_sampler_solver_profile_loop(dc_sampler* s, const float* d_noise, float* d_out, int32_t n, const int32_t* h_timesteps,
+                                             const float* h_rows, int32_t flags, float* h_ms, int32_t* h_count, int32_t n_kernels,
+                                             void* stream);
 
 /* Sampling around known values (no counterpart in the reference's DDIM loop; its ancestral p_sample has a pre_seq hook,
  * gaussian_diffusion.py:634-646, with fresh noise per step - not this).  d_known, d_mask, d_known_noise: fp32 [B,T,P] each, for the
