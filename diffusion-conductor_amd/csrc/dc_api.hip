@@ -110,7 +110,8 @@ struct dc_sampler : Formats {     // (set_precision(cfg.precision))
     // up to three parked ones for other batch shapes (a dataset's last, smaller batch; a service whose batch size varies): a shape
     // seen before replays its graph instead of paying a capture (tens of ms) every time the shape changes.  The workspace's
     // addresses are baked into every captured graph, so whatever re-allocates a buffer drops them all (drop_graph).
-    using GraphKey = std::tuple<int, int, int, int, unsigned long long>;
+    // (+ the period at which the takes of one music wrap their FiLM tile reads, takes_key_period: 0 without shared takes)
+    using GraphKey = std::tuple<int, int, int, int, unsigned long long, int>;
     std::vector<std::pair<GraphKey, hipGraphExec_t>> graphs;
     // DDIM update options of the loop being enqueued (dc_sampler_ddim_loop_ex) and the device status word
     int upd_flags = 0;              // DC_UPD_* of the loop being enqueued (incl. the internal NOISY / ZSTEP bits)
@@ -127,6 +128,7 @@ struct dc_sampler : Formats {     // (set_precision(cfg.precision))
     const float *known_val = nullptr, *known_mask = nullptr, *known_noise = nullptr;
     int known_B = 0, known_Tx = 0;            // the CALLER's clips (user_B()) and frames the tensors were set for ...
     bool known_guided = false;                // ... and whether that conditioning was guided: any other (B, T, guided) clears them
+    int known_takes = 1;                      // ... and its takes per music: the same clips in another take order are another geometry
     const float** d_kslot = nullptr;
     // Savitzky-Golay smoothing applied by the loop's final write (dc_sampler_set_smoothing; window 0 = off)
     int smooth_window = 0, smooth_order = 0, smooth_table_window = 0;     // (table_window: the hat matrix d_smooth_coef holds)
@@ -140,7 +142,15 @@ struct dc_sampler : Formats {     // (set_precision(cfg.precision))
     size_t cap_raw = 0;
     float *d_xf2_proj = nullptr, *d_xf2_out = nullptr;      // feature images [B][Tx][64] of the internal batch (second half: the null pair)
     size_t cap_xf2 = 0;
-    int user_B() const { return guided ? B / 2 : B; }       // clips of the caller's tensors
+    int user_B() const { return guided ? B / 2 : B; }       // clips of the caller's tensors (takes x the musics)
+    // Takes (dc_sampler_set_conditioning_takes): the conditional clips are `takes` runs of the same musics, take-major; the feature images of
+    // the internal batch live in d_xf2_* as they do for guidance
+    int takes = 1;
+    // guided takes: the operand image of a FiLM GEMM over one take + the null column (film_share: Gc + 1 groups) - the first Gc groups of
+    // d_pp, then its first shadow group.  (In d_pp itself group Gc is take 1's first group, and the GEMM reads its groups in order.)
+    float* d_pp_share = nullptr;
+    size_t cap_pp_share = 0;
+    const float* pp_last = nullptr;      // the operand image the last enqueued step's FiLM GEMM read (dc_sampler_status re-runs it)
     int last_film_groups = 0;       // groups of d_E the last enqueued step's FiLM GEMM wrote (dc_sampler_status scans no others)
 
     DcModel h_model_split{};     // fp16 precision: the same model with the layer stage images in their split form ([hi][lo][consts]): the loop's precise tail
@@ -777,7 +787,7 @@ unsigned long long form_key(const dc_sampler* s, const Switches& w) {
     k |= (s->l16_own ? 1ull : 0ull) << 24;
     k |= (unsigned long long)((s->clip_aligned + 1) & 3) << 25;
     // guided loops: another last-layer store, k_guided_update, and - bit 28 - the FiLM GEMM over the shared column's groups
-    k |= guided_key_bits(s->guided, s->guided && guided_film_groups(s->B, s->T, s->G, !s->split_film, w) < s->G);
+    k |= guided_key_bits(s->guided, s->guided && film_share(s->B, s->T, s->G, true, s->takes, !s->split_film, w).groups < s->G);
     return k;
 }
 
@@ -836,7 +846,12 @@ int enqueue_step(dc_sampler* s, hipStream_t st, const Step& c, const Switches& w
     if (f.g1_tiles) fa.bias_ft = s->h_model.film_b_g1, fa.bias16 = s->h_model.film_b16_g1;
     if (f.film_tail) fa.W16 = s->h_model.film_w16_tail;
     s->last_film_groups = f.film_groups;
-    fa.G = f.film_groups;       // (guided, shared column: the conditional half's groups + one for every shadow group; else G)
+    fa.G = f.film_groups;       // (film_share: one take's groups, + one for every shadow group of a guided step; nothing shared: G)
+    if (f.guided && f.film_period < f.film_wrap) {      // guided takes: one take's groups, then the null column
+        if (!s->d_pp_share || (size_t)f.film_groups > s->cap_pp_share) return fail(DC_ERR_INVALID, "internal: no operand image for the shared takes of a guided step");
+        fa.pp = s->d_pp_share;
+    }
+    s->pp_last = fa.pp;
     fa.clk = want_stamps ? s->d_stamps + 252 : nullptr;
     if (f.adapt) fa.rate_in = s->d_film_rate + 1024 * s->film_rate_parity, fa.rate_out = s->d_film_rate + 1024 * (s->film_rate_parity ^ 1);
     fa.iter_base = iter_base;
@@ -852,7 +867,7 @@ int enqueue_step(dc_sampler* s, hipStream_t st, const Step& c, const Switches& w
     DcLayerArgs la{};
     la.dm = dmod, la.hbuf = s->d_h, la.E = s->d_E, la.NT = s->NT, la.recs = s->d_recs, la.length = s->d_length, la.xin = c.x_src, la.xout = c.x_dst;
     la.out_mode = (c.loop_mode && !f.guided) ? 1 : 0, la.coef_cur = coef_src, la.snap_cur = snap_src, la.snaps = s->d_snaps, la.iter_base = iter_base;
-    la.M = M, la.T = T, la.G = G, la.B = B, la.Tx = Tx, la.e_groups = f.film_groups;
+    la.M = M, la.T = T, la.G = G, la.B = B, la.Tx = Tx, la.e_groups = f.film_groups, la.e_period = f.film_period, la.e_wrap = f.film_wrap, la.e_magic = film_magic(f.film_period, f.film_wrap);
     if (f.guided) la.xout = s->d_raw;      // the raw output of all 2 B clips; k_guided_update (below) combines the halves and updates x
     la.upd = DcUpdate{s->d_zslot, s->d_status, (c.loop_mode ? s->upd_flags : 0) | f.upd_flags, folded ? graph_step : -1, nullptr, s->d_kslot, s->d_x0_prev};
     DcLayerArgs la_stamps = la;      // (stage stamps of layer 3 in diagnostic builds: DcUpdate::stamps carries the buffer)
@@ -922,7 +937,8 @@ int loop_common(dc_sampler* s, const float* d_noise, float* d_out, int S, const 
                                         "use linear attention, or eta > 0");
     // known values (dc_sampler_set_known) serve the loops of the geometry they were set for; another (B, T) clears them
     // (the caller's geometry: on a guided conditioning B is the internal batch, twice the clips the known tensors hold)
-    if (s->known_mask && (s->known_B != s->user_B() || s->known_Tx != s->Tx || s->known_guided != s->guided))
+    // (... and the takes count: the same number of clips in another take order is another geometry)
+    if (s->known_mask && (s->known_B != s->user_B() || s->known_Tx != s->Tx || s->known_guided != s->guided || s->known_takes != s->takes))
         s->known_val = s->known_mask = s->known_noise = nullptr;
     const bool known = s->known_mask != nullptr;
     if (known && S > 1 && !(h_coef[5] > 0.f))      // (the first iteration's row: abar_prev < 1 there)
@@ -1022,7 +1038,7 @@ int loop_common(dc_sampler* s, const float* d_noise, float* d_out, int S, const 
         for (int i = 0; i < n; ++i) {
             Step c;
             c.loop_mode = true, c.x_src = c.x_dst = s->d_x, c.graph_step = graph ? i : -1, c.split = i >= n - split_n, c.g1_loop = tail > 0;
-            c.next_plain = i + 1 < n - split_n, c.embedded = embedded, c.profile = profile, c.known = known, c.guided = s->guided;
+            c.next_plain = i + 1 < n - split_n, c.embedded = embedded, c.profile = profile, c.known = known, c.guided = s->guided, c.takes = s->takes;
             StepDone d;
             if (int rc = enqueue_step(s, st, c, sw, &d)) return rc;
             embedded = d.embedded_next, folded = d.folded;
@@ -1041,7 +1057,8 @@ int loop_common(dc_sampler* s, const float* d_noise, float* d_out, int S, const 
         // (g1 bit: the plain evaluations of a loop WITH a tail read G' scale tiles, those of a loop without one G' - 1 tiles - two
         // different captures of the same part-0 graph when S > 64)
         const unsigned long long fk = form_key(s, sw) | ((unsigned long long)tail_here << 40) | ((tail > 0 ? 1ull : 0ull) << 39);
-        const dc_sampler::GraphKey key{s->B, s->T, s->Tx, K, fk};
+        const int key_period = takes_key_period(film_share(s->B, s->T, s->G, s->guided, s->takes, !s->split_film, sw));
+        const dc_sampler::GraphKey key{s->B, s->T, s->Tx, K, fk, key_period};
         auto& gs = s->graphs;
         if (gs.empty() || gs.back().first != key) {
             if (gs.size() > 3) {        // the current graph is parked: the oldest parked one makes room
@@ -1167,6 +1184,9 @@ int denoise(dc_sampler* s, const float* d_x, const int32_t* h_timesteps, float* 
     if (s->guided)
         return fail(DC_ERR_INVALID, "the conditioning is guided (dc_sampler_set_conditioning_guided): single evaluations are not guided - per-clip "
                                     "timesteps break the unconditional half's shared FiLM column; call dc_sampler_set_conditioning and combine on your side");
+    if (s->takes > 1)
+        return fail(DC_ERR_INVALID, "the conditioning holds %d takes per music (dc_sampler_set_conditioning_takes): single evaluations take per-clip "
+                                    "timesteps, which break the takes' shared FiLM tiles; call dc_sampler_set_conditioning on tiled features", s->takes);
     for (int b = 0; b < s->B; ++b)
         if (h_timesteps[b] < 0 || h_timesteps[b] >= s->cfg.max_timesteps)
             return fail(DC_ERR_INVALID, "timestep %d outside [0,%d)", h_timesteps[b], s->cfg.max_timesteps);
@@ -1343,7 +1363,7 @@ void dc_sampler_destroy(dc_sampler* s) {
                     s->d_a_ca, s->d_x, s->d_snaps, s->d_recs_ca, s->d_nh_hi, s->d_nh_lo, s->d_iter,
                     s->d_t_clip, s->d_snap_cur, s->d_t_of_iter, s->d_snap_of_iter, s->d_coef_cur, s->d_x0_prev, s->d_coef_of_iter,
                     s->d_kv_sa[0], s->d_kv_sa[1], s->d_kv_ca, s->d_stamps, s->d_film_rate, s->d_status, s->d_smooth_coef, s->d_zslot, s->d_kslot, s->d_zstep, s->d_a_ca16, s->d_gran,
-                    s->d_wslot, s->d_raw, s->d_xf2_proj, s->d_xf2_out};
+                    s->d_wslot, s->d_raw, s->d_xf2_proj, s->d_xf2_out, s->d_pp_share};
     for (void* p : ptrs)
         if (p) hipFree(p);
     dc_music_destroy(s->music);
@@ -1425,6 +1445,7 @@ static int set_conditioning(dc_sampler* s, const float* d_xf_proj, const float* 
     HIP_TRY(hipSetDevice(s->cfg.device));
     int rc;
     if ((rc = ensure_workspace(s, B, T))) return rc;
+    s->pp_last = nullptr;      // (no FiLM GEMM has run on this conditioning yet)
     std::vector<int> len(B, T);
     if (h_length)
         for (int b = 0; b < B; ++b) {
@@ -1480,59 +1501,99 @@ static int set_conditioning(dc_sampler* s, const float* d_xf_proj, const float* 
 int dc_sampler_set_conditioning(dc_sampler* s, const float* d_xf_proj, const float* d_xf_out, const int32_t* h_length,
                                 int32_t B, int32_t T, void* stream) {
     const int rc = set_conditioning(s, d_xf_proj, d_xf_out, h_length, B, T, stream);
-    // a plain conditioning switches guidance off (a failed call on a guided sampler leaves no conditioning set: the internal batch
-    // may be half rebuilt)
-    if (s && s->guided) s->guided = false, s->cond_set = rc == DC_OK;
-    return rc;      // (known values set on the guided conditioning are dropped by the next loop: known_guided)
+    // a plain conditioning switches guidance and takes off (a failed call on such a sampler leaves no conditioning set: the internal
+    // batch may be half rebuilt)
+    if (s && (s->guided || s->takes > 1)) s->guided = false, s->takes = 1, s->cond_set = rc == DC_OK;
+    return rc;      // (known values set on the guided / takes conditioning are dropped by the next loop: known_guided, known_takes)
 }
 
-// Classifier-free guidance.  The reference trains its denoiser for it - MotionTransformer.encode_music (models/transformer.py:389,451-459)
+// The conditionings whose internal batch is built here: `takes` runs of the caller's B clips (take-major), then - guided - as many
+// unconditional shadows, every frame carrying the null pair.  takes = 1 guided is dc_sampler_set_conditioning_guided.
+// Classifier-free guidance: the reference trains its denoiser for it - MotionTransformer.encode_music (models/transformer.py:389,451-459)
 // zeroes a token's music features with probability cond_mask_prob = 0.1 before `proj` - and has no sampling counterpart.
+static int set_conditioning_images(dc_sampler* s, const float* d_xf_proj, const float* d_xf_out, const int32_t* h_length, int32_t B,
+                                   int32_t T, int32_t takes, const float* h_null_proj, const float* h_null_out, void* stream) {
+    const bool guided = h_null_proj != nullptr;
+    if (!d_xf_proj || !d_xf_out || B < 1 || T < 1) return fail(DC_ERR_INVALID, "bad conditioning arguments (need B >= 1, T >= 1)");
+    const long long Bi = (long long)B * takes * (guided ? 2 : 1);      // internal clips
+    if (Bi > (1 << 30)) return fail(DC_ERR_INVALID, "B=%d, takes=%d: the internal batch holds %lld clips", B, takes, Bi);
+    if (s->host_only) return fail(DC_ERR_NO_DEVICE, "host-only sampler (sanitizer build without a device)");
+    HIP_TRY(hipSetDevice(s->cfg.device));
+    s->guided = false, s->takes = 1, s->cond_set = false;
+    // the feature images of the internal clips: the caller's B, `takes` times, then every frame of the shadows carrying the null pair
+    const size_t rows = (size_t)B * T, crows = rows * takes, irows = (size_t)Bi * T;
+    int rc;
+    if (irows * 64 > s->cap_xf2) {
+        s->cap_xf2 = 0;
+        if ((rc = dev_alloc(s, s->d_xf2_proj, irows * 64 * 4))) return rc;
+        if ((rc = dev_alloc(s, s->d_xf2_out, irows * 64 * 4))) return rc;
+        s->cap_xf2 = irows * 64;
+    }
+    hipStream_t user = (hipStream_t)stream;
+    for (int j = 0; j < takes; ++j) {
+        HIP_TRY(hipMemcpyAsync(s->d_xf2_proj + (size_t)j * rows * 64, d_xf_proj, rows * 64 * 4, hipMemcpyDeviceToDevice, user));
+        HIP_TRY(hipMemcpyAsync(s->d_xf2_out + (size_t)j * rows * 64, d_xf_out, rows * 64 * 4, hipMemcpyDeviceToDevice, user));
+    }
+    if (guided) {
+        DcNull64 np{}, no{};
+        memcpy(np.v, h_null_proj, sizeof np.v);
+        memcpy(no.v, h_null_out, sizeof no.v);
+        HIP_TRY(dc_launch_fill_rows64(user, s->d_xf2_proj + crows * 64, crows, np));
+        HIP_TRY(dc_launch_fill_rows64(user, s->d_xf2_out + crows * 64, crows, no));
+    }
+    std::vector<int32_t> len2;
+    if (h_length)
+        for (long long j = 0; j < Bi / B; ++j) len2.insert(len2.end(), h_length, h_length + B);
+    if ((rc = set_conditioning(s, s->d_xf2_proj, s->d_xf2_out, h_length ? len2.data() : nullptr, (int)Bi, T, stream))) return rc;
+    s->cond_set = false;
+    if (guided) {
+        const size_t raw = irows * s->cfg.input_feats;
+        if (raw > s->cap_raw) {
+            drop_graph(s);          // (the buffer's address is an argument of the captured launches)
+            s->cap_raw = 0;
+            if ((rc = dev_alloc(s, s->d_raw, raw * 4))) return rc;
+            s->cap_raw = raw;
+        }
+        if (!s->d_wslot && (rc = dev_alloc(s, s->d_wslot, 16))) return rc;
+        s->guide_w = 1.f;
+        // guided takes: the FiLM GEMM over one take and the null column reads an operand image of its own (whatever the switches say
+        // now: they are read again by every loop) - behind the pre-pass, which the caller's stream has been ordered after
+        const FilmShare sh = film_share(s->B, s->T, s->G, true, takes, !s->split_film, Switches{});
+        if (sh.period < sh.wrap) {
+            const size_t gbytes = (size_t)32 * 64 * 8 * 4;      // one group of d_pp (ensure_workspace)
+            if ((size_t)sh.groups > s->cap_pp_share) {
+                drop_graph(s);
+                s->cap_pp_share = 0;
+                if ((rc = dev_alloc(s, s->d_pp_share, (size_t)sh.groups * gbytes))) return rc;
+                s->cap_pp_share = (size_t)sh.groups;
+            }
+            char* dst = reinterpret_cast<char*>(s->d_pp_share);
+            const char* src = reinterpret_cast<const char*>(s->d_pp);
+            HIP_TRY(hipMemcpyAsync(dst, src, (size_t)sh.period * gbytes, hipMemcpyDeviceToDevice, user));
+            HIP_TRY(hipMemcpyAsync(dst + (size_t)sh.period * gbytes, src + (size_t)sh.wrap * gbytes, gbytes, hipMemcpyDeviceToDevice, user));
+        }
+    }
+    s->guided = guided;
+    s->takes = takes;
+    s->cond_set = true;
+    return DC_OK;
+}
+
 int dc_sampler_set_conditioning_guided(dc_sampler* s, const float* d_xf_proj, const float* d_xf_out, const int32_t* h_length, int32_t B,
                                        int32_t T, const float* h_null_proj, const float* h_null_out, void* stream) {
     if (!s || !s->finalized) return fail(DC_ERR_INVALID, "sampler not finalized");
     if (!h_null_proj || !h_null_out) return fail(DC_ERR_INVALID, "guided conditioning: the null pair (h_null_proj[64], h_null_out[64]) is NULL");
-    if (!d_xf_proj || !d_xf_out || B < 1 || T < 1) return fail(DC_ERR_INVALID, "bad conditioning arguments (need B >= 1, T >= 1)");
-    if (B > (1 << 29)) return fail(DC_ERR_INVALID, "B=%d: the guided batch holds 2 B clips", B);
-    if (s->host_only) return fail(DC_ERR_NO_DEVICE, "host-only sampler (sanitizer build without a device)");
-    HIP_TRY(hipSetDevice(s->cfg.device));
-    s->guided = false, s->cond_set = false;
-    // the feature images of the 2 B internal clips: the caller's B, then every frame of B shadows carrying the null pair
-    const size_t rows = (size_t)B * T;
-    int rc;
-    if (2 * rows * 64 > s->cap_xf2) {
-        s->cap_xf2 = 0;
-        if ((rc = dev_alloc(s, s->d_xf2_proj, 2 * rows * 64 * 4))) return rc;
-        if ((rc = dev_alloc(s, s->d_xf2_out, 2 * rows * 64 * 4))) return rc;
-        s->cap_xf2 = 2 * rows * 64;
-    }
-    DcNull64 np{}, no{};
-    memcpy(np.v, h_null_proj, sizeof np.v);
-    memcpy(no.v, h_null_out, sizeof no.v);
-    hipStream_t user = (hipStream_t)stream;
-    HIP_TRY(hipMemcpyAsync(s->d_xf2_proj, d_xf_proj, rows * 64 * 4, hipMemcpyDeviceToDevice, user));
-    HIP_TRY(hipMemcpyAsync(s->d_xf2_out, d_xf_out, rows * 64 * 4, hipMemcpyDeviceToDevice, user));
-    HIP_TRY(dc_launch_fill_rows64(user, s->d_xf2_proj + rows * 64, rows, np));
-    HIP_TRY(dc_launch_fill_rows64(user, s->d_xf2_out + rows * 64, rows, no));
-    std::vector<int32_t> len2;
-    if (h_length) {
-        len2.assign(h_length, h_length + B);
-        len2.insert(len2.end(), h_length, h_length + B);
-    }
-    if ((rc = set_conditioning(s, s->d_xf2_proj, s->d_xf2_out, h_length ? len2.data() : nullptr, 2 * B, T, stream))) return rc;
-    s->cond_set = false;
-    const size_t raw = 2 * rows * s->cfg.input_feats;
-    if (raw > s->cap_raw) {
-        drop_graph(s);          // (the buffer's address is an argument of the captured launches)
-        s->cap_raw = 0;
-        if ((rc = dev_alloc(s, s->d_raw, raw * 4))) return rc;
-        s->cap_raw = raw;
-    }
-    if (!s->d_wslot && (rc = dev_alloc(s, s->d_wslot, 16))) return rc;
-    s->guide_w = 1.f;
-    s->guided = true;
-    s->cond_set = true;
-    return DC_OK;
+    return set_conditioning_images(s, d_xf_proj, d_xf_out, h_length, B, T, 1, h_null_proj, h_null_out, stream);
+}
+
+int dc_sampler_set_conditioning_takes(dc_sampler* s, const float* d_xf_proj, const float* d_xf_out, const int32_t* h_length, int32_t B,
+                                      int32_t T, int32_t takes, const float* h_null_proj, const float* h_null_out, void* stream) {
+    if (!s || !s->finalized) return fail(DC_ERR_INVALID, "sampler not finalized");
+    if (takes < 1) return fail(DC_ERR_INVALID, "takes=%d: a conditioning holds at least one take per music", takes);
+    if ((h_null_proj != nullptr) != (h_null_out != nullptr))
+        return fail(DC_ERR_INVALID, "takes: the null pair is both vectors (guided) or neither (unguided); one of h_null_proj, h_null_out is NULL");
+    if (takes == 1 && !h_null_proj) return dc_sampler_set_conditioning(s, d_xf_proj, d_xf_out, h_length, B, T, stream);
+    return set_conditioning_images(s, d_xf_proj, d_xf_out, h_length, B, T, takes, h_null_proj, h_null_out, stream);
 }
 
 int dc_sampler_set_guidance_scale(dc_sampler* s, float w) {
@@ -1741,7 +1802,7 @@ int dc_sampler_set_known(dc_sampler* s, const float* d_known, const float* d_mas
     if (!d_mask) return fail(DC_ERR_INVALID, "known values: values or noise without a mask (d_mask is NULL)");
     if (!s->cond_set) return fail(DC_ERR_INVALID, "dc_sampler_set_conditioning must be called first: known values belong to its (B, T)");
     s->known_val = d_known, s->known_mask = d_mask, s->known_noise = d_known_noise;
-    s->known_B = s->user_B(), s->known_Tx = s->Tx, s->known_guided = s->guided;
+    s->known_B = s->user_B(), s->known_Tx = s->Tx, s->known_guided = s->guided, s->known_takes = s->takes;
     return DC_OK;
 }
 
@@ -1797,7 +1858,7 @@ int dc_sampler_status(dc_sampler* s, int32_t* h_status, int32_t clear) {
                 HIP_TRY(hipMemcpy(s->d_t_clip, tc.data(), tc.size() * 4, hipMemcpyHostToDevice));
                 if (s->split_film)
                     HIP_TRY(dc_launch_silu_emb(s->stream, s->film_fmt, true, s->d_pp, s->h_model.temb, s->d_t_clip, s->d_s_hi, s->d_s_lo, s->G, s->T, s->B));
-                DcFilmArgs fa = film_args(s, s->split_film ? nullptr : s->d_pp, s->d_t_clip);
+                DcFilmArgs fa = film_args(s, s->split_film ? nullptr : (s->pp_last ? s->pp_last : s->d_pp), s->d_t_clip);
                 fa.G = eg;
                 HIP_TRY(dc_launch_film_gemm(s->stream, s->film_fmt, s->split_film, fa));
                 HIP_TRY(dc_launch_scan_f16(s->stream, s->d_E, ebytes, s->d_status));
@@ -1843,6 +1904,7 @@ int dc_sampler_debug_layer(dc_sampler* s, const float* h_h, const int32_t* h_tim
     if (!s || !s->finalized || !s->cond_set) return fail(DC_ERR_INVALID, "sampler not ready (finalize + set_conditioning first)");
     if (!h_h || !h_timesteps) return fail(DC_ERR_INVALID, "null pointer argument");
     if (s->guided) return fail(DC_ERR_INVALID, "the conditioning is guided (dc_sampler_set_conditioning_guided): the debug entry points run plain conditionings");
+    if (s->takes > 1) return fail(DC_ERR_INVALID, "the conditioning holds %d takes per music (dc_sampler_set_conditioning_takes): the debug entry points run plain conditionings", s->takes);
     if (layer < 0 || layer >= s->cfg.num_layers || first_stage < 1 || stage > 3 || first_stage > stage)
         return fail(DC_ERR_INVALID, "layer / stage out of range (need 1 <= first_stage <= last_stage <= 3)");
     if (s->cfg.no_eff) return fail(DC_ERR_UNSUPPORTED, "dc_sampler_debug_layer covers the linear-attention layers");

@@ -679,6 +679,16 @@ DEV RowRange valid_rows_clip(const GroupCtx& cx, int clip, int B, int M, int T, 
 // last one partial - no unit and no group spans two clips, and a clip's result no longer depends on its place in the batch.
 // The unit arithmetic of the wg_* helpers (which units make up a clip, record slots) runs in a "unit space" in which every clip is
 // Tu = upc*NW*32 tokens long; group / token indices of h, E, pp stay compact (clip stride T).
+// The group of FiLM tiles token group g reads (film_share, dc_form.h): the takes of one music wrap onto the groups of take 0, the
+// unconditional shadows of a guided step read the last group - the null column.  Nothing shared: e_period = e_wrap = e_groups = G, g itself.
+// g is wave-uniform: the whole mapping stays on the scalar unit and has no branch and no division - the quotient g / e_period comes from
+// the reciprocal the host prepared (film_magic, dc_form.h: exact for every g < e_wrap; 0 where nothing wraps, and the quotient with it).
+DEV int film_tile_group(int g, int e_period, int e_wrap, int e_groups, unsigned e_magic) {
+    const int r = __builtin_amdgcn_readfirstlane(g);
+    const int q = (int)__umulhi((unsigned)r, e_magic);
+    return r < e_wrap ? r - q * e_period : e_groups - 1;
+}
+
 struct WgMap {
     int g;            // this wave's group (clamped to a valid one when the wave is idle)
     bool active;

@@ -34,7 +34,7 @@ struct Formats {
     X(no_fuse_embed, "DC_NO_FUSE_EMBED") X(film_static, "DC_FILM_STATIC") X(begin_step, "DC_BEGIN_STEP") X(no_pad, "DC_NO_PAD")      \
     X(no_layer16, "DC_NO_LAYER16") X(l16_own_combine, "DC_L16_OWN_COMBINE") X(l16_test_drop_slice, "DC_L16_TEST_DROP_SLICE")         \
     X(tail_film_bf16, "DC_TAIL_FILM_BF16") X(flat_units, "DC_FLAT_UNITS") X(no_embed_next, "DC_NO_EMBED_NEXT")                  \
-    X(guide_full_film, "DC_GUIDE_FULL_FILM")
+    X(guide_full_film, "DC_GUIDE_FULL_FILM") X(takes_full_film, "DC_TAKES_FULL_FILM")
 struct Switches {
 #define X(field, name) bool field = false;
     DC_FORM_SWITCHES(X)
@@ -46,7 +46,7 @@ struct Switches {
 #undef X
         return w;
     }
-    unsigned long long bits() const {      // one bit per switch, in the list's order (< 16 bits)
+    unsigned long long bits() const {      // one bit per switch, in the list's order (<= 16 bits)
         unsigned long long k = 0;
         int i = 0;
 #define X(field, name) k |= (field ? 1ull : 0ull) << i++;
@@ -69,7 +69,7 @@ struct Geometry {
 };
 
 // what a guided loop adds to the key of its captured graph (form_key, dc_api.hip; bits 27 and 28): the guided bit - another store in the
-// last layer, k_guided_update behind it - and the shared-column bit - the FiLM GEMM's group count and the clamp of the tile reads
+// last layer, k_guided_update behind it - and the shared-column bit - the FiLM GEMM's group count and the mapping of the tile reads
 inline unsigned long long guided_key_bits(bool guided, bool shared_film) {
     return (guided ? 1ull << 27 : 0ull) | ((guided && shared_film) ? 1ull << 28 : 0ull);
 }
@@ -104,6 +104,8 @@ struct StepOpts {
     bool embedded = false;        // the previous step's last layer has embedded x and run layer 0's front half for this step
     bool profile = false;         // events around every launch
     bool known = false;           // loops: known values are set (dc_sampler_set_known): the update replaces them (DC_UPD_KNOWN); no form is given up
+    int takes = 1;                // loops: takes per music (dc_sampler_set_conditioning_takes): the conditional clips are `takes` runs of the same
+                                  // musics, take-major, and share their FiLM tiles (film_share)
     bool guided = false;          // loops: classifier-free guidance (dc_sampler_set_conditioning_guided): the geometry's B clips are B / 2 conditional
                                   // clips followed by their B / 2 unconditional shadows; the last layer stores the raw model output and
                                   // k_guided_update combines the halves and updates x (no embed_next: x_{t-1} is not in the last layer's registers)
@@ -125,27 +127,54 @@ struct StepForm {
     int upd_flags = 0;            // DC_UPD_* bits the form adds to the loop's (TEST_DROP_SLICE, EMBED_NEXT, KNOWN)
     int nl_run = 0, stop_stage = 0;      // layers to run; the stop stage handed to the last of them (0 = the whole layer)
     bool guided = false;          // the last layer writes the raw output of all clips; k_guided_update follows it
-    bool shared_film = false;     // guided: the FiLM GEMM covers film_groups < G groups and the shadow half reads group film_groups - 1
-    int film_groups = 0;          // groups the FiLM GEMM computes = the e_groups the layer kernels clamp their tile reads to (unguided: G)
+    bool shared_film = false;     // the FiLM GEMM covers film_groups < G groups (film_share): takes wrap, the guided shadow half reads group film_groups - 1
+    int film_groups = 0;          // groups the FiLM GEMM computes = the e_groups of the layer kernels' tile reads (nothing shared: G)
+    int film_period = 0, film_wrap = 0;      // token group g reads the tiles of group g < film_wrap ? g % film_period : film_groups - 1 (nothing shared: G, G)
 };
 
-// Guided loops: the token groups the FiLM GEMM has to compute.  Every frame of every unconditional shadow clip carries the same
-// conditioning (the null pair) and a loop's step has one timestep, so emb - and with it every FiLM tile column - is one vector for the
-// whole shadow half.  When the conditional half is a whole number Gc of 32-token groups, group Gc is the first 32 tokens of the token
-// space's shadow half, and lane n of it serves lane n of every shadow group:
+// The token groups the FiLM GEMM has to compute, and which of them a token group reads.  A loop's step has one timestep, so a FiLM tile
+// column depends on its token's conditioning alone (emb = SiLU(temb[t] + linear(xf_proj))), never on x: tokens with equal conditioning
+// at equal lanes share their tiles bit for bit.
+// Takes (dc_sampler_set_conditioning_takes): the conditional clips are `takes` runs of the same Bm musics, take-major.  When one run is a
+// whole number Gc = Bm T / 32 of 32-token groups, token group g of take j holds the very tokens of group g - j Gc of take 0 - same
+// musics, same frames, same padding rows, whatever the clip stride - and the GEMM runs over one take: group g reads group g % Gc.
+// Guided loops: every frame of every unconditional shadow clip carries the same conditioning (the null pair), so every tile column is
+// one vector for the whole shadow half.  When the conditional half is a whole number of 32-token groups, the first group of the token
+// space's shadow half serves lane n of every shadow group with its lane n:
 //   - clip stride == frames per clip (no padding): every lane of every shadow group is a frame of a shadow clip, all with null pp;
 //   - clip stride 32 for clips shorter than 32 frames: one group per clip, lane n is frame n of its clip in every group (null pp below
 //     the frame count, the padding rows' value above it - zeros from k_cond_pp64, linear(0) from k_cond_embed: by position alone either way);
-//   - clip stride padded to whole groups (>= 256 frames): group Gc holds frames 0 .. 31 of shadow clip 0, all null pp; the padding lanes
+//   - clip stride padded to whole groups (>= 256 frames): that group holds frames 0 .. 31 of shadow clip 0, all null pp; the padding lanes
 //     of later groups then read the null column instead of the padding rows' own - rows that no record, no output and no other token reads.
-// The GEMM then runs over Gc + 1 groups and the layer kernels read group min(g, Gc).  Needs the GEMM that builds its operand from
-// pp + temb (non-split FiLM formats); DC_GUIDE_FULL_FILM=1 keeps all 2 Gc groups.  Returns G when nothing is shared.
-inline int guided_film_groups(int B, int T, int G, bool film_from_pp, const Switches& w) {
-    const long long mc = (long long)(B / 2) * T;
-    if (B % 2 || !film_from_pp || w.guide_full_film || mc % 32 != 0) return G;
-    const int gc = (int)(mc / 32);
-    return (2 * gc == G && gc + 1 < G) ? gc + 1 : G;
+// The GEMM then runs one more group behind the conditional ones - the null column - and every shadow group reads that last group.
+// With `wrap` the groups of all conditional clips and `period` those the GEMM computes of them (Gc, or all of them):
+//   tile group of token group g  =  g < wrap ? g % period : groups - 1          (film_tile_group, dc_dev.h; film_magic below)
+// Needs the GEMM that builds its operand from pp + temb (non-split FiLM formats).  DC_GUIDE_FULL_FILM=1 keeps all groups of a guided loop,
+// DC_TAKES_FULL_FILM=1 all groups of the conditional clips (period = wrap).  Nothing shared: period = wrap = groups = G.
+struct FilmShare {
+    int period = 0, wrap = 0, groups = 0;
+};
+inline FilmShare film_share(int B, int T, int G, bool guided, int takes, bool film_from_pp, const Switches& w) {
+    const FilmShare full{G, G, G};
+    const int Bc = guided ? B / 2 : B;      // conditional clips
+    if ((guided && B % 2) || takes < 1 || Bc % takes || !film_from_pp || (guided && w.guide_full_film)) return full;
+    const long long mc = (long long)(Bc / takes) * T;      // tokens of one take
+    if (mc % 32 != 0) return full;
+    const long long gc = mc / 32, wrap = gc * takes;
+    if ((guided ? 2 * wrap : wrap) != G) return full;
+    // (gc >= 2 and wrap * gc < 2^32: what the kernels' reciprocal needs to exist in 32 bits and to be exact, film_magic - a take of one
+    // group is a single clip of at most 32 frames, 65536 groups are two million tokens)
+    const int period = (int)((takes > 1 && !w.takes_full_film && gc >= 2 && wrap * gc < (1ll << 32)) ? gc : wrap), groups = period + (guided ? 1 : 0);
+    return groups < G ? FilmShare{period, (int)wrap, groups} : full;
 }
+// The reciprocal the layer kernels take g / period from: with m = floor(2^32 / period) + 1, (g m) >> 32 == g / period for every g with
+// g period < 2^32 (the error of g m / 2^32 against g / period is below g / 2^32 < 1 / period) - every g < wrap, by film_share's condition;
+// period >= 2, so that m fits 32 bits.
+// 0 where nothing wraps (period == wrap): the quotient is then 0 and the kernels read g itself.
+inline unsigned film_magic(int period, int wrap) { return period < wrap ? (unsigned)((1ull << 32) / (unsigned)period) + 1u : 0u; }
+// what takes add to the key of a captured graph (dc_api.hip, GraphKey): the period the tile reads wrap at, 0 where no take shares another's
+// tiles - 2 takes x 2 musics and a plain 4-clip conditioning have one internal geometry and different launches
+inline int takes_key_period(const FilmShare& f) { return f.period < f.wrap ? f.period : 0; }
 
 // split-operand evaluations (the precise tail, dc_sampler_set_precise_forward) exist for: fp16 / bf16 precision, no test hooks
 inline bool can_split_steps(const Settings& s, const Hooks& dbg) {
@@ -180,7 +209,12 @@ inline StepForm step_form(const Geometry& g, const Settings& s, const Switches& 
     f.folded = o.loop_mode && o.graph_step >= 0 && fuse_silu && !s.no_eff && !w.begin_step && dbg.stage == 0;
     // adaptive work shares of the persistent FiLM GEMM (dc_kernels.hip, film_shares); DC_FILM_STATIC=1 keeps equal shares
     f.adapt = !w.film_static && g.num_cu <= 1024;
-    f.film_groups = guided ? guided_film_groups(B, T, G, fuse_silu, w) : G;
+    if (o.takes < 1 || (guided ? B / 2 : B) % o.takes != 0) {
+        f.error = "internal: the conditional clips are not a whole number of takes";
+        return f;
+    }
+    const FilmShare share = film_share(B, T, G, guided, o.takes, fuse_silu, w);
+    f.film_groups = share.groups, f.film_period = share.period, f.film_wrap = share.wrap;
     f.shared_film = f.film_groups < G;
     f.nl_run = (dbg.layers >= 0 && dbg.layers < s.num_layers) ? dbg.layers : s.num_layers;
     // (full attention: the last layer of a shortened run stops after its FFN block)

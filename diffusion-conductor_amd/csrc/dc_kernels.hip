@@ -1368,7 +1368,7 @@ void k_layer(const DcModel* __restrict__ dm, int l, float* __restrict__ hbuf, co
              float* __restrict__ snaps, int M, int T, int G, int B, int dbg,
              unsigned long long* __restrict__ stamps, size_t rec_stride, const int* __restrict__ iter_base,
              int Tx /* frames per clip of xin / xout / snaps (<= the clip stride T) */, int upc /* workgroups per clip (WgMap) or 0 */,
-             int e_groups /* groups of FiLM tiles behind E (DcLayerArgs) */, const DcUpdate upd) {
+             int e_groups /* groups of FiLM tiles behind E (DcLayerArgs) */, int e_period, int e_wrap, unsigned e_magic /* film_tile_group */, const DcUpdate upd) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     static_assert(!NARROW || (WGR && !SPLIT && !DBG), "narrow workgroups: workgroup-record form, non-split formats, no test hooks");
     constexpr int NW = NARROW ? 4 : (SPLIT ? DC_SPLIT_NW : 8);
@@ -1446,7 +1446,7 @@ void k_layer(const DcModel* __restrict__ dm, int l, float* __restrict__ hbuf, co
     const W* af = reinterpret_cast<const W*>(lds + OFF_AF);
     const DcLayer& L = dm->layer[l];
     const bool last = l + 1 >= nl;
-    const f16x8* Eg = reinterpret_cast<const f16x8*>(E) + ((size_t)min(g, e_groups - 1) * NT + (size_t)l * 24) * 128;   // 3 blocks x 8 tiles
+    const f16x8* Eg = reinterpret_cast<const f16x8*>(E) + ((size_t)film_tile_group(g, e_period, e_wrap, e_groups, e_magic) * NT + (size_t)l * 24) * 128;   // 3 blocks x 8 tiles
     const W* acl = a_ca + (size_t)l * B * 16 * 64;
     const float* recs_in = recs + (size_t)(l & 1) * rec_stride;
     float* recs_out = recs + (size_t)((l + 1) & 1) * rec_stride;
@@ -2549,7 +2549,8 @@ __global__ __launch_bounds__(512, 2) void k_layer_full(const DcModel* __restrict
                                                        const int* __restrict__ length, const float* __restrict__ xin,
                                                        float* __restrict__ xout, int out_mode, const float* __restrict__ coef_cur,
                                                        const int* __restrict__ snap_cur, float* __restrict__ snaps, int M, int T,
-                                                       int B, int KT, int WPC, int stop_after, int e_groups, const DcUpdate upd) {
+                                                       int B, int KT, int WPC, int stop_after, int e_groups, int e_period, int e_wrap, unsigned e_magic,
+                                                       const DcUpdate upd) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     using W = v8<T16>;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -2561,7 +2562,7 @@ __global__ __launch_bounds__(512, 2) void k_layer_full(const DcModel* __restrict
     const bool any_pad = len < T;
     const bool q_pad = cx.n >= len;
     const int key_lo = cx.b * T, key_hi = min((cx.b + 1) * T, M);
-    const f16x8* Eg = reinterpret_cast<const f16x8*>(E) + ((size_t)min(cx.g, e_groups - 1) * NT + (size_t)l * 24) * 128;
+    const f16x8* Eg = reinterpret_cast<const f16x8*>(E) + ((size_t)film_tile_group(cx.g, e_period, e_wrap, e_groups, e_magic) * NT + (size_t)l * 24) * 128;
     constexpr int HL = SPLIT ? 2 : 1;
     auto consts = [](const bf16x8* img) { return reinterpret_cast<const float*>(reinterpret_cast<const W*>(img) + 32 * 64 * HL); };
     f32x16 h[4];
@@ -3028,7 +3029,7 @@ static hipError_t launch_layer_t(hipStream_t st, const DcLayerArgs& a, int l, co
     if (hipError_t e = lds_optin((const void*)k_layer<T16, SP, DBG, STAMP, WGR, NARROW, G1>, (int)shm, optin_done)) return e;
     k_layer<T16, SP, DBG, STAMP, WGR, NARROW, G1><<<dim3((WGR && upc) ? a.B * upc : (a.G + NW - 1) / NW), dim3(NW * 64), shm, st>>>(
         a.dm, l, a.hbuf, (const f16x16*)a.E, a.NT, (const v8<T16>*)a_sa, (const v8<T16>*)a_ca, a.recs, a.length, a.xin, a.xout, a.out_mode,
-        a.coef_cur, a.snap_cur, a.snaps, a.M, a.T, a.G, a.B, dbg, stamps, rec_stride, a.iter_base, a.Tx, WGR ? upc : 0, a.e_groups, a.upd);
+        a.coef_cur, a.snap_cur, a.snaps, a.M, a.T, a.G, a.B, dbg, stamps, rec_stride, a.iter_base, a.Tx, WGR ? upc : 0, a.e_groups, a.e_period, a.e_wrap, a.e_magic, a.upd);
     return hipGetLastError();
 }
 
@@ -3044,6 +3045,7 @@ static hipError_t launch_layer_t(hipStream_t st, const DcLayerArgs& a, int l, co
 hipError_t dc_launch_layer(hipStream_t st, const DcLayerForm& f, const DcLayerArgs& a, int l, const void* a_sa, const void* a_ca, int dbg,
                            unsigned long long* stamps) {
     if (f.wgr && f.split && f.upc <= 0) return hipErrorInvalidValue;      // split formats: workgroup records on clip-aligned units only
+    if (!a.tiles_ok()) return hipErrorInvalidValue;
     const bool stop = dbg != 0, stamp = stamps != nullptr && !stop;       // (a stopped layer takes no stamps)
 #define X(SP, DBG, STAMP, WGR, NARROW, G1)                                                                      \
     if (f.split == SP && stop == DBG && stamp == STAMP && f.wgr == WGR && f.narrow == NARROW && f.g1 == G1)     \
@@ -3064,7 +3066,7 @@ static hipError_t launch_full_t(hipStream_t st, const DcLayerArgs& a, int l, con
     if (hipError_t e = lds_optin((const void*)k_layer_full<T16, SP>, DC_FULL_LDS, optin_done)) return e;
     k_layer_full<T16, SP><<<dim3(a.B * WPC), dim3(512), DC_FULL_LDS, st>>>(
         a.dm, l, a.hbuf, (const f16x16*)a.E, a.NT, (const v8<T16>*)kv_cur, (v8<T16>*)kv_next, (const v8<T16>*)kv_ca, a.length, a.xin, a.xout,
-        a.out_mode, a.coef_cur, a.snap_cur, a.snaps, a.M, a.T, a.B, KT, WPC, stop_after, a.e_groups, a.upd);
+        a.out_mode, a.coef_cur, a.snap_cur, a.snaps, a.M, a.T, a.B, KT, WPC, stop_after, a.e_groups, a.e_period, a.e_wrap, a.e_magic, a.upd);
     return hipGetLastError();
 }
 hipError_t dc_launch_embed_front_full(hipStream_t st, int fmt, bool split, const DcModel* dm, const float* x, float* hbuf, void* kv_next,
@@ -3079,7 +3081,7 @@ hipError_t dc_launch_embed_front_full(hipStream_t st, int fmt, bool split, const
 }
 hipError_t dc_launch_layer_full(hipStream_t st, int fmt, bool split, const DcLayerArgs& a, int l, const void* kv_cur, void* kv_next,
                                 const void* kv_ca, int KT, int stop_after) {
-    if (fmt != 1) return hipErrorInvalidValue;
+    if (fmt != 1 || !a.tiles_ok()) return hipErrorInvalidValue;
     return (split ? launch_full_t<_Float16, true> : launch_full_t<_Float16, false>)(st, a, l, kv_cur, kv_next, kv_ca, KT, stop_after);
 }
 hipError_t dc_launch_ca_kv(hipStream_t st, int fmt, const DcModel* dm, const void* nh_hi, const void* nh_lo, void* kv_ca,

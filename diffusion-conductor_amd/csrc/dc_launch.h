@@ -80,9 +80,14 @@ struct DcLayerArgs {
     const int* iter_base;
     int M, T, G, B;
     int Tx;                      // frames per clip of xin / xout / snaps
-    int e_groups;                // groups of FiLM tiles behind E: group g reads the tiles of group min(g, e_groups - 1) (G; a guided step whose
-                                 // unconditional half shares one column: the conditional half's groups + 1, dc_form.h)
+    int e_groups;                // groups of FiLM tiles behind E (film_share, dc_form.h): token group g reads the tiles of group
+    int e_period, e_wrap;        // g < e_wrap ? g % e_period : e_groups - 1 (film_tile_group).  Nothing shared: all three G.  Guided, one
+                                 // shared null column: e_period = e_wrap = the conditional half's groups, e_groups one more.  Takes:
+                                 // e_period = one take's groups, e_wrap = the groups of all conditional clips
+    unsigned e_magic;            // film_magic(e_period, e_wrap): the reciprocal the kernels take g / e_period from (0 where e_period == e_wrap)
     DcUpdate upd;                // options of the fused DDIM update + the status word (dc_common.h)
+    // what film_tile_group relies on (checked by every layer launcher): the mapping stays inside the e_groups groups the GEMM wrote
+    bool tiles_ok() const { return e_period >= 1 && e_wrap >= e_period && e_groups >= 1 && e_period <= e_groups && (e_magic != 0) == (e_period < e_wrap); }
 };
 hipError_t dc_launch_layer(hipStream_t st, const DcLayerForm& f, const DcLayerArgs& a, int l, const void* a_sa, const void* a_ca,
                            int dbg /* stop stage of this layer (test hook), 0 = the whole layer */,

@@ -561,7 +561,7 @@ void k_layer16(const DcModel* __restrict__ dm, int l, float* __restrict__ hbuf, 
                const int* __restrict__ iter_base, int Tx, const DcUpdate upd,
                unsigned long long* __restrict__ gran /* [B][1024] granules of the shared combine, or nullptr: every workgroup combines alone */,
                unsigned tag_base /* + 16 * (*iter_base) + l + 1 = this launch's tag */,
-               int e_groups /* groups of FiLM tiles behind E (DcLayerArgs) */) {
+               int e_groups /* groups of FiLM tiles behind E (DcLayerArgs) */, int e_period, int e_wrap, unsigned e_magic /* film_tile_group */) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     using W = v8<T16>;
     constexpr int NW = L16_NW;
@@ -603,7 +603,6 @@ void k_layer16(const DcModel* __restrict__ dm, int l, float* __restrict__ hbuf, 
     const DcLayer16& L = dm->l16[l];
     const int nl = dm->num_layers;
     const bool last = l + 1 >= nl;
-    const f16x8* Eg = reinterpret_cast<const f16x8*>(E) + ((size_t)min(c.g, e_groups - 1) * NT + (size_t)l * 24) * 128;   // 3 blocks x 8 tiles
     const float* recs_in = recs + (size_t)(l & 1) * rec_stride;
     float* recs_out = recs + (size_t)((l + 1) & 1) * rec_stride;
 
@@ -627,6 +626,9 @@ void k_layer16(const DcModel* __restrict__ dm, int l, float* __restrict__ hbuf, 
     } else
         wg_combine_attn16<T16>(recs_in, stride_in, nu_in, c.b, reinterpret_cast<W*>(lds + L16_OFF_AF), reinterpret_cast<float*>(buf1),
                                reinterpret_cast<float*>(lds + L16_OFF_PST) /* the tail's 36 KiB: free until then */, tid);
+    // (here, not in the prologue: there the mapping's three arguments split the kernel-argument loads into two scalar-memory round trips
+    // in front of the first load of h - +1.8 % per loop at one clip)
+    const f16x8* Eg = reinterpret_cast<const f16x8*>(E) + ((size_t)film_tile_group(c.g, e_period, e_wrap, e_groups, e_magic) * NT + (size_t)l * 24) * 128;   // 3 blocks x 8 tiles
     e16_load(e, Eg, c);                          // (behind the combine, whose record batches need the registers; first used in stage 2)
     LSTAMP(1);
     // closer that leaves the 16 FiLM-tile loads just issued in flight (they are the wave's youngest vector-memory operations; the
@@ -968,14 +970,14 @@ hipError_t launch_layer16_t(hipStream_t st, const DcLayerArgs& a, int l, const v
     k_layer16<T16, G1><<<dim3(a.B * upc), dim3(256), L16_LDS, st>>>(a.dm, l, a.hbuf, (const f16x16*)a.E, a.NT, (const v8<T16>*)a_ca16, a.recs,
                                                                     a.length, a.xin, a.xout, a.out_mode, a.coef_cur, a.snap_cur, a.snaps, a.M,
                                                                     a.T, a.B, upc, rec_stride, nu_in, stride_in, a.iter_base, a.Tx, a.upd, gran,
-                                                                    tag_base, a.e_groups);
+                                                                    tag_base, a.e_groups, a.e_period, a.e_wrap, a.e_magic);
     return hipGetLastError();
 }
 }  // namespace
 
 hipError_t dc_launch_layer16(hipStream_t st, int fmt, const DcLayerArgs& a, int l, const void* a_ca16, int upc, size_t rec_stride, int nu_in,
                              size_t stride_in, unsigned long long* gran, unsigned tag_base, bool g1) {
-    if (nu_in < 1 || nu_in > L16_MAXU || upc < 1 || (a.T & 31)) return hipErrorInvalidValue;
+    if (nu_in < 1 || nu_in > L16_MAXU || upc < 1 || (a.T & 31) || !a.tiles_ok()) return hipErrorInvalidValue;
     const auto f = fmt == 1 ? (g1 ? launch_layer16_t<_Float16, true> : launch_layer16_t<_Float16, false>)
                             : (g1 ? launch_layer16_t<__bf16, true> : launch_layer16_t<__bf16, false>);
     return f(st, a, l, a_ca16, upc, rec_stride, nu_in, stride_in, gran, tag_base);

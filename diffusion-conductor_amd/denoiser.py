@@ -254,8 +254,9 @@ class MotionTransformer(nn.Module):
         proj.bias.  The reference has no sampling counterpart."""
         return self.get_parameter("proj.bias").detach().float().cpu().reshape(64), torch.zeros(64)
 
-    def set_conditioning(self, xf_proj, xf_out, length=None, guided=False):
-        """`guided`: the conditioning of a guided loop (include/dc_ddim.h, dc_sampler_set_conditioning_guided) with null_conditioning()."""
+    def set_conditioning(self, xf_proj, xf_out, length=None, guided=False, takes=1):
+        """`guided`: the conditioning of a guided loop (include/dc_ddim.h, dc_sampler_set_conditioning_guided) with null_conditioning().
+        `takes`: samples per music (dc_sampler_set_conditioning_takes): the loops then run takes x the musics, take-major."""
         nat = self._ensure_native(xf_proj.device)
         T = xf_proj.shape[1]
         if length is None:
@@ -266,12 +267,12 @@ class MotionTransformer(nn.Module):
         # caching allocator hands the same address to a new tensor.
         k = self._cond_key
         same = (k is not None and k[0] is xf_proj and k[1] is xf_out and k[2] == (xf_proj._version, xf_out._version)
-                and k[3] == ln and k[4] == bool(guided))
+                and k[3] == ln and k[4] == bool(guided) and k[5] == int(takes))
         if not same:
             self._cond_key = None
             nat.set_conditioning(xf_proj.contiguous().float(), xf_out.contiguous().float(), list(ln),
-                                 null=self.null_conditioning() if guided else None)
-            self._cond_key = (xf_proj, xf_out, (xf_proj._version, xf_out._version), ln, bool(guided))
+                                 null=self.null_conditioning() if guided else None, takes=int(takes))
+            self._cond_key = (xf_proj, xf_out, (xf_proj._version, xf_out._version), ln, bool(guided), int(takes))
         return nat
 
     def forward(self, x, timesteps, length=None, text=None, xf_proj=None, xf_out=None):

@@ -69,15 +69,16 @@ class DDPMTrainer(object):
             return {}
         return {"steps": steps, "spacing": spacing, "solver": solver}
 
-    def _sample_local(self, mel, noise, dim_pose, idxs, smooth=None, guidance_scale=None, skw={}):
+    def _sample_local(self, mel, noise, dim_pose, idxs, smooth=None, guidance_scale=None, skw={}, takes=1):
         xf_proj, xf_out = self.encoder.encode_music(mel, self.device)
         B, T = mel.shape[0], xf_proj.shape[1]
+        tkw = {} if takes == 1 else {"takes": takes}      # (one take: the loop is called as before)
         try:
             return self.diffusion.ddim_sample_loop(
-                self.encoder, (B, T, dim_pose), noise=noise, clip_denoised=False, progress=False,
+                self.encoder, (takes * B, T, dim_pose), noise=noise, clip_denoised=False, progress=False,
                 model_kwargs={"xf_proj": xf_proj, "xf_out": xf_out,
                               "length": torch.LongTensor([T] * B)},
-                idxs=idxs, smooth=smooth, guidance_scale=guidance_scale, **skw)
+                idxs=idxs, smooth=smooth, guidance_scale=guidance_scale, **skw, **tkw)
         except FloatingPointError:
             # The loop's numeric check failed.  If the music features themselves are not finite, the fp16-plane MusicEncoder
             # overflowed (an activation beyond 65504; the reference's mel is normalised to [0, 1], so this takes unusual input):
@@ -88,11 +89,15 @@ class DDPMTrainer(object):
             nat = getattr(self.encoder, "_native", None)
             if nat is not None:
                 nat.set_encoder_format("split")
-            return self._sample_local(mel, noise, dim_pose, idxs, smooth, guidance_scale, skw)
+            return self._sample_local(mel, noise, dim_pose, idxs, smooth, guidance_scale, skw, takes)
 
     def generate_music_motion(self, music_mel, dim_pose, batch_size=1024, idxs=[], noise=None, seed=None, smooth=None,
-                              guidance_scale=None, steps=None, spacing="uniform", solver="ddim"):
+                              guidance_scale=None, steps=None, spacing="uniform", solver="ddim", takes=1):
         """music_mel: np.ndarray/tensor [5400,128] (reference) or [B,5400,128] -> tensor [B,1800,dim_pose].
+        takes: samples per music (default 1) -> tensor [takes * B, 1800, dim_pose], TAKE-MAJOR: row j * B + b is take j of music b
+        (result.view(takes, B, 1800, dim_pose)[j, b]).  The music is encoded once and the takes share every step's conditioning work
+        (GaussianDiffusion.ddim_sample_loop, takes=); `noise`, when given, is [takes * B, 1800, dim_pose] in the same order, and `seed`
+        draws that many clips - the takes differ through their noise alone.  Not sharded over the ranks of a group yet.
         smooth: None, or the Savitzky-Golay kernel size (order 5) tools/visualization.py:126 smooths the keypoints with - applied
         by the sampling loop's final write.
         guidance_scale: None, or the classifier-free guidance scale of the loop (GaussianDiffusion.ddim_sample_loop; each rank of a
@@ -114,6 +119,11 @@ class DDPMTrainer(object):
         _, world = dist_info()
         if skw and world > 1:
             raise NotImplementedError("steps= / solver= are not sharded over the ranks of a torch.distributed group yet")
+        if int(takes) != takes or int(takes) < 1:
+            raise ValueError(f"takes must be an integer >= 1, got {takes!r}")
+        takes = int(takes)
+        if takes > 1 and world > 1:
+            raise NotImplementedError("takes= are not sharded over the ranks of a torch.distributed group yet")
         grouped = torch.distributed.is_available() and torch.distributed.is_initialized()     # a world-size-1 group still gathers
         if noise is None and (seed is not None or world > 1):
             # x_T for the WHOLE batch from one generator, sliced per shard: with every rank drawing from its own default
@@ -128,13 +138,13 @@ class DDPMTrainer(object):
                     import torch.distributed as dist
                     dist.broadcast(s0, src=0)
                 g.manual_seed(int(s0.item()))
-            noise = torch.randn(B, T, dim_pose, generator=g)
+            noise = torch.randn(takes * B, T, dim_pose, generator=g)
         if noise is not None:
             noise = torch.as_tensor(noise).to(self.device, dtype=torch.float32)
         sm = (int(smooth), 5) if smooth else None
         with torch.no_grad():
-            if not grouped or len(idxs):
-                return self._sample_local(mel, noise, dim_pose, idxs, sm, guidance_scale, skw)
+            if not grouped or len(idxs) or takes > 1:      # (takes: a single rank, checked above)
+                return self._sample_local(mel, noise, dim_pose, idxs, sm, guidance_scale, skw, takes)
             return sharded_sample(lambda m, n: self._sample_local(m, n, dim_pose, [], sm, guidance_scale, skw), mel, noise, out_shape=(T, dim_pose),
                                   device=self.device)
 

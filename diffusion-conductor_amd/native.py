@@ -32,6 +32,7 @@ EXPORTS = [
     "dc_m2snet_create", "dc_m2snet_destroy", "dc_m2snet_set_param", "dc_m2snet_finalize", "dc_m2snet_encode_music", "dc_m2snet_fuse",
     "dc_m2snet_score",
     "dc_solver_table", "dc_sampler_solver_loop", "dc_sampler_solver_profile_loop",
+    "dc_sampler_set_conditioning_takes",
 ]
 
 UPDATE_CLIP_DENOISED, UPDATE_EPSILON = 1, 2          # flags of dc_sampler_ddim_loop_ex
@@ -146,6 +147,7 @@ def lib():
     L.dc_sampler_set_known.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.dc_sampler_set_conditioning_guided.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, ip, C.c_int32, C.c_int32, fp, fp, C.c_void_p]
     L.dc_sampler_set_guidance_scale.argtypes = [C.c_void_p, C.c_float]
+    L.dc_sampler_set_conditioning_takes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, ip, C.c_int32, C.c_int32, C.c_int32, fp, fp, C.c_void_p]
     L.dc_sampler_set_step_noise_seed.argtypes = [C.c_void_p, C.c_uint64]
     L.dc_sampler_set_step_noise_seed_at.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64]
     L.dc_step_noise_fill.argtypes = [C.c_void_p, C.c_int64, C.c_uint64, C.c_int32, C.c_void_p]
@@ -338,6 +340,7 @@ class NativeSampler:
         self.cfg, self.precision, self.device, self.max_timesteps = cfg, precision, int(device), int(max_timesteps)
         self.B = self.T = 0
         self.guided = False
+        self.takes = 1
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
@@ -365,10 +368,12 @@ class NativeSampler:
         import torch
         return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
-    def set_conditioning(self, xf_proj, xf_out, length=None, null=None):
+    def set_conditioning(self, xf_proj, xf_out, length=None, null=None, takes=1):
         """dc_sampler_set_conditioning, or - `null` = the pair (null_proj[64], null_out[64]) - dc_sampler_set_conditioning_guided: the
         loops then run with classifier-free guidance at the scale of set_guidance_scale (1 after this call); every tensor handed to
-        them stays [B, T, P]."""
+        them stays [B, T, P].
+        `takes` > 1: dc_sampler_set_conditioning_takes - `takes` samples of each of the B musics.  The loops then run takes * B clips,
+        take-major (clip j * B + b is take j of music b), and every tensor handed to them is [takes * B, T, P]; self.B is that count."""
         import torch
         assert xf_proj.is_cuda and xf_proj.dtype == torch.float32 and xf_proj.is_contiguous()
         assert xf_out.is_cuda and xf_out.dtype == torch.float32 and xf_out.is_contiguous()
@@ -379,15 +384,21 @@ class NativeSampler:
             la = np.ascontiguousarray(np.asarray(length.cpu() if hasattr(length, "cpu") else length), np.int32)
             assert la.shape == (B,)
             lp = _iptr(la)
-        if null is None:
-            _check(lib().dc_sampler_set_conditioning(self._h, xf_proj.data_ptr(), xf_out.data_ptr(), lp, B, T, self._stream()))
-        else:
+        nv = [None, None]
+        if null is not None:
             nv = [None if v is None else
                   np.ascontiguousarray(np.asarray(v.detach().cpu() if hasattr(v, "detach") else v), np.float32).reshape(-1) for v in null]
             assert len(nv) == 2 and all(v is None or v.shape == (64,) for v in nv), "null = (null_proj[64], null_out[64])"
+        if int(takes) != 1:
+            _check(lib().dc_sampler_set_conditioning_takes(self._h, xf_proj.data_ptr(), xf_out.data_ptr(), lp, B, T, int(takes),
+                                                           *[None if v is None else _fptr(v) for v in nv], self._stream()))
+        elif null is None:
+            _check(lib().dc_sampler_set_conditioning(self._h, xf_proj.data_ptr(), xf_out.data_ptr(), lp, B, T, self._stream()))
+        else:
             _check(lib().dc_sampler_set_conditioning_guided(self._h, xf_proj.data_ptr(), xf_out.data_ptr(), lp, B, T,
                                                             *[None if v is None else _fptr(v) for v in nv], self._stream()))
-        self.B, self.T = B, T
+        self.takes = int(takes)
+        self.B, self.T = B * self.takes, T
         self.guided = null is not None
 
     def set_guidance_scale(self, w):

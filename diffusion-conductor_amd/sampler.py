@@ -348,6 +348,22 @@ class GaussianDiffusion:
         if not math.isfinite(float(guidance_scale)):
             raise ValueError(f"guidance_scale must be finite, got {guidance_scale!r}")
 
+    def _check_takes(self, model, takes, shape, model_kwargs, denoised_fn, cond_fn, stepped=False):
+        """takes= runs inside the native loop only, over takes x the musics of model_kwargs: ValueError otherwise."""
+        if int(takes) != takes or int(takes) < 1:
+            raise ValueError(f"takes must be an integer >= 1, got {takes!r}")
+        takes = int(takes)
+        if takes == 1:
+            return 1
+        if stepped or not self._fast_path_ok(model, denoised_fn, cond_fn):
+            raise ValueError("takes= share their conditioning inside the native loop; "
+                             f"{'the progressive generator' if stepped else 'this call'} steps through ddim_sample - tile the music instead")
+        mk = model_kwargs or {}
+        ref = mk.get("xf_proj") if mk.get("xf_proj") is not None else mk.get("text")
+        if ref is not None and int(shape[0]) != takes * int(ref.shape[0]):
+            raise ValueError(f"shape[0]={shape[0]} must be takes x musics = {takes} x {int(ref.shape[0])}")
+        return takes
+
     def _solver_timesteps(self, model, steps, spacing, timesteps, solver, eta, denoised_fn, cond_fn, stepped=False):
         """The list of a loop on a sub-sequence (steps= / timesteps= / solver=), or None when none of them was given (today's loop).
         Such a loop runs natively only: ValueError where the call would step through ddim_sample, as for guidance_scale=."""
@@ -374,7 +390,7 @@ class GaussianDiffusion:
         return ts
 
     def _native_loop(self, model, img, mk, clip_denoised, eta, snap, step_noise, smooth=None, step_noise_seed=None, known=None,
-                     guidance_scale=None, timesteps=None, solver="ddim"):
+                     guidance_scale=None, timesteps=None, solver="ddim", takes=1):
         """The captured loop on `model`'s sampler; returns (out, snaps).  Numeric health is checked once per call
         (`model.check_numerics`): a non-finite x0 under precision="auto" falls back to the bf16-range mode in a fresh sampler.
         `timesteps` (a list) runs dc_sampler_solver_loop on it with `solver`'s table; None the loop over every timestep."""
@@ -404,10 +420,11 @@ class GaussianDiffusion:
             coef = self.native_coefficients(None if plain else eta) if known is None else self.native_coefficients_known(eta)
         retried = False
         while True:
+            tk = {} if takes == 1 else {"takes": takes}      # (one take: the model is called as before)
             if guidance_scale is None:
-                nat = model.set_conditioning(mk["xf_proj"], mk["xf_out"], mk.get("length"))
+                nat = model.set_conditioning(mk["xf_proj"], mk["xf_out"], mk.get("length"), **tk)
             else:        # (inside the retry loop: precision="auto"'s re-run on a fresh sampler keeps the scale)
-                nat = model.set_conditioning(mk["xf_proj"], mk["xf_out"], mk.get("length"), guided=True)
+                nat = model.set_conditioning(mk["xf_proj"], mk["xf_out"], mk.get("length"), guided=True, **tk)
                 nat.set_guidance_scale(guidance_scale)
             nat.set_smoothing(*(smooth if smooth else (0, 0)))
             nat.set_known(*(known if known is not None else (None, None, None)))
@@ -433,7 +450,7 @@ class GaussianDiffusion:
     def ddim_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                          model_kwargs=None, device=None, progress=False, eta=0.0, idxs=[], step_noise=None, smooth=None,
                          step_noise_seed=None, known=None, known_mask=None, known_noise=None, known_noise_seed=None,
-                         guidance_scale=None, steps=None, spacing="uniform", timesteps=None, solver="ddim"):
+                         guidance_scale=None, steps=None, spacing="uniform", timesteps=None, solver="ddim", takes=1):
         """gaussian_diffusion.py:871-915.  Returns the final sample, or when `idxs` is non-empty a
         dict {iteration: sample} for the listed iterations plus {num_timesteps: final}.
         `steps`, `spacing`, `timesteps`, `solver` (extension, native loop only; none given = today's loop over every timestep, bit for
@@ -457,8 +474,13 @@ class GaussianDiffusion:
         `guidance_scale` (extension, native loop only; None = no guidance, today's loop bit for bit): classifier-free guidance at
         scale w - every step evaluates the model on the music and on the model's null_conditioning() and continues from
         c + (w - 1)(c - u) (include/dc_ddim.h, dc_sampler_set_conditioning_guided; the reference trains for it, transformer.py:389,
-        451-459, and never samples with it).  ValueError with denoised_fn, cond_fn, PREVIOUS_X or a learned variance."""
+        451-459, and never samples with it).  ValueError with denoised_fn, cond_fn, PREVIOUS_X or a learned variance.
+        `takes` (extension, native loop only; 1 = today's loop): samples per music.  `model_kwargs` holds B musics and `shape[0]` must be
+        takes * B (ValueError otherwise): clip j * B + b of `noise`, of the result and of every other [.., T, P] argument is take j of
+        music b.  The takes share each step's FiLM tiles (include/dc_ddim.h, dc_sampler_set_conditioning_takes); the result equals the
+        loop over the music tiled `takes` times, bit for bit.  ValueError where the loop would step through ddim_sample."""
         self._check_guidance(model, guidance_scale, denoised_fn, cond_fn)
+        takes = self._check_takes(model, takes, shape, model_kwargs, denoised_fn, cond_fn)
         ts = self._solver_timesteps(model, steps, spacing, timesteps, solver, eta, denoised_fn, cond_fn)
         n_iter = self.num_timesteps if ts is None else len(ts)
         self._refuse_epsilon_full_attention(model, eta)
@@ -475,7 +497,7 @@ class GaussianDiffusion:
             snap = sorted(int(i) for i in set(idxs) if 0 <= int(i) < n_iter)
             kn = self._known_tensors(img, known, known_mask, known_noise, known_noise_seed)
             out, snaps = self._native_loop(model, img, mk, bool(clip_denoised), float(eta), snap, step_noise, smooth, step_noise_seed, kn,
-                                            guidance_scale, ts, solver)
+                                            guidance_scale, ts, solver, takes)
             if len(idxs) == 0:
                 return out
             result = {it: snaps[k] for k, it in enumerate(snap)}
@@ -505,11 +527,13 @@ class GaussianDiffusion:
 
     def ddim_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None,
                                      cond_fn=None, model_kwargs=None, device=None, progress=False, eta=0.0,
-                                     step_noise=None, guidance_scale=None, steps=None, spacing="uniform", timesteps=None, solver="ddim"):
+                                     step_noise=None, guidance_scale=None, steps=None, spacing="uniform", timesteps=None, solver="ddim",
+                                     takes=1):
         """gaussian_diffusion.py:917-965: yields {"sample","pred_xstart"} after every step.  `guidance_scale`, `steps`, `timesteps`,
-        `solver`: the defaults only - this generator steps through ddim_sample (ValueError otherwise; ddim_sample_loop guides, and
+        `solver`, `takes`: the defaults only - this generator steps through ddim_sample (ValueError otherwise; ddim_sample_loop guides, and
         samples on a sub-sequence, inside the captured loop)."""
         self._check_guidance(model, guidance_scale, denoised_fn, cond_fn, stepped=True)
+        self._check_takes(model, takes, shape, model_kwargs, denoised_fn, cond_fn, stepped=True)
         self._solver_timesteps(model, steps, spacing, timesteps, solver, eta, denoised_fn, cond_fn, stepped=True)
         self._refuse_epsilon_full_attention(model, eta)
         if device is None:

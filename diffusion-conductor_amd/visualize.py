@@ -129,6 +129,9 @@ def make_parser():
     parser.add_argument('--solver', type=str, default="ddim", choices=["ddim", "dpmpp2m"], help="first-order DDIM or the second-order multistep update")
     parser.add_argument('--guidance_scale', type=float, default=None,
                         help="classifier-free guidance scale of the sampling loops (omitted: no guidance, the reference's sampling)")
+    parser.add_argument('--takes', type=int, default=1,
+                        help="samples per music: one output per take, --npy_path NAME.npy becomes NAME_take<j>.npy (the takes differ "
+                             "through their noise and share the conditioning work of every step)")
     return parser
 
 
@@ -150,8 +153,14 @@ def main(argv=None):
     gkw = {} if args.guidance_scale is None else {"guidance_scale": args.guidance_scale}
     if args.steps is not None or args.solver != "ddim":
         gkw.update(steps=args.steps, spacing=args.spacing, solver=args.solver)
+    if args.takes < 1:
+        raise SystemExit("--takes must be at least 1")
     with torch.no_grad():
         mel, names = load_mels(args.music_path)
+        if args.takes > 1:
+            if args.full_length and mel.shape[-2] > 3 * opt.max_motion_length:
+                raise SystemExit("--takes samples one window per take: it does not combine with --full_length on a longer mel")
+            gkw["takes"] = args.takes
         # [B, T, 26] on the device; --smooth: smooth_motion(kernel=19) (:126) happens in the loop's final write
         if args.full_length and mel.shape[-2] > 3 * opt.max_motion_length:
             pred_motions = trainer.generate_long_music_motion(mel, opt.dim_pose, seed=args.seed, smooth=19 if args.smooth else None, **gkw)
@@ -159,6 +168,16 @@ def main(argv=None):
             pred_motions = trainer.generate_music_motion(mel, opt.dim_pose, seed=args.seed, smooth=19 if args.smooth else None, **gkw)
         B, T = pred_motions.shape[0], pred_motions.shape[1]
         motion = pred_motions.view(B, T, 13, 2).cpu().numpy()
+    if args.takes > 1:      # take-major rows (generate_music_motion): one output per take, each shaped as a single take's
+        per_take = motion.reshape(args.takes, B // args.takes, T, 13, 2)
+        outs = [m[0] if mel.ndim == 2 else m for m in per_take]
+        print(" #%d frames x %d clip(s) x %d takes: %s" % (T, B // args.takes, args.takes, ", ".join(names)))
+        if args.npy_path:
+            stem, ext = os.path.splitext(args.npy_path)
+            for j, o in enumerate(outs):
+                np.save("%s_take%d%s" % (stem, j, ext or ".npy"), o)
+                print("saved", "%s_take%d%s" % (stem, j, ext or ".npy"), o.shape)
+        return np.stack(outs)
     out = motion[0] if mel.ndim == 2 else motion
     print(" #%d frames x %d clip(s): %s" % (T, B, ", ".join(names)))
     if args.npy_path:

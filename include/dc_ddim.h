@@ -283,7 +283,7 @@ DC_EXPORT int dc_sampler_solver_profile_loop(dc_sampler* s, const float* d_noise
  * prediction of every element.  An all-zero mask gives the bits of a loop without known values.  The loops then need the table of
  * dc_ddim_coefficients_known (DC_ERR_INVALID with any other).  The tensors are read while a loop runs and their addresses go through
  * device slots: other tensors on the next call do not re-capture the hipGraph.  The setting serves the following loops until it is
- * cleared - three NULLs - or dc_sampler_set_conditioning / dc_sampler_set_conditioning_guided changes the caller's (B, T) or switches
+ * cleared - three NULLs - or dc_sampler_set_conditioning / _guided / _takes changes the caller's (B, T) or its takes count, or switches
  * guidance on or off (the tensors belong to the conditioning they were set on).  DC_ERR_INVALID: a mask without values, a mask without noise,
  * values or noise without a mask. */
 DC_EXPORT int dc_sampler_set_known(dc_sampler* s, const float* d_known, const float* d_mask, const float* d_known_noise);
@@ -305,6 +305,28 @@ DC_EXPORT int dc_sampler_set_known(dc_sampler* s, const float* d_known, const fl
  * dc_sampler_set_conditioning switches guidance off again.  DC_ERR_INVALID: NULL null vectors. */
 DC_EXPORT int dc_sampler_set_conditioning_guided(dc_sampler* s, const float* d_xf_proj, const float* d_xf_out, const int32_t* h_length,
                                        int32_t B, int32_t T, const float* h_null_proj, const float* h_null_out, void* stream);
+
+/* Several TAKES per music (no counterpart in the reference, whose sampler draws one motion per music and call:
+ * trainers/ddpm_trainer.py:186-200).  dc_sampler_set_conditioning for `takes` >= 1 samples of each of B musics (d_xf_proj, d_xf_out
+ * [B,T,64], h_length[B] as there): the sampler then runs takes * B clips, TAKE-MAJOR - caller clip j * B + b is take j of music b, with
+ * music b's features and length.  Everything the caller hands to the loops and to dc_sampler_set_known is [takes * B, T, P] in that
+ * order: d_noise, d_out, snapshots, step noise, seeded step noise and its first_element, the known tensors.  The takes of one music differ
+ * through their noise alone.  What they share is the conditioning: a loop step has one timestep, so the FiLM scale / shift tiles of take
+ * j are those of take 0 bit for bit, and where one take is a whole number Gc = B T' / 32 of 32-token groups (T' the clip stride,
+ * dc_sampler_clip_stride) the step's FiLM GEMM computes one take's groups and token group g reads the tiles of group g mod Gc - a
+ * `takes`-th of the loop's largest kernel.  Elsewhere (B T' no multiple of 32, Gc = 1 - one clip of at most 32 frames -, DC_PREC_BF16X3,
+ * DC_TAKES_FULL_FILM=1 in the environment) the GEMM covers every group.  Either way the result equals, bit for bit, dc_sampler_set_conditioning on the features tiled `takes`
+ * times.  The one-time pre-pass runs over all takes * B clips.
+ * h_null_proj, h_null_out: both NULL - unguided; both given - guided as dc_sampler_set_conditioning_guided, 2 * takes * B internal clips,
+ * the conditional clips first, then their shadows (which share one null column as there); exactly one NULL: DC_ERR_INVALID.
+ * takes = 1 is dc_sampler_set_conditioning / dc_sampler_set_conditioning_guided, bit for bit.  A plain dc_sampler_set_conditioning
+ * switches takes off.  dc_sampler_denoise and the debug entry points return DC_ERR_INVALID on a conditioning with takes > 1 (their
+ * per-clip timesteps break the sharing).  Known values belong to the (B, T, guided, takes) they were set on.  The captured hipGraph is
+ * keyed by the wrap period as well: 2 takes of 2 musics and a plain conditioning of 4 clips never replay each other's graph.
+ * DC_ERR_INVALID: takes < 1. */
+DC_EXPORT int dc_sampler_set_conditioning_takes(dc_sampler* s, const float* d_xf_proj, const float* d_xf_out, const int32_t* h_length,
+                                                int32_t B, int32_t T, int32_t takes, const float* h_null_proj, const float* h_null_out,
+                                                void* stream);
 
 /* The guidance scale w of the loops on a guided conditioning (same reference lines: transformer.py:389,451-459 train for it, no sampling
  * counterpart).  1 after every dc_sampler_set_conditioning_guided.  Must be finite (DC_ERR_INVALID), and a guided conditioning must be
