@@ -106,12 +106,11 @@ struct dc_sampler : Formats {     // (set_precision(cfg.precision))
     std::vector<int> tab_t, tab_snap;
     std::vector<float> tab_coef_iter;
 
-    // graph cache, keyed by (B, T, Tx, steps per graph, form_key() of the captured launches): the current graph (the last entry) and
+    // graph cache, keyed by the GraphKey loop_plan (dc_form.h) builds for the captured launches: the current graph (the last entry) and
     // up to three parked ones for other batch shapes (a dataset's last, smaller batch; a service whose batch size varies): a shape
     // seen before replays its graph instead of paying a capture (tens of ms) every time the shape changes.  The workspace's
-    // addresses are baked into every captured graph, so whatever re-allocates a buffer drops them all (drop_graph).
-    // (+ the period at which the takes of one music wrap their FiLM tile reads, takes_key_period: 0 without shared takes)
-    using GraphKey = std::tuple<int, int, int, int, unsigned long long, int>;
+    // addresses are baked into every captured graph, so whatever re-allocates a buffer drops them all (drop_graph); find_or_capture
+    // is the cache's only other entry.
     std::vector<std::pair<GraphKey, hipGraphExec_t>> graphs;
     // DDIM update options of the loop being enqueued (dc_sampler_ddim_loop_ex) and the device status word
     int upd_flags = 0;              // DC_UPD_* of the loop being enqueued (incl. the internal NOISY / ZSTEP bits)
@@ -123,12 +122,16 @@ struct dc_sampler : Formats {     // (set_precision(cfg.precision))
     int* d_status = nullptr;
     float* d_x0_prev = nullptr;     // DC_UPD_MULTISTEP: the previous step's predicted x0 [user_B][Tx][P], zeroed when such a loop starts
     size_t cap_x0_prev = 0;
-    // known values (dc_sampler_set_known): the caller's three [B][Tx][P] tensors, valid for clips of (known_B, known_Tx); the kernels read
-    // their addresses from d_kslot
+    // known values (dc_sampler_set_known): the caller's three [B][Tx][P] tensors, valid for the conditioning they were set for; the kernels
+    // read their addresses from d_kslot
     const float *known_val = nullptr, *known_mask = nullptr, *known_noise = nullptr;
-    int known_B = 0, known_Tx = 0;            // the CALLER's clips (user_B()) and frames the tensors were set for ...
-    bool known_guided = false;                // ... and whether that conditioning was guided: any other (B, T, guided) clears them
-    int known_takes = 1;                      // ... and its takes per music: the same clips in another take order are another geometry
+    struct KnownFor {             // the CALLER's clips and frames, whether the conditioning was guided, and its takes per music (the same clips
+        int user_B = 0, Tx = 0;   // in another take order are another geometry): a loop over any other conditioning clears the tensors
+        bool guided = false;
+        int takes = 1;
+        bool operator==(const KnownFor& o) const { return user_B == o.user_B && Tx == o.Tx && guided == o.guided && takes == o.takes; }
+    } known_set_for;
+    KnownFor known_for() const { return {user_B(), Tx, guided, takes}; }      // ... of the current conditioning
     const float** d_kslot = nullptr;
     // Savitzky-Golay smoothing applied by the loop's final write (dc_sampler_set_smoothing; window 0 = off)
     int smooth_window = 0, smooth_order = 0, smooth_table_window = 0;     // (table_window: the hat matrix d_smooth_coef holds)
@@ -141,7 +144,7 @@ struct dc_sampler : Formats {     // (set_precision(cfg.precision))
     float* d_raw = nullptr;         // the last layer's raw model output of all internal clips [B][Tx][P]
     size_t cap_raw = 0;
     float *d_xf2_proj = nullptr, *d_xf2_out = nullptr;      // feature images [B][Tx][64] of the internal batch (second half: the null pair)
-    size_t cap_xf2 = 0;
+    size_t cap_xf2_proj = 0, cap_xf2_out = 0;
     int user_B() const { return guided ? B / 2 : B; }       // clips of the caller's tensors (takes x the musics)
     // Takes (dc_sampler_set_conditioning_takes): the conditional clips are `takes` runs of the same musics, take-major; the feature images of
     // the internal batch live in d_xf2_* as they do for guidance
@@ -193,6 +196,18 @@ int dev_alloc(dc_sampler* s, P*& p, size_t bytes) {
 void drop_graph(dc_sampler* s) {
     for (auto& g : s->graphs) hipGraphExecDestroy(g.second);
     s->graphs.clear();
+}
+
+// Grows one buffer with a capacity of its own to `need` elements of `elem_bytes`.  in_graphs: the buffer's address is an argument of
+// captured launches, so a new one drops the graphs.  The capacity follows dev_alloc's rule: reset first, raised last.
+template <class P>
+int grow(dc_sampler* s, P*& p, size_t& cap, size_t need, size_t elem_bytes, bool in_graphs) {
+    if (need <= cap) return DC_OK;
+    if (in_graphs) drop_graph(s);
+    cap = 0;
+    if (int rc = dev_alloc(s, p, need * elem_bytes)) return rc;
+    cap = need;
+    return DC_OK;
 }
 
 const std::vector<float>* find(dc_sampler* s, const std::string& n) {
@@ -779,18 +794,6 @@ int ensure_steps(dc_sampler* s, int S) {
         }                                                             \
     } while (0)
 
-// Everything a captured graph bakes in besides (B, T, K): the environment switches that pick the launch form (every switch step_form
-// can see: Switches::bits) and the update options of the loop.
-unsigned long long form_key(const dc_sampler* s, const Switches& w) {
-    unsigned long long k = w.bits();
-    k |= (unsigned long long)(s->upd_flags & 0xff) << 16;     // (the noise / known tensors' addresses are not baked in: the kernels read them from d_zslot / d_kslot)
-    k |= (s->l16_own ? 1ull : 0ull) << 24;
-    k |= (unsigned long long)((s->clip_aligned + 1) & 3) << 25;
-    // guided loops: another last-layer store, k_guided_update, and - bit 28 - the FiLM GEMM over the shared column's groups
-    k |= guided_key_bits(s->guided, s->guided && film_share(s->B, s->T, s->G, true, s->takes, !s->split_film, w).groups < s->G);
-    return k;
-}
-
 // One enqueue_step call: the options that decide its form (dc_form.h) and its tensors ...
 struct Step : StepOpts {
     const float* x_src = nullptr;
@@ -919,15 +922,35 @@ int sync_out(dc_sampler* s, hipStream_t user) {
     return DC_OK;
 }
 
-// S iterations; h_t: the timestep the model sees at each ([S], strictly decreasing, validated by the caller; nullptr = S-1 .. 0);
-// h_coef: [S][DC_COEF] scalars of the update PER ITERATION (dc_common.h); flags: DC_UPD_*; d_step_noise: [S][B][Tx][P] or nullptr
-int loop_common(dc_sampler* s, const float* d_noise, float* d_out, int S, const int32_t* h_t, const float* h_coef,
-                const int32_t* h_snap_iters, int n_snap, float* d_snaps_user, hipStream_t user, bool profile,
-                int flags = 0, const float* d_step_noise = nullptr) {
+// What the five public loop entry points pass: run_loop validates the caller's half of it, loop_common runs it
+struct LoopCall {
+    const float* d_noise = nullptr;
+    float* d_out = nullptr;
+    int n = 0;                                // iterations
+    bool listed = false;                      // the entry point takes a timestep list (dc_sampler_solver_loop): h_timesteps is required
+    const int32_t* h_timesteps = nullptr;     // the timestep the model sees at each iteration ([n], strictly decreasing); nullptr = n-1 .. 0
+    const float* h_rows = nullptr;            // [n][DC_COEF] scalars of the update PER ITERATION (dc_common.h)
+    int flags = 0;                            // the caller's DC_UPD_CLIP | DC_UPD_EPS
+    const float* d_step_noise = nullptr;      // [n][B][Tx][P] or nullptr
+    const int32_t* h_snap_iters = nullptr;
+    int n_snap = 0;
+    float* d_snaps = nullptr;
+    bool profile = false;                     // events around every launch of an eager loop, summed per kernel into h_ms / h_count [n_kernels]
+    float* h_ms = nullptr;
+    int32_t* h_count = nullptr;
+    int n_kernels = 0;
+    void* stream = nullptr;
+};
+
+// loop_common, step 1: what the sampler's state refuses.  flags: DC_UPD_*, the caller's + NOISY / MULTISTEP; gains KNOWN
+int loop_validate(dc_sampler* s, const LoopCall& c, int& flags) {
+    const int S = c.n;
+    const float* h_coef = c.h_rows;
+    const bool profile = c.profile;
     if (!s || !s->finalized) return fail(DC_ERR_INVALID, "sampler not finalized");
     if (!s->cond_set) return fail(DC_ERR_INVALID, "dc_sampler_set_conditioning must be called first");
     if (S < 1 || S > s->cfg.max_timesteps) return fail(DC_ERR_INVALID, "num_steps %d outside [1, max_timesteps=%d]", S, s->cfg.max_timesteps);
-    if (!d_noise || !d_out || !h_coef) return fail(DC_ERR_INVALID, "null pointer argument");
+    if (!c.d_noise || !c.d_out || !h_coef) return fail(DC_ERR_INVALID, "null pointer argument");
     // EPSILON model x full attention x eta = 0: outside the 1e-3 bound on some loops even with every GEMM on split operands (scores, weights
     // and values of the attention stay plain fp16, and a deterministic EPSILON chain keeps every evaluation's error in x_t): 2.3e-4 ... 1.26e-3
     // over 14 randomized loops of tools/fuzz_sampler.py (profiles/r06_fuzz_final.txt).  Refused, not returned; with eta > 0 the fresh noise
@@ -935,11 +958,8 @@ int loop_common(dc_sampler* s, const float* d_noise, float* d_out, int S, const 
     if ((flags & DC_UPD_EPS) && s->cfg.no_eff && !(flags & DC_UPD_NOISY) && !getenv("DC_ALLOW_EPSILON_NO_EFF_ETA0"))
         return fail(DC_ERR_UNSUPPORTED, "EPSILON model with full attention (no_eff) at eta = 0 is outside the 1e-3 parity bound (up to 1.3e-3); "
                                         "use linear attention, or eta > 0");
-    // known values (dc_sampler_set_known) serve the loops of the geometry they were set for; another (B, T) clears them
-    // (the caller's geometry: on a guided conditioning B is the internal batch, twice the clips the known tensors hold)
-    // (... and the takes count: the same number of clips in another take order is another geometry)
-    if (s->known_mask && (s->known_B != s->user_B() || s->known_Tx != s->Tx || s->known_guided != s->guided || s->known_takes != s->takes))
-        s->known_val = s->known_mask = s->known_noise = nullptr;
+    // known values (dc_sampler_set_known) serve the loops of the conditioning they were set for; any other clears them
+    if (s->known_mask && !(s->known_set_for == s->known_for())) s->known_val = s->known_mask = s->known_noise = nullptr;
     const bool known = s->known_mask != nullptr;
     if (known && S > 1 && !(h_coef[5] > 0.f))      // (the first iteration's row: abar_prev < 1 there)
         return fail(DC_ERR_INVALID, "known values are set: the loop needs the [S][8] table of dc_ddim_coefficients_known (slot 5 = sqrt(1 - abar_prev))");
@@ -947,15 +967,18 @@ int loop_common(dc_sampler* s, const float* d_noise, float* d_out, int S, const 
     if (known) flags |= DC_UPD_KNOWN;
     if (s->smooth_window > 0 && s->Tx < s->smooth_window)       // (before anything is enqueued: a failed call leaves no work and no half-ordered streams)
         return fail(DC_ERR_INVALID, "smoothing window %d exceeds the %d frames of a clip", s->smooth_window, s->Tx);
+    return DC_OK;
+}
+
+// loop_common, step 2: the loop's buffers, its per-iteration tables and its starting state, enqueued behind the caller's stream.
+// flags gains ZSTEP.  MP: elements of x and of one snapshot, in the caller's layout (guided: its B clips, half the internal batch)
+int loop_prepare(dc_sampler* s, const LoopCall& c, int& flags, size_t MP) {
+    const int S = c.n, n_snap = c.n_snap;
+    const int32_t *h_t = c.h_timesteps, *h_snap_iters = c.h_snap_iters;
+    const float* h_coef = c.h_rows;
     int rc;
     if ((rc = ensure_steps(s, S))) return rc;
-    const size_t MP = (size_t)s->user_B() * s->Tx * s->cfg.input_feats;          // x, snapshots: the caller's layout (guided: its B clips, half the internal batch)
-    if ((size_t)n_snap * MP > s->cap_snap) {          // (capacity in elements: the batch may have grown since the last call)
-        drop_graph(s);
-        s->cap_snap = 0;
-        if ((rc = dev_alloc(s, s->d_snaps, (size_t)n_snap * MP * 4))) return rc;
-        s->cap_snap = (size_t)n_snap * MP;
-    }
+    if ((rc = grow(s, s->d_snaps, s->cap_snap, (size_t)n_snap * MP, 4, true))) return rc;      // (in elements: the batch may have grown since the last call)
     // Per-iteration tables on the device: uploaded only when (S, coefficients, snapshot iterations) differ from the
     // previous call - a sampling service calls the loop with the same schedule every time, and the four small H2D
     // copies + the stream synchronisation they need cost as much as several kernels at bs=1.
@@ -968,32 +991,18 @@ int loop_common(dc_sampler* s, const float* d_noise, float* d_out, int S, const 
     for (int i = 0; i < S; ++i) t_of_iter[i] = h_t ? h_t[i] : S - 1 - i;            // indices = range(num_timesteps)[::-1] (gaussian_diffusion.py:943)
     const bool same_tables = s->tables_S == S && s->tab_snap == snap_of_iter && s->tab_t == t_of_iter &&
                              memcmp(s->tab_coef_iter.data(), h_coef, (size_t)S * DC_COEF * 4) == 0;
-    if (flags & DC_UPD_MULTISTEP) {          // the history of the second-order update: one more [B][Tx][P] buffer, zeroed below
-        if (MP > s->cap_x0_prev) {
-            drop_graph(s);          // (its address is baked into the captured launches)
-            s->cap_x0_prev = 0;
-            if ((rc = dev_alloc(s, s->d_x0_prev, MP * 4))) return rc;
-            s->cap_x0_prev = MP;
-        }
-    }
+    // the history of the second-order update: one more [B][Tx][P] buffer, zeroed below
+    if ((flags & DC_UPD_MULTISTEP) && (rc = grow(s, s->d_x0_prev, s->cap_x0_prev, MP, 4, true))) return rc;
     // eta > 0: the caller's [S][B][Tx][P] draws, or - none given, a seed set - one iteration's draws generated at the head of every step
-    const float* zbase = nullptr;
-    if (flags & DC_UPD_NOISY) {
-        if (d_step_noise) {
-            zbase = d_step_noise;
-        } else {
-            if (MP > s->cap_zstep) {
-                drop_graph(s);          // (the buffer's address is an argument of the captured k_step_noise launches)
-                s->cap_zstep = 0;
-                if ((rc = dev_alloc(s, s->d_zstep, MP * 4))) return rc;
-                s->cap_zstep = MP;
-            }
-            zbase = s->d_zstep;
-            flags |= DC_UPD_ZSTEP;
-        }
+    // (d_zstep is an argument of the captured k_step_noise launches)
+    const float* zbase = (flags & DC_UPD_NOISY) ? c.d_step_noise : nullptr;
+    if ((flags & DC_UPD_NOISY) && !zbase) {
+        if ((rc = grow(s, s->d_zstep, s->cap_zstep, MP, 4, true))) return rc;
+        zbase = s->d_zstep;
+        flags |= DC_UPD_ZSTEP;
     }
     s->upd_flags = flags;
-    if ((rc = sync_in(s, user))) return rc;
+    if ((rc = sync_in(s, (hipStream_t)c.stream))) return rc;
     hipStream_t st = s->stream;
     // the status word reports on THIS loop: bits left by earlier work on the sampler (a dc_sampler_denoise, a loop nobody asked
     // about) must not fail it
@@ -1014,8 +1023,8 @@ int loop_common(dc_sampler* s, const float* d_noise, float* d_out, int S, const 
     }
     HIP_TRY(hipMemsetAsync(s->d_iter, 0, 16, st));
     if (flags & DC_UPD_MULTISTEP) HIP_TRY(hipMemsetAsync(s->d_x0_prev, 0, MP * 4, st));      // (kappa is 0 in the first step: the zeros are read, never used)
-    HIP_TRY(hipMemcpyAsync(s->d_x, d_noise, MP * 4, hipMemcpyDeviceToDevice, st));
-    if (known) {      // x_T of the known elements at the loop's starting level (slots 6, 7 of the first step's row)
+    HIP_TRY(hipMemcpyAsync(s->d_x, c.d_noise, MP * 4, hipMemcpyDeviceToDevice, st));
+    if (flags & DC_UPD_KNOWN) {      // x_T of the known elements at the loop's starting level (slots 6, 7 of the first step's row)
         const float* c0 = h_coef;
         HIP_TRY(dc_launch_set_known(st, s->d_kslot, s->known_val, s->known_mask, s->known_noise));
         HIP_TRY(dc_launch_known_blend(st, s->d_x, s->known_val, s->known_mask, s->known_noise, c0[6], c0[7], MP));
@@ -1024,83 +1033,91 @@ int loop_common(dc_sampler* s, const float* d_noise, float* d_out, int S, const 
         HIP_TRY(hipMemcpyAsync(s->d_x + MP, s->d_x, MP * 4, hipMemcpyDeviceToDevice, st));
         HIP_TRY(dc_launch_set_scale(st, s->d_wslot, s->guide_w));
     }
-    const bool no_graph = getenv("DC_DISABLE_GRAPH") != nullptr;
-    // precise tail: the loop's last `tail` model evaluations on split operands (loop_tail, dc_form.h; DC_PRECISE_TAIL=k overrides)
-    const char* env_tail = getenv("DC_PRECISE_TAIL");
-    const LoopTail lt = loop_tail(settings_of(s), s->tail_split, env_tail ? std::optional<int>(atoi(env_tail)) : std::nullopt, flags, s->Tx, S);
-    const int tail = lt.tail;
-    const bool tail_all = lt.tail_all;
+    return DC_OK;
+}
+
+// The graph cache's lookup: makes the graph of `key` the current one (the last entry) - the current one already, a parked one, or a new
+// capture of what `enqueue` puts on st - and returns it
+template <class F>
+int find_or_capture(dc_sampler* s, hipStream_t st, const GraphKey& key, hipGraphExec_t* out, F&& enqueue) {
+    auto& gs = s->graphs;
+    if (gs.empty() || gs.back().first != key) {
+        if (gs.size() > 3) {        // the current graph is parked: the oldest parked one makes room
+            hipGraphExecDestroy(gs.front().second);
+            gs.erase(gs.begin());
+        }
+        auto it = std::find_if(gs.begin(), gs.end(), [&](const auto& g) { return g.first == key; });
+        if (it != gs.end()) {
+            std::rotate(it, it + 1, gs.end());      // captured before: it becomes the current graph
+        } else {
+            hipGraph_t g = nullptr;
+            HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+            if (int rc = enqueue()) {
+                hipStreamEndCapture(st, &g);
+                if (g) hipGraphDestroy(g);
+                return rc;
+            }
+            HIP_TRY(hipStreamEndCapture(st, &g));
+            hipGraphExec_t exec = nullptr;
+            hipError_t e = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
+            hipGraphDestroy(g);
+            if (e != hipSuccess) return fail(DC_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e));
+            gs.push_back({key, exec});
+        }
+    }
+    *out = gs.back().second;
+    return DC_OK;
+}
+
+// One sampling loop: validate, prepare, plan (loop_plan, dc_form.h: eager or captured, which graphs, how often), then run the plan's
+// parts and write the result.  flags: the caller's DC_UPD_* + NOISY / MULTISTEP as run_loop found them in the rows
+int loop_common(dc_sampler* s, const LoopCall& c, int flags) {
+    int rc;
+    if ((rc = loop_validate(s, c, flags))) return rc;
+    const size_t MP = (size_t)s->user_B() * s->Tx * s->cfg.input_feats;
+    if ((rc = loop_prepare(s, c, flags, MP))) return rc;
+    hipStream_t st = s->stream;
+    const char* env_tail = getenv("DC_PRECISE_TAIL");      // (DC_PRECISE_TAIL=k overrides the sampler's precise tail: loop_tail)
+    LoopOpts lo;
+    lo.S = c.n, lo.flags = flags, lo.guided = s->guided, lo.takes = s->takes, lo.profile = c.profile;
+    lo.no_graph = getenv("DC_DISABLE_GRAPH") != nullptr, lo.tail_split = s->tail_split;
+    if (env_tail) lo.env_tail = atoi(env_tail);
     const Switches sw = Switches::read();
-    // n steps of the loop, the last split_n of them on split operands (graph: the steps of a capture)
-    bool folded = false;            // the last step enqueued looks its timestep up through *d_iter (StepDone::folded)
-    auto enqueue_steps = [&](int n, int split_n, bool graph) -> int {
-        bool embedded = false;      // (a sequence's first step does its own front work, its last step nobody else's)
-        for (int i = 0; i < n; ++i) {
-            Step c;
-            c.loop_mode = true, c.x_src = c.x_dst = s->d_x, c.graph_step = graph ? i : -1, c.split = i >= n - split_n, c.g1_loop = tail > 0;
-            c.next_plain = i + 1 < n - split_n, c.embedded = embedded, c.profile = profile, c.known = known, c.guided = s->guided, c.takes = s->takes;
+    const LoopPlan plan = loop_plan(Geometry{s->B, s->T, s->Tx, s->G, s->num_cu, s->cap_rec_floats}, settings_of(s), sw, lo);
+    for (const LoopPart& part : plan.parts) {
+        auto enqueue_part = [&]() -> int {
+            bool embedded = false;      // (a sequence's first step does its own front work, its last step nobody else's)
             StepDone d;
-            if (int rc = enqueue_step(s, st, c, sw, &d)) return rc;
-            embedded = d.embedded_next, folded = d.folded;
-        }
-        return DC_OK;
-    };
-    if (profile || no_graph) {
-        if ((rc = enqueue_steps(S, tail_all ? S : tail, false))) return rc;
-    } else {
-        const int K = steps_per_graph(S);
-        const int replays = S / K;
-      // (with a precise tail and several replays per loop - S > 64 - the LAST replay runs a second graph whose final steps are split)
-      for (int part = 0; part < ((tail && replays > 1) ? 2 : 1); ++part) {
-        const int tail_here = (part == 1 || replays == 1) ? tail : (tail_all ? K : 0);
-        const int launches = (tail && replays > 1) ? (part == 0 ? replays - 1 : 1) : replays;
-        // (g1 bit: the plain evaluations of a loop WITH a tail read G' scale tiles, those of a loop without one G' - 1 tiles - two
-        // different captures of the same part-0 graph when S > 64)
-        const unsigned long long fk = form_key(s, sw) | ((unsigned long long)tail_here << 40) | ((tail > 0 ? 1ull : 0ull) << 39);
-        const int key_period = takes_key_period(film_share(s->B, s->T, s->G, s->guided, s->takes, !s->split_film, sw));
-        const dc_sampler::GraphKey key{s->B, s->T, s->Tx, K, fk, key_period};
-        auto& gs = s->graphs;
-        if (gs.empty() || gs.back().first != key) {
-            if (gs.size() > 3) {        // the current graph is parked: the oldest parked one makes room
-                hipGraphExecDestroy(gs.front().second);
-                gs.erase(gs.begin());
+            for (int i = 0; i < part.steps; ++i) {
+                Step step;
+                static_cast<StepOpts&>(step) = loop_step(plan, part, lo, i);
+                step.embedded = embedded, step.x_src = step.x_dst = s->d_x;
+                if (int rc = enqueue_step(s, st, step, sw, &d)) return rc;
+                embedded = d.embedded_next;
             }
-            auto it = std::find_if(gs.begin(), gs.end(), [&](const auto& g) { return g.first == key; });
-            if (it != gs.end()) {
-                std::rotate(it, it + 1, gs.end());      // captured before: it becomes the current graph
-            } else {
-                hipGraph_t g = nullptr;
-                HIP_TRY(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-                rc = enqueue_steps(K, tail_here, true);
-                // steps that indexed the iteration tables themselves did not advance the counter (see enqueue_step)
-                if (!rc && folded)
-                    if (hipError_t ea = dc_launch_advance_iter(st, s->d_iter, K)) rc = fail(DC_ERR_HIP, "k_advance_iter: %s", hipGetErrorString(ea));
-                if (rc) {
-                    hipStreamEndCapture(st, &g);
-                    if (g) hipGraphDestroy(g);
-                    return rc;
-                }
-                HIP_TRY(hipStreamEndCapture(st, &g));
-                hipGraphExec_t exec = nullptr;
-                hipError_t e = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
-                hipGraphDestroy(g);
-                if (e != hipSuccess) return fail(DC_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e));
-                gs.push_back({key, exec});
-            }
+            // captured steps that indexed the iteration tables themselves did not advance the counter (see enqueue_step)
+            if (!plan.eager && d.folded)
+                if (hipError_t ea = dc_launch_advance_iter(st, s->d_iter, part.steps)) return fail(DC_ERR_HIP, "k_advance_iter: %s", hipGetErrorString(ea));
+            return DC_OK;
+        };
+        if (plan.eager) {
+            if ((rc = enqueue_part())) return rc;
+            continue;
         }
-        for (int i = 0; i < launches; ++i) HIP_TRY(hipGraphLaunch(gs.back().second, st));
-      }
+        hipGraphExec_t graph = nullptr;
+        if ((rc = find_or_capture(s, st, part.key, &graph, enqueue_part))) return rc;
+        for (int i = 0; i < part.launches; ++i) HIP_TRY(hipGraphLaunch(graph, st));
     }
     // the final write x0 -> the caller's tensor: a copy, or (dc_sampler_set_smoothing) the Savitzky-Golay filter along time
     // (tools/visualization.py:20-26,126) reading the loop's x0 and writing the caller's tensor directly - no pass of its own
     if (s->smooth_window > 0) {
-        HIP_TRY(dc_launch_savgol(st, s->d_x, d_out, s->d_smooth_coef, s->user_B(), s->Tx, s->cfg.input_feats, s->smooth_window));      // (guided: the first half)
+        HIP_TRY(dc_launch_savgol(st, s->d_x, c.d_out, s->d_smooth_coef, s->user_B(), s->Tx, s->cfg.input_feats, s->smooth_window));      // (guided: the first half)
     } else {
-        HIP_TRY(hipMemcpyAsync(d_out, s->d_x, MP * 4, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(c.d_out, s->d_x, MP * 4, hipMemcpyDeviceToDevice, st));
     }
-    if (n_snap > 0 && d_snaps_user)
-        HIP_TRY(hipMemcpyAsync(d_snaps_user, s->d_snaps, (size_t)n_snap * MP * 4, hipMemcpyDeviceToDevice, st));
-    return sync_out(s, user);
+    if (c.n_snap > 0 && c.d_snaps)
+        HIP_TRY(hipMemcpyAsync(c.d_snaps, s->d_snaps, (size_t)c.n_snap * MP * 4, hipMemcpyDeviceToDevice, st));
+    return sync_out(s, (hipStream_t)c.stream);
 }
 
 // A public per-TIMESTEP table [S][width] (width 4: dc_ddim_coefficients, sigma = 0; 8: dc_ddim_coefficients_ex / _known) as the rows
@@ -1129,31 +1146,6 @@ void ddim_row8(double a64, bool last, double an64, float eta, float* c) {
     c[7] = sqrtf(1.0f - a);
 }
 
-// dc_sampler_solver_loop and its profiled twin: validation of the caller's list and rows, then loop_common
-int solver_loop(dc_sampler* s, const float* d_noise, float* d_out, int n, const int32_t* h_t, const float* h_rows, int flags,
-                const float* d_step_noise, const int32_t* h_snap_iters, int n_snap, float* d_snaps, void* stream, bool profile) {
-    if (!s) return fail(DC_ERR_INVALID, "null sampler");
-    if (n_snap < 0 || (n_snap > 0 && (!h_snap_iters || !d_snaps))) return fail(DC_ERR_INVALID, "bad snapshot arguments");
-    if (flags & ~(DC_UPD_CLIP | DC_UPD_EPS)) return fail(DC_ERR_INVALID, "unknown update flags 0x%x", flags);
-    if (!h_t || !h_rows) return fail(DC_ERR_INVALID, "null pointer argument");
-    if (n < 1 || n > s->cfg.max_timesteps) return fail(DC_ERR_INVALID, "%d timesteps outside [1, max_timesteps=%d]", n, s->cfg.max_timesteps);
-    bool noisy = false, multi = false;
-    for (int i = 0; i < n; ++i) {
-        if (h_t[i] < 0 || h_t[i] >= s->cfg.max_timesteps || (i > 0 && h_t[i] >= h_t[i - 1]))
-            return fail(DC_ERR_INVALID, "timesteps must be strictly decreasing inside [0, max_timesteps=%d): entry %d is %d", s->cfg.max_timesteps, i, h_t[i]);
-        noisy = noisy || h_rows[(size_t)DC_COEF * i + 4] != 0.f;
-        multi = multi || h_rows[(size_t)DC_COEF * i + 8] != 0.f;
-    }
-    if (multi && (h_rows[8] != 0.f || h_rows[(size_t)DC_COEF * (n - 1) + 8] != 0.f))
-        return fail(DC_ERR_INVALID, "the history coefficient (slot 8) must be 0 in the first row (no history yet) and in the last (the final sample is the model's x0)");
-    if (multi && noisy) return fail(DC_ERR_INVALID, "the second-order multistep update is deterministic: rows with a history coefficient need sigma = 0 (eta = 0)");
-    if (noisy && !d_step_noise && !s->noise_seed_set)
-        return fail(DC_ERR_INVALID, "sigma != 0 (eta > 0) needs the per-iteration noise: the tensor d_step_noise [n][B][T][P], or a seed "
-                    "(dc_sampler_set_step_noise_seed) for draws generated step by step");
-    return loop_common(s, d_noise, d_out, n, h_t, h_rows, h_snap_iters, n_snap, d_snaps, (hipStream_t)stream, profile,
-                       flags | (noisy ? DC_UPD_NOISY : 0) | (multi ? DC_UPD_MULTISTEP : 0), noisy ? d_step_noise : nullptr);
-}
-
 // the per-kernel sums of a profiled loop's events (dc_sampler_profile_loop, dc_sampler_solver_profile_loop)
 int collect_profile(dc_sampler* s, float* h_ms, int32_t* h_count, int n) {
     HIP_TRY(hipStreamSynchronize(s->stream));
@@ -1174,6 +1166,37 @@ int collect_profile(dc_sampler* s, float* h_ms, int32_t* h_count, int n) {
     s->prof.ev.clear();
     s->prof.ids.clear();
     return DC_OK;
+}
+
+// The one loop call behind the five public entry points: the checks of the caller's arguments, then loop_common (and, profiled, the sums)
+int run_loop(dc_sampler* s, const LoopCall& c) {
+    if (c.profile && (!s || !c.h_ms || !c.h_count)) return fail(DC_ERR_INVALID, "null argument");
+    if (s) HIP_TRY(hipSetDevice(s->cfg.device));
+    if (c.profile) s->prof.ev.clear(), s->prof.ids.clear();
+    if (c.listed && !s) return fail(DC_ERR_INVALID, "null sampler");
+    if (c.n_snap < 0 || (c.n_snap > 0 && (!c.h_snap_iters || !c.d_snaps))) return fail(DC_ERR_INVALID, "bad snapshot arguments");
+    if (c.flags & ~(DC_UPD_CLIP | DC_UPD_EPS)) return fail(DC_ERR_INVALID, "unknown update flags 0x%x", c.flags);
+    const int32_t* h_t = c.h_timesteps;
+    if (c.listed) {
+        if (!h_t || !c.h_rows) return fail(DC_ERR_INVALID, "null pointer argument");
+        if (c.n < 1 || c.n > s->cfg.max_timesteps) return fail(DC_ERR_INVALID, "%d timesteps outside [1, max_timesteps=%d]", c.n, s->cfg.max_timesteps);
+    }
+    // (a table converted by rows_of_table has no slot 8: only a caller's rows can ask for the multistep update)
+    bool noisy = false, multi = false;
+    for (int i = 0; c.h_rows && i < c.n; ++i) {
+        if (c.listed && (h_t[i] < 0 || h_t[i] >= s->cfg.max_timesteps || (i > 0 && h_t[i] >= h_t[i - 1])))
+            return fail(DC_ERR_INVALID, "timesteps must be strictly decreasing inside [0, max_timesteps=%d): entry %d is %d", s->cfg.max_timesteps, i, h_t[i]);
+        noisy = noisy || c.h_rows[(size_t)DC_COEF * i + 4] != 0.f;
+        multi = multi || c.h_rows[(size_t)DC_COEF * i + 8] != 0.f;
+    }
+    if (multi && (c.h_rows[8] != 0.f || c.h_rows[(size_t)DC_COEF * (c.n - 1) + 8] != 0.f))
+        return fail(DC_ERR_INVALID, "the history coefficient (slot 8) must be 0 in the first row (no history yet) and in the last (the final sample is the model's x0)");
+    if (multi && noisy) return fail(DC_ERR_INVALID, "the second-order multistep update is deterministic: rows with a history coefficient need sigma = 0 (eta = 0)");
+    if (noisy && !c.d_step_noise && !(s && s->noise_seed_set))
+        return fail(DC_ERR_INVALID, "sigma != 0 (eta > 0) needs the per-iteration noise: the tensor d_step_noise [%s][B][T][P], or a seed "
+                    "(dc_sampler_set_step_noise_seed) for draws generated step by step", c.listed ? "n" : "S");
+    const int rc = loop_common(s, c, c.flags | (noisy ? DC_UPD_NOISY : 0) | (multi ? DC_UPD_MULTISTEP : 0));
+    return (rc || !c.profile) ? rc : collect_profile(s, c.h_ms, c.h_count, c.n_kernels);
 }
 
 // dc_sampler_denoise; the debug entry points run it with their test hooks
@@ -1504,7 +1527,7 @@ int dc_sampler_set_conditioning(dc_sampler* s, const float* d_xf_proj, const flo
     // a plain conditioning switches guidance and takes off (a failed call on such a sampler leaves no conditioning set: the internal
     // batch may be half rebuilt)
     if (s && (s->guided || s->takes > 1)) s->guided = false, s->takes = 1, s->cond_set = rc == DC_OK;
-    return rc;      // (known values set on the guided / takes conditioning are dropped by the next loop: known_guided, known_takes)
+    return rc;      // (known values set on the guided / takes conditioning are dropped by the next loop: known_set_for)
 }
 
 // The conditionings whose internal batch is built here: `takes` runs of the caller's B clips (take-major), then - guided - as many
@@ -1523,12 +1546,9 @@ static int set_conditioning_images(dc_sampler* s, const float* d_xf_proj, const 
     // the feature images of the internal clips: the caller's B, `takes` times, then every frame of the shadows carrying the null pair
     const size_t rows = (size_t)B * T, crows = rows * takes, irows = (size_t)Bi * T;
     int rc;
-    if (irows * 64 > s->cap_xf2) {
-        s->cap_xf2 = 0;
-        if ((rc = dev_alloc(s, s->d_xf2_proj, irows * 64 * 4))) return rc;
-        if ((rc = dev_alloc(s, s->d_xf2_out, irows * 64 * 4))) return rc;
-        s->cap_xf2 = irows * 64;
-    }
+    // (no captured launch reads the two images: the pre-pass below runs on the stream itself)
+    if ((rc = grow(s, s->d_xf2_proj, s->cap_xf2_proj, irows * 64, 4, false))) return rc;
+    if ((rc = grow(s, s->d_xf2_out, s->cap_xf2_out, irows * 64, 4, false))) return rc;
     hipStream_t user = (hipStream_t)stream;
     for (int j = 0; j < takes; ++j) {
         HIP_TRY(hipMemcpyAsync(s->d_xf2_proj + (size_t)j * rows * 64, d_xf_proj, rows * 64 * 4, hipMemcpyDeviceToDevice, user));
@@ -1547,13 +1567,7 @@ static int set_conditioning_images(dc_sampler* s, const float* d_xf_proj, const 
     if ((rc = set_conditioning(s, s->d_xf2_proj, s->d_xf2_out, h_length ? len2.data() : nullptr, (int)Bi, T, stream))) return rc;
     s->cond_set = false;
     if (guided) {
-        const size_t raw = irows * s->cfg.input_feats;
-        if (raw > s->cap_raw) {
-            drop_graph(s);          // (the buffer's address is an argument of the captured launches)
-            s->cap_raw = 0;
-            if ((rc = dev_alloc(s, s->d_raw, raw * 4))) return rc;
-            s->cap_raw = raw;
-        }
+        if ((rc = grow(s, s->d_raw, s->cap_raw, irows * s->cfg.input_feats, 4, true))) return rc;
         if (!s->d_wslot && (rc = dev_alloc(s, s->d_wslot, 16))) return rc;
         s->guide_w = 1.f;
         // guided takes: the FiLM GEMM over one take and the null column reads an operand image of its own (whatever the switches say
@@ -1561,12 +1575,7 @@ static int set_conditioning_images(dc_sampler* s, const float* d_xf_proj, const 
         const FilmShare sh = film_share(s->B, s->T, s->G, true, takes, !s->split_film, Switches{});
         if (sh.period < sh.wrap) {
             const size_t gbytes = (size_t)32 * 64 * 8 * 4;      // one group of d_pp (ensure_workspace)
-            if ((size_t)sh.groups > s->cap_pp_share) {
-                drop_graph(s);
-                s->cap_pp_share = 0;
-                if ((rc = dev_alloc(s, s->d_pp_share, (size_t)sh.groups * gbytes))) return rc;
-                s->cap_pp_share = (size_t)sh.groups;
-            }
+            if ((rc = grow(s, s->d_pp_share, s->cap_pp_share, (size_t)sh.groups, gbytes, true))) return rc;
             char* dst = reinterpret_cast<char*>(s->d_pp_share);
             const char* src = reinterpret_cast<const char*>(s->d_pp);
             HIP_TRY(hipMemcpyAsync(dst, src, (size_t)sh.period * gbytes, hipMemcpyDeviceToDevice, user));
@@ -1762,33 +1771,29 @@ int dc_sampler_denoise(dc_sampler* s, const float* d_x, const int32_t* h_timeste
 
 int dc_sampler_ddim_loop(dc_sampler* s, const float* d_noise, float* d_out, int32_t num_steps, const float* h_coef,
                          const int32_t* h_snap_iters, int32_t n_snap, float* d_snaps, void* stream) {
-    if (s) HIP_TRY(hipSetDevice(s->cfg.device));
-    if (n_snap < 0 || (n_snap > 0 && (!h_snap_iters || !d_snaps))) return fail(DC_ERR_INVALID, "bad snapshot arguments");
     const std::vector<float> rows = rows_of_table(h_coef, num_steps, 4);
-    return loop_common(s, d_noise, d_out, num_steps, nullptr, h_coef ? rows.data() : nullptr, h_snap_iters, n_snap, d_snaps, (hipStream_t)stream, false);
+    LoopCall c;
+    c.d_noise = d_noise, c.d_out = d_out, c.n = num_steps, c.h_rows = h_coef ? rows.data() : nullptr;
+    c.h_snap_iters = h_snap_iters, c.n_snap = n_snap, c.d_snaps = d_snaps, c.stream = stream;
+    return run_loop(s, c);
 }
 
 int dc_sampler_ddim_loop_ex(dc_sampler* s, const float* d_noise, float* d_out, int32_t num_steps, const float* h_coef8,
                             int32_t flags, const float* d_step_noise, const int32_t* h_snap_iters, int32_t n_snap, float* d_snaps,
                             void* stream) {
-    if (s) HIP_TRY(hipSetDevice(s->cfg.device));
-    if (n_snap < 0 || (n_snap > 0 && (!h_snap_iters || !d_snaps))) return fail(DC_ERR_INVALID, "bad snapshot arguments");
-    if (flags & ~(DC_UPD_CLIP | DC_UPD_EPS)) return fail(DC_ERR_INVALID, "unknown update flags 0x%x", flags);
-    bool noisy = false;
-    if (h_coef8 && num_steps > 0)
-        for (int t = 0; t < num_steps; ++t) noisy = noisy || h_coef8[(size_t)8 * t + 4] != 0.f;
-    if (noisy && !d_step_noise && !(s && s->noise_seed_set))
-        return fail(DC_ERR_INVALID, "sigma != 0 (eta > 0) needs the per-iteration noise: the tensor d_step_noise [S][B][T][P], or a seed "
-                    "(dc_sampler_set_step_noise_seed) for draws generated step by step");
     const std::vector<float> rows = rows_of_table(h_coef8, num_steps, 8);
-    return loop_common(s, d_noise, d_out, num_steps, nullptr, h_coef8 ? rows.data() : nullptr, h_snap_iters, n_snap, d_snaps, (hipStream_t)stream, false,
-                       flags | (noisy ? DC_UPD_NOISY : 0), noisy ? d_step_noise : nullptr);
+    LoopCall c;
+    c.d_noise = d_noise, c.d_out = d_out, c.n = num_steps, c.h_rows = h_coef8 ? rows.data() : nullptr, c.flags = flags, c.d_step_noise = d_step_noise;
+    c.h_snap_iters = h_snap_iters, c.n_snap = n_snap, c.d_snaps = d_snaps, c.stream = stream;
+    return run_loop(s, c);
 }
 
 int dc_sampler_solver_loop(dc_sampler* s, const float* d_noise, float* d_out, int32_t n, const int32_t* h_timesteps, const float* h_rows,
                            int32_t flags, const float* d_step_noise, const int32_t* h_snap_iters, int32_t n_snap, float* d_snaps, void* stream) {
-    if (s) HIP_TRY(hipSetDevice(s->cfg.device));
-    return solver_loop(s, d_noise, d_out, n, h_timesteps, h_rows, flags, d_step_noise, h_snap_iters, n_snap, d_snaps, stream, false);
+    LoopCall c;
+    c.d_noise = d_noise, c.d_out = d_out, c.n = n, c.listed = true, c.h_timesteps = h_timesteps, c.h_rows = h_rows, c.flags = flags;
+    c.d_step_noise = d_step_noise, c.h_snap_iters = h_snap_iters, c.n_snap = n_snap, c.d_snaps = d_snaps, c.stream = stream;
+    return run_loop(s, c);
 }
 
 int dc_sampler_set_known(dc_sampler* s, const float* d_known, const float* d_mask, const float* d_known_noise) {
@@ -1802,7 +1807,7 @@ int dc_sampler_set_known(dc_sampler* s, const float* d_known, const float* d_mas
     if (!d_mask) return fail(DC_ERR_INVALID, "known values: values or noise without a mask (d_mask is NULL)");
     if (!s->cond_set) return fail(DC_ERR_INVALID, "dc_sampler_set_conditioning must be called first: known values belong to its (B, T)");
     s->known_val = d_known, s->known_mask = d_mask, s->known_noise = d_known_noise;
-    s->known_B = s->user_B(), s->known_Tx = s->Tx, s->known_guided = s->guided, s->known_takes = s->takes;
+    s->known_set_for = s->known_for();
     return DC_OK;
 }
 
@@ -1873,24 +1878,19 @@ int dc_sampler_status(dc_sampler* s, int32_t* h_status, int32_t clear) {
 
 int dc_sampler_profile_loop(dc_sampler* s, const float* d_noise, float* d_out, int32_t num_steps, const float* h_coef,
                             float* h_ms, int32_t* h_count, int32_t n, void* stream) {
-    if (!s || !h_ms || !h_count) return fail(DC_ERR_INVALID, "null argument");
-    HIP_TRY(hipSetDevice(s->cfg.device));
-    s->prof.ev.clear();
-    s->prof.ids.clear();
     const std::vector<float> rows = rows_of_table(h_coef, num_steps, 4);
-    int rc = loop_common(s, d_noise, d_out, num_steps, nullptr, h_coef ? rows.data() : nullptr, nullptr, 0, nullptr, (hipStream_t)stream, true);
-    if (rc) return rc;
-    return collect_profile(s, h_ms, h_count, n);
+    LoopCall c;
+    c.d_noise = d_noise, c.d_out = d_out, c.n = num_steps, c.h_rows = h_coef ? rows.data() : nullptr, c.stream = stream;
+    c.profile = true, c.h_ms = h_ms, c.h_count = h_count, c.n_kernels = n;
+    return run_loop(s, c);
 }
 
 int dc_sampler_solver_profile_loop(dc_sampler* s, const float* d_noise, float* d_out, int32_t n, const int32_t* h_timesteps, const float* h_rows,
                                    int32_t flags, float* h_ms, int32_t* h_count, int32_t n_kernels, void* stream) {
-    if (!s || !h_ms || !h_count) return fail(DC_ERR_INVALID, "null argument");
-    HIP_TRY(hipSetDevice(s->cfg.device));
-    s->prof.ev.clear();
-    s->prof.ids.clear();
-    if (int rc = solver_loop(s, d_noise, d_out, n, h_timesteps, h_rows, flags, nullptr, nullptr, 0, nullptr, stream, true)) return rc;
-    return collect_profile(s, h_ms, h_count, n_kernels);
+    LoopCall c;
+    c.d_noise = d_noise, c.d_out = d_out, c.n = n, c.listed = true, c.h_timesteps = h_timesteps, c.h_rows = h_rows, c.flags = flags, c.stream = stream;
+    c.profile = true, c.h_ms = h_ms, c.h_count = h_count, c.n_kernels = n_kernels;
+    return run_loop(s, c);
 }
 
 int dc_sampler_debug_denoise(dc_sampler* s, const float* d_x, const int32_t* h_timesteps, float* d_out,

@@ -1,13 +1,16 @@
 // dc_form.h - host-only: which form a denoiser evaluation takes (no kernels, no HIP call, no side effect).  step_form decides the
 // launch form of one evaluation from the geometry, the sampler's settings, the environment switches and the step's options;
-// clip_stride, steps_per_graph and loop_tail decide the workspace stride, the graph size and the precise tail of a loop.  dc_api.hip
-// launches what they say; tests/form_probe.cpp checks the rule on the CPU (tests/test_host_form.py).
+// clip_stride, steps_per_graph and loop_tail decide the workspace stride, the graph size and the precise tail of a loop; loop_plan
+// decides a whole loop - eager or captured, its graphs, their keys and replays - and loop_step the options of each of its steps.
+// dc_api.hip launches what they say; tests/form_probe.cpp checks the rules on the CPU (tests/test_host_form.py, _known, _guided, _takes).
 #pragma once
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <optional>
 #include <string>
+#include <tuple>
+#include <vector>
 
 #include "dc_common.h"
 
@@ -27,7 +30,7 @@ struct Formats {
 };
 
 // The environment switches that select a launch form or a stride.  One list: the fields, read() and bits() are made from it, so a
-// switch step_form can see is in the graph key (form_key, dc_api.hip) by construction.  read() is called once per API call that
+// switch step_form can see is in the graph key (loop_plan) by construction.  read() is called once per API call that
 // enqueues or sizes the workspace and is never cached: one process can A/B the switches between calls (a change re-captures).
 #define DC_FORM_SWITCHES(X)                                                                                                            \
     X(no_wgrec, "DC_NO_WGREC") X(no_narrow, "DC_NO_NARROW") X(no_align, "DC_NO_ALIGN") X(align, "DC_ALIGN")                          \
@@ -68,7 +71,7 @@ struct Geometry {
     size_t cap_rec_floats = 0;            // rec_capacity of the workspace
 };
 
-// what a guided loop adds to the key of its captured graph (form_key, dc_api.hip; bits 27 and 28): the guided bit - another store in the
+// what a guided loop adds to the key of its captured graph (loop_plan; bits 27 and 28): the guided bit - another store in the
 // last layer, k_guided_update behind it - and the shared-column bit - the FiLM GEMM's group count and the mapping of the tile reads
 inline unsigned long long guided_key_bits(bool guided, bool shared_film) {
     return (guided ? 1ull << 27 : 0ull) | ((guided && shared_film) ? 1ull << 28 : 0ull);
@@ -172,7 +175,7 @@ inline FilmShare film_share(int B, int T, int G, bool guided, int takes, bool fi
 // period >= 2, so that m fits 32 bits.
 // 0 where nothing wraps (period == wrap): the quotient is then 0 and the kernels read g itself.
 inline unsigned film_magic(int period, int wrap) { return period < wrap ? (unsigned)((1ull << 32) / (unsigned)period) + 1u : 0u; }
-// what takes add to the key of a captured graph (dc_api.hip, GraphKey): the period the tile reads wrap at, 0 where no take shares another's
+// what takes add to the key of a captured graph (GraphKey, loop_plan): the period the tile reads wrap at, 0 where no take shares another's
 // tiles - 2 takes x 2 musics and a plain 4-clip conditioning have one internal geometry and different launches
 inline int takes_key_period(const FilmShare& f) { return f.period < f.wrap ? f.period : 0; }
 
@@ -358,4 +361,68 @@ inline LoopTail loop_tail(const Settings& s, int tail_split, std::optional<int> 
     // (a tail of the whole loop splits every replay's graph; any shorter one lives in the last replay and is clipped to its steps)
     const bool tail_all = tail >= S;
     return {std::max(0, std::min(tail, std::min(S, steps_per_graph(S)))), tail_all};
+}
+
+// ---- the loop: which graphs it replays how often, and what each of their steps is (dc_api.hip's loop_common executes the plan) ----------
+// What a captured graph bakes in: (B, T, Tx, steps, form bits, takes_key_period).  The form bits, built in loop_plan alone:
+//   0 .. 15  the environment switches (Switches::bits: every switch step_form can see)
+//   16 .. 23 the loop's DC_UPD_* flags (the noise / known tensors' addresses are not baked in: the kernels read them from their slots)
+//   24       l16_own            25, 26  clip_aligned + 1            27, 28  guided_key_bits
+//   39       the loop has a precise tail: its plain evaluations read G' scale tiles, those of a loop without one G' - 1 tiles
+//   40 ..    the split evaluations at the end of this graph
+using GraphKey = std::tuple<int, int, int, int, unsigned long long, int>;
+
+struct LoopOpts {
+    int S = 1;                    // iterations
+    int flags = 0;                // DC_UPD_* of the loop, the internal NOISY / ZSTEP / MULTISTEP / KNOWN bits resolved
+    bool guided = false;          // the conditioning (StepOpts::guided, ::takes)
+    int takes = 1;
+    bool profile = false;         // events around every launch: an eager loop
+    bool no_graph = false;        // DC_DISABLE_GRAPH: an eager loop
+    int tail_split = -1;          // loop_tail's arguments
+    std::optional<int> env_tail;
+};
+struct LoopPart {
+    int steps = 0;                // steps of one enqueue sequence (captured: of the graph) ...
+    int split_n = 0;              // ... the last split_n of them on split operands
+    int launches = 1;             // replays of the graph
+    GraphKey key{};               // captured parts
+};
+struct LoopPlan {
+    bool g1_loop = false;         // the loop has a precise tail
+    bool eager = false;           // one part, enqueued on the stream itself
+    std::vector<LoopPart> parts;
+};
+inline LoopPlan loop_plan(const Geometry& g, const Settings& s, const Switches& w, const LoopOpts& o) {
+    const LoopTail lt = loop_tail(s, o.tail_split, o.env_tail, o.flags, g.Tx, o.S);
+    LoopPlan p;
+    p.g1_loop = lt.tail > 0, p.eager = o.profile || o.no_graph;
+    if (p.eager) {
+        p.parts.push_back({o.S, lt.tail_all ? o.S : lt.tail, 1, GraphKey{}});
+        return p;
+    }
+    const FilmShare share = film_share(g.B, g.T, g.G, o.guided, o.takes, !s.fmt.split_film, w);
+    const unsigned long long bits = w.bits() | (unsigned long long)(o.flags & 0xff) << 16 | (s.l16_own ? 1ull : 0ull) << 24 |
+                                    (unsigned long long)((s.clip_aligned + 1) & 3) << 25 | guided_key_bits(o.guided, share.groups < g.G) |
+                                    (p.g1_loop ? 1ull : 0ull) << 39;
+    const int K = steps_per_graph(o.S), replays = o.S / K;
+    const auto part = [&](int split_n, int launches) {
+        p.parts.push_back({K, split_n, launches, GraphKey{g.B, g.T, g.Tx, K, bits | (unsigned long long)split_n << 40, takes_key_period(share)}});
+    };
+    // (with a precise tail and several replays per loop - S > 64 - the LAST replay runs a second graph whose final steps are split)
+    if (lt.tail && replays > 1) {
+        part(lt.tail_all ? K : 0, replays - 1);
+        part(lt.tail, 1);
+    } else {
+        part(replays == 1 ? lt.tail : (lt.tail_all ? K : 0), replays);
+    }
+    return p;
+}
+// step i of a part (`embedded` is the executor's: StepDone::embedded_next of step i - 1)
+inline StepOpts loop_step(const LoopPlan& p, const LoopPart& part, const LoopOpts& o, int i) {
+    StepOpts c;
+    c.loop_mode = true, c.graph_step = p.eager ? -1 : i, c.split = i >= part.steps - part.split_n, c.g1_loop = p.g1_loop;
+    c.next_plain = i + 1 < part.steps - part.split_n, c.profile = o.profile, c.known = (o.flags & DC_UPD_KNOWN) != 0;
+    c.guided = o.guided, c.takes = o.takes;
+    return c;
 }

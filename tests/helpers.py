@@ -1,5 +1,8 @@
 """Shared test utilities (tests may import oracle/; the product may not)."""
+import json
 import os
+import shutil
+import subprocess
 import sys
 
 import numpy as np
@@ -44,6 +47,50 @@ def cpu_gemm_matches_fixtures():
     if "gemm" not in _cache:
         _cache["gemm"] = bool(np.array_equal(cpu_gemm_probe(), golden("g0_cpu_gemm_probe.npz")["y"]))
     return _cache["gemm"]
+
+
+def form_probe(tmp_path_factory):
+    """tests/form_probe.cpp, compiled once per session with the host compiler: run(*cases) -> what csrc/dc_form.h decides for each
+    case, a list of dicts (one JSON line per case; DC_* variables of the caller's environment do not reach the probe)."""
+    import pytest
+
+    from diffusion_conductor_amd import native
+    if "form_probe" not in _cache:
+        cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++") or "/opt/rocm/lib/llvm/bin/clang++"
+        if not os.path.exists(cxx):
+            pytest.skip("no C++ compiler")
+        exe = str(tmp_path_factory.mktemp("form") / "form_probe")
+        subprocess.run([cxx, "-std=c++17", "-O1", "-I", native.CSRC, os.path.join(ROOT, "tests", "form_probe.cpp"), "-o", exe], check=True)
+        _cache["form_probe"] = exe
+
+    def run(*cases):
+        env = {k: v for k, v in os.environ.items() if not k.startswith("DC_")}
+        out = subprocess.run([_cache["form_probe"]], input="\n".join(cases) + "\n", env=env, check=True, capture_output=True, text=True).stdout
+        res = [json.loads(ln) for ln in out.splitlines()]
+        assert len(res) == len(cases)
+        return res
+    return run
+
+
+# the fields of StepForm tests/form_probe.cpp prints for every step (the modules that compare whole answers name the ones they mean)
+STEP_FORM_FIELDS = ("ss", "film_tail", "fs", "ff", "fuse_silu", "folded", "adapt", "wgr", "narrow", "aligned", "layer16", "l16_shared", "upc",
+                    "upc16", "upc_narrow", "nwg", "rec_stride", "mixed_form", "embed_next", "fuse_embed", "fuse_extra", "g1_tiles", "upd_flags",
+                    "nl_run", "stop_stage")
+# ... and what the tests of guidance and of takes compare of a step (the probe prints more: a module names the fields it means)
+GUIDED_FIELDS = ("stride", "G", "error", "switch_bits", "key_bits") + STEP_FORM_FIELDS + ("guided", "shared_film", "film_groups")
+TAKES_FIELDS = ("B", "stride", "G", "error", "switch_bits", "key_bits", "key_period", "share_period", "share_wrap", "share_groups") + \
+    STEP_FORM_FIELDS + ("guided", "shared_film", "film_groups", "film_period", "film_wrap")
+
+
+def loop_step_probe(tmp_path_factory, fields=None):
+    """form_probe for cases that are a captured loop step with a plain successor, in a loop with a tail (a case may say otherwise);
+    `fields`: the keys of an answer to keep (the reciprocal's cases, magic_period=, are kept whole)."""
+    run = form_probe(tmp_path_factory)
+
+    def steps(*cases):
+        res = run(*["form loop=1 graph_step=0 g1_loop=1 next_plain=1 " + c for c in cases])
+        return [r if fields is None or "magic" in r else {k: r[k] for k in fields} for r in res]
+    return steps
 
 
 def state_dict_np():

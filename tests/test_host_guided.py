@@ -1,18 +1,11 @@
 """Classifier-free guidance, the host half (no GPU): the checker of the GPU tests (helpers_guided.ddim_guided_loop) against the oracle's
-own loop, and the launch rule with StepOpts::guided (csrc/dc_form.h through tests/guided_form_probe.cpp) for the internal shapes of
+own loop, and the launch rule with StepOpts::guided (csrc/dc_form.h through tests/form_probe.cpp) for the internal shapes of
 tests/test_gpu_guided.py."""
-import json
-import os
-import shutil
-import subprocess
-
 import pytest
 import torch
 
-from helpers import O, ROOT, batch_noise, oracle_params, rel_l2, xf_pair
+from helpers import GUIDED_FIELDS, O, batch_noise, loop_step_probe, oracle_params, rel_l2, xf_pair
 from helpers_guided import ddim_guided_loop, null_pair
-
-from diffusion_conductor_amd import native
 
 UPD_EMBED_NEXT = 32          # dc_common.h
 KEY_GUIDED, KEY_SHARED = 1 << 27, 1 << 28          # dc_form.h, guided_key_bits
@@ -54,19 +47,7 @@ def test_null_pair():
 
 @pytest.fixture(scope="module")
 def probe(tmp_path_factory):
-    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++") or "/opt/rocm/lib/llvm/bin/clang++"
-    if not os.path.exists(cxx):
-        pytest.skip("no C++ compiler")
-    exe = str(tmp_path_factory.mktemp("guided_form") / "guided_form_probe")
-    subprocess.run([cxx, "-std=c++17", "-O1", "-I", native.CSRC, os.path.join(ROOT, "tests", "guided_form_probe.cpp"), "-o", exe], check=True)
-
-    def run(*cases):
-        env = {k: v for k, v in os.environ.items() if not k.startswith("DC_")}
-        out = subprocess.run([exe], input="\n".join(cases) + "\n", env=env, check=True, capture_output=True, text=True).stdout
-        res = [json.loads(ln) for ln in out.splitlines()]
-        assert len(res) == len(cases)
-        return res
-    return run
+    return loop_step_probe(tmp_path_factory, GUIDED_FIELDS)
 
 
 # the INTERNAL shapes (B = 2 x the caller's clips) of tests/test_gpu_guided.py, the form each is there for (256 compute units, fp16

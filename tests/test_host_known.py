@@ -1,16 +1,11 @@
 """Sampling around known values, the host half (no GPU): the coefficient table of dc_ddim_coefficients_known, the launch rule with the
-DC_UPD_KNOWN bit (csrc/dc_form.h through tests/known_form_probe.cpp), the window planner of generate_long_music_motion, and the
+DC_UPD_KNOWN bit (csrc/dc_form.h through tests/form_probe.cpp), the window planner of generate_long_music_motion, and the
 checker of the GPU tests (helpers_known.ddim_known_loop) against the oracle's own loop."""
-import json
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 import torch
 
-from helpers import O, ROOT, batch_noise, oracle_params, xf_pair
+from helpers import O, batch_noise, loop_step_probe, oracle_params, xf_pair
 from helpers_known import ddim_known_loop, known_levels, prefix_mask
 
 from diffusion_conductor_amd import native
@@ -40,19 +35,7 @@ def test_known_coefficients(S, eta):
 
 @pytest.fixture(scope="module")
 def probe(tmp_path_factory):
-    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++") or "/opt/rocm/lib/llvm/bin/clang++"
-    if not os.path.exists(cxx):
-        pytest.skip("no C++ compiler")
-    exe = str(tmp_path_factory.mktemp("known_form") / "known_form_probe")
-    subprocess.run([cxx, "-std=c++17", "-O1", "-I", native.CSRC, os.path.join(ROOT, "tests", "known_form_probe.cpp"), "-o", exe], check=True)
-
-    def run(*cases):
-        env = {k: v for k, v in os.environ.items() if not k.startswith("DC_")}
-        out = subprocess.run([exe], input="\n".join(cases) + "\n", env=env, check=True, capture_output=True, text=True).stdout
-        res = [json.loads(ln) for ln in out.splitlines()]
-        assert len(res) == len(cases)
-        return res
-    return run
+    return loop_step_probe(tmp_path_factory)
 
 
 # the shapes of tests/test_gpu_known.py and the form each is there for (256 compute units, fp16 unless said)

@@ -1,45 +1,26 @@
 """Several takes per music, the host half (no GPU): the period / group rule of the shared FiLM GEMM (film_share, csrc/dc_form.h), the
 launch form of every shape of tests/test_gpu_takes.py, the graph key, and takes = 1 against the rule as it was - through
-tests/takes_form_probe.cpp; the guided cases also through tests/guided_form_probe.cpp, the probe of the rule before takes existed."""
+tests/form_probe.cpp; takes = 1 also as the tests of guidance ask it, by the internal batch and for the fields recorded from the rule
+before takes existed."""
 import json
 import os
-import shutil
-import subprocess
 
 import pytest
 
-from helpers import ROOT
-
-from diffusion_conductor_amd import native
+from helpers import GUIDED_FIELDS, ROOT, TAKES_FIELDS, loop_step_probe
 
 UPD_EMBED_NEXT = 32          # dc_common.h
 KEY_GUIDED, KEY_SHARED = 1 << 27, 1 << 28          # dc_form.h, guided_key_bits
 
 
-def _build(tmp, name):
-    cxx = shutil.which("c++") or shutil.which("g++") or shutil.which("clang++") or "/opt/rocm/lib/llvm/bin/clang++"
-    if not os.path.exists(cxx):
-        pytest.skip("no C++ compiler")
-    exe = str(tmp / name)
-    subprocess.run([cxx, "-std=c++17", "-O1", "-I", native.CSRC, os.path.join(ROOT, "tests", name + ".cpp"), "-o", exe], check=True)
-
-    def run(*cases):
-        env = {k: v for k, v in os.environ.items() if not k.startswith("DC_")}
-        out = subprocess.run([exe], input="\n".join(cases) + "\n", env=env, check=True, capture_output=True, text=True).stdout
-        res = [json.loads(ln) for ln in out.splitlines()]
-        assert len(res) == len(cases)
-        return res
-    return run
-
-
 @pytest.fixture(scope="module")
 def probe(tmp_path_factory):
-    return _build(tmp_path_factory.mktemp("takes_form"), "takes_form_probe")
+    return loop_step_probe(tmp_path_factory, TAKES_FIELDS)
 
 
 @pytest.fixture(scope="module")
 def guided_probe(tmp_path_factory):
-    return _build(tmp_path_factory.mktemp("takes_guided_form"), "guided_form_probe")
+    return loop_step_probe(tmp_path_factory, GUIDED_FIELDS)
 
 
 # (musics, takes, Tx, extra) of tests/test_gpu_takes.py, the form each is there for (256 compute units, fp16 unless said) and the period
@@ -143,14 +124,15 @@ ONE_TAKE = ["musics=1 Tx=256", "musics=36 Tx=256", "musics=80 Tx=256", "musics=5
 
 
 def _case_without_takes(case, guided):
-    """The same case for the probe of the rule without takes: B is the internal batch there."""
+    """The same case as the rule without takes was asked: by B, the internal batch."""
     head, _, rest = case.partition(" ")
     return f"B={int(head.split('=')[1]) * (2 if guided else 1)} {rest} guided={guided}".replace("  ", " ")
 
 
 @pytest.fixture(scope="module")
 def parent_forms():
-    """What guided_form_probe printed for the cases of ONE_TAKE on the rule as it was before takes existed (recorded once)."""
+    """What the probe of guidance printed (GUIDED_FIELDS) for the cases of ONE_TAKE on the rule as it was before takes existed
+    (recorded once)."""
     with open(os.path.join(ROOT, "tests", "golden", "takes_one_take_forms.json")) as fh:
         return json.load(fh)
 
