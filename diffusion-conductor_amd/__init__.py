@@ -11,7 +11,7 @@ from .param_spec import DenoiserConfig, param_shapes  # noqa: F401
 
 __version__ = "0.1.0"
 __all__ = ["MotionTransformer", "GaussianDiffusion", "DDPMTrainer", "DenoiserConfig", "param_shapes", "evaluate_dataset",
-           "smooth_motion"]
+           "smooth_motion", "validation_dataset"]
 
 
 def __getattr__(name):   # lazy: torch is only imported when the classes are used
@@ -24,7 +24,7 @@ def __getattr__(name):   # lazy: torch is only imported when the classes are use
     if name == "DDPMTrainer":
         from .harness import DDPMTrainer
         return DDPMTrainer
-    if name in ("evaluate_dataset", "smooth_motion", "mse_loss", "list_clips"):
+    if name in ("evaluate_dataset", "smooth_motion", "mse_loss", "list_clips", "validation_dataset", "validation_grid"):
         from . import evaluate
         return getattr(evaluate, name)
     raise AttributeError(name)

@@ -11,6 +11,9 @@ threads in pinned host buffers while the GPU samples the previous batch, the bat
 initialised ``torch.distributed`` group by ``DDPMTrainer.generate_music_motion``, the poses come back with one
 copy behind an event and are scored on a third thread - the GPU's queue never runs dry (tools/time_evaluate.py).  ``smooth_motion`` is tools/visualization.py:20-26 (Savitzky-Golay, kernel 19, order 5 at
 :126) on the GPU.
+
+``validation_dataset`` (``--val_loss``) scores a checkpoint WITHOUT sampling it: the held-out value of the denoising objective it was
+trained on (models/gaussian_diffusion.py:1002-1090, trainers/ddpm_trainer.py:223-268), per noise level.
 """
 from __future__ import annotations
 
@@ -416,6 +419,87 @@ def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed
     return out
 
 
+def validation_grid(num_timesteps, k):
+    """The noise levels of a `k`-point loss curve: unique(round(linspace(0, S - 1, k))), increasing."""
+    S, k = int(num_timesteps), int(k)
+    if not 1 <= k:
+        raise ValueError(f"the grid needs at least one timestep, got {k}")
+    return sorted({int(v) for v in np.floor(np.linspace(0, S - 1, k) + 0.5)})
+
+
+_VAL_SCALARS = ("loss", "loss_mot_rec", "loss_mot_feat", "loss_velocity", "loss_velocity_elbow", "loss_velocity_head",
+                "loss_velocity_body", "velocity_elbow", "mse")
+
+
+def validation_dataset(trainer, root, timesteps=None, batch_size=32, seed=0, motion_encoder=None, limit=None):
+    """Scores a checkpoint by its held-out DENOISING losses (DDPMTrainer.validation_losses) over every clip under `root` - one
+    model evaluation per clip and noise level, no sampling loop.
+    `timesteps`: an int K - the grid validation_grid(S, K), every clip evaluated at every grid timestep; a list - those timesteps;
+    None - the training protocol, one uniform timestep per clip (drawn on the host from `seed`, by clip index).
+    Each batch's music is encoded once and its conditioning pre-pass set once, then reused across the grid.  Noise comes from the
+    library's device stream with iteration = grid index and first_element = clip_index * T * 26, so a clip's draw - and with it
+    every number here - does not depend on batch_size or order.  The scalars are combined on the host from the per-clip terms of
+    the WHOLE data set (metrics.denoising_loss_scalars).
+    Returns {"clips", "timesteps" (the grid, or None), "per_timestep": [{"t": grid timestep or None, "loss", "loss_mot_rec",
+    "loss_mot_feat" (None without `motion_encoder`), "loss_velocity", "loss_velocity_elbow", "loss_velocity_head",
+    "loss_velocity_body", "velocity_elbow", "mse", "feat_included"}], "average": the same scalars averaged over the grid,
+    "evaluations" (model evaluations per clip), "seconds"}."""
+    from .metrics import denoising_loss_scalars
+    ids = list_clips(root)
+    if limit is not None:
+        ids = ids[:int(limit)]
+    if not ids:
+        raise FileNotFoundError(f"no <id>/mel.npy + <id>/motion.npy pairs under {root}")
+    S = int(trainer.diffusion.num_timesteps)
+    if timesteps is None:
+        grid, drawn = None, np.random.RandomState(int(seed) & 0xffffffff).choice(S, size=(len(ids),), p=np.ones(S) / S)
+    else:
+        grid = validation_grid(S, timesteps) if np.ndim(timesteps) == 0 else [int(v) for v in timesteps]
+        if not grid or any(not 0 <= v < S for v in grid):
+            raise ValueError(f"timesteps must be inside [0, {S}), got {grid}")
+    mel_shape = tuple(np.load(pjoin(root, ids[0], "mel.npy"), mmap_mode="r").shape)
+    T = (mel_shape[0] - 1) // 3 + 1
+    nb = (len(ids) + batch_size - 1) // batch_size
+    pf = _Prefetcher(root, ids, batch_size, mel_shape)
+    pf.start(0)
+    dev = trainer.device
+    slot_free = [None, None]
+    n_levels = 1 if grid is None else len(grid)
+    terms = [[] for _ in range(n_levels)]
+    feats = [[] for _ in range(n_levels)]
+    t0 = time.perf_counter()
+    for k in range(nb):
+        bid, mel, gts = pf.take()
+        if k + 1 < nb:
+            pf.start(k + 1, after=slot_free[(k + 1) & 1])
+        bad = [(cid, np.shape(g)) for cid, g in zip(bid, gts) if int(np.prod(np.shape(g))) != T * 26]
+        if bad:
+            raise ValueError(f"the music gives {T} frames, but these motions differ: {bad[:4]}")
+        B = len(bid)
+        x0 = torch.from_numpy(np.ascontiguousarray(np.stack([np.reshape(g, (T, 26)) for g in gts]), np.float32)).to(dev)
+        with torch.no_grad():
+            xf_proj, xf_out = trainer.encoder.encode_music(mel, dev)
+        if torch.device(dev).type == "cuda":
+            slot_free[k & 1] = torch.cuda.Event()
+            slot_free[k & 1].record()
+        first = k * batch_size
+        for gi in range(n_levels):
+            t = drawn[first:first + B] if grid is None else np.full(B, grid[gi], np.int64)
+            r = trainer._validation_batch(xf_proj, xf_out, x0, np.full(B, T, np.int64), t, noise_seed=(seed, gi, first * T * 26),
+                                          motion_encoder=motion_encoder)
+            terms[gi].append(r["terms"])
+            if motion_encoder is not None:
+                feats[gi].append(r["latent_l1"])
+    dt = time.perf_counter() - t0
+    rows = []
+    for gi in range(n_levels):
+        sc = denoising_loss_scalars(np.concatenate(terms[gi]), np.full(len(ids), T), np.concatenate(feats[gi]) if feats[gi] else None)
+        rows.append({"t": None if grid is None else grid[gi], **sc})
+    avg = {key: (None if rows[0][key] is None else float(np.mean([r[key] for r in rows]))) for key in _VAL_SCALARS}
+    avg["feat_included"] = rows[0]["feat_included"]
+    return {"clips": len(ids), "timesteps": grid, "per_timestep": rows, "average": avg, "evaluations": n_levels, "seconds": dt}
+
+
 def main(argv=None):
     """python -m diffusion_conductor_amd.evaluate --data_root <dir> [--model latest.tar] [--batch_size 32]"""
     import argparse
@@ -441,6 +525,10 @@ def main(argv=None):
     ap.add_argument("--solver", default="ddim", choices=["ddim", "dpmpp2m"], help="first-order DDIM or the second-order multistep update")
     ap.add_argument("--sync", action="store_true", help="also M2SNet's synchronisation score of the sampled poses against the music "
                                                         "(m2snet.py; every entry of --m2snet, or seeded synthetic weights)")
+    ap.add_argument("--val_loss", action="store_true", help="score the checkpoint by its held-out denoising losses instead of sampling it: "
+                                                            "one JSON line, no sampling loop (validation_dataset)")
+    ap.add_argument("--val_timesteps", type=int, default=None, help="--val_loss on a grid of this many noise levels (omitted: one uniform "
+                                                                    "timestep per clip, the training protocol)")
     args = ap.parse_args(argv)
     from . import DDPMTrainer, MotionTransformer
     dev = torch.device("cuda", args.gpu_id)
@@ -474,6 +562,11 @@ def main(argv=None):
             from .synthetic import synthetic_m2snet_state_dict
             m2s = M2SNet(dev).load_state_dict(synthetic_m2snet_state_dict())
             print("--sync without --m2snet: M2SNet has seeded synthetic weights, so the m2s_* scores only check the pipeline")
+    if args.val_loss:
+        import json
+        r = validation_dataset(tr, args.data_root, args.val_timesteps, args.batch_size, args.seed, motion_encoder=menc, limit=args.limit)
+        print(json.dumps(r))
+        return 0
     r = evaluate_dataset(tr, args.data_root, 26, args.batch_size, args.limit, args.seed, args.smooth, motion_encoder=menc,
                          diversity_seed=args.diversity_seed, m2snet=m2s, guidance_scale=args.guidance_scale,
                          steps=args.steps, spacing=args.spacing, solver=args.solver)

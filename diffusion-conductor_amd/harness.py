@@ -6,7 +6,8 @@ MotionPretrain/ST-GCN and mmcv imports), ``load`` (:303-319), ``eval_mode``, ``t
 batch ``[B,5400,128]``; ``noise=`` / ``seed=`` make sampling reproducible; under an initialised
 ``torch.distributed`` group the clips are sharded over ranks (sharding.py);
 ``generate_long_music_motion`` conducts music longer than one window by chaining windows around
-the frames already generated (``plan_windows``).
+the frames already generated (``plan_windows``); ``validation_losses`` is the forward value of
+``forward`` + ``backward_G`` (:132-163, 223-268) on held-out clips, without gradients.
 """
 from __future__ import annotations
 
@@ -147,6 +148,65 @@ class DDPMTrainer(object):
                 return self._sample_local(mel, noise, dim_pose, idxs, sm, guidance_scale, skw, takes)
             return sharded_sample(lambda m, n: self._sample_local(m, n, dim_pose, [], sm, guidance_scale, skw), mel, noise, out_shape=(T, dim_pose),
                                   device=self.device)
+
+    def _validation_batch(self, xf_proj, xf_out, x0, lengths, t, noise=None, noise_seed=None, motion_encoder=None):
+        """One noise level of validation_losses on music that is already encoded: x0 [B, T, 26] on the device, lengths / t host
+        int arrays [B].  Handing the SAME xf_proj / xf_out tensors to several calls reuses the conditioning pre-pass (the encoder
+        keys it by tensor identity)."""
+        from . import native
+        from .metrics import denoising_loss_scalars
+        B, T = int(x0.shape[0]), int(x0.shape[1])
+        tt = torch.as_tensor(np.asarray(t, np.int64)).to(x0.device)
+        out = self.diffusion.training_losses(self.encoder, x0, tt, noise=noise, noise_seed=noise_seed,
+                                             model_kwargs={"xf_proj": xf_proj, "xf_out": xf_out, "length": torch.as_tensor(np.asarray(lengths, np.int64))})
+        feat = None
+        if motion_encoder is not None:
+            # features(.)[-1] of the prediction and of the target (ddpm_trainer.py:225-229), right behind the reductions on the stream
+            fake = motion_encoder.latent(out["pred"].reshape(B, T, 13, 2))
+            real = motion_encoder.latent(out["target"].reshape(B, T, 13, 2))
+            feat = native.latent_l1(fake, real) if fake.is_cuda else (fake - real).abs().mean(dim=(1, 2))
+        terms = out["terms"].cpu()              # the one wait: every number below is host arithmetic on these B x 8 floats
+        res = denoising_loss_scalars(terms, lengths, None if feat is None else feat.cpu())
+        res.update(t=[int(v) for v in t], mse_per_clip=terms[:, 0].tolist(), terms=terms.numpy(),
+                   latent_l1=None if feat is None else feat.cpu().numpy())
+        return res
+
+    def validation_losses(self, music_mel, motions, m_lens=None, t=None, noise=None, seed=None, motion_encoder=None, noise_seed=None):
+        """The held-out value of the training objective (DDPMTrainer.forward + backward_G, ddpm_trainer.py:132-163, 223-268, without
+        gradients): music_mel [B, 5400, 128] and motions [B, T, 13, 2] (or [B, T, 26]), or one clip of each; m_lens [B] frame counts
+        (None: all T; values beyond T count as T, :143).  ONE model evaluation per clip.
+        t: per-clip timesteps [B] or one int for all; None draws one uniform timestep per clip on the host from `seed` (the reference's
+        UniformSampler protocol: np.random.choice over the schedule with equal weights).
+        noise: the tensor to add ([B, T, 13, 2] or [B, T, 26]); None: the library's device stream, keyed by `noise_seed` = seed or
+        (seed, iteration, first_element) (default: `seed`, or one drawn from torch's generator).
+        motion_encoder (motion_encoder.MotionEncoder_STGCN or anything with its `latent`): adds the latent feature term.
+        Returns the per-clip "t", "mse_per_clip", "terms" [B, 8] (and "latent_l1" [B] or None), the batch scalars "loss_mot_rec",
+        "loss_mot_feat" (None without an encoder), "loss_velocity", "loss_velocity_elbow", "loss_velocity_head", "loss_velocity_body",
+        and the total "loss" with "feat_included" (metrics.denoising_loss_scalars)."""
+        mel = torch.as_tensor(np.asarray(music_mel) if not torch.is_tensor(music_mel) else music_mel)
+        x0 = torch.as_tensor(np.asarray(motions) if not torch.is_tensor(motions) else motions)
+        if mel.dim() == 2:
+            mel = mel.unsqueeze(0)
+        if x0.dim() == 3 and x0.shape[-1] == 2:
+            x0 = x0.unsqueeze(0)
+        B, T = int(x0.shape[0]), int(x0.shape[1])
+        if mel.shape[0] != B:
+            raise ValueError(f"{mel.shape[0]} musics for {B} motions")
+        x0 = x0.to(self.device, dtype=torch.float32).reshape(B, T, -1).contiguous()
+        lengths = np.full(B, T, np.int64) if m_lens is None else np.minimum(np.asarray(m_lens, np.int64).reshape(B), T)
+        S = self.diffusion.num_timesteps
+        if t is None:
+            t = np.random.RandomState(None if seed is None else int(seed) & 0xffffffff).choice(S, size=(B,), p=np.ones(S) / S)
+        t = np.broadcast_to(np.asarray(t.cpu() if torch.is_tensor(t) else t, np.int64).reshape(-1), (B,)).copy()
+        if noise is not None:
+            noise = torch.as_tensor(noise).to(self.device, dtype=torch.float32).reshape(B, T, -1).contiguous()
+        elif noise_seed is None:
+            noise_seed = int(seed) if seed is not None else int(torch.randint(0, 2 ** 62, (1,)).item())
+        with torch.no_grad():
+            xf_proj, xf_out = self.encoder.encode_music(mel if mel.is_cuda else mel.to(self.device, dtype=torch.float32), self.device)
+            if xf_proj.shape[1] != T:
+                raise ValueError(f"the music gives {xf_proj.shape[1]} frames, the motions have {T}")
+            return self._validation_batch(xf_proj, xf_out, x0, lengths, t, noise, noise_seed, motion_encoder)
 
     def generate_long_music_motion(self, music_mel, dim_pose, overlap=LONG_OVERLAP, noise=None, seed=None, smooth=None, window=None,
                                    guidance_scale=None, steps=None, spacing="uniform", solver="ddim"):

@@ -15,6 +15,9 @@ Host numpy / scipy over the ST-GCN latents of motion_encoder.py (``latent(x)`` =
 ``sync_stats`` is the one score that looks at the music: the mean predictions and the 0.5-threshold accuracy of M2SNet
 (m2snet.py) over matched and mismatched music / motion pairs, as Contrastive_Stage/M2SNet_eval.py:58-107 reports them.
 
+``denoising_loss_scalars`` is not a score of sampled motion: it combines the per-clip terms of the held-out denoising objective
+(native.motion_loss_terms, native.latent_l1) into the batch scalars of DDPMTrainer.backward_G (trainers/ddpm_trainer.py:223-268).
+
 Beat consistency (BC) is not here: its music side is librosa's onset / beat tracker.
 """
 from __future__ import annotations
@@ -129,3 +132,43 @@ def sync_stats(pred_matched, pred_mismatched=None):
     tf = np.sum(n.numpy() < 0.5)
     return {"sync": torch.mean(m).item(), "non_sync": torch.mean(n).item() if n.numel() else float("nan"),
             "accuracy": ((tp + tf) / (m.numel() + n.numel())).item()}
+
+
+# the weights of DDPMTrainer.backward_G (ddpm_trainer.py:252-256) and the clamp of its elbow term (:245)
+LAMBDA_REC, LAMBDA_FEAT, LAMBDA_VELOCITY, LAMBDA_ELBOW, LAMBDA_HEAD = 1.0, 1e-6, 0.1, 0.1, 0.1
+ELBOW_CLAMP = 2e-4
+
+
+def denoising_loss_scalars(terms, lengths, latent_l1=None):
+    """The batch scalars of DDPMTrainer.backward_G (ddpm_trainer.py:223-268) from per-clip numbers, in float64 on the host:
+    `terms` [B, 8] (native.motion_loss_terms / GaussianDiffusion.training_losses()["terms"]: mse, masked reconstruction sum,
+    velocity body / elbow / head, velocity), `lengths` [B] (the frames the reconstruction sum covered), `latent_l1` [B] (the per-clip
+    mean |features(pred)[-1] - features(target)[-1]|, native.latent_l1) or None.
+      loss_mot_rec        sum rec_b / sum length_b                                             (:232-233)
+      loss_mot_feat       mean of latent_l1 over clips; None without it                        (:237-238)
+      loss_velocity, loss_velocity_head, loss_velocity_body      means over clips              (:241-250; gaussian_diffusion.py:1080-1083)
+      loss_velocity_elbow the clip mean clamped to [-2e-4, 2e-4], as the reference keeps it    (:245); velocity_elbow: unclamped
+      mse                 mean of mse_b over clips                                             (gaussian_diffusion.py:1079)
+      loss                rec + 1e-6 feat + 0.1 velocity - 0.1 loss_velocity_elbow + 0.1 head  (:258); the feat term is left out when
+                          it is None, and "feat_included" says which."""
+    t = np.asarray(terms.detach().cpu() if hasattr(terms, "detach") else terms, np.float64)
+    if t.ndim != 2 or t.shape[1] != 8 or t.shape[0] < 1:
+        raise ValueError(f"terms must be [B, 8] with B >= 1, got {t.shape}")
+    ln = np.asarray(lengths.detach().cpu() if hasattr(lengths, "detach") else lengths, np.float64).reshape(-1)
+    if ln.shape != (t.shape[0],) or (ln < 1).any():
+        raise ValueError(f"lengths must be [{t.shape[0]}] positive frame counts, got {ln.tolist()}")
+    feat = None
+    if latent_l1 is not None:
+        f = np.asarray(latent_l1.detach().cpu() if hasattr(latent_l1, "detach") else latent_l1, np.float64).reshape(-1)
+        if f.shape != (t.shape[0],):
+            raise ValueError(f"latent_l1 must be [{t.shape[0]}], got {f.shape}")
+        feat = float(f.mean())
+    rec = float(t[:, 1].sum() / ln.sum())
+    body, elbow, head, vel = (float(t[:, k].mean()) for k in (2, 3, 4, 5))
+    elbow_c = min(max(elbow, -ELBOW_CLAMP), ELBOW_CLAMP)
+    loss = LAMBDA_REC * rec + LAMBDA_VELOCITY * vel - LAMBDA_ELBOW * elbow_c + LAMBDA_HEAD * head
+    if feat is not None:
+        loss += LAMBDA_FEAT * feat
+    return {"loss": loss, "loss_mot_rec": rec, "loss_mot_feat": feat, "loss_velocity": vel, "loss_velocity_elbow": elbow_c,
+            "loss_velocity_head": head, "loss_velocity_body": body, "velocity_elbow": elbow, "mse": float(t[:, 0].mean()),
+            "feat_included": feat is not None}

@@ -33,12 +33,14 @@ EXPORTS = [
     "dc_m2snet_score",
     "dc_solver_table", "dc_sampler_solver_loop", "dc_sampler_solver_profile_loop",
     "dc_sampler_set_conditioning_takes",
+    "dc_q_sample_coefficients", "dc_q_sample", "dc_motion_loss_terms", "dc_latent_l1",
 ]
 
 UPDATE_CLIP_DENOISED, UPDATE_EPSILON = 1, 2          # flags of dc_sampler_ddim_loop_ex
 STATUS_NONFINITE, STATUS_F16_SATURATED, STATUS_TIMEOUT = 1, 2, 4        # bits of dc_sampler_status
 SOLVER_ROW = 12                                       # DC_SOLVER_ROW: floats per row of dc_solver_table
 SOLVER_ORDER = {"ddim": 1, "dpmpp2m": 2}              # solver= of the Python surfaces -> order of dc_solver_table
+LOSS_TERMS = 8                                        # DC_LOSS_TERMS: floats per clip of dc_motion_loss_terms
 
 
 class DcConfig(C.Structure):
@@ -50,7 +52,7 @@ class DcError(RuntimeError):
     pass
 
 
-SOURCES = ("dc_kernels.hip", "dc_api.hip", "dc_music.hip", "dc_layer16.hip", "dc_stgcn.hip", "dc_m2snet.hip")
+SOURCES = ("dc_kernels.hip", "dc_api.hip", "dc_music.hip", "dc_layer16.hip", "dc_stgcn.hip", "dc_m2snet.hip", "dc_loss.hip")
 HEADERS = ("dc_common.h", "dc_dev.h", "dc_form.h", "dc_launch.h", "dc_music.h", "dc_pack.h")
 EXTRA_FLAGS = {}      # per-source compiler flags
 
@@ -172,6 +174,11 @@ def lib():
     L.dc_m2snet_fuse.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.dc_m2snet_score.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                   C.c_void_p]
+    L.dc_q_sample_coefficients.argtypes = [C.c_int32, dp, ip, C.c_int32, fp, fp]
+    L.dc_q_sample.argtypes = [C.c_void_p, C.c_void_p, fp, fp, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_uint64,
+                              C.c_void_p, C.c_void_p, C.c_void_p]
+    L.dc_motion_loss_terms.argtypes = [C.c_void_p, C.c_void_p, ip, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    L.dc_latent_l1.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -265,6 +272,84 @@ def step_noise(shape, seed: int, iteration: int, device):
     with torch.cuda.device(out.device):
         _check(lib().dc_step_noise_fill(out.data_ptr(), out.numel(), C.c_uint64(int(seed) & (2 ** 64 - 1)), int(iteration),
                                         C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    return out
+
+
+def q_sample_coefficients(alphas_cumprod: np.ndarray, timesteps):
+    """dc_q_sample_coefficients: (a [B], s [B]) = (float)sqrt(abar[t]), (float)sqrt(1 - abar[t]) per clip (host only).  DcError for a
+    timestep outside the schedule."""
+    ac = np.ascontiguousarray(alphas_cumprod, np.float64)
+    ts = np.ascontiguousarray(np.asarray(timesteps.cpu() if hasattr(timesteps, "cpu") else timesteps).reshape(-1), np.int32)
+    a, s = np.empty(max(ts.shape[0], 1), np.float32), np.empty(max(ts.shape[0], 1), np.float32)
+    _check(lib().dc_q_sample_coefficients(ac.shape[0], ac.ctypes.data_as(C.POINTER(C.c_double)), _iptr(ts), ts.shape[0], _fptr(a), _fptr(s)))
+    return a, s
+
+
+def _loss_tensor(t, name, shape=None):
+    import torch
+    assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous(), f"{name} must be a contiguous fp32 device tensor"
+    assert shape is None or tuple(t.shape) == tuple(shape), f"{name} must be {tuple(shape)}, got {tuple(t.shape)}"
+    return t
+
+
+def q_sample(x_start, a, s, noise=None, noise_seed=None, return_noise=False):
+    """dc_q_sample on fp32 device tensors: x_t = a_b x_start + s_b noise over [B, T, ...] with the host arrays (a, s) of
+    q_sample_coefficients.  `noise`: the tensor to use; else `noise_seed` = seed or (seed, iteration, first_element): the library's
+    draws (step_noise's for (seed, iteration), starting at first_element).  return_noise: (x_t, the draws) - seeded path only."""
+    import torch
+    x = _loss_tensor(x_start, "x_start")
+    B, T = int(x.shape[0]), int(x.shape[1])
+    P = x.numel() // max(B * T, 1)
+    a, s = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(s, np.float32)
+    assert a.shape == (B,) and s.shape == (B,), "one (a, s) pair per clip"
+    xt = torch.empty_like(x)
+    seed = it = first = 0
+    zout = None
+    if noise is not None:
+        assert noise_seed is None and not return_noise, "noise= and noise_seed= exclude each other"
+        _loss_tensor(noise, "noise", x.shape)
+    else:
+        assert noise_seed is not None, "q_sample needs noise= or noise_seed="
+        seed, it, first = noise_seed if isinstance(noise_seed, (tuple, list)) else (noise_seed, 0, 0)
+        zout = torch.empty_like(x) if return_noise else None
+    with torch.cuda.device(x.device):
+        _check(lib().dc_q_sample(x.data_ptr(), None if noise is None else noise.data_ptr(), _fptr(a), _fptr(s), B, T, P,
+                                 C.c_uint64(int(seed) & (2 ** 64 - 1)), int(it), C.c_uint64(int(first)),
+                                 None if zout is None else zout.data_ptr(), xt.data_ptr(),
+                                 C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    return (xt, zout) if return_noise else xt
+
+
+def motion_loss_terms(pred, target, length=None):
+    """dc_motion_loss_terms: pred, target fp32 [B, T, 26] on the device, length [B] (None: all T) -> terms fp32 [B, LOSS_TERMS] per
+    clip: mse, masked reconstruction sum, velocity body / elbow / head, velocity, 0, 0 (include/dc_ddim.h)."""
+    import torch
+    p = _loss_tensor(pred, "pred")
+    B, T = int(p.shape[0]), int(p.shape[1])
+    P = p.numel() // max(B * T, 1)
+    g = _loss_tensor(target, "target", p.shape)
+    lp = None
+    if length is not None:
+        la = np.ascontiguousarray(np.asarray(length.cpu() if hasattr(length, "cpu") else length).reshape(-1), np.int32)
+        assert la.shape == (B,), "one length per clip"
+        lp = _iptr(la)
+    out = torch.empty((B, LOSS_TERMS), dtype=torch.float32, device=p.device)
+    with torch.cuda.device(p.device):
+        _check(lib().dc_motion_loss_terms(p.data_ptr(), g.data_ptr(), lp, B, T, P, out.data_ptr(),
+                                          C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    return out
+
+
+def latent_l1(a, b):
+    """dc_latent_l1: latents fp32 [B, 64, T] on the device -> the per-clip mean |a - b|, fp32 [B]."""
+    import torch
+    a = _loss_tensor(a, "a")
+    assert a.dim() == 3 and a.shape[1] == 64, f"latents are [B, 64, T], got {tuple(a.shape)}"
+    b = _loss_tensor(b, "b", a.shape)
+    out = torch.empty((int(a.shape[0]),), dtype=torch.float32, device=a.device)
+    with torch.cuda.device(a.device):
+        _check(lib().dc_latent_l1(a.data_ptr(), b.data_ptr(), int(a.shape[0]), int(a.shape[2]), out.data_ptr(),
+                                  C.c_void_p(torch.cuda.current_stream().cuda_stream)))
     return out
 
 

@@ -16,8 +16,12 @@ from the extension keyword ``step_noise=`` so that runs can be reproduced).  A h
 :472-486) or the progressive generator run the same update rule step by step with the model
 call still going through the native denoiser; ``p_mean_variance`` (:442-536) is provided whole.
 
-Training-time members (losses, VLB terms, ancestral p_sample, schedule samplers) are out of
-scope for this path and are not provided.
+The FORWARD VALUE of the training objective is here as an evaluator: ``q_sample`` (:398-416) and
+``training_losses`` (:1002-1090) for the MSE loss types, under ``no_grad`` - with this package's
+MotionTransformer on a GPU the noising and the reductions are the kernels of csrc/dc_loss.hip, with
+any other callable or device the same definitions in plain torch.  Gradients, the optimiser, the
+variational bound (``LossType.KL`` / ``RESCALED_KL``, learned variances), ancestral ``p_sample``
+and the loss-aware schedule samplers stay out of scope and are not provided.
 """
 from __future__ import annotations
 
@@ -247,6 +251,105 @@ class GaussianDiffusion:
         if "mean" in out:
             out["mean"], _, _ = self.q_posterior_mean_variance(x_start=out["pred_xstart"], x_t=x, t=t)
         return out
+
+    # ---- the denoising objective, forward value ------------------------------------------
+    def q_sample(self, x_start, t, noise=None, noise_seed=None):
+        """gaussian_diffusion.py:398-416: x_t = sqrt(abar_t) x_start + sqrt(1 - abar_t) noise, per-clip t [B].  On a GPU tensor this is
+        dc_q_sample, on the host the same fp32 expression in torch - the reference's bits either way.
+        `noise_seed` (extension, GPU only): seed, or (seed, iteration, first_element) - the library's own draws in place of
+        th.randn_like (native.step_noise's for (seed, iteration), from element first_element on)."""
+        x = th.as_tensor(x_start)
+        if noise is not None and noise_seed is not None:
+            raise ValueError("noise= and noise_seed= exclude each other")
+        if noise is None and noise_seed is None:
+            noise = th.randn_like(x)
+        if x.is_cuda:
+            a, s = native.q_sample_coefficients(self.alphas_cumprod, t)
+            xc = x.to(th.float32).contiguous()
+            if noise is not None:
+                assert noise.shape == x.shape
+                return native.q_sample(xc, a, s, noise=noise.to(device=x.device, dtype=th.float32).contiguous())
+            return native.q_sample(xc, a, s, noise_seed=noise_seed)
+        if noise is None:
+            raise ValueError("noise_seed= draws on the device; on the host pass noise=")
+        assert noise.shape == x.shape
+        return _extract(self.sqrt_alphas_cumprod, t, x.shape) * x + _extract(self.sqrt_one_minus_alphas_cumprod, t, x.shape) * noise
+
+    BODY_JOINTS_IDX = (10, 11, 12, 13, 22, 23, 24, 25)      # gaussian_diffusion.py:1075-1077
+    ELBOW_JOINTS_IDX = (14, 15, 16, 17, 18, 19, 20, 21)
+    HEAD_JOINTS_IDX = (0, 1, 2, 3, 4, 5, 6, 7, 8, 9)
+
+    @classmethod
+    def loss_terms_torch(cls, pred, target, length=None):
+        """native.motion_loss_terms in plain torch (fp32, any device): [B, 8] per clip - mse, masked reconstruction sum, velocity body /
+        elbow / head, velocity, 0, 0 (include/dc_ddim.h, dc_motion_loss_terms)."""
+        B, T = pred.shape[:2]
+        d2 = (target - pred) ** 2
+        ln = th.full((B,), T, dtype=th.long) if length is None else th.as_tensor(length).long().cpu().reshape(B)
+        if bool((ln < 1).any()) or bool((ln > T).any()):
+            raise ValueError(f"length must be inside [1, {T}], got {ln.tolist()}")
+        mask = (th.arange(T)[None, :] < ln[:, None]).to(pred)
+        vp = pred[:, 1:] - pred[:, :-1]
+        vt = target[:, 1:] - target[:, :-1]
+        cols = [d2.mean(dim=(1, 2)), (d2.mean(dim=-1) * mask).sum(dim=1)]
+        cols += [(vp[:, :, list(idx)] ** 2).mean(dim=(1, 2)) for idx in (cls.BODY_JOINTS_IDX, cls.ELBOW_JOINTS_IDX, cls.HEAD_JOINTS_IDX)]
+        cols += [((vt - vp) ** 2).mean(dim=(1, 2)), th.zeros_like(cols[0]), th.zeros_like(cols[0])]
+        return th.stack(cols, dim=1)
+
+    def training_losses(self, model, x_start, t, model_kwargs=None, noise=None, noise_seed=None):
+        """gaussian_diffusion.py:1002-1090 as an evaluator (no_grad): the reference's keys with the reference's shapes - "mse" [B],
+        "velocity_body", "velocity_elbow", "velocity_head", "velocity" (0-dim), "target" and "pred" [B, T, 26] - plus "terms" [B, 8],
+        the per-clip numbers they are means of (include/dc_ddim.h, dc_motion_loss_terms; its masked reconstruction sum reads
+        model_kwargs["length"], all T without one).  x_start [B, T, 13, 2] as in the reference; [B, T, 26] is accepted as well.
+        The target is x_start (START_X), the noise (EPSILON) or the posterior mean (PREVIOUS_X).
+        `noise_seed` (extension, GPU only): as q_sample.  With this package's MotionTransformer on a GPU the noising and the
+        reductions are libdc_ddim's kernels; with any other callable or device the same definitions in plain torch.
+        NotImplementedError: LossType.KL / RESCALED_KL and learned variances (the variational bound is out of scope).
+        ValueError: T < 2 - the velocity means run over no elements there and the reference returns NaN."""
+        if self.loss_type.is_vb():
+            raise NotImplementedError(f"{self.loss_type}: the variational bound is out of scope; LossType.MSE / RESCALED_MSE only")
+        if self.model_var_type in (ModelVarType.LEARNED, ModelVarType.LEARNED_RANGE):
+            raise NotImplementedError(f"{self.model_var_type}: a learned variance adds the variational-bound term, which is out of scope")
+        if self.loss_type not in (LossType.MSE, LossType.RESCALED_MSE):
+            raise NotImplementedError(self.loss_type)
+        mk = {} if model_kwargs is None else model_kwargs
+        x = th.as_tensor(x_start)
+        if x.dim() not in (3, 4) or x[0, 0].numel() != 26:
+            raise ValueError(f"x_start must be [B, T, 13, 2] or [B, T, 26], got {tuple(x.shape)}")
+        B, T = int(x.shape[0]), int(x.shape[1])
+        if T < 2:
+            raise ValueError(f"T = {T}: the velocity terms are means over T - 1 frames; the reference returns NaN for them at T = 1")
+        on_gpu = x.is_cuda and isinstance(model, MotionTransformer)
+        with th.no_grad():
+            x = x.to(th.float32).contiguous()
+            t = th.as_tensor(t).to(x.device).long()
+            drawn = None
+            if on_gpu and noise is None and noise_seed is not None:
+                a, s = native.q_sample_coefficients(self.alphas_cumprod, t)
+                if self.model_mean_type == ModelMeanType.EPSILON:
+                    x_t, drawn = native.q_sample(x, a, s, noise_seed=noise_seed, return_noise=True)
+                else:
+                    x_t = native.q_sample(x, a, s, noise_seed=noise_seed)
+            else:
+                if noise is None and noise_seed is not None:
+                    raise ValueError("noise_seed= draws on the device (a MotionTransformer on a GPU); pass noise= here")
+                drawn = th.randn_like(x) if noise is None else th.as_tensor(noise).to(device=x.device, dtype=th.float32).reshape(x.shape).contiguous()
+                x_t = self.q_sample(x, t, noise=drawn)
+            model_output = model(x_t, self._scale_timesteps(t), **mk)
+            if self.model_mean_type == ModelMeanType.PREVIOUS_X:
+                target = self.q_posterior_mean_variance(x_start=x, x_t=x_t, t=t)[0]
+            elif self.model_mean_type == ModelMeanType.START_X:
+                target = x
+            elif self.model_mean_type == ModelMeanType.EPSILON:
+                target = drawn
+            else:
+                raise NotImplementedError(self.model_mean_type)
+            target = target.reshape(B, T, 26).contiguous()
+            pred = th.as_tensor(model_output).to(th.float32).reshape(B, T, 26).contiguous()
+            length = mk.get("length")
+            terms = native.motion_loss_terms(pred, target, length) if on_gpu else self.loss_terms_torch(pred, target, length)
+        return {"mse": terms[:, 0], "velocity_body": terms[:, 2].mean(), "velocity_elbow": terms[:, 3].mean(),
+                "velocity_head": terms[:, 4].mean(), "velocity": terms[:, 5].mean(), "target": target, "pred": pred, "terms": terms}
 
     # ---- DDIM ---------------------------------------------------------------------------
     def ddim_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,

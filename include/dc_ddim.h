@@ -497,6 +497,55 @@ DC_EXPORT int dc_m2snet_fuse(dc_m2snet* n, const float* d_music_latent, const fl
 DC_EXPORT int dc_m2snet_score(dc_m2snet* n, const float* d_mel, const float* d_motion, int32_t B, int32_t Tm, int32_t T,
                               float* d_prob, float* d_logit, void* stream);
 
+/* ---- Held-out denoising losses: the forward value of the objective a checkpoint was trained on ---------------------------------
+ * GaussianDiffusion.training_losses (models/gaussian_diffusion.py:1002-1090) and the weighting of DDPMTrainer.backward_G
+ * (trainers/ddpm_trainer.py:223-268) as an EVALUATOR: one model evaluation per clip and noise level, no gradients.  The model
+ * evaluation between the noising and the reductions is dc_sampler_denoise (per-clip timesteps), the latents of the feature term are
+ * dc_motion_encoder_encode.  Implemented in csrc/dc_loss.hip; none of it is on the sampling path. */
+
+/* The two scalars of q_sample per clip, from the tables GaussianDiffusion.__init__ builds at :352-353 (sqrt_alphas_cumprod,
+ * sqrt_one_minus_alphas_cumprod), cast the way _extract_into_tensor (:1168-1181) casts them: for h_timesteps int32 [B]
+ *   h_a[b] = (float)sqrt(abar[t_b]),   h_s[b] = (float)sqrt(1.0 - abar[t_b])       (fp64, rounded once)
+ * h_alphas_cumprod fp64 [n_train].  DC_ERR_INVALID for a timestep outside [0, n_train).  Host only. */
+DC_EXPORT int dc_q_sample_coefficients(int32_t n_train, const double* h_alphas_cumprod, const int32_t* h_timesteps, int32_t B,
+                                       float* h_a, float* h_s);
+
+/* GaussianDiffusion.q_sample (models/gaussian_diffusion.py:398-416): d_xt[b] = h_a[b] * d_x0[b] + h_s[b] * noise[b] over fp32
+ * [B, T, P], h_a / h_s host arrays [B] (dc_q_sample_coefficients).  Two rounded products and one rounded sum per element, never
+ * contracted: the bits of the reference's fp32 tensor expression.
+ *   d_noise != NULL: that tensor (the reference's `noise=` argument); seed, iteration, first_element are not read and d_noise_out
+ *                    must be NULL.
+ *   d_noise == NULL: the library's Philox stream, draw (seed, iteration, first_element + element) - exactly what
+ *                    dc_step_noise_fill writes for (seed, iteration) at that element, so a clip's draw does not depend on the batch
+ *                    it sits in when first_element is its offset in the whole data set's draw.  The reference draws th.randn_like
+ *                    on its own generator (:1017-1018).  d_noise_out (may be NULL) receives the draws: an EPSILON model's target.
+ * d_xt, d_noise_out and d_x0 are distinct buffers.  B, T, P >= 1. */
+DC_EXPORT int dc_q_sample(const float* d_x0, const float* d_noise, const float* h_a, const float* h_s, int32_t B, int32_t T, int32_t P,
+                          uint64_t seed, int32_t iteration, uint64_t first_element, float* d_noise_out, float* d_xt, void* stream);
+
+/* The reductions of training_losses (:1075-1083) and the masked reconstruction sum of backward_G (ddpm_trainer.py:232-233), PER CLIP:
+ * d_pred, d_target fp32 [B, T, 26] (8-byte aligned), h_length int32 [B] (NULL = all T) -> d_terms fp32 [B][DC_LOSS_TERMS]:
+ *   [0]  mse_b = mean over (T, 26) of (target - pred)^2                               (:1079; not masked, as in the reference)
+ *   [1]  rec_b = sum over frames t < length_b of the mean over the 26 channels of (pred - target)^2
+ *                                                       (the numerator of ddpm_trainer.py:232-233; the batch scalar is sum rec_b / sum length_b)
+ *   [2] [3] [4]  mean over (T - 1, group) of (pred[t+1] - pred[t])^2, channel groups body {10..13, 22..25}, elbow {14..21},
+ *                head {0..9}                                                                                     (:1075-1082)
+ *   [5]  mean over (T - 1, 26) of ((target[t+1] - target[t]) - (pred[t+1] - pred[t]))^2                          (:1083)
+ *   [6] [7]  0
+ * Every clip has the same element count, so the reference's batch scalars are the plain means of these over the clips, and a clip's
+ * numbers do not depend on its neighbours.  One workgroup of 256 threads per clip: a fixed number of fp32 partials combined in a
+ * fixed tree, no floating-point atomics - a rerun is bit-identical (orders and the error bound they give: csrc/dc_loss.hip).
+ * DC_ERR_INVALID before any device call: P != 26, T < 2 (the velocity means run over no elements; the reference returns NaN there),
+ * a length outside [1, T], a NULL or misaligned tensor. */
+#define DC_LOSS_TERMS 8
+DC_EXPORT int dc_motion_loss_terms(const float* d_pred, const float* d_target, const int32_t* h_length, int32_t B, int32_t T, int32_t P,
+                                   float* d_terms, void* stream);
+
+/* The latent feature term of backward_G (ddpm_trainer.py:237-238: L1Loss of features(fake)[-1] against features(real)[-1]), PER CLIP:
+ * d_a, d_b fp32 [B, 64, T] as dc_motion_encoder_encode writes them (16-byte aligned) -> d_out fp32 [B], the clip's mean |a - b|.
+ * The reference's scalar is the plain mean over the clips.  Same reduction rules as dc_motion_loss_terms.  B, T >= 1. */
+DC_EXPORT int dc_latent_l1(const float* d_a, const float* d_b, int32_t B, int32_t T, float* d_out, void* stream);
+
 /* Introspection used by tests: bytes of device workspace currently held; frames per clip of the sampler's internal token space
  * (the T of dc_sampler_set_conditioning, padded to whole 32-frame groups where the clip-aligned kernels run): the layout of the
  * buffers dc_sampler_debug_read returns. */
