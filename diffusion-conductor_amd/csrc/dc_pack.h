@@ -1,6 +1,7 @@
 // dc_pack.h - host-only half of the weight preparation (no kernels, no HIP call): 16-bit conversions, the MFMA fragment
-// packers, the 256-byte-aligned host arena, and the MusicEncoder's folded image.  Included by dc_api.hip (denoiser image,
-// dc_pack_weight) and dc_music.hip; the single copy of every rounding routine both must agree on bit for bit.
+// packers, the 256-byte-aligned host arena, the MusicEncoder's folded image, M2SNet's fuse head and the M2S-GAN generator's image.
+// Included by dc_api.hip (denoiser image, dc_pack_weight), dc_music.hip, dc_m2snet.hip and dc_m2sgan.hip; the single copy of every
+// rounding routine they must agree on bit for bit.
 #pragma once
 #include <stdint.h>
 
@@ -324,4 +325,136 @@ inline std::vector<float> m2s_head_pack(const DcParams& params) {
     memcpy(img.data() + kHeadB1, P("fuse_layer.2.bias").data(), kHeadHid * sizeof(float));
     img[kHeadB2] = P("fuse_layer.4.bias")[0];
     return img;
+}
+
+// ---- M2S-GAN generator image (kernels: dc_m2sgan.hip) -------------------------------------------------------------
+// The decoder of Contrastive_Stage/models/Generator.py:52-77: six TemporalBlocks (models/TCN.py:19-52; Conv1d kernel 5, dilation
+// 2^i, weight norm, eval-mode BatchNorm), TCN.linear, the fc head, and the noise branch's four ConvTranspose1d + noise_BN.
+constexpr int kGanC = 64, kGanIn = 128, kGanTaps = 5, kGanBlocks = 6, kGanPose = 26, kGanLatent = 8;
+struct GanConvT {
+    int cin, cout, k, stride, pad;
+};
+constexpr GanConvT kGanNoise[4] = {{8, 16, 3, 1, 1}, {16, 16, 11, 5, 3}, {16, 32, 5, 3, 1}, {32, 64, 6, 2, 2}};
+inline std::string gan_block(int i) { return "tcn.TCN.tcn.tcn.network." + std::to_string(i) + "."; }
+
+// One weight-normed Conv1d with the eval-mode BatchNorm behind it as ONE weight and bias:
+//   W[o][tap cin + ci] = s_o g_o v[o][ci][tap] / |v[o]|,   b[o] = (cb_o - mean_o) s_o + beta_o,   s_o = gamma_o / sqrt(var_o + eps)
+// (|v[o]| over (ci, tap): torch's weight_norm with dim = 0).  v [cout][cin][k]; W [cout][k cin], tap-major - the k order of the
+// convolution's GEMM.  Computed in fp64 and rounded once.
+inline void gan_fold_conv(const float* g, const float* v, const float* cb, const float* gamma, const float* beta, const float* mean,
+                          const float* var, int cout, int cin, int k, float* W, float* b) {
+    for (int o = 0; o < cout; ++o) {
+        double n2 = 0.0;
+        for (int i = 0; i < cin * k; ++i) n2 += (double)v[(size_t)o * cin * k + i] * v[(size_t)o * cin * k + i];
+        const double s = (double)gamma[o] / std::sqrt((double)var[o] + (double)kBnEps), a = s * g[o] / std::sqrt(n2);
+        for (int ci = 0; ci < cin; ++ci)
+            for (int tap = 0; tap < k; ++tap)
+                W[(size_t)o * k * cin + (size_t)tap * cin + ci] = (float)(a * v[((size_t)o * cin + ci) * k + tap]);
+        b[o] = (float)(((double)cb[o] - mean[o]) * s + beta[o]);
+    }
+}
+
+// v_mfma_f32_32x32x2_f32 A fragments of a 64-row W [64][k_in] with both output tiles of a k-step side by side, so a lane reads
+// them as one 8-byte load: dst[(ks 64 + l) 2 + mt] = W[32 mt + (l & 31)][2 ks + (l >> 5)]
+inline void gan_pack_frags2(const float* W, int k_in, float* dst) {
+    for (int ks = 0; ks < k_in / 2; ++ks)
+        for (int l = 0; l < 64; ++l)
+            for (int mt = 0; mt < 2; ++mt) dst[((size_t)ks * 64 + l) * 2 + mt] = W[(size_t)(32 * mt + (l & 31)) * k_in + 2 * ks + (l >> 5)];
+}
+
+struct GanImage {
+    std::vector<float> img;      // every entry at a multiple of 64 floats
+    struct Block {
+        size_t w1, b1, w2, b2;   // gan_pack_frags2 images (K = 5 cin) and plain [64] biases
+    } block[kGanBlocks];
+    size_t wd, bd;               // block 0's 1x1 downsample: gan_pack_frags2 (K = 128), plain bias
+    size_t hw[4], hb[4];         // TCN.linear, fc.0, fc.2, fc.4: head_pack_frags images ([mt][ks][lane]), plain biases
+    size_t nw[4], nb[4];         // noise branch: the ConvTranspose1d weights [cin][cout][k] and biases as they are
+    size_t nscale, nshift;       // noise_BN behind the last ReLU: y = scale x + shift
+    size_t add(const std::vector<float>& v) {
+        const size_t off = (img.size() + 63) & ~(size_t)63;
+        img.resize(off + v.size());
+        memcpy(img.data() + off, v.data(), v.size() * sizeof(float));
+        return off;
+    }
+};
+
+// names and sizes of the state_dict entries the generator's decoder computes with (the `music_encoder.*` ones: dc_music_required)
+inline std::vector<std::pair<std::string, size_t>> gan_required() {
+    std::vector<std::pair<std::string, size_t>> r;
+    for (int i = 0; i < kGanBlocks; ++i) {
+        const std::string p = gan_block(i);
+        for (int c = 1; c <= 2; ++c) {
+            const std::string cv = p + "conv" + std::to_string(c), bn = p + "bn" + std::to_string(c);
+            const size_t cin = (i == 0 && c == 1) ? kGanIn : kGanC;
+            r.push_back({cv + ".bias", kGanC});
+            r.push_back({cv + ".weight_g", kGanC});
+            r.push_back({cv + ".weight_v", kGanC * cin * kGanTaps});
+            for (const char* s : {".weight", ".bias", ".running_mean", ".running_var"}) r.push_back({bn + s, kGanC});
+        }
+        if (i == 0) {
+            r.push_back({p + "downsample.weight", (size_t)kGanC * kGanIn});
+            r.push_back({p + "downsample.bias", kGanC});
+        }
+    }
+    r.push_back({"tcn.TCN.tcn.linear.weight", (size_t)kGanC * kGanC});
+    r.push_back({"tcn.TCN.tcn.linear.bias", kGanC});
+    for (int i = 0; i < 3; ++i) {
+        const size_t n = i == 2 ? kGanPose : kGanC;
+        r.push_back({"tcn.fc." + std::to_string(2 * i) + ".weight", n * kGanC});
+        r.push_back({"tcn.fc." + std::to_string(2 * i) + ".bias", n});
+    }
+    for (int i = 0; i < 4; ++i) {
+        const GanConvT& c = kGanNoise[i];
+        r.push_back({"noise_convTranspose." + std::to_string(2 * i) + ".weight", (size_t)c.cin * c.cout * c.k});
+        r.push_back({"noise_convTranspose." + std::to_string(2 * i) + ".bias", (size_t)c.cout});
+    }
+    for (const char* s : {".weight", ".bias", ".running_mean", ".running_var"}) r.push_back({std::string("noise_BN") + s, kGanC});
+    return r;
+}
+
+// params: every entry of gan_required, with its size
+inline GanImage gan_pack(const DcParams& params) {
+    const auto P = [&](const std::string& n) -> const float* { return params.find(n)->second.data(); };
+    GanImage I;
+    const auto conv = [&](const std::string& cv, const std::string& bn, int cin, size_t& w, size_t& b) {
+        std::vector<float> W((size_t)kGanC * kGanTaps * cin), bias(kGanC), frags(W.size());
+        gan_fold_conv(P(cv + ".weight_g"), P(cv + ".weight_v"), P(cv + ".bias"), P(bn + ".weight"), P(bn + ".bias"), P(bn + ".running_mean"),
+                      P(bn + ".running_var"), kGanC, cin, kGanTaps, W.data(), bias.data());
+        gan_pack_frags2(W.data(), kGanTaps * cin, frags.data());
+        w = I.add(frags);
+        b = I.add(bias);
+    };
+    for (int i = 0; i < kGanBlocks; ++i) {
+        const std::string p = gan_block(i);
+        conv(p + "conv1", p + "bn1", i == 0 ? kGanIn : kGanC, I.block[i].w1, I.block[i].b1);
+        conv(p + "conv2", p + "bn2", kGanC, I.block[i].w2, I.block[i].b2);
+    }
+    std::vector<float> fd((size_t)kGanC * kGanIn);
+    gan_pack_frags2(P(gan_block(0) + "downsample.weight"), kGanIn, fd.data());
+    I.wd = I.add(fd);
+    I.bd = I.add(params.find(gan_block(0) + "downsample.bias")->second);
+    const std::string head[4] = {"tcn.TCN.tcn.linear", "tcn.fc.0", "tcn.fc.2", "tcn.fc.4"};
+    for (int i = 0; i < 4; ++i) {
+        const int n = i == 3 ? kGanPose : kGanC;
+        std::vector<float> f((size_t)cdiv(n, 32) * (kGanC / 2) * 64), b(kGanC, 0.f);
+        head_pack_frags(P(head[i] + ".weight"), n, kGanC, f.data());
+        memcpy(b.data(), P(head[i] + ".bias"), n * sizeof(float));
+        I.hw[i] = I.add(f);
+        I.hb[i] = I.add(b);
+    }
+    for (int i = 0; i < 4; ++i) {
+        const std::string p = "noise_convTranspose." + std::to_string(2 * i);
+        I.nw[i] = I.add(params.find(p + ".weight")->second);
+        I.nb[i] = I.add(params.find(p + ".bias")->second);
+    }
+    std::vector<float> sc(kGanC), sh(kGanC);
+    for (int c = 0; c < kGanC; ++c) {
+        const double s = (double)P("noise_BN.weight")[c] / std::sqrt((double)P("noise_BN.running_var")[c] + (double)kBnEps);
+        sc[c] = (float)s;
+        sh[c] = (float)((double)P("noise_BN.bias")[c] - (double)P("noise_BN.running_mean")[c] * s);
+    }
+    I.nscale = I.add(sc);
+    I.nshift = I.add(sh);
+    return I;
 }

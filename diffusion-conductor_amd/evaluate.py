@@ -500,6 +500,42 @@ def validation_dataset(trainer, root, timesteps=None, batch_size=32, seed=0, mot
     return {"clips": len(ids), "timesteps": grid, "per_timestep": rows, "average": avg, "evaluations": n_levels, "seconds": dt}
 
 
+def _evaluation_encoders(args, dev):
+    """(motion encoder for --metrics | None, M2SNet for --sync | None) as main's flags ask for them."""
+    menc = None
+    if args.metrics or args.m2snet:
+        from .motion_encoder import MotionEncoder_STGCN, load_m2snet
+        if args.m2snet:
+            menc = load_m2snet(args.m2snet, dev)
+        else:
+            from .synthetic import synthetic_motion_encoder_state_dict
+            menc = MotionEncoder_STGCN(dev).load_state_dict(synthetic_motion_encoder_state_dict())
+            print("--metrics without --m2snet: the motion encoder has seeded synthetic weights, so SE / FGD / feat_dist / diversity "
+                  "only check the pipeline, they say nothing about the motions")
+    m2s = None
+    if args.sync:
+        from .m2snet import M2SNet, load_m2snet_full
+        if args.m2snet:
+            m2s = load_m2snet_full(args.m2snet, dev)
+        else:
+            from .synthetic import synthetic_m2snet_state_dict
+            m2s = M2SNet(dev).load_state_dict(synthetic_m2snet_state_dict())
+            print("--sync without --m2snet: M2SNet has seeded synthetic weights, so the m2s_* scores only check the pipeline")
+    return menc, m2s
+
+
+def _baseline_main(args, dev):
+    """--baseline_generator: evaluate_dataset on the M2S-GAN generator (generator.GeneratorBaseline), one JSON line."""
+    import json
+    from .generator import GeneratorBaseline, load_m2sgan_generator
+    gen = load_m2sgan_generator(args.baseline_generator, dev)
+    menc, m2s = _evaluation_encoders(args, dev)
+    r = evaluate_dataset(GeneratorBaseline(gen), args.data_root, 26, args.batch_size, args.limit, args.seed, args.smooth, verbose=False,
+                         motion_encoder=menc, diversity_seed=args.diversity_seed, m2snet=m2s)
+    print(json.dumps({"model": "m2sgan", **r}))
+    return 0
+
+
 def main(argv=None):
     """python -m diffusion_conductor_amd.evaluate --data_root <dir> [--model latest.tar] [--batch_size 32]"""
     import argparse
@@ -529,10 +565,22 @@ def main(argv=None):
                                                             "one JSON line, no sampling loop (validation_dataset)")
     ap.add_argument("--val_timesteps", type=int, default=None, help="--val_loss on a grid of this many noise levels (omitted: one uniform "
                                                                     "timestep per clip, the training protocol)")
+    ap.add_argument("--baseline_generator", default=None, help="score the M2S-GAN generator of this checkpoint (a plain state_dict, "
+                                                               "M2SGAN_eval.py:451) instead of the denoiser: the same evaluation, one JSON "
+                                                               "line with \"model\": \"m2sgan\" (generator.py)")
     args = ap.parse_args(argv)
+    if args.baseline_generator:
+        clash = [f for f, on in (("--model", args.model), ("--val_loss", args.val_loss), ("--guidance_scale", args.guidance_scale is not None),
+                                 ("--steps", args.steps is not None), ("--solver", args.solver != "ddim"), ("--spacing", args.spacing != "uniform"),
+                                 ("--no_eff", args.no_eff), ("--diffusion_steps", args.diffusion_steps != 1000)) if on]
+        if clash:
+            ap.error(f"--baseline_generator scores the M2S-GAN generator, one forward pass per clip: {', '.join(clash)} belong"
+                     f"{'s' if len(clash) == 1 else ''} to the diffusion denoiser and cannot be combined with it")
     from . import DDPMTrainer, MotionTransformer
     dev = torch.device("cuda", args.gpu_id)
     torch.cuda.set_device(dev)
+    if args.baseline_generator:
+        return _baseline_main(args, dev)
     enc = MotionTransformer(input_feats=26, num_frames=1800, num_layers=8, latent_dim=128, no_clip=True, no_eff=args.no_eff,
                             device=dev, music_model_path=None)
     opt = types.SimpleNamespace(device=dev, diffusion_steps=args.diffusion_steps, is_train=False)
@@ -543,25 +591,7 @@ def main(argv=None):
         from .synthetic import synthetic_state_dict
         enc.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in synthetic_state_dict().items()}, strict=True)
     tr.eval_mode()
-    menc = None
-    if args.metrics or args.m2snet:
-        from .motion_encoder import MotionEncoder_STGCN, load_m2snet
-        if args.m2snet:
-            menc = load_m2snet(args.m2snet, dev)
-        else:
-            from .synthetic import synthetic_motion_encoder_state_dict
-            menc = MotionEncoder_STGCN(dev).load_state_dict(synthetic_motion_encoder_state_dict())
-            print("--metrics without --m2snet: the motion encoder has seeded synthetic weights, so SE / FGD / feat_dist / diversity "
-                  "only check the pipeline, they say nothing about the motions")
-    m2s = None
-    if args.sync:
-        from .m2snet import M2SNet, load_m2snet_full
-        if args.m2snet:
-            m2s = load_m2snet_full(args.m2snet, dev)
-        else:
-            from .synthetic import synthetic_m2snet_state_dict
-            m2s = M2SNet(dev).load_state_dict(synthetic_m2snet_state_dict())
-            print("--sync without --m2snet: M2SNet has seeded synthetic weights, so the m2s_* scores only check the pipeline")
+    menc, m2s = _evaluation_encoders(args, dev)
     if args.val_loss:
         import json
         r = validation_dataset(tr, args.data_root, args.val_timesteps, args.batch_size, args.seed, motion_encoder=menc, limit=args.limit)

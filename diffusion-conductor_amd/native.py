@@ -34,6 +34,8 @@ EXPORTS = [
     "dc_solver_table", "dc_sampler_solver_loop", "dc_sampler_solver_profile_loop",
     "dc_sampler_set_conditioning_takes",
     "dc_q_sample_coefficients", "dc_q_sample", "dc_motion_loss_terms", "dc_latent_l1",
+    "dc_m2sgan_create", "dc_m2sgan_destroy", "dc_m2sgan_set_param", "dc_m2sgan_finalize", "dc_m2sgan_features", "dc_m2sgan_decode",
+    "dc_m2sgan_generate", "dc_m2sgan_debug_blocks", "dc_m2sgan_fold_conv",
 ]
 
 UPDATE_CLIP_DENOISED, UPDATE_EPSILON = 1, 2          # flags of dc_sampler_ddim_loop_ex
@@ -52,8 +54,8 @@ class DcError(RuntimeError):
     pass
 
 
-SOURCES = ("dc_kernels.hip", "dc_api.hip", "dc_music.hip", "dc_layer16.hip", "dc_stgcn.hip", "dc_m2snet.hip", "dc_loss.hip")
-HEADERS = ("dc_common.h", "dc_dev.h", "dc_form.h", "dc_launch.h", "dc_music.h", "dc_pack.h")
+SOURCES = ("dc_kernels.hip", "dc_api.hip", "dc_music.hip", "dc_layer16.hip", "dc_stgcn.hip", "dc_m2snet.hip", "dc_loss.hip", "dc_m2sgan.hip")
+HEADERS = ("dc_common.h", "dc_dev.h", "dc_form.h", "dc_launch.h", "dc_mfma_f32.h", "dc_music.h", "dc_pack.h")
 EXTRA_FLAGS = {}      # per-source compiler flags
 
 
@@ -179,6 +181,16 @@ def lib():
                               C.c_void_p, C.c_void_p, C.c_void_p]
     L.dc_motion_loss_terms.argtypes = [C.c_void_p, C.c_void_p, ip, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     L.dc_latent_l1.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    L.dc_m2sgan_create.argtypes = [C.c_int32, C.POINTER(C.c_void_p)]
+    L.dc_m2sgan_destroy.argtypes = [C.c_void_p]
+    L.dc_m2sgan_destroy.restype = None
+    L.dc_m2sgan_set_param.argtypes = [C.c_void_p, C.c_char_p, fp, C.c_int64]
+    L.dc_m2sgan_finalize.argtypes = [C.c_void_p]
+    L.dc_m2sgan_features.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    L.dc_m2sgan_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    L.dc_m2sgan_generate.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    L.dc_m2sgan_debug_blocks.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    L.dc_m2sgan_fold_conv.argtypes = [fp] * 7 + [C.c_int32] * 3 + [fp, fp]
     _lib = L
     return L
 
@@ -351,6 +363,18 @@ def latent_l1(a, b):
         _check(lib().dc_latent_l1(a.data_ptr(), b.data_ptr(), int(a.shape[0]), int(a.shape[2]), out.data_ptr(),
                                   C.c_void_p(torch.cuda.current_stream().cuda_stream)))
     return out
+
+
+def m2sgan_fold_conv(weight_g, weight_v, conv_bias, bn_weight, bn_bias, bn_mean, bn_var):
+    """dc_m2sgan_fold_conv: one weight-normed Conv1d (weight_g [cout, 1, 1], weight_v [cout, cin, k], bias) and the eval-mode BatchNorm
+    behind it as the generator's finalize folds them -> (W fp32 [cout, k * cin], column tap * cin + ci; b fp32 [cout]).  Host only."""
+    v = np.ascontiguousarray(weight_v, np.float32)
+    cout, cin, k = v.shape
+    vecs = [np.ascontiguousarray(np.asarray(a, np.float32).reshape(-1)) for a in (weight_g, conv_bias, bn_weight, bn_bias, bn_mean, bn_var)]
+    assert all(a.shape == (cout,) for a in vecs), "one value per output channel"
+    W, b = np.empty((cout, k * cin), np.float32), np.empty(cout, np.float32)
+    _check(lib().dc_m2sgan_fold_conv(_fptr(vecs[0]), _fptr(v), *[_fptr(a) for a in vecs[1:]], cout, cin, k, _fptr(W), _fptr(b)))
+    return W, b
 
 
 def describe_status(st: int, precision: str) -> str:
@@ -819,3 +843,91 @@ class NativeM2SNet:
             _check(lib().dc_m2snet_score(self._h, mel.data_ptr(), motion.data_ptr(), B, Tm, T, prob.data_ptr(),
                                          logit.data_ptr() if logits else None, self._stream()))
         return (prob, logit) if logits else prob
+
+
+# ---------------------------------------------------------------------------------------
+# the M2S-GAN generator (the baseline of the evaluation table)
+# ---------------------------------------------------------------------------------------
+class NativeM2SGAN:
+    """Owns one dc_m2sgan (dc_ddim.h).  Tensors are torch CUDA(ROCm) tensors; only their data_ptr() crosses the ABI.  Shapes the
+    library refuses (T <= 128, T != 30 Ln, T != (Tm-1)//3+1) raise ValueError before the call."""
+
+    def __init__(self, device=0):
+        self._h = C.c_void_p()
+        _check(lib().dc_m2sgan_create(int(device), C.byref(self._h)))
+        self.device = int(device)
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            lib().dc_m2sgan_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_param(self, name, a):
+        a = np.ascontiguousarray(np.asarray(a), np.float32)
+        _check(lib().dc_m2sgan_set_param(self._h, name.encode(), _fptr(a), a.size))
+
+    def finalize(self):
+        _check(lib().dc_m2sgan_finalize(self._h))
+
+    _ok = staticmethod(NativeM2SNet._ok)
+    _stream = staticmethod(NativeM2SNet._stream)
+
+    @staticmethod
+    def check_frames(T, Tm=None, Ln=None):
+        """The library's shape rules (dc_ddim.h) as ValueErrors."""
+        if Tm is not None and (Tm < 4 or T != (Tm - 1) // 3 + 1):
+            raise ValueError(f"{Tm} mel frames make {(Tm - 1) // 3 + 1 if Tm >= 4 else 0} frames, not {T} (and at least 4 are needed)")
+        if Ln is not None and T != 30 * Ln:
+            raise ValueError(f"a latent of {Ln} steps makes {30 * Ln} frames, the music has {T}")
+        if T <= 128:
+            raise ValueError(f"{T} frames: the generator's last temporal block reflects 128 frames and needs T > 128 (T >= 150)")
+
+    def _inputs(self, mel, noise):
+        self._ok(mel)
+        self._ok(noise)
+        assert mel.dim() == 3 and mel.shape[2] == 128, tuple(mel.shape)
+        B, Tm, Ln = int(mel.shape[0]), int(mel.shape[1]), int(noise.shape[1])
+        self._ok(noise, (B, Ln, 8))
+        T = (Tm - 1) // 3 + 1 if Tm >= 4 else 0
+        self.check_frames(T, Tm, Ln)
+        return B, Tm, Ln, T
+
+    def features(self, mel, noise):
+        """mel fp32 [B, Tm, 128], noise fp32 [B, Ln, 8] on the device -> Generator.features fp32 [B, T, 128]."""
+        import torch
+        B, Tm, Ln, T = self._inputs(mel, noise)
+        out = torch.empty((B, T, 128), dtype=torch.float32, device=mel.device)
+        with torch.cuda.device(mel.device):
+            _check(lib().dc_m2sgan_features(self._h, mel.data_ptr(), B, Tm, noise.data_ptr(), Ln, out.data_ptr(), self._stream()))
+        return out
+
+    def generate(self, mel, noise):
+        """mel fp32 [B, Tm, 128], noise fp32 [B, Ln, 8] on the device -> poses fp32 [B, T, 26]."""
+        import torch
+        B, Tm, Ln, T = self._inputs(mel, noise)
+        out = torch.empty((B, T, 26), dtype=torch.float32, device=mel.device)
+        with torch.cuda.device(mel.device):
+            _check(lib().dc_m2sgan_generate(self._h, mel.data_ptr(), B, Tm, noise.data_ptr(), Ln, out.data_ptr(), self._stream()))
+        return out
+
+    def decode(self, feat, n_blocks=None):
+        """features fp32 [B, T, 128] on the device -> poses fp32 [B, T, 26]; `n_blocks` in 1 .. 6 (test hook): the residual stream
+        [B, T, 64] after that many temporal blocks instead."""
+        import torch
+        self._ok(feat)
+        assert feat.dim() == 3 and feat.shape[2] == 128, tuple(feat.shape)
+        B, T = int(feat.shape[0]), int(feat.shape[1])
+        self.check_frames(T)
+        out = torch.empty((B, T, 26 if n_blocks is None else 64), dtype=torch.float32, device=feat.device)
+        with torch.cuda.device(feat.device):
+            if n_blocks is None:
+                _check(lib().dc_m2sgan_decode(self._h, feat.data_ptr(), B, T, out.data_ptr(), self._stream()))
+            else:
+                _check(lib().dc_m2sgan_debug_blocks(self._h, feat.data_ptr(), B, T, int(n_blocks), out.data_ptr(), self._stream()))
+        return out

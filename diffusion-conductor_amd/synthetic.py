@@ -279,3 +279,62 @@ def synthetic_m2snet_state_dict(seed: int = 0):
                 a = np.full(shape, M2SNET_FUSE_LAST_BIAS)
             out[name] = np.ascontiguousarray(a, dtype=np.float32)
     return out
+
+
+# the seeded M2S-GAN decoder (see synthetic_m2sgan_state_dict): gain of the temporal blocks' weight-norm magnitudes, size of the
+# BatchNorm shifts that pin a few units dead / live, gains of TCN.linear and the three fc layers, gain of the noise branch
+M2SGAN_CONV_GAIN = 0.5
+M2SGAN_PIN_SHIFT = 6.0
+M2SGAN_HEAD_GAIN = (1.0, 1.5, 2.0, 3.0)
+M2SGAN_NOISE_GAIN = 3.0
+
+
+def synthetic_m2sgan_state_dict(seed: int = 0):
+    """name -> np.ndarray for every state_dict entry of the M2S-GAN Generator (generator.py), in the reference module's order: the
+    `music_encoder.*` entries of synthetic_state_dict(seed) and a seeded decoder.  At the reference's own initialiser scale
+    (normal_(0, 0.01)) every pose sits within 0.03 of 0.5, which tests nothing, so: `weight_v` ~ U(-1, 1) / sqrt(fan_in) and
+    `weight_g` = M2SGAN_CONV_GAIN U(0.6, 1.6) - not |weight_v| -, BatchNorm affines and running statistics away from the identity,
+    with two units per BatchNorm of the temporal blocks shifted by -/+ M2SGAN_PIN_SHIFT (dead / live on every frame), the head's
+    weights U(-1, 1) / sqrt(fan_in) times M2SGAN_HEAD_GAIN per layer and the noise branch's times M2SGAN_NOISE_GAIN.  On the
+    fixture's inputs (tools/make_golden_m2sgan.py asserts it) the poses span more than [0.2, 0.8], every ReLU of the temporal blocks
+    has dead, live and switching units, and the latent moves the poses by more than 1e-2.  The `net.N.*` aliases equal their twins."""
+    from .generator import ALIASES, m2sgan_shapes
+    den = synthetic_state_dict(seed=seed)
+    shapes = m2sgan_shapes()
+    head = {"tcn.TCN.tcn.linear": 0, "tcn.fc.0": 1, "tcn.fc.2": 2, "tcn.fc.4": 3}
+    out = OrderedDict()
+    for name, shape in shapes.items():
+        if name.startswith("music_encoder."):
+            out[name] = den[name]
+            continue
+        canon = name
+        for alias, twin in ALIASES:
+            canon = canon.replace(f".{alias}.", f".{twin}.")
+        if canon != name:
+            out[name] = out[canon]
+            continue
+        g = _rng(seed, "m2sgan:" + name)
+        mod, leaf = name.rsplit(".", 1)
+        bn = ".bn" in name or name.startswith("noise_BN")
+        if leaf == "num_batches_tracked":
+            out[name] = np.asarray(1000, dtype=np.int64)
+            continue
+        if leaf == "running_mean":
+            a = 0.1 * g.standard_normal(shape)
+        elif leaf == "running_var":
+            a = g.uniform(0.5, 1.5, shape)
+        elif bn:
+            a = (1.0 + 0.2 * g.standard_normal(shape)) if leaf == "weight" else 0.2 * g.standard_normal(shape)
+            if leaf == "bias" and ".bn" in name:
+                pin = _rng(seed, "m2sgan:pin:" + name).choice(shape[0], size=4, replace=False)
+                a[pin[:2]], a[pin[2:]] = -M2SGAN_PIN_SHIFT, M2SGAN_PIN_SHIFT
+        elif leaf == "weight_g":
+            a = M2SGAN_CONV_GAIN * g.uniform(0.6, 1.6, shape)
+        else:
+            wshape = shapes[mod + (".weight_v" if (mod + ".weight_v") in shapes else ".weight")]
+            # (ConvTranspose1d weights are [cin, cout, k]: fan_in = cin k)
+            fan_in = wshape[0] * wshape[2] if name.startswith("noise_convTranspose") else int(np.prod(wshape[1:]))
+            gain = M2SGAN_HEAD_GAIN[head[mod]] if mod in head else (M2SGAN_NOISE_GAIN if name.startswith("noise_convTranspose") else 1.0)
+            a = g.uniform(-1.0, 1.0, shape) * (gain / np.sqrt(fan_in))
+        out[name] = np.ascontiguousarray(a, dtype=np.float32)
+    return out

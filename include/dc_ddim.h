@@ -497,6 +497,56 @@ DC_EXPORT int dc_m2snet_fuse(dc_m2snet* n, const float* d_music_latent, const fl
 DC_EXPORT int dc_m2snet_score(dc_m2snet* n, const float* d_mel, const float* d_motion, int32_t B, int32_t Tm, int32_t T,
                               float* d_prob, float* d_logit, void* stream);
 
+/* ---- M2S-GAN generator: the baseline the diffusion denoiser is compared against ----------------------------------------------
+ * Replaces constructing Generator (Contrastive_Stage/models/Generator.py:52-65: a MusicEncoder, the noise branch's four
+ * ConvTranspose1d + noise_BN, and PoseDecoderTCN on the DialtedCNN of models/TCN.py) on the device `device`.  Implemented in
+ * csrc/dc_m2sgan.hip; none of it is on the sampling path. */
+typedef struct dc_m2sgan dc_m2sgan;
+DC_EXPORT int dc_m2sgan_create(int32_t device, dc_m2sgan** out);
+DC_EXPORT void dc_m2sgan_destroy(dc_m2sgan* g);
+
+/* Replaces Generator.load_state_dict (Contrastive_Stage/M2SGAN_eval.py:451 loads the plain state_dict): one call per entry - 278
+ * of them - with its key and contiguous fp32 data.  The parameters are "music_encoder.*" (MusicEncoder.py:30-53),
+ * "tcn.TCN.tcn.tcn.network.{0..5}.{conv1,conv2}.{bias,weight_g,weight_v}", ".{bn1,bn2}.{weight,bias,running_mean,running_var}",
+ * "tcn.TCN.tcn.tcn.network.0.downsample.{weight,bias}" (TCN.py:22-39), "tcn.TCN.tcn.linear.*" (:77), "tcn.fc.{0,2,4}.*"
+ * (Generator.py:39-43), "noise_convTranspose.{0,2,4,6}.*" and "noise_BN.*" (:59-65).  The ".net.{0,2,5,7}.*" entries of a block -
+ * the same tensors under their nn.Sequential names - and the num_batches_tracked counters are accepted (their sizes checked)
+ * and ignored.  Unknown key or wrong numel -> DC_ERR_PARAM. */
+DC_EXPORT int dc_m2sgan_set_param(dc_m2sgan* g, const char* name, const float* h_data, int64_t numel);
+
+/* Replaces Generator.eval() + .to(device): folds weight norm (TCN.py:22, 29) and every BatchNorm (running statistics) into one
+ * fp32 weight and bias per convolution, noise_BN into a scale and shift behind the last ReLU of the noise branch, packs and
+ * uploads.  An entry the generator computes with that was never set -> DC_ERR_PARAM.  Synchronous.  Every entry point below
+ * returns DC_ERR_INVALID before it. */
+DC_EXPORT int dc_m2sgan_finalize(dc_m2sgan* g);
+
+/* The shapes of the entry points below: d_mel fp32 [B, Tm, 128], d_noise fp32 [B, Ln, 8], T = (Tm-1)/3+1 = 30 Ln frames.
+ * DC_ERR_INVALID before anything is enqueued: B < 1, Tm < 4, T != (Tm-1)/3+1, T != 30 Ln, T <= 128 (the reference raises there:
+ * the last temporal block's reflection padding of 128 frames needs T > 128; the shortest length is T = 150), a NULL pointer.
+ * Every product of the temporal blocks and the head is exact fp32 in k order; a clip's result is bit-identical whatever the batch
+ * around it, and on every rerun.  Intermediate planes live in the handle's workspace (grown on demand; 32 clips per pass).
+ * A handle serves ONE stream at a time: its workspace and weight image are shared by all its calls, and growing the workspace
+ * waits for the calling stream only.  Calls on another stream must be ordered behind the earlier ones by the caller; not thread-safe.
+ *
+ * dc_m2sgan_features replaces Generator.features (Generator.py:79-86): cat(music_encoder(x), noise_BN(noise_convTranspose(noise^T))^T)
+ * -> d_feat fp32 [B, T, 128].  The music encoder always runs the DC_ME_SPLIT format; DC_ME_PREC does not apply to it. */
+DC_EXPORT int dc_m2sgan_features(dc_m2sgan* g, const float* d_mel, int32_t B, int32_t Tm, const float* d_noise, int32_t Ln, float* d_feat,
+                                 void* stream);
+/* Replaces self.tcn(input) (Generator.py:73; PoseDecoderTCN.forward :45-49, TCN.forward TCN.py:83-86, TemporalBlock.forward
+ * :49-52) on features the caller holds: d_feat fp32 [B, T, 128] (16-byte aligned) -> d_pose fp32 [B, T, 26]. */
+DC_EXPORT int dc_m2sgan_decode(dc_m2sgan* g, const float* d_feat, int32_t B, int32_t T, float* d_pose, void* stream);
+/* Replaces Generator.forward (Generator.py:67-77): -> d_pose fp32 [B, T, 26] (the reference views it as [B, T, 13, 2]). */
+DC_EXPORT int dc_m2sgan_generate(dc_m2sgan* g, const float* d_mel, int32_t B, int32_t Tm, const float* d_noise, int32_t Ln, float* d_pose,
+                                 void* stream);
+/* Test hook: the residual stream after the first n_blocks (1 .. 6) TemporalBlocks (TCN.py:49-52) of d_feat -> d_h fp32 [B, T, 64]. */
+DC_EXPORT int dc_m2sgan_debug_blocks(dc_m2sgan* g, const float* d_feat, int32_t B, int32_t T, int32_t n_blocks, float* d_h, void* stream);
+/* Test hook, host only: one weight-normed Conv1d (weight_g [cout], weight_v [cout, cin, k], bias; TCN.py:22-23) and the eval-mode
+ * BatchNorm1d behind it (:25) as finalize folds them -> h_w fp32 [cout, k cin] (column tap cin + ci: the k order of the
+ * convolution's GEMM), h_b fp32 [cout].  Computed in fp64, rounded once. */
+DC_EXPORT int dc_m2sgan_fold_conv(const float* weight_g, const float* weight_v, const float* conv_bias, const float* bn_weight,
+                                  const float* bn_bias, const float* bn_mean, const float* bn_var, int32_t cout, int32_t cin, int32_t k,
+                                  float* h_w, float* h_b);
+
 /* ---- Held-out denoising losses: the forward value of the objective a checkpoint was trained on ---------------------------------
  * GaussianDiffusion.training_losses (models/gaussian_diffusion.py:1002-1090) and the weighting of DDPMTrainer.backward_G
  * (trainers/ddpm_trainer.py:223-268) as an EVALUATOR: one model evaluation per clip and noise level, no gradients.  The model
