@@ -21,11 +21,9 @@
 #include <cstdint>
 #include <string>
 
-#include "../../include/dc_ddim.h"
 #include "dc_common.h"
+#include "dc_handle.h"
 #include "dc_launch.h"
-
-int dc_set_error(int code, const char* msg);      // dc_api.hip: sets dc_last_error's message
 
 // No contraction anywhere in this file: hipcc's default (-ffp-contract=fast) fuses a product into the addition that consumes it.
 // HIP's __fmul_rn / __fadd_rn do not prevent that - they are inline functions of plain operators compiled under the default, and
@@ -38,12 +36,6 @@ int dc_set_error(int code, const char* msg);      // dc_api.hip: sets dc_last_er
                                 // allocation, nothing for a stream capture to trip over)
 
 namespace {
-
-#define HIP_TRY(expr)                                                                                                          \
-    do {                                                                                                                       \
-        hipError_t e_ = (expr);                                                                                                \
-        if (e_ != hipSuccess) return dc_set_error(DC_ERR_HIP, (std::string(#expr) + " failed: " + hipGetErrorString(e_)).c_str()); \
-    } while (0)
 
 struct ClipScalars {
     float a[DC_LOSS_CHUNK], s[DC_LOSS_CHUNK];
@@ -193,7 +185,7 @@ int dc_q_sample(const float* d_x0, const float* d_noise, const float* h_a, const
     if (!nz) {
         // the draws of dc_step_noise_fill, by the same kernel; without d_noise_out they land in d_xt and are replaced in place
         float* buf = d_noise_out ? d_noise_out : d_xt;
-        HIP_TRY(dc_launch_step_noise(st, buf, (size_t)B * per_clip, seed, nullptr, nullptr, iteration, nullptr, first_element));
+        DC_HIP_TRY(dc_launch_step_noise(st, buf, (size_t)B * per_clip, seed, nullptr, nullptr, iteration, nullptr, first_element));
         nz = buf;
     }
     const bool vec = (per_clip & 3) == 0 && aligned(d_x0, 16) && aligned(nz, 16) && aligned(d_xt, 16);
@@ -208,7 +200,7 @@ int dc_q_sample(const float* d_x0, const float* d_noise, const float* h_a, const
             k_q_sample<true><<<dim3(gx ? gx : 1, nb), dim3(256), 0, st>>>(d_x0 + off, nz + off, d_xt + off, per_clip, cs);
         else
             k_q_sample<false><<<dim3(gx ? gx : 1, nb), dim3(256), 0, st>>>(d_x0 + off, nz + off, d_xt + off, per_clip, cs);
-        HIP_TRY(hipGetLastError());
+        DC_HIP_TRY(hipGetLastError());
     }
     return DC_OK;
 }
@@ -233,7 +225,7 @@ int dc_motion_loss_terms(const float* d_pred, const float* d_target, const int32
         for (int i = 0; i < DC_LOSS_CHUNK; ++i) cl.len[i] = i < nb ? (h_length ? h_length[b0 + i] : T) : 0;
         const size_t off = (size_t)b0 * T * 26;
         k_motion_loss_terms<<<dim3(nb), dim3(DC_LOSS_THREADS), 0, st>>>(d_pred + off, d_target + off, d_terms + (size_t)b0 * DC_LOSS_TERMS, T, cl);
-        HIP_TRY(hipGetLastError());
+        DC_HIP_TRY(hipGetLastError());
     }
     return DC_OK;
 }
@@ -244,7 +236,7 @@ int dc_latent_l1(const float* d_a, const float* d_b, int32_t B, int32_t T, float
     if ((int64_t)T * 16 > INT32_MAX) return dc_set_error(DC_ERR_INVALID, "dc_latent_l1: T is too large");
     if (!aligned(d_a, 16) || !aligned(d_b, 16)) return dc_set_error(DC_ERR_INVALID, "dc_latent_l1: the latents must be 16-byte aligned");
     k_latent_l1<<<dim3(B), dim3(DC_LOSS_THREADS), 0, (hipStream_t)stream>>>(d_a, d_b, d_out, T);
-    HIP_TRY(hipGetLastError());
+    DC_HIP_TRY(hipGetLastError());
     return DC_OK;
 }
 

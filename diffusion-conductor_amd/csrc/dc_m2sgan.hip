@@ -30,12 +30,9 @@
 #include <string>
 #include <vector>
 
-#include "../../include/dc_ddim.h"
 #include "dc_common.h"
+#include "dc_handle.h"
 #include "dc_mfma_f32.h"
-#include "dc_music.h"
-
-int dc_set_error(int code, const char* msg);      // dc_api.hip: sets dc_last_error's message
 
 namespace {
 
@@ -72,16 +69,15 @@ __global__ __launch_bounds__(64 * G_WAVES) void k_gan_conv(const float* __restri
     f32x16 a0 = {}, a1 = {}, r0 = {}, r1 = {};
 #pragma unroll 1
     for (int tap = 0; tap < 5; ++tap) {
-        const f32x4* row = reinterpret_cast<const f32x4*>(xb + (size_t)reflect(tc + (tap - 2) * d, T) * CIN);
+        const float* row = xb + (size_t)reflect(tc + (tap - 2) * d, T) * CIN;
 #pragma unroll 1
         for (int cc = 0; cc < CH; ++cc) {
             f32x4 m[16];
-#pragma unroll
-            for (int i = 0; i < 16; ++i) m[i] = row[cc * 16 + i];
+            load_row64(row + cc * 64, m);
             const float2* wq = w2 + (size_t)(tap * CH + cc) * 32 * 64;
 #pragma unroll
             for (int ks = 0; ks < 32; ++ks) {
-                const float v = h ? m[ks >> 1][2 * (ks & 1) + 1] : m[ks >> 1][2 * (ks & 1)];      // channel 64 cc + 2 ks + h
+                const float v = row_operand(m, ks, h);      // channel 64 cc + 2 ks + h
                 const float2 ww = wq[ks * 64];
                 a0 = mfma2(ww.x, v, a0);
                 a1 = mfma2(ww.y, v, a1);
@@ -90,7 +86,7 @@ __global__ __launch_bounds__(64 * G_WAVES) void k_gan_conv(const float* __restri
                 const float2* wq = wd2 + (size_t)cc * 32 * 64;
 #pragma unroll
                 for (int ks = 0; ks < 32; ++ks) {
-                    const float v = h ? m[ks >> 1][2 * (ks & 1) + 1] : m[ks >> 1][2 * (ks & 1)];
+                    const float v = row_operand(m, ks, h);
                     const float2 ww = wq[ks * 64];
                     r0 = mfma2(ww.x, v, r0);
                     r1 = mfma2(ww.y, v, r1);
@@ -106,7 +102,7 @@ __global__ __launch_bounds__(64 * G_WAVES) void k_gan_conv(const float* __restri
         f32x4 y0, y1;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const int c = 8 * q + 4 * h + e;
+            const int c = tile_channel(4 * q + e, h);
             y0[e] = relu(a0[4 * q + e] + bias[c]);
             y1[e] = relu(a1[4 * q + e] + bias[c + 32]);
         }
@@ -129,7 +125,7 @@ __global__ __launch_bounds__(64 * G_WAVES) void k_gan_conv(const float* __restri
             f32x4 d0, d1;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const int c = 8 * q + 4 * h + e;
+                const int c = tile_channel(4 * q + e, h);
                 d0[e] = r0[4 * q + e] + bd[c];
                 d1[e] = r1[4 * q + e] + bd[c + 32];
             }
@@ -152,51 +148,31 @@ __global__ __launch_bounds__(64 * G_WAVES) void k_gan_head(const float* __restri
     const int t = t0 + j;
     const bool inside = t < T;
     const size_t frame = (size_t)blockIdx.y * T + (inside ? t : T - 1);
-    const f32x4* row = reinterpret_cast<const f32x4*>(hid + frame * 64);
     f32x4 m[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) m[i] = row[i];
+    load_row64(hid + frame * 64, m);
     const float* w0 = P + hd.w[0];
     f32x16 a0 = {}, a1 = {};
 #pragma unroll
     for (int ks = 0; ks < 32; ++ks) {
-        const float v = h ? m[ks >> 1][2 * (ks & 1) + 1] : m[ks >> 1][2 * (ks & 1)];      // channel 2 ks + h
+        const float v = row_operand(m, ks, h);
         a0 = mfma2(w0[ks * 64 + lane], v, a0);
         a1 = mfma2(w0[(32 + ks) * 64 + lane], v, a1);
     }
-    const float* b = P + hd.b[0];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int o = (r & 3) + 8 * (r >> 2) + 4 * h;
-        a0[r] += b[o];
-        a1[r] += b[o + 32];
-    }
+    add_bias<false>(a0, a1, P + hd.b[0], h);
     f32x16 c0 = {}, c1 = {};
     Layer<0, 32>::run<2, 32>(P + hd.w[1], lane, h, a0, a1, c0, c1);
-    b = P + hd.b[1];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int o = (r & 3) + 8 * (r >> 2) + 4 * h;
-        c0[r] = relu(c0[r] + b[o]);
-        c1[r] = relu(c1[r] + b[o + 32]);
-    }
+    add_bias<true>(c0, c1, P + hd.b[1], h);
     f32x16 e0 = {}, e1 = {};
     Layer<0, 32>::run<2, 32>(P + hd.w[2], lane, h, c0, c1, e0, e1);
-    b = P + hd.b[2];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int o = (r & 3) + 8 * (r >> 2) + 4 * h;
-        e0[r] = relu(e0[r] + b[o]);
-        e1[r] = relu(e1[r] + b[o + 32]);
-    }
+    add_bias<true>(e0, e1, P + hd.b[2], h);
     f32x16 p0 = {}, p1 = {};
     Layer<0, 32>::run<1, 32>(P + hd.w[3], lane, h, e0, e1, p0, p1);      // 26 rows of one tile
-    b = P + hd.b[3];
+    const float* b = P + hd.b[3];
     if (!inside) return;
     float* dst = pose + frame * 26;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int o = (r & 3) + 8 * (r >> 2) + 4 * h;
+        const int o = tile_channel(r, h);
         if (o < 26) dst[o] = 1.f / (1.f + expf(-(p0[r] + b[o])));
     }
 }
@@ -227,14 +203,7 @@ __global__ __launch_bounds__(256) void k_gan_convt(const float* __restrict__ x, 
     if (copy) y[rowi * ystride + co] = copy[rowi * 64 + co];
 }
 
-#define GAN_TRY(expr)                                                                                                 \
-    do {                                                                                                              \
-        hipError_t e_ = (expr);                                                                                       \
-        if (e_ != hipSuccess) return dc_set_error(DC_ERR_HIP, (std::string(#expr) + " failed: " + hipGetErrorString(e_)).c_str()); \
-    } while (0)
-
-bool starts_with(const std::string& s, const std::string& p) { return s.rfind(p, 0) == 0; }
-bool ends_with(const std::string& s, const std::string& e) { return s.size() >= e.size() && s.compare(s.size() - e.size(), e.size(), e) == 0; }
+const char* const kWhat = "M2S-GAN";
 
 // `net.N` of a TemporalBlock's nn.Sequential -> the attribute the same module is registered under first (TCN.py:22-38)
 std::string unalias(const std::string& k) {
@@ -251,12 +220,11 @@ std::string unalias(const std::string& k) {
 
 struct dc_m2sgan {
     int device = 0;
-    DcParams music_params, params;
-    dc_music* music = nullptr;
+    DcOwnedMusic music;                  // from the generator's own `music_encoder.*` entries
+    DcParams params;
     GanImage image;                      // offsets (the floats themselves are dropped after the upload)
     float* d_img = nullptr;
-    float* d_ws = nullptr;
-    size_t ws_floats = 0;
+    DcWorkspace ws;
     bool finalized = false;
 };
 
@@ -277,23 +245,10 @@ struct GanPlan {
     size_t floats() const { return 7 * plane + noise; }      // hx, feat (2 planes), x0, x1, h, res
 };
 
-int grow(dc_m2sgan* g, const GanPlan& pl, hipStream_t st) {
-    if (g->ws_floats >= pl.floats()) return DC_OK;
-    if (g->d_ws) {
-        GAN_TRY(hipStreamSynchronize(st));    // (the previous call's work on this stream may still read the old planes)
-        GAN_TRY(hipFree(g->d_ws));
-        g->d_ws = nullptr;
-        g->ws_floats = 0;
-    }
-    GAN_TRY(hipMalloc((void**)&g->d_ws, pl.floats() * sizeof(float)));
-    g->ws_floats = pl.floats();
-    return DC_OK;
-}
-
 // feat [nb][T][128] -> after n_blocks TemporalBlocks the residual stream [nb][T][64] at *hid (one of the workspace planes)
 int blocks_run(dc_m2sgan* g, const GanPlan& pl, const float* feat, int nb, int T, int n_blocks, const float** hid, hipStream_t st) {
-    float* xs[2] = {g->d_ws + 3 * pl.plane, g->d_ws + 4 * pl.plane};
-    float *hp = g->d_ws + 5 * pl.plane, *rp = g->d_ws + 6 * pl.plane;
+    float* xs[2] = {g->ws.p + 3 * pl.plane, g->ws.p + 4 * pl.plane};
+    float *hp = g->ws.p + 5 * pl.plane, *rp = g->ws.p + 6 * pl.plane;
     const float* P = g->d_img;
     const GanImage& I = g->image;
     const dim3 g32(pl.gx32, nb), g30(pl.gx30, nb);
@@ -308,7 +263,7 @@ int blocks_run(dc_m2sgan* g, const GanPlan& pl, const float* feat, int nb, int T
         k_gan_conv<64, false, true><<<g30, 64 * G_WAVES, 0, st>>>(hp, P + bk.w2, P + bk.b2, nullptr, nullptr, i == 0 ? rp : x, y, nullptr, T, 1 << i);
         x = y;
     }
-    GAN_TRY(hipGetLastError());
+    DC_HIP_TRY(hipGetLastError());
     *hid = x;
     return DC_OK;
 }
@@ -319,18 +274,16 @@ int decode_run(dc_m2sgan* g, const GanPlan& pl, const float* feat, int nb, int T
     GanHead hd;
     for (int i = 0; i < 4; ++i) hd.w[i] = (unsigned)g->image.hw[i], hd.b[i] = (unsigned)g->image.hb[i];
     k_gan_head<<<dim3(pl.gx32, nb), 64 * G_WAVES, 0, st>>>(hid, g->d_img, hd, pose, T);
-    GAN_TRY(hipGetLastError());
+    DC_HIP_TRY(hipGetLastError());
     return DC_OK;
 }
 
 // mel [nb][Tm][128], noise [nb][Ln][8] -> feat [nb][T][128]
 int features_run(dc_m2sgan* g, const GanPlan& pl, const float* mel, int nb, int Tm, const float* noise, int Ln, int T, float* feat,
                  hipStream_t st) {
-    float* hx = g->d_ws;
-    std::string err;
-    const hipError_t e = dc_music_encode(g->music, mel, nb, Tm, nullptr, hx, st, &err);
-    if (e != hipSuccess) return dc_set_error(DC_ERR_HIP, (std::string("M2S-GAN music encoder: ") + hipGetErrorString(e) + " " + err).c_str());
-    float* np = g->d_ws + 7 * pl.plane;
+    float* hx = g->ws.p;
+    if (const int rc = g->music.encode(kWhat, mel, nb, Tm, hx, st)) return rc;
+    float* np = g->ws.p + 7 * pl.plane;
     float* planes[3] = {np, np + (size_t)nb * Ln * 16, np + (size_t)nb * Ln * (16 + 5 * 16)};
     const float* P = g->d_img;
     const GanImage& I = g->image;
@@ -347,7 +300,7 @@ int features_run(dc_m2sgan* g, const GanPlan& pl, const float* mel, int nb, int 
         x = y;
         L = Lout;
     }
-    GAN_TRY(hipGetLastError());
+    DC_HIP_TRY(hipGetLastError());
     return DC_OK;
 }
 
@@ -375,9 +328,7 @@ extern "C" {
 int dc_m2sgan_create(int32_t device, dc_m2sgan** out) {
     if (!out) return dc_set_error(DC_ERR_INVALID, "dc_m2sgan_create: out is NULL");
     *out = nullptr;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n < 1) return dc_set_error(DC_ERR_NO_DEVICE, "dc_m2sgan_create: no HIP device visible");
-    if (device < 0 || device >= n) return dc_set_error(DC_ERR_INVALID, ("dc_m2sgan_create: no device " + std::to_string(device)).c_str());
+    if (const int rc = dc_check_device("dc_m2sgan_create", device)) return rc;
     auto* g = new dc_m2sgan;
     g->device = device;
     *out = g;
@@ -386,63 +337,35 @@ int dc_m2sgan_create(int32_t device, dc_m2sgan** out) {
 
 void dc_m2sgan_destroy(dc_m2sgan* g) {
     if (!g) return;
-    int cur = -1;                        // (a failure here has nobody to report to; the caller's device is put back)
-    (void)hipGetDevice(&cur);
-    (void)hipSetDevice(g->device);
-    dc_music_destroy(g->music);
+    const DcDeviceGuard on(g->device);
+    g->music.release();
     if (g->d_img) (void)hipFree(g->d_img);
-    if (g->d_ws) (void)hipFree(g->d_ws);
-    if (cur >= 0) (void)hipSetDevice(cur);
+    g->ws.release();
     delete g;
 }
 
 int dc_m2sgan_set_param(dc_m2sgan* g, const char* name, const float* h_data, int64_t numel) {
     if (!g || !name || !h_data) return dc_set_error(DC_ERR_INVALID, "dc_m2sgan_set_param: NULL argument");
     const std::string given(name), k = unalias(given);
-    const auto wrong = [&](size_t want) {
-        return dc_set_error(DC_ERR_PARAM, ("M2S-GAN parameter " + given + " has " + std::to_string(numel) + " elements, expected " +
-                                           std::to_string(want)).c_str());
-    };
-    const bool music = starts_with(k, "music_encoder.");
-    const std::vector<std::pair<std::string, size_t>> req = music ? dc_music_required(kGanC, false) : gan_required();
-    for (const auto& r : req)
-        if (r.first == k) {
-            if ((size_t)numel != r.second) return wrong(r.second);
-            if (k != given) return DC_OK;                // a `net.N.*` alias: the same tensor as its conv / bn twin, which is the parameter
-            (music ? g->music_params : g->params)[k].assign(h_data, h_data + numel);
-            g->finalized = false;
-            return DC_OK;
-        }
-    // the BatchNorm counters: state_dict entries eval mode never applies
-    const std::string nbt = ".num_batches_tracked";
-    if (ends_with(k, nbt)) {
-        const std::string rm = k.substr(0, k.size() - nbt.size()) + ".running_mean";
-        for (const auto& r : req)
-            if (r.first == rm) return numel == 1 ? DC_OK : wrong(1);
-    }
-    return dc_set_error(DC_ERR_PARAM, ("unknown M2S-GAN parameter " + given).c_str());
+    bool changed = false;
+    // a `net.N.*` alias (k != given) is the same tensor as its conv / bn twin, which is the parameter: checked and dropped
+    const int rc = starts_with(k, "music_encoder.") ? g->music.take(kWhat, kGanC, k, h_data, numel, &changed)
+                                                    : dc_param_take(kWhat, gan_required(), {}, k, given, h_data, numel, k == given ? &g->params : nullptr, &changed);
+    if (changed) g->finalized = false;
+    return rc;
 }
 
 int dc_m2sgan_finalize(dc_m2sgan* g) {
     if (!g) return dc_set_error(DC_ERR_INVALID, "dc_m2sgan_finalize: NULL handle");
     g->finalized = false;
-    std::string err;
-    if (!dc_music_check(g->music_params, kGanC, &err, false)) return dc_set_error(DC_ERR_PARAM, ("M2S-GAN music encoder: " + err).c_str());
-    for (const auto& r : gan_required())
-        if (!g->params.count(r.first)) return dc_set_error(DC_ERR_PARAM, ("M2S-GAN parameter " + r.first + " was not set").c_str());
-    GAN_TRY(hipSetDevice(g->device));
-    if (g->music) {
-        GAN_TRY(hipDeviceSynchronize());     // (work of earlier calls may still read the old weights)
-        dc_music_destroy(g->music);
-        g->music = nullptr;
-    }
-    g->music = dc_music_build(g->music_params, kGanC, &err, false);
-    if (!g->music) return dc_set_error(DC_ERR_PARAM, ("M2S-GAN music encoder: " + err).c_str());
-    dc_music_pin_format(g->music, DC_ME_SPLIT);      // a baseline's numbers must not move with DC_ME_PREC
+    if (const int rc = g->music.check(kWhat, kGanC)) return rc;
+    if (const int rc = dc_param_complete(kWhat, gan_required(), g->params)) return rc;
+    DC_HIP_TRY(hipSetDevice(g->device));
+    if (const int rc = g->music.rebuild(kWhat, kGanC)) return rc;
     g->image = gan_pack(g->params);
     const size_t bytes = g->image.img.size() * sizeof(float);
-    if (!g->d_img) GAN_TRY(hipMalloc((void**)&g->d_img, bytes));
-    GAN_TRY(hipMemcpy(g->d_img, g->image.img.data(), bytes, hipMemcpyHostToDevice));
+    if (!g->d_img) DC_HIP_TRY(hipMalloc((void**)&g->d_img, bytes));
+    DC_HIP_TRY(hipMemcpy(g->d_img, g->image.img.data(), bytes, hipMemcpyHostToDevice));
     g->image.img = std::vector<float>();
     g->finalized = true;
     return DC_OK;
@@ -453,32 +376,26 @@ int dc_m2sgan_features(dc_m2sgan* g, const float* d_mel, int32_t B, int32_t Tm, 
     if (!g || !d_mel || !d_noise || !d_feat) return dc_set_error(DC_ERR_INVALID, "dc_m2sgan_features: NULL argument");
     const int T = Tm >= 4 ? dc_music_frames(Tm) : 0;
     if (const int rc = check_shapes("dc_m2sgan_features", g, B, Tm, Ln, T)) return rc;
-    GAN_TRY(hipSetDevice(g->device));
+    DC_HIP_TRY(hipSetDevice(g->device));
     hipStream_t st = (hipStream_t)stream;
     const GanPlan pl(B, T);
-    if (const int rc = grow(g, pl, st)) return rc;
-    for (int b0 = 0; b0 < B; b0 += pl.chunk) {
-        const int nb = B - b0 < pl.chunk ? B - b0 : pl.chunk;
-        if (const int rc = features_run(g, pl, d_mel + (size_t)b0 * Tm * 128, nb, Tm, d_noise + (size_t)b0 * Ln * kGanLatent, Ln, T,
-                                        d_feat + (size_t)b0 * T * 128, st))
-            return rc;
-    }
-    return DC_OK;
+    if (const int rc = g->ws.reserve(pl.floats(), st)) return rc;
+    return dc_chunks(B, pl.chunk, [&](int b0, int nb) -> int {
+        return features_run(g, pl, d_mel + (size_t)b0 * Tm * 128, nb, Tm, d_noise + (size_t)b0 * Ln * kGanLatent, Ln, T, d_feat + (size_t)b0 * T * 128, st);
+    });
 }
 
 int dc_m2sgan_decode(dc_m2sgan* g, const float* d_feat, int32_t B, int32_t T, float* d_pose, void* stream) {
     if (!g || !d_feat || !d_pose) return dc_set_error(DC_ERR_INVALID, "dc_m2sgan_decode: NULL argument");
     if (const int rc = check_shapes("dc_m2sgan_decode", g, B, -1, -1, T)) return rc;
     if ((uintptr_t)d_feat & 15) return dc_set_error(DC_ERR_INVALID, "dc_m2sgan_decode: the features must be 16-byte aligned");
-    GAN_TRY(hipSetDevice(g->device));
+    DC_HIP_TRY(hipSetDevice(g->device));
     hipStream_t st = (hipStream_t)stream;
     const GanPlan pl(B, T);
-    if (const int rc = grow(g, pl, st)) return rc;
-    for (int b0 = 0; b0 < B; b0 += pl.chunk) {
-        const int nb = B - b0 < pl.chunk ? B - b0 : pl.chunk;
-        if (const int rc = decode_run(g, pl, d_feat + (size_t)b0 * T * 128, nb, T, d_pose + (size_t)b0 * T * kGanPose, st)) return rc;
-    }
-    return DC_OK;
+    if (const int rc = g->ws.reserve(pl.floats(), st)) return rc;
+    return dc_chunks(B, pl.chunk, [&](int b0, int nb) -> int {
+        return decode_run(g, pl, d_feat + (size_t)b0 * T * 128, nb, T, d_pose + (size_t)b0 * T * kGanPose, st);
+    });
 }
 
 int dc_m2sgan_generate(dc_m2sgan* g, const float* d_mel, int32_t B, int32_t Tm, const float* d_noise, int32_t Ln, float* d_pose,
@@ -486,18 +403,16 @@ int dc_m2sgan_generate(dc_m2sgan* g, const float* d_mel, int32_t B, int32_t Tm, 
     if (!g || !d_mel || !d_noise || !d_pose) return dc_set_error(DC_ERR_INVALID, "dc_m2sgan_generate: NULL argument");
     const int T = Tm >= 4 ? dc_music_frames(Tm) : 0;
     if (const int rc = check_shapes("dc_m2sgan_generate", g, B, Tm, Ln, T)) return rc;
-    GAN_TRY(hipSetDevice(g->device));
+    DC_HIP_TRY(hipSetDevice(g->device));
     hipStream_t st = (hipStream_t)stream;
     const GanPlan pl(B, T);
-    if (const int rc = grow(g, pl, st)) return rc;
-    float* feat = g->d_ws + pl.plane;
-    for (int b0 = 0; b0 < B; b0 += pl.chunk) {
-        const int nb = B - b0 < pl.chunk ? B - b0 : pl.chunk;
+    if (const int rc = g->ws.reserve(pl.floats(), st)) return rc;
+    float* feat = g->ws.p + pl.plane;
+    return dc_chunks(B, pl.chunk, [&](int b0, int nb) -> int {
         if (const int rc = features_run(g, pl, d_mel + (size_t)b0 * Tm * 128, nb, Tm, d_noise + (size_t)b0 * Ln * kGanLatent, Ln, T, feat, st))
             return rc;
-        if (const int rc = decode_run(g, pl, feat, nb, T, d_pose + (size_t)b0 * T * kGanPose, st)) return rc;
-    }
-    return DC_OK;
+        return decode_run(g, pl, feat, nb, T, d_pose + (size_t)b0 * T * kGanPose, st);
+    });
 }
 
 int dc_m2sgan_debug_blocks(dc_m2sgan* g, const float* d_feat, int32_t B, int32_t T, int32_t n_blocks, float* d_h, void* stream) {
@@ -505,17 +420,16 @@ int dc_m2sgan_debug_blocks(dc_m2sgan* g, const float* d_feat, int32_t B, int32_t
     if (const int rc = check_shapes("dc_m2sgan_debug_blocks", g, B, -1, -1, T)) return rc;
     if (n_blocks < 1 || n_blocks > kGanBlocks) return dc_set_error(DC_ERR_INVALID, "dc_m2sgan_debug_blocks: n_blocks must be 1 .. 6");
     if ((uintptr_t)d_feat & 15) return dc_set_error(DC_ERR_INVALID, "dc_m2sgan_debug_blocks: the features must be 16-byte aligned");
-    GAN_TRY(hipSetDevice(g->device));
+    DC_HIP_TRY(hipSetDevice(g->device));
     hipStream_t st = (hipStream_t)stream;
     const GanPlan pl(B, T);
-    if (const int rc = grow(g, pl, st)) return rc;
-    for (int b0 = 0; b0 < B; b0 += pl.chunk) {
-        const int nb = B - b0 < pl.chunk ? B - b0 : pl.chunk;
+    if (const int rc = g->ws.reserve(pl.floats(), st)) return rc;
+    return dc_chunks(B, pl.chunk, [&](int b0, int nb) -> int {
         const float* hid = nullptr;
         if (const int rc = blocks_run(g, pl, d_feat + (size_t)b0 * T * 128, nb, T, n_blocks, &hid, st)) return rc;
-        GAN_TRY(hipMemcpyAsync(d_h + (size_t)b0 * T * 64, hid, (size_t)nb * T * 64 * sizeof(float), hipMemcpyDeviceToDevice, st));
-    }
-    return DC_OK;
+        DC_HIP_TRY(hipMemcpyAsync(d_h + (size_t)b0 * T * 64, hid, (size_t)nb * T * 64 * sizeof(float), hipMemcpyDeviceToDevice, st));
+        return DC_OK;
+    });
 }
 
 int dc_m2sgan_fold_conv(const float* weight_g, const float* weight_v, const float* conv_bias, const float* bn_weight, const float* bn_bias,

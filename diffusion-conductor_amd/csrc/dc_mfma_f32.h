@@ -1,4 +1,4 @@
-// dc_mfma_f32.h - device helpers of the exact-fp32 heads on v_mfma_f32_32x32x2_f32 (dc_m2snet.hip, dc_m2sgan.hip): one wave = 32
+// dc_mfma_f32.h - device helpers of the exact-fp32 kernels on v_mfma_f32_32x32x2_f32 (dc_stgcn.hip, dc_m2snet.hip, dc_m2sgan.hip): one wave = 32
 // frames of one clip on the lanes (lane l: frame l & 31, k half l >> 5), the weights as lane-major A fragments read from L2
 // (dc_pack.h, head_pack_frags), an accumulator tile handed on as the next layer's B operand.  Every output is one k-ordered fmaf
 // chain: no partial sums and no reduction across lanes, so a frame's result depends on that frame's inputs alone.
@@ -16,6 +16,29 @@ namespace dc_f32 {
 DEV f32x16 mfma2(float a, float b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
 // torch.relu: NaN stays NaN (fmaxf is v_max_f32, which returns the non-NaN operand)
 DEV float relu(float y) { return y < 0.f ? 0.f : y; }
+
+// the row (channel) of its 32-row tile that accumulator register r of lane half h holds (dc_pack.h's tile_row, on the device)
+DEV int tile_channel(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
+
+// A lane's frame as a channel-contiguous row of 64 floats (16-byte aligned): 16 float4 loads, then channel 2 ks + h as the B
+// operand of k-step ks.  ks must be a constant where this is called (a fully unrolled loop), or m[] goes to scratch.
+DEV void load_row64(const float* row, f32x4 (&m)[16]) {
+    const f32x4* p = reinterpret_cast<const f32x4*>(row);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) m[i] = p[i];
+}
+DEV float row_operand(const f32x4 (&m)[16], int ks, int h) { return h ? m[ks >> 1][2 * (ks & 1) + 1] : m[ks >> 1][2 * (ks & 1)]; }
+
+// + bias (, ReLU) over a 64-channel activation held as two accumulator tiles (channels 0 .. 31 in lo, 32 .. 63 in hi)
+template <bool RELU>
+DEV void add_bias(f32x16& lo, f32x16& hi, const float* b, int h) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int o = tile_channel(r, h);
+        lo[r] = RELU ? relu(lo[r] + b[o]) : lo[r] + b[o];
+        hi[r] = RELU ? relu(hi[r] + b[o + 32]) : hi[r] + b[o + 32];
+    }
+}
 
 // B operand of k-step S (channels 2 S and 2 S + 1) out of a 64-channel activation held as two accumulator tiles (channels
 // 0 .. 31 in lo, 32 .. 63 in hi; register r of lane half h = channel (r & 3) + 8 (r >> 2) + 4 h).  Both channels sit in half HC

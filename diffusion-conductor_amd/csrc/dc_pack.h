@@ -1,7 +1,7 @@
 // dc_pack.h - host-only half of the weight preparation (no kernels, no HIP call): 16-bit conversions, the MFMA fragment
-// packers, the 256-byte-aligned host arena, the MusicEncoder's folded image, M2SNet's fuse head and the M2S-GAN generator's image.
-// Included by dc_api.hip (denoiser image, dc_pack_weight), dc_music.hip, dc_m2snet.hip and dc_m2sgan.hip; the single copy of every
-// rounding routine they must agree on bit for bit.
+// packers, the 256-byte-aligned host arena, the MusicEncoder's folded image, M2SNet's fuse head, the M2S-GAN generator's image and
+// the ST-GCN motion encoder's.  Included by dc_api.hip (denoiser image, dc_pack_weight), dc_music.hip, dc_m2snet.hip, dc_m2sgan.hip
+// and dc_stgcn.hip; the single copy of every rounding routine they must agree on bit for bit.
 #pragma once
 #include <stdint.h>
 
@@ -158,6 +158,7 @@ struct Arena {
 };
 
 using DcParams = std::map<std::string, std::vector<float>>;
+using DcParamList = std::vector<std::pair<std::string, size_t>>;      // (name, numel) of state_dict entries
 
 // ---- MusicEncoder image (kernels: dc_music.hip) -------------------------------------------------------------------
 struct MusicConvSpec {
@@ -380,8 +381,8 @@ struct GanImage {
 };
 
 // names and sizes of the state_dict entries the generator's decoder computes with (the `music_encoder.*` ones: dc_music_required)
-inline std::vector<std::pair<std::string, size_t>> gan_required() {
-    std::vector<std::pair<std::string, size_t>> r;
+inline DcParamList gan_required() {
+    DcParamList r;
     for (int i = 0; i < kGanBlocks; ++i) {
         const std::string p = gan_block(i);
         for (int c = 1; c <= 2; ++c) {
@@ -457,4 +458,115 @@ inline GanImage gan_pack(const DcParams& params) {
     I.nscale = I.add(sc);
     I.nshift = I.add(sh);
     return I;
+}
+
+// ---- ST-GCN motion encoder image (kernels: dc_stgcn.hip) ----------------------------------------------------------
+// MotionEncoder_STGCN in eval mode; the network and the folding formulas are at the head of dc_stgcn.hip.  Everything is computed
+// in fp64 and rounded once, except Ahat = A * edge_importance, the reference's own fp32 product.
+constexpr int kStgcnV = 13, kStgcnC = 32, kStgcnL = 10, kStgcnOut = 64, kStgcnK = kStgcnC * kStgcnV;   // joints, channels, blocks, latent, fc K
+// device parameter image (floats).  Per block: W1 fragments [16 kk][64 lanes] (lane l = W1'[l & 31][2 kk + (l >> 5)]; block 0
+// uses kk = 0 only), W2 fragments [3 tap][16 kk][64], b1' [13 w][32 c], b2' [32], Ahat [13 w][13 v] (+ pad).
+constexpr int kStgcnW1 = 0, kStgcnW2 = kStgcnW1 + 16 * 64, kStgcnB1 = kStgcnW2 + 3 * 16 * 64, kStgcnB2 = kStgcnB1 + kStgcnV * kStgcnC,
+              kStgcnAhat = kStgcnB2 + kStgcnC, kStgcnBlockFloats = kStgcnAhat + 176;
+constexpr int kStgcnDbn = kStgcnL * kStgcnBlockFloats;           // data_bn scale [26] at +0, shift [26] at +32
+constexpr int kStgcnFcW = kStgcnDbn + 64;                        // fc fragments [2 mt][208 ks][64]: lane l = W'[32 mt + (l & 31)][2 ks + (l >> 5)]
+constexpr int kStgcnFcB = kStgcnFcW + 2 * (kStgcnK / 2) * 64;    // fc bias' [64]
+constexpr int kStgcnFloats = kStgcnFcB + kStgcnOut;
+// This fold has always added BatchNorm's epsilon as the double 1e-5; kBnEps widened is 2.5e-13 smaller, enough to move a folded
+// weight by an ulp where running_var is small.  Kept, so that the image stays what it was bit for bit.
+constexpr double kStgcnBnEps = 1e-5;
+inline std::string stgcn_block(int l) { return "st_gcn.st_gcn_networks." + std::to_string(l) + "."; }
+
+// names and sizes of the state_dict entries the encoder computes with ...
+inline DcParamList stgcn_required() {
+    DcParamList r;
+    const auto bn = [&](const std::string& p, size_t n) {
+        for (const char* s : {"weight", "bias", "running_mean", "running_var"}) r.push_back({p + s, n});
+    };
+    r.push_back({"st_gcn.A", kStgcnV * kStgcnV});
+    bn("st_gcn.data_bn.", 2 * kStgcnV);
+    for (int l = 0; l < kStgcnL; ++l) {
+        const std::string p = stgcn_block(l);
+        r.push_back({p + "gcn.conv.weight", (size_t)kStgcnC * (l == 0 ? 2 : kStgcnC)});
+        r.push_back({p + "gcn.conv.bias", kStgcnC});
+        bn(p + "tcn.0.", kStgcnC);
+        r.push_back({p + "tcn.2.weight", kStgcnC * kStgcnC * 3});
+        r.push_back({p + "tcn.2.bias", kStgcnC});
+        bn(p + "tcn.3.", kStgcnC);
+        r.push_back({"st_gcn.edge_importance." + std::to_string(l), kStgcnV * kStgcnV});
+    }
+    r.push_back({"fc.0.weight", (size_t)kStgcnOut * kStgcnK});
+    r.push_back({"fc.0.bias", kStgcnOut});
+    bn("fc.1.", kStgcnOut);
+    return r;
+}
+// ... and of those it never applies: ST_GCN's classification head (the BatchNorm counters go by the rule of dc_handle.h)
+inline DcParamList stgcn_ignored() { return {{"st_gcn.fcn.weight", 32 * 256}, {"st_gcn.fcn.bias", 32}}; }
+
+// params: every entry of stgcn_required, with its size
+inline std::vector<float> stgcn_pack(const DcParams& params) {
+    const auto P = [&](const std::string& n) -> const std::vector<float>& { return params.find(n)->second; };
+    // eval-mode BatchNorm as y = s x + h
+    const auto bn_affine = [&](const std::string& p, size_t n, std::vector<double>& s, std::vector<double>& h) {
+        const auto &g = P(p + "weight"), &be = P(p + "bias"), &rm = P(p + "running_mean"), &rv = P(p + "running_var");
+        s.resize(n);
+        h.resize(n);
+        for (size_t i = 0; i < n; ++i) {
+            s[i] = (double)g[i] / std::sqrt((double)rv[i] + kStgcnBnEps);
+            h[i] = (double)be[i] - (double)rm[i] * s[i];
+        }
+    };
+    std::vector<float> img(kStgcnFloats, 0.f);
+    const auto& A = P("st_gcn.A");
+    std::vector<double> s0, h0, s3, h3;
+    for (int l = 0; l < kStgcnL; ++l) {
+        const std::string p = stgcn_block(l);
+        const int cin = l == 0 ? 2 : kStgcnC;
+        float* blk = img.data() + (size_t)l * kStgcnBlockFloats;
+        const auto& E = P("st_gcn.edge_importance." + std::to_string(l));
+        const auto &W1 = P(p + "gcn.conv.weight"), &bb1 = P(p + "gcn.conv.bias");
+        const auto &W2 = P(p + "tcn.2.weight"), &bb2 = P(p + "tcn.2.bias");
+        bn_affine(p + "tcn.0.", kStgcnC, s0, h0);
+        bn_affine(p + "tcn.3.", kStgcnC, s3, h3);
+        double colsum[kStgcnV];
+        for (int w = 0; w < kStgcnV; ++w) {
+            colsum[w] = 0.0;
+            for (int v = 0; v < kStgcnV; ++v) {
+                const float a = A[v * kStgcnV + w] * E[v * kStgcnV + w];      // the reference's A * importance, in fp32
+                blk[kStgcnAhat + w * kStgcnV + v] = a;
+                colsum[w] += a;
+            }
+        }
+        for (int lane = 0; lane < 64; ++lane) {
+            const int c = lane & 31, hh = lane >> 5;
+            for (int kk = 0; kk < (l == 0 ? 1 : 16); ++kk) {
+                const int ci = 2 * kk + hh;
+                blk[kStgcnW1 + kk * 64 + lane] = (float)(s0[c] * W1[c * cin + ci]);
+            }
+            for (int k = 0; k < 3; ++k)
+                for (int kk = 0; kk < 16; ++kk) {
+                    const int ci = 2 * kk + hh;     // tcn.2.weight [c][ci][k][0]
+                    blk[kStgcnW2 + (k * 16 + kk) * 64 + lane] = (float)(s3[c] * W2[(c * kStgcnC + ci) * 3 + k]);
+                }
+        }
+        for (int w = 0; w < kStgcnV; ++w)
+            for (int c = 0; c < kStgcnC; ++c) blk[kStgcnB1 + w * kStgcnC + c] = (float)(s0[c] * bb1[c] * colsum[w] + h0[c]);
+        for (int c = 0; c < kStgcnC; ++c) blk[kStgcnB2 + c] = (float)(s3[c] * bb2[c] + h3[c]);
+    }
+    std::vector<double> sd, hd, sf, hf;
+    bn_affine("st_gcn.data_bn.", 2 * kStgcnV, sd, hd);
+    for (int i = 0; i < 2 * kStgcnV; ++i) {
+        img[kStgcnDbn + i] = (float)sd[i];
+        img[kStgcnDbn + 32 + i] = (float)hd[i];
+    }
+    bn_affine("fc.1.", kStgcnOut, sf, hf);
+    const auto &Wf = P("fc.0.weight"), &bf = P("fc.0.bias");
+    for (int mt = 0; mt < 2; ++mt)
+        for (int ks = 0; ks < kStgcnK / 2; ++ks)
+            for (int lane = 0; lane < 64; ++lane) {
+                const int o = 32 * mt + (lane & 31), k = 2 * ks + (lane >> 5);
+                img[kStgcnFcW + ((size_t)mt * (kStgcnK / 2) + ks) * 64 + lane] = (float)(sf[o] * Wf[(size_t)o * kStgcnK + k]);
+            }
+    for (int o = 0; o < kStgcnOut; ++o) img[kStgcnFcB + o] = (float)(sf[o] * bf[o] + hf[o]);
+    return img;
 }

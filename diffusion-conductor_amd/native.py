@@ -55,7 +55,7 @@ class DcError(RuntimeError):
 
 
 SOURCES = ("dc_kernels.hip", "dc_api.hip", "dc_music.hip", "dc_layer16.hip", "dc_stgcn.hip", "dc_m2snet.hip", "dc_loss.hip", "dc_m2sgan.hip")
-HEADERS = ("dc_common.h", "dc_dev.h", "dc_form.h", "dc_launch.h", "dc_mfma_f32.h", "dc_music.h", "dc_pack.h")
+HEADERS = ("dc_common.h", "dc_dev.h", "dc_form.h", "dc_handle.h", "dc_launch.h", "dc_mfma_f32.h", "dc_music.h", "dc_pack.h")
 EXTRA_FLAGS = {}      # per-source compiler flags
 
 
@@ -717,19 +717,24 @@ class NativeSampler:
 
 
 # ---------------------------------------------------------------------------------------
-# the motion encoder (M2SNet's ST-GCN, the evaluation metrics' latent space)
+# the evaluation networks' handles
 # ---------------------------------------------------------------------------------------
-class NativeMotionEncoder:
-    """Owns one dc_motion_encoder (dc_ddim.h).  Tensors are torch CUDA(ROCm) tensors; only their data_ptr() crosses the ABI."""
+class _NativeHandle:
+    """Owns one C handle of dc_ddim.h with PREFIX_create(device, &h) / _destroy / _set_param / _finalize.  Tensors are torch
+    CUDA(ROCm) tensors; only their data_ptr() crosses the ABI."""
+    _prefix = None
 
     def __init__(self, device=0):
         self._h = C.c_void_p()
-        _check(lib().dc_motion_encoder_create(int(device), C.byref(self._h)))
+        _check(self._fn("create")(int(device), C.byref(self._h)))
         self.device = int(device)
+
+    def _fn(self, name):
+        return getattr(lib(), f"{self._prefix}_{name}")
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
-            lib().dc_motion_encoder_destroy(self._h)
+            self._fn("destroy")(self._h)
             self._h = C.c_void_p()
 
     def __del__(self):
@@ -740,54 +745,10 @@ class NativeMotionEncoder:
 
     def set_param(self, name, a):
         a = np.ascontiguousarray(np.asarray(a), np.float32)
-        _check(lib().dc_motion_encoder_set_param(self._h, name.encode(), _fptr(a), a.size))
+        _check(self._fn("set_param")(self._h, name.encode(), _fptr(a), a.size))
 
     def finalize(self):
-        _check(lib().dc_motion_encoder_finalize(self._h))
-
-    def encode(self, motion, out=None):
-        """motion fp32 [B, T, 13, 2] (or [B, T, 26]) on the device -> latent fp32 [B, 64, T] (`out`: a tensor to fill)."""
-        import torch
-        assert motion.is_cuda and motion.dtype == torch.float32 and motion.is_contiguous()
-        B, T = int(motion.shape[0]), int(motion.shape[1])
-        assert motion.numel() == B * T * 26, tuple(motion.shape)
-        if out is None:
-            out = torch.empty((B, 64, T), dtype=torch.float32, device=motion.device)
-        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (B, 64, T)
-        with torch.cuda.device(motion.device):
-            _check(lib().dc_motion_encoder_encode(self._h, motion.data_ptr(), B, T, out.data_ptr(),
-                                                  C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-        return out
-
-
-# ---------------------------------------------------------------------------------------
-# M2SNet (the learned music-motion synchronisation score)
-# ---------------------------------------------------------------------------------------
-class NativeM2SNet:
-    """Owns one dc_m2snet (dc_ddim.h).  Tensors are torch CUDA(ROCm) tensors; only their data_ptr() crosses the ABI."""
-
-    def __init__(self, device=0):
-        self._h = C.c_void_p()
-        _check(lib().dc_m2snet_create(int(device), C.byref(self._h)))
-        self.device = int(device)
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            lib().dc_m2snet_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_param(self, name, a):
-        a = np.ascontiguousarray(np.asarray(a), np.float32)
-        _check(lib().dc_m2snet_set_param(self._h, name.encode(), _fptr(a), a.size))
-
-    def finalize(self):
-        _check(lib().dc_m2snet_finalize(self._h))
+        _check(self._fn("finalize")(self._h))
 
     @staticmethod
     def _ok(t, shape=None):
@@ -799,6 +760,35 @@ class NativeM2SNet:
     def _stream():
         import torch
         return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+# ---------------------------------------------------------------------------------------
+# the motion encoder (M2SNet's ST-GCN, the evaluation metrics' latent space)
+# ---------------------------------------------------------------------------------------
+class NativeMotionEncoder(_NativeHandle):
+    """Owns one dc_motion_encoder."""
+    _prefix = "dc_motion_encoder"
+
+    def encode(self, motion, out=None):
+        """motion fp32 [B, T, 13, 2] (or [B, T, 26]) on the device -> latent fp32 [B, 64, T] (`out`: a tensor to fill)."""
+        import torch
+        assert motion.is_cuda and motion.dtype == torch.float32 and motion.is_contiguous()
+        B, T = int(motion.shape[0]), int(motion.shape[1])
+        assert motion.numel() == B * T * 26, tuple(motion.shape)
+        if out is None:
+            out = torch.empty((B, 64, T), dtype=torch.float32, device=motion.device)
+        assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (B, 64, T)
+        with torch.cuda.device(motion.device):
+            _check(lib().dc_motion_encoder_encode(self._h, motion.data_ptr(), B, T, out.data_ptr(), self._stream()))
+        return out
+
+
+# ---------------------------------------------------------------------------------------
+# M2SNet (the learned music-motion synchronisation score)
+# ---------------------------------------------------------------------------------------
+class NativeM2SNet(_NativeHandle):
+    """Owns one dc_m2snet."""
+    _prefix = "dc_m2snet"
 
     def encode_music(self, mel, out=None):
         """mel fp32 [B, Tm, 128] on the device -> music latent fp32 [B, (Tm-1)//3+1, 64] (`out`: a tensor to fill)."""
@@ -848,35 +838,9 @@ class NativeM2SNet:
 # ---------------------------------------------------------------------------------------
 # the M2S-GAN generator (the baseline of the evaluation table)
 # ---------------------------------------------------------------------------------------
-class NativeM2SGAN:
-    """Owns one dc_m2sgan (dc_ddim.h).  Tensors are torch CUDA(ROCm) tensors; only their data_ptr() crosses the ABI.  Shapes the
-    library refuses (T <= 128, T != 30 Ln, T != (Tm-1)//3+1) raise ValueError before the call."""
-
-    def __init__(self, device=0):
-        self._h = C.c_void_p()
-        _check(lib().dc_m2sgan_create(int(device), C.byref(self._h)))
-        self.device = int(device)
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            lib().dc_m2sgan_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def set_param(self, name, a):
-        a = np.ascontiguousarray(np.asarray(a), np.float32)
-        _check(lib().dc_m2sgan_set_param(self._h, name.encode(), _fptr(a), a.size))
-
-    def finalize(self):
-        _check(lib().dc_m2sgan_finalize(self._h))
-
-    _ok = staticmethod(NativeM2SNet._ok)
-    _stream = staticmethod(NativeM2SNet._stream)
+class NativeM2SGAN(_NativeHandle):
+    """Owns one dc_m2sgan.  Shapes the library refuses (T <= 128, T != 30 Ln, T != (Tm-1)//3+1) raise ValueError before the call."""
+    _prefix = "dc_m2sgan"
 
     @staticmethod
     def check_frames(T, Tm=None, Ln=None):

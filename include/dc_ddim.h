@@ -437,7 +437,8 @@ DC_EXPORT int dc_savgol_filter(const float* d_in, float* d_out, int32_t B, int32
 
 /* Opaque handle of one encoder (device-resident folded weights + activation planes).  Not thread-safe.
  * Replaces constructing MotionEncoder_STGCN (trainers/ddpm_trainer.py:27-43; tools/eval_new_metrics.py:39-55) on the
- * device `device`. */
+ * device `device`.  dc_motion_encoder_destroy, like dc_m2snet_destroy and dc_m2sgan_destroy below, frees on the handle's device and
+ * puts the caller's current device back. */
 typedef struct dc_motion_encoder dc_motion_encoder;
 DC_EXPORT int dc_motion_encoder_create(int32_t device, dc_motion_encoder** out);
 DC_EXPORT void dc_motion_encoder_destroy(dc_motion_encoder* e);
