@@ -1,4 +1,4 @@
-// dc_handle.h - host scaffold of the evaluation networks' handles (dc_stgcn.hip, dc_m2snet.hip, dc_m2sgan.hip; dc_loss.hip takes
+// dc_handle.h - host scaffold of the evaluation networks' handles (dc_stgcn.hip, dc_m2snet.hip, dc_m2sgan.hip, dc_rhythm.hip; dc_loss.hip takes
 // the error macro): what each of them needs around its kernels and at least two of them share.  Internal, host only.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,4 +1,4 @@
-// dc_mfma_f32.h - device helpers of the exact-fp32 kernels on v_mfma_f32_32x32x2_f32 (dc_stgcn.hip, dc_m2snet.hip, dc_m2sgan.hip): one wave = 32
+// dc_mfma_f32.h - device helpers of the exact-fp32 kernels on v_mfma_f32_32x32x2_f32 (dc_stgcn.hip, dc_m2snet.hip, dc_m2sgan.hip, dc_rhythm.hip): one wave = 32
 // frames of one clip on the lanes (lane l: frame l & 31, k half l >> 5), the weights as lane-major A fragments read from L2
 // (dc_pack.h, head_pack_frags), an accumulator tile handed on as the next layer's B operand.  Every output is one k-ordered fmaf
 // chain: no partial sums and no reduction across lanes, so a frame's result depends on that frame's inputs alone.

@@ -1,7 +1,8 @@
 // dc_pack.h - host-only half of the weight preparation (no kernels, no HIP call): 16-bit conversions, the MFMA fragment
-// packers, the 256-byte-aligned host arena, the MusicEncoder's folded image, M2SNet's fuse head, the M2S-GAN generator's image and
-// the ST-GCN motion encoder's.  Included by dc_api.hip (denoiser image, dc_pack_weight), dc_music.hip, dc_m2snet.hip, dc_m2sgan.hip
-// and dc_stgcn.hip; the single copy of every rounding routine they must agree on bit for bit.
+// packers, the 256-byte-aligned host arena, the MusicEncoder's folded image, M2SNet's fuse head, the M2S-GAN generator's image, the
+// ST-GCN motion encoder's, the M2S-GAN critic's and the Welch table.  Included by dc_api.hip (denoiser image, dc_pack_weight),
+// dc_music.hip, dc_m2snet.hip, dc_m2sgan.hip, dc_stgcn.hip and dc_rhythm.hip; the single copy of every rounding routine they must
+// agree on bit for bit.
 #pragma once
 #include <stdint.h>
 
@@ -569,4 +570,96 @@ inline std::vector<float> stgcn_pack(const DcParams& params) {
             }
     for (int o = 0; o < kStgcnOut; ++o) img[kStgcnFcB + o] = (float)(sf[o] * bf[o] + hf[o]);
     return img;
+}
+
+// ---- M2S-GAN critic image (kernels: dc_rhythm.hip) ----------------------------------------------------------------
+// Discriminator_1DCNN of Contrastive_Stage/models/Discriminator.py:5-27: three Conv1d(kernel 5, zero padding 2) + ReLU +
+// MaxPool1d(5, stride 3 / 2 / 2) on 26 -> 64 -> 64 -> 64 channels, then fc 64 -> 32 -> 32 -> 1 per pooled frame.  Nothing to fold:
+// the weights are permuted into the k order of the convolution's GEMM (column tap cin + ci) and packed as A fragments.
+constexpr int kDiscC = 64, kDiscIn = 26, kDiscTaps = 5, kDiscHid = 32, kDiscStages = 3;
+constexpr int kDiscStride[kDiscStages] = {3, 2, 2};      // MaxPool1d(5, stride)
+constexpr int kDiscMinT = 41;                            // the shortest clip with one pooled frame behind the third stage
+inline int disc_pooled(int L, int stride) { return L < kDiscTaps ? 0 : (L - kDiscTaps) / stride + 1; }
+
+struct DiscImage {
+    std::vector<float> img;      // every entry at a multiple of 64 floats
+    size_t w[kDiscStages], b[kDiscStages];      // gan_pack_frags2 images (K = 5 cin, tap-major) and plain [64] biases
+    size_t fw[3], fb[3];                        // fc.0, fc.2, fc.4: head_pack_frags images ([ks][lane], one output tile), biases padded to 64
+    size_t add(const std::vector<float>& v) {
+        const size_t off = (img.size() + 63) & ~(size_t)63;
+        img.resize(off + v.size());
+        memcpy(img.data() + off, v.data(), v.size() * sizeof(float));
+        return off;
+    }
+};
+
+// names and sizes of the critic's 12 state_dict entries, in the reference module's order
+inline DcParamList disc_required() {
+    DcParamList r;
+    for (int i = 0; i < kDiscStages; ++i) {
+        const std::string p = "motion_encoder." + std::to_string(3 * i);
+        r.push_back({p + ".weight", (size_t)kDiscC * (i == 0 ? kDiscIn : kDiscC) * kDiscTaps});
+        r.push_back({p + ".bias", kDiscC});
+    }
+    const size_t fin[3] = {kDiscC, kDiscHid, kDiscHid}, fout[3] = {kDiscHid, kDiscHid, 1};
+    for (int i = 0; i < 3; ++i) {
+        r.push_back({"fc." + std::to_string(2 * i) + ".weight", fout[i] * fin[i]});
+        r.push_back({"fc." + std::to_string(2 * i) + ".bias", fout[i]});
+    }
+    return r;
+}
+
+// params: every entry of disc_required, with its size
+inline DiscImage disc_pack(const DcParams& params) {
+    const auto P = [&](const std::string& n) -> const std::vector<float>& { return params.find(n)->second; };
+    DiscImage I;
+    for (int i = 0; i < kDiscStages; ++i) {
+        const std::string p = "motion_encoder." + std::to_string(3 * i);
+        const int cin = i == 0 ? kDiscIn : kDiscC, K = kDiscTaps * cin;
+        const std::vector<float>& w = P(p + ".weight");      // [64][cin][5]
+        std::vector<float> W((size_t)kDiscC * K), frags(W.size());
+        for (int o = 0; o < kDiscC; ++o)
+            for (int ci = 0; ci < cin; ++ci)
+                for (int tap = 0; tap < kDiscTaps; ++tap) W[(size_t)o * K + tap * cin + ci] = w[((size_t)o * cin + ci) * kDiscTaps + tap];
+        gan_pack_frags2(W.data(), K, frags.data());
+        I.w[i] = I.add(frags);
+        I.b[i] = I.add(P(p + ".bias"));
+    }
+    const int fin[3] = {kDiscC, kDiscHid, kDiscHid}, fout[3] = {kDiscHid, kDiscHid, 1};
+    for (int i = 0; i < 3; ++i) {
+        const std::string p = "fc." + std::to_string(2 * i);
+        std::vector<float> f((size_t)(fin[i] / 2) * 64), b(64, 0.f);
+        head_pack_frags(P(p + ".weight").data(), fout[i], fin[i], f.data());
+        memcpy(b.data(), P(p + ".bias").data(), fout[i] * sizeof(float));
+        I.fw[i] = I.add(f);
+        I.fb[i] = I.add(b);
+    }
+    return I;
+}
+
+// ---- Welch window-and-twiddle table (kernel: dc_rhythm.hip) -------------------------------------------------------
+// scipy.signal.welch(x, fs = 30) with its defaults as ONE matrix on the detrended segment: nperseg = 256, periodic Hann window w,
+// `density` scaling 1 / (fs sum w^2), one-sided doubling of every bin but 0.  Row k (bins 0 .. 31) holds g_k w[n] cos(2 pi k n / 256),
+// row 32 + k holds g_k w[n] sin(2 pi k n / 256), g_k = sqrt((k ? 2 : 1) / (30 sum w^2)): |row_k . x|^2 + |row_{32+k} . x|^2 is the
+// segment's PSD at bin k.  Computed in fp64, rounded once.  [64][256] row-major.
+constexpr int kWelchSeg = 256, kWelchHop = 128, kWelchBins = 32;
+constexpr double kWelchFs = 30.0;
+inline std::vector<float> welch_table() {
+    const double pi = 3.14159265358979323846;
+    std::vector<double> w(kWelchSeg);
+    double s2 = 0.0;
+    for (int n = 0; n < kWelchSeg; ++n) {
+        w[n] = 0.5 - 0.5 * std::cos(2.0 * pi * n / kWelchSeg);
+        s2 += w[n] * w[n];
+    }
+    std::vector<float> tab((size_t)2 * kWelchBins * kWelchSeg);
+    for (int k = 0; k < kWelchBins; ++k) {
+        const double g = std::sqrt((k ? 2.0 : 1.0) / (kWelchFs * s2));
+        for (int n = 0; n < kWelchSeg; ++n) {
+            const double a = 2.0 * pi * ((k * n) % kWelchSeg) / kWelchSeg;      // (the argument reduced exactly)
+            tab[(size_t)k * kWelchSeg + n] = (float)(g * w[n] * std::cos(a));
+            tab[(size_t)(kWelchBins + k) * kWelchSeg + n] = (float)(g * w[n] * std::sin(a));
+        }
+    }
+    return tab;
 }

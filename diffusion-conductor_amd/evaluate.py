@@ -177,6 +177,52 @@ def _sync_predictions(m2snet, mel, pred, gts, dim_pose):
     return real, gen, mis
 
 
+def _rhythm_columns(rhythm, discriminator, T):
+    """Floats per clip of _rhythm_arrays' rows: [psd generated 32 | psd real 32 | contour generated W | contour real W | sd generated |
+    sd real] with `rhythm`, then [D(generated) | D(real)] with `discriminator`."""
+    W = (T - 60) // 30 + 1
+    return (2 * 32 + 2 * W + 2 if rhythm is not None else 0) + (2 if discriminator is not None else 0)
+
+
+def _rhythm_arrays(rhythm, discriminator, pred, gts, dim_pose, ids):
+    """One row [B, _rhythm_columns] per clip of what RDE, SCE, SD and the W-distance are made of, for the sampled poses and the ground
+    truth, enqueued on the current stream right behind the sampling (the ground truth is uploaded to the poses' device first)."""
+    B, T = pred.shape[0], pred.shape[1]
+    bad = [(cid, np.shape(g)) for cid, g in zip(ids, gts) if int(np.prod(np.shape(g))) != T * dim_pose]
+    if bad:
+        raise ValueError(f"the rhythm scores compare clips of {T} frames, but these ground truths differ: {bad[:4]}")
+    gt = torch.from_numpy(np.ascontiguousarray(np.stack([np.reshape(g, (T, dim_pose)) for g in gts]), np.float32))
+    if pred.is_cuda:
+        gt = gt.pin_memory().to(pred.device, non_blocking=True)
+    gen = pred.reshape(B, T, dim_pose).contiguous()
+    cols = []
+    if rhythm is not None:
+        cg, sg = rhythm.contour_and_std(gen)
+        cr, sr = rhythm.contour_and_std(gt)
+        cols += [rhythm.psd(gen), rhythm.psd(gt), cg, cr, sg.reshape(B, 1), sr.reshape(B, 1)]
+    if discriminator is not None:
+        cols += [discriminator.forward(gen).reshape(B, 1), discriminator.forward(gt).reshape(B, 1)]
+    return torch.cat(cols, dim=1)
+
+
+def _rhythm_scores(rows, ids, T, rhythm, discriminator):
+    """The result keys of the rhythm scores from every clip's row (_rhythm_columns), in clip order."""
+    from .metrics import rhythm_density_error, strength_contour_error, w_distance
+    out, W, at = {}, (T - 60) // 30 + 1, 0
+    if rhythm is not None:
+        psd_g, psd_r, c_g, c_r = rows[:, 0:32], rows[:, 32:64], rows[:, 64:64 + W], rows[:, 64 + W:64 + 2 * W]
+        at = 64 + 2 * W
+        rde, out["rde"] = rhythm_density_error(psd_r, psd_g)
+        sce, out["sce"] = strength_contour_error(c_r, c_g)
+        out["rde_per_clip"] = {cid: float(v) for cid, v in zip(ids, rde)}
+        out["sce_per_clip"] = {cid: float(v) for cid, v in zip(ids, sce)}
+        out["sd_gen"], out["sd_real"] = float(rows[:, at].astype(np.float64).mean()), float(rows[:, at + 1].astype(np.float64).mean())
+        at += 2
+    if discriminator is not None:
+        out["w_distance"] = w_distance(rows[:, at + 1], rows[:, at])
+    return out
+
+
 def _latent_scores(results, nb, diversity_seed):
     """FGD, feat_dist and diversity (metrics.py) over every clip's latents in clip order."""
     from .metrics import diversity_score, frechet_gesture_distance
@@ -246,7 +292,8 @@ class _Scorer:
 
 
 def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed=0, smooth=False, verbose=True, motion_encoder=None,
-                     diversity_seed=0, m2snet=None, guidance_scale=None, steps=None, spacing="uniform", solver="ddim"):
+                     diversity_seed=0, m2snet=None, guidance_scale=None, steps=None, spacing="uniform", solver="ddim", rhythm=None,
+                     discriminator=None):
     """Samples every clip under `root` and returns {"per_clip": {id: mse}, "total_loss", "final_mse", "clips",
     "seconds", "frames_per_s"}.  Clip i (in sorted order) starts from noise seeded with (seed, i), so the result
     does not depend on batch_size or on the number of ranks.
@@ -266,6 +313,15 @@ def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed
     batch of one clip, so the control depends on `batch_size`).  Adds "m2s_sync_real", "m2s_sync_gen", "m2s_sync_mismatched" (mean
     per-frame predictions over all clips; nan when no batch had two clips) and "m2s_accuracy_gen" (metrics.sync_stats: matched =
     generated, mismatched = rolled).  Without it the result is unchanged.
+
+    `rhythm` (a rhythm.MotionRhythm, or anything with its `psd` and `contour_and_std`): the scores of the M2S-GAN evaluation that look
+    at how the motion moves (Contrastive_Stage/M2SGAN_eval.py:100-133, metrics.py) - "rde" and "sce" (the means over the clips of
+    "rde_per_clip" and "sce_per_clip", {id: value}; the reference evaluates clip by clip), "sd_gen" and "sd_real".  Needs clips of
+    at least 256 frames.  `discriminator` (a discriminator.Discriminator_1DCNN, or anything with its `forward`): "w_distance", the
+    mean of D(real) - D(generated); at least 41 frames.  Both run on the device right behind each batch's sampling, on the same
+    stream; only the per-clip arrays ([B, 32] spectra, [B, W] contours, [B] deviations and scores) come back, with the poses.  As
+    with the latents, with `smooth` these are the scores of the SMOOTHED poses.  Without the two arguments the result and the work
+    done are exactly what they were before these scores existed.
 
     `guidance_scale`: None, or the classifier-free guidance scale every batch is sampled with (generate_music_motion).
     `steps`, `spacing`, `solver`: every batch is sampled on `steps` of the schedule's timesteps (generate_music_motion; the defaults
@@ -287,6 +343,12 @@ def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed
     mel_shape = tuple(np.load(pjoin(root, ids[0], "mel.npy"), mmap_mode="r").shape)
     T = (mel_shape[0] - 1) // 3 + 1
     nb = (len(ids) + batch_size - 1) // batch_size
+    moves = rhythm is not None or discriminator is not None
+    if rhythm is not None and T < 256:
+        raise ValueError(f"clips of {T} frames: the rhythm scores need at least 256 (Welch's segment)")
+    if discriminator is not None and T < 41:
+        raise ValueError(f"clips of {T} frames: the critic needs at least 41 (one pooled frame behind its third stage)")
+    rh_rows = None                       # pinned [clips, _rhythm_columns]: every clip's row, read after the last batch's event
     pf = _Prefetcher(root, ids, batch_size, mel_shape, noise=(seed, T, dim_pose))
     pf.start(0)
     scorer = _Scorer(dim_pose)
@@ -341,6 +403,11 @@ def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed
                 lat_h[1].copy_(lats[1], non_blocking=True)
             if m2snet is not None:
                 sync[k] = _sync_predictions(m2snet, mel, pred, gts, dim_pose)
+            if moves:
+                if rh_rows is None:
+                    rh_rows = torch.empty((len(ids), _rhythm_columns(rhythm, discriminator, T)), dtype=torch.float32, pin_memory=pred.is_cuda)
+                rh_rows[k * batch_size:k * batch_size + pred.shape[0]].copy_(_rhythm_arrays(rhythm, discriminator, pred, gts, dim_pose, bid),
+                                                                             non_blocking=True)
             ph.copy_(pred, non_blocking=True)
             ev = None
             if pred.is_cuda:
@@ -367,6 +434,8 @@ def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed
                 lats = _encode_pair(motion_encoder, pred_d, gts, dim_pose, bid) if motion_encoder is not None else None
                 if m2snet is not None:
                     sync[k] = _sync_predictions(m2snet, mel, pred_d, gts, dim_pose)
+                if moves:
+                    rh_rows[k * batch_size:k * batch_size + pred_d.shape[0]].copy_(_rhythm_arrays(rhythm, discriminator, pred_d, gts, dim_pose, bid))
                 pred = pred_d.cpu().numpy()
                 results[k] = [(cid, mse_loss(gts[i], pred[i].reshape([pred[i].shape[0], dim_pose // 2, 2]))) for i, cid in enumerate(bid)]
                 if lats is not None:
@@ -416,6 +485,10 @@ def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed
         if verbose:
             print(f"m2s_sync_real: {out['m2s_sync_real']}  m2s_sync_gen: {out['m2s_sync_gen']}  "
                   f"m2s_sync_mismatched: {out['m2s_sync_mismatched']}  m2s_accuracy_gen: {out['m2s_accuracy_gen']}")
+    if moves:
+        out.update(_rhythm_scores(rh_rows.numpy(), ids, T, rhythm, discriminator))
+        if verbose:
+            print("  ".join(f"{key}: {out[key]}" for key in ("rde", "sce", "sd_gen", "sd_real", "w_distance") if key in out))
     return out
 
 
@@ -524,14 +597,27 @@ def _evaluation_encoders(args, dev):
     return menc, m2s
 
 
+def _movement_scorers(args, dev):
+    """(MotionRhythm for --rhythm | None, the critic for --discriminator | None) as main's flags ask for them."""
+    rh = disc = None
+    if args.rhythm:
+        from .rhythm import MotionRhythm
+        rh = MotionRhythm(dev)
+    if args.discriminator:
+        from .discriminator import load_m2sgan_discriminator
+        disc = load_m2sgan_discriminator(args.discriminator, dev)
+    return rh, disc
+
+
 def _baseline_main(args, dev):
     """--baseline_generator: evaluate_dataset on the M2S-GAN generator (generator.GeneratorBaseline), one JSON line."""
     import json
     from .generator import GeneratorBaseline, load_m2sgan_generator
     gen = load_m2sgan_generator(args.baseline_generator, dev)
     menc, m2s = _evaluation_encoders(args, dev)
+    rh, disc = _movement_scorers(args, dev)
     r = evaluate_dataset(GeneratorBaseline(gen), args.data_root, 26, args.batch_size, args.limit, args.seed, args.smooth, verbose=False,
-                         motion_encoder=menc, diversity_seed=args.diversity_seed, m2snet=m2s)
+                         motion_encoder=menc, diversity_seed=args.diversity_seed, m2snet=m2s, rhythm=rh, discriminator=disc)
     print(json.dumps({"model": "m2sgan", **r}))
     return 0
 
@@ -565,6 +651,10 @@ def main(argv=None):
                                                             "one JSON line, no sampling loop (validation_dataset)")
     ap.add_argument("--val_timesteps", type=int, default=None, help="--val_loss on a grid of this many noise levels (omitted: one uniform "
                                                                     "timestep per clip, the training protocol)")
+    ap.add_argument("--rhythm", action="store_true", help="also RDE, SCE and the standard deviations of the sampled and the real motion "
+                                                          "(M2SGAN_eval.py:100-133; rhythm.py, metrics.py)")
+    ap.add_argument("--discriminator", default=None, help="M2S-GAN critic checkpoint (a plain state_dict, M2SGAN_eval.py:453): also the "
+                                                          "W-distance D(real) - D(generated) (discriminator.py)")
     ap.add_argument("--baseline_generator", default=None, help="score the M2S-GAN generator of this checkpoint (a plain state_dict, "
                                                                "M2SGAN_eval.py:451) instead of the denoiser: the same evaluation, one JSON "
                                                                "line with \"model\": \"m2sgan\" (generator.py)")
@@ -576,6 +666,9 @@ def main(argv=None):
         if clash:
             ap.error(f"--baseline_generator scores the M2S-GAN generator, one forward pass per clip: {', '.join(clash)} belong"
                      f"{'s' if len(clash) == 1 else ''} to the diffusion denoiser and cannot be combined with it")
+    if args.val_loss and (args.rhythm or args.discriminator):
+        ap.error("--val_loss scores the checkpoint without sampling it: --rhythm and --discriminator score sampled motion and cannot be "
+                 "combined with it")
     from . import DDPMTrainer, MotionTransformer
     dev = torch.device("cuda", args.gpu_id)
     torch.cuda.set_device(dev)
@@ -597,9 +690,10 @@ def main(argv=None):
         r = validation_dataset(tr, args.data_root, args.val_timesteps, args.batch_size, args.seed, motion_encoder=menc, limit=args.limit)
         print(json.dumps(r))
         return 0
+    rh, disc = _movement_scorers(args, dev)
     r = evaluate_dataset(tr, args.data_root, 26, args.batch_size, args.limit, args.seed, args.smooth, motion_encoder=menc,
                          diversity_seed=args.diversity_seed, m2snet=m2s, guidance_scale=args.guidance_scale,
-                         steps=args.steps, spacing=args.spacing, solver=args.solver)
+                         steps=args.steps, spacing=args.spacing, solver=args.solver, rhythm=rh, discriminator=disc)
     print(f"{r['clips']} clips in {r['seconds']:.2f} s = {r['frames_per_s']:.0f} frames/s")
     return 0
 

@@ -18,6 +18,11 @@ Host numpy / scipy over the ST-GCN latents of motion_encoder.py (``latent(x)`` =
 ``denoising_loss_scalars`` is not a score of sampled motion: it combines the per-clip terms of the held-out denoising objective
 (native.motion_loss_terms, native.latent_l1) into the batch scalars of DDPMTrainer.backward_G (trainers/ddpm_trainer.py:223-268).
 
+``rhythm_density_error``, ``strength_contour_error`` and ``w_distance`` are the scores of the M2S-GAN evaluation
+(Contrastive_Stage/M2SGAN_eval.py:100-133) that look at how the motion moves, over the small per-clip arrays rhythm.MotionRhythm
+and discriminator.Discriminator_1DCNN compute on the device.  The reference evaluates at batch size 1 and averages the per-clip
+values; these do the same.
+
 Beat consistency (BC) is not here: its music side is librosa's onset / beat tracker.
 """
 from __future__ import annotations
@@ -172,3 +177,48 @@ def denoising_loss_scalars(terms, lengths, latent_l1=None):
     return {"loss": loss, "loss_mot_rec": rec, "loss_mot_feat": feat, "loss_velocity": vel, "loss_velocity_elbow": elbow_c,
             "loss_velocity_head": head, "loss_velocity_body": body, "velocity_elbow": elbow, "mse": float(t[:, 0].mean()),
             "feat_included": feat is not None}
+
+
+RDE_BAND = (6, 26)      # `threshold`, `bins` of rhythm_density_error (loss.py:183-184): 0.70 .. 2.93 Hz at fs = 30, nperseg = 256
+
+
+def _per_clip(a, what, width=None):
+    a = np.asarray(a.detach().cpu() if hasattr(a, "detach") else a)
+    a = a if a.dtype in (np.float32, np.float64) else a.astype(np.float32)
+    if a.ndim == 1:
+        a = a[None]
+    if a.ndim != 2 or (width is not None and a.shape[1] < width):
+        raise ValueError(f"{what}: expected one row per clip, got {a.shape}")
+    return a
+
+
+def rhythm_density_error(psd_real, psd_gen):
+    """RDE of Contrastive_Stage/utils/loss.py:183-190 from the channel-averaged Welch PSDs [n, >= 26] (rhythm.MotionRhythm.psd) of the
+    real and the generated clips: per clip log(mean((r[6:26] - g[6:26])^2) * 1e7 + 1) - the mean in the arrays' own dtype, the
+    logarithm in float64, as in the reference - and the mean over the clips (M2SGAN_eval.py:162).  -> (per clip float64 [n], mean)."""
+    r, g = _per_clip(psd_real, "psd_real", RDE_BAND[1]), _per_clip(psd_gen, "psd_gen", RDE_BAND[1])
+    if r.shape != g.shape:
+        raise ValueError(f"rhythm_density_error: {r.shape} real and {g.shape} generated spectra")
+    lo, hi = RDE_BAND
+    per = np.array([np.log(np.float64(((r[i, lo:hi] - g[i, lo:hi]) ** 2).mean()) * 1e7 + 1) for i in range(r.shape[0])], np.float64)
+    return per, float(per.mean())
+
+
+def strength_contour_error(contour_real, contour_gen):
+    """SCE of loss.py:149-151 from the speed contours [n, W] (rhythm.MotionRhythm.contour): per clip log(mean_w((g - r)^2) * 1e7 + 1)
+    in float32, as the reference's torch expression, and the mean over the clips (M2SGAN_eval.py:163).  -> (per clip float32 [n], mean)."""
+    r, g = _per_clip(contour_real, "contour_real"), _per_clip(contour_gen, "contour_gen")
+    if r.shape != g.shape:
+        raise ValueError(f"strength_contour_error: {r.shape} real and {g.shape} generated contours")
+    r, g = r.astype(np.float32), g.astype(np.float32)
+    per = np.array([np.log(((g[i] - r[i]) ** 2).mean(dtype=np.float32) * np.float32(1e7) + np.float32(1)) for i in range(r.shape[0])], np.float32)
+    return per, float(per.astype(np.float64).mean())
+
+
+def w_distance(d_real, d_gen):
+    """The W-distance of M2SGAN_eval.py:107-109, 150-151: the mean over the clips of D(real) - D(fake), critic scores [n] or [n, 1]."""
+    r = np.asarray(d_real.detach().cpu() if hasattr(d_real, "detach") else d_real, np.float32).reshape(-1)
+    g = np.asarray(d_gen.detach().cpu() if hasattr(d_gen, "detach") else d_gen, np.float32).reshape(-1)
+    if r.shape != g.shape or not r.size:
+        raise ValueError(f"w_distance: {r.shape} real and {g.shape} generated scores")
+    return float((r - g).astype(np.float64).mean())

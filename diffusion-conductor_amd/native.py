@@ -36,6 +36,9 @@ EXPORTS = [
     "dc_q_sample_coefficients", "dc_q_sample", "dc_motion_loss_terms", "dc_latent_l1",
     "dc_m2sgan_create", "dc_m2sgan_destroy", "dc_m2sgan_set_param", "dc_m2sgan_finalize", "dc_m2sgan_features", "dc_m2sgan_decode",
     "dc_m2sgan_generate", "dc_m2sgan_debug_blocks", "dc_m2sgan_fold_conv",
+    "dc_rhythm_create", "dc_rhythm_destroy", "dc_rhythm_psd", "dc_rhythm_contour",
+    "dc_discriminator_create", "dc_discriminator_destroy", "dc_discriminator_set_param", "dc_discriminator_finalize",
+    "dc_discriminator_features", "dc_discriminator_score",
 ]
 
 UPDATE_CLIP_DENOISED, UPDATE_EPSILON = 1, 2          # flags of dc_sampler_ddim_loop_ex
@@ -54,7 +57,8 @@ class DcError(RuntimeError):
     pass
 
 
-SOURCES = ("dc_kernels.hip", "dc_api.hip", "dc_music.hip", "dc_layer16.hip", "dc_stgcn.hip", "dc_m2snet.hip", "dc_loss.hip", "dc_m2sgan.hip")
+SOURCES = ("dc_kernels.hip", "dc_api.hip", "dc_music.hip", "dc_layer16.hip", "dc_stgcn.hip", "dc_m2snet.hip", "dc_loss.hip", "dc_m2sgan.hip",
+           "dc_rhythm.hip")
 HEADERS = ("dc_common.h", "dc_dev.h", "dc_form.h", "dc_handle.h", "dc_launch.h", "dc_mfma_f32.h", "dc_music.h", "dc_pack.h")
 EXTRA_FLAGS = {}      # per-source compiler flags
 
@@ -191,6 +195,18 @@ def lib():
     L.dc_m2sgan_generate.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     L.dc_m2sgan_debug_blocks.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     L.dc_m2sgan_fold_conv.argtypes = [fp] * 7 + [C.c_int32] * 3 + [fp, fp]
+    L.dc_rhythm_create.argtypes = [C.c_int32, C.POINTER(C.c_void_p)]
+    L.dc_rhythm_destroy.argtypes = [C.c_void_p]
+    L.dc_rhythm_destroy.restype = None
+    L.dc_rhythm_psd.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    L.dc_rhythm_contour.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.dc_discriminator_create.argtypes = [C.c_int32, C.POINTER(C.c_void_p)]
+    L.dc_discriminator_destroy.argtypes = [C.c_void_p]
+    L.dc_discriminator_destroy.restype = None
+    L.dc_discriminator_set_param.argtypes = [C.c_void_p, C.c_char_p, fp, C.c_int64]
+    L.dc_discriminator_finalize.argtypes = [C.c_void_p]
+    L.dc_discriminator_features.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    L.dc_discriminator_score.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -894,4 +910,88 @@ class NativeM2SGAN(_NativeHandle):
                 _check(lib().dc_m2sgan_decode(self._h, feat.data_ptr(), B, T, out.data_ptr(), self._stream()))
             else:
                 _check(lib().dc_m2sgan_debug_blocks(self._h, feat.data_ptr(), B, T, int(n_blocks), out.data_ptr(), self._stream()))
+        return out
+
+
+# ---------------------------------------------------------------------------------------
+# realism and rhythm: the Welch spectrum, the speed contour, the standard deviation; the M2S-GAN critic
+# ---------------------------------------------------------------------------------------
+def _motion26(handle, motion):
+    """(B, T) of a motion tensor fp32 [B, T, 26] (or [B, T, 13, 2]) on the device."""
+    handle._ok(motion)
+    B, T = int(motion.shape[0]), int(motion.shape[1])
+    assert motion.dim() in (3, 4) and motion.numel() == B * T * 26, tuple(motion.shape)
+    return B, T
+
+
+class NativeRhythm(_NativeHandle):
+    """Owns one dc_rhythm (no parameters: the handle is ready after create).  Shapes the library refuses raise ValueError before
+    the call."""
+    _prefix = "dc_rhythm"
+    PSD_BINS, MIN_PSD_T, MIN_CONTOUR_T = 32, 256, 60
+
+    @staticmethod
+    def windows(T):
+        """W of the contour: AvgPool1d(60, 30) over T frames."""
+        return (T - 60) // 30 + 1
+
+    def psd(self, motion):
+        """motion fp32 [B, T, 26] on the device -> bins 0 .. 31 of the channel-averaged Welch PSD, fp32 [B, 32]."""
+        import torch
+        B, T = _motion26(self, motion)
+        if T < self.MIN_PSD_T:
+            raise ValueError(f"{T} frames: Welch's 256-frame segment needs T >= 256")
+        out = torch.empty((B, self.PSD_BINS), dtype=torch.float32, device=motion.device)
+        with torch.cuda.device(motion.device):
+            _check(lib().dc_rhythm_psd(self._h, motion.data_ptr(), B, T, out.data_ptr(), self._stream()))
+        return out
+
+    def contour(self, motion, contour=True, sd=True):
+        """motion fp32 [B, T, 26] on the device -> (speed contour fp32 [B, W] | None, standard deviation fp32 [B] | None)."""
+        import torch
+        B, T = _motion26(self, motion)
+        if T < self.MIN_CONTOUR_T:
+            raise ValueError(f"{T} frames: the contour's 60-frame window needs T >= 60")
+        c = torch.empty((B, self.windows(T)), dtype=torch.float32, device=motion.device) if contour else None
+        s = torch.empty((B,), dtype=torch.float32, device=motion.device) if sd else None
+        with torch.cuda.device(motion.device):
+            _check(lib().dc_rhythm_contour(self._h, motion.data_ptr(), B, T, c.data_ptr() if contour else None,
+                                           s.data_ptr() if sd else None, self._stream()))
+        return c, s
+
+
+class NativeDiscriminator(_NativeHandle):
+    """Owns one dc_discriminator.  T < 41 (no pooled frame behind the third stage) raises ValueError before the call."""
+    _prefix = "dc_discriminator"
+    MIN_T = 41
+
+    @staticmethod
+    def pooled_frames(T):
+        """(L1, L2, L3) behind the three Conv1d + MaxPool1d(5, stride 3 / 2 / 2) stages."""
+        L1 = (T - 5) // 3 + 1
+        L2 = (L1 - 5) // 2 + 1
+        return L1, L2, (L2 - 5) // 2 + 1
+
+    def _frames(self, motion):
+        B, T = _motion26(self, motion)
+        if T < self.MIN_T:
+            raise ValueError(f"{T} frames leave no pooled frame behind the critic's third stage (T >= 41)")
+        return B, T
+
+    def features(self, motion):
+        """motion fp32 [B, T, 26] on the device -> Discriminator_1DCNN.features' tensor fp32 [B, 64, L3]."""
+        import torch
+        B, T = self._frames(motion)
+        out = torch.empty((B, 64, self.pooled_frames(T)[2]), dtype=torch.float32, device=motion.device)
+        with torch.cuda.device(motion.device):
+            _check(lib().dc_discriminator_features(self._h, motion.data_ptr(), B, T, out.data_ptr(), self._stream()))
+        return out
+
+    def score(self, motion):
+        """motion fp32 [B, T, 26] on the device -> D(x) fp32 [B]."""
+        import torch
+        B, T = self._frames(motion)
+        out = torch.empty((B,), dtype=torch.float32, device=motion.device)
+        with torch.cuda.device(motion.device):
+            _check(lib().dc_discriminator_score(self._h, motion.data_ptr(), B, T, out.data_ptr(), self._stream()))
         return out

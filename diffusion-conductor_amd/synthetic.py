@@ -338,3 +338,28 @@ def synthetic_m2sgan_state_dict(seed: int = 0):
             a = g.uniform(-1.0, 1.0, shape) * (gain / np.sqrt(fan_in))
         out[name] = np.ascontiguousarray(a, dtype=np.float32)
     return out
+
+
+# gains of the seeded critic over PyTorch's default initialiser bound, per convolution stage and per fc layer (see
+# synthetic_discriminator_state_dict)
+DISCRIMINATOR_CONV_GAIN = (6.0, 2.0, 2.0)
+DISCRIMINATOR_FC_GAIN = (2.0, 3.0, 4.0)
+
+
+def synthetic_discriminator_state_dict(seed: int = 0):
+    """name -> np.ndarray for the 12 state_dict entries of the M2S-GAN critic (discriminator.py), in the reference module's order:
+    weights U(-1, 1) / sqrt(fan_in) times DISCRIMINATOR_CONV_GAIN / DISCRIMINATOR_FC_GAIN, biases U(-1, 1) / sqrt(fan_in).  The
+    gains keep the ReLUs switching and the pooled maxima away from 0 on pose-like inputs (values around 0.5 that move by
+    hundredths per frame), so that a wrong tap, padding or pooling window moves the score (tools/make_golden_rhythm.py asserts it)."""
+    from .discriminator import discriminator_shapes
+    shapes = discriminator_shapes()
+    out = OrderedDict()
+    for name, shape in shapes.items():
+        mod, leaf = name.rsplit(".", 1)
+        wshape = shapes[mod + ".weight"]
+        fan_in = int(np.prod(wshape[1:]))
+        idx = int(mod.rsplit(".", 1)[1])
+        gain = DISCRIMINATOR_CONV_GAIN[idx // 3] if mod.startswith("motion_encoder") else DISCRIMINATOR_FC_GAIN[idx // 2]
+        a = _rng(seed, "discriminator:" + name).uniform(-1.0, 1.0, shape) * ((gain if leaf == "weight" else 1.0) / np.sqrt(fan_in))
+        out[name] = np.ascontiguousarray(a, dtype=np.float32)
+    return out

@@ -548,6 +548,61 @@ DC_EXPORT int dc_m2sgan_fold_conv(const float* weight_g, const float* weight_v, 
                                   const float* bn_bias, const float* bn_mean, const float* bn_var, int32_t cout, int32_t cin, int32_t k,
                                   float* h_w, float* h_b);
 
+/* ---- Realism and rhythm: the Welch spectrum, the speed contour, the standard deviation and the M2S-GAN critic -------------------
+ * The four scores of Contrastive_Stage/M2SGAN_eval.py:100-133 that look at how the motion moves.  Implemented in
+ * csrc/dc_rhythm.hip; none of it is on the sampling path.  All arithmetic is fp32, every output is a fixed-order sum without
+ * atomics: a clip's numbers are bit-identical on every rerun, in any batch and at any place in it.  A handle serves ONE stream at
+ * a time (its workspace is shared by all its calls); not thread-safe.
+ *
+ * dc_rhythm owns the Welch window-and-twiddle table (built in fp64 on the host at create time, rounded once) and a workspace. */
+typedef struct dc_rhythm dc_rhythm;
+DC_EXPORT int dc_rhythm_create(int32_t device, dc_rhythm** out);
+DC_EXPORT void dc_rhythm_destroy(dc_rhythm* h);
+
+/* Replaces the scipy.signal.welch(x, 30) calls of rhythm_density_error (Contrastive_Stage/utils/loss.py:173-186) and the sum over
+ * the 26 channels with its "/= 26": d_motion fp32 [B, T, 26] -> d_psd fp32 [B, 32], bins 0 .. 31 of PSD.sum(channels) / 26 (the
+ * error itself reads bins 6 .. 25: metrics.rhythm_density_error).  scipy's defaults: nperseg = 256, noverlap = 128, periodic
+ * Hann window, constant detrend per segment (removed BEFORE the window), density scaling |X_k|^2 / (30 sum w^2), one-sided doubling
+ * of bins 1 .. 127, the mean over the (T - 128) / 128 segments (the tail is dropped, nothing is padded).  fs = 30 whatever the
+ * clip's frame rate, as in the reference.  The signal.spectrogram calls at loss.py:168-171 fill arrays nobody reads and have no
+ * counterpart.  DC_ERR_INVALID before anything is enqueued: B < 1, T < 256 (scipy shortens the window there, and the score
+ * changes meaning), a NULL pointer. */
+DC_EXPORT int dc_rhythm_psd(dc_rhythm* h, const float* d_motion, int32_t B, int32_t T, float* d_psd, void* stream);
+
+/* Replaces the speed contour of strengh_contour_error (loss.py:129-142) and the standard deviation of M2SGAN_eval.py:101-102:
+ * d_motion fp32 [B, T, 26] ->
+ *   d_contour fp32 [B, W], W = (T - 60) / 30 + 1: d_contour[b, w] = the mean over frames 30 w .. 30 w + 59 of
+ *             |mean over the 26 channels of (x[t-1] - x[t])|, the velocity at frame 0 being 0 (AvgPool1d(60, 30); per clip - the
+ *             reference's unsqueeze(0) would mix the clips of a batch larger than 1);
+ *   d_sd fp32 [B]: the mean over the 26 channels of the unbiased standard deviation over time (two passes, mean first).
+ * Either output may be NULL.  DC_ERR_INVALID before anything is enqueued: B < 1, T < 60, a NULL handle or motion. */
+DC_EXPORT int dc_rhythm_contour(dc_rhythm* h, const float* d_motion, int32_t B, int32_t T, float* d_contour, float* d_sd, void* stream);
+
+/* Replaces constructing Discriminator_1DCNN (Contrastive_Stage/models/Discriminator.py:5-27), the M2S-GAN critic whose
+ * D(real) - D(fake) is the W-distance of M2SGAN_eval.py:107-109, on the device `device`. */
+typedef struct dc_discriminator dc_discriminator;
+DC_EXPORT int dc_discriminator_create(int32_t device, dc_discriminator** out);
+DC_EXPORT void dc_discriminator_destroy(dc_discriminator* d);
+
+/* Replaces Discriminator_1DCNN.load_state_dict (M2SGAN_eval.py:453 loads the plain state_dict): one call per entry - 12 of them,
+ * "motion_encoder.{0,3,6}.{weight,bias}" (Discriminator.py:8-20) and "fc.{0,2,4}.{weight,bias}" (:21-27), 52 641 values - with its
+ * key (WITHOUT a DataParallel "module." prefix: the Python loaders strip it) and contiguous fp32 data.  Unknown key or wrong numel
+ * -> DC_ERR_PARAM. */
+DC_EXPORT int dc_discriminator_set_param(dc_discriminator* d, const char* name, const float* h_data, int64_t numel);
+
+/* Replaces .eval() + .to(device): permutes the convolutions' weights into the k order of their GEMMs, packs and uploads.  An
+ * entry that was never set -> DC_ERR_PARAM.  Synchronous.  The two entry points below return DC_ERR_INVALID before it. */
+DC_EXPORT int dc_discriminator_finalize(dc_discriminator* d);
+
+/* Replaces Discriminator_1DCNN.features (Discriminator.py:36-41): d_motion fp32 [B, T, 26] -> d_feat fp32 [B, 64, L3] behind three
+ * stages of Conv1d(kernel 5, zero padding 2) + ReLU + MaxPool1d(5, stride 3 / 2 / 2); L1 = (T-5)/3+1, L2 = (L1-5)/2+1,
+ * L3 = (L2-5)/2+1 (a pool's tail is dropped).  Exact-fp32 products in k order (K = 130, 320, 320).  DC_ERR_INVALID before anything
+ * is enqueued: B < 1, T < 41 (L3 < 1), a NULL pointer.  The pooled planes live in the handle's workspace (32 clips per pass). */
+DC_EXPORT int dc_discriminator_features(dc_discriminator* d, const float* d_motion, int32_t B, int32_t T, float* d_feat, void* stream);
+/* Replaces Discriminator_1DCNN.forward (Discriminator.py:29-34): the per-frame fc (64 -> 32 -> 32 -> 1, ReLU between) on the
+ * features and the mean over the L3 frames -> d_out fp32 [B]. */
+DC_EXPORT int dc_discriminator_score(dc_discriminator* d, const float* d_motion, int32_t B, int32_t T, float* d_out, void* stream);
+
 /* ---- Held-out denoising losses: the forward value of the objective a checkpoint was trained on ---------------------------------
  * GaussianDiffusion.training_losses (models/gaussian_diffusion.py:1002-1090) and the weighting of DDPMTrainer.backward_G
  * (trainers/ddpm_trainer.py:223-268) as an EVALUATOR: one model evaluation per clip and noise level, no gradients.  The model
