@@ -161,6 +161,7 @@ struct dc_sampler : Formats {     // (set_precision(cfg.precision))
     dc_music* music = nullptr;   // MusicEncoder (built when its parameters were supplied)
     int me_format = -1;          // dc_sampler_set_encoder_format (-1: by precision)
     int clip_aligned = -1;         // dc_sampler_set_clip_aligned: 1 clip-aligned units in the wide form too, 0 flat units, -1 the library's rule
+    bool idle_wave_path = true;    // dc_sampler_set_idle_wave_path: padding waves of the wide plain layer kernel pass it barrier-only (0: they run the whole layer)
     bool precise_forward = false;  // dc_sampler_set_precise_forward: dc_sampler_denoise on split operands (the precise tail's evaluation form)
     int tail_split = -1;         // dc_sampler_set_precise_tail: the loop's last evaluations with split operands (-1: by precision - fp16 1, bf16 DC_BF16_TAIL_DEFAULT = 6)
     bool host_only = false;      // -DDC_HOST_SANITIZE builds without a device: the host half only (tests/test_host_sanitize.py)
@@ -679,7 +680,7 @@ Settings settings_of(const dc_sampler* s) {
     Settings r;
     r.precision = s->cfg.precision, r.fmt = *s, r.no_eff = s->cfg.no_eff != 0, r.clip_aligned = s->clip_aligned, r.l16_own = s->l16_own;
     r.num_layers = s->cfg.num_layers, r.split_model = s->d_model_split != nullptr, r.film_w16 = s->h_model.film_w16 != nullptr;
-    r.film_w16_tail = s->h_model.film_w16_tail != nullptr, r.l16_max_units = dc_layer16_max_units();
+    r.film_w16_tail = s->h_model.film_w16_tail != nullptr, r.l16_max_units = dc_layer16_max_units(), r.idle_wave_path = s->idle_wave_path;
     return r;
 }
 int clip_stride(const dc_sampler* s, int B, int Tx) { return clip_stride(settings_of(s), Switches::read(), B, Tx, s->num_cu); }
@@ -885,7 +886,7 @@ int enqueue_step(dc_sampler* s, hipStream_t st, const Step& c, const Switches& w
                                                     s->d_snaps, iter_base, s->d_wslot, la.upd));
         return DC_OK;
     }
-    const DcLayerForm lf{fs, ss, f.wgr, f.narrow, f.g1_tiles, f.upc, f.rec_stride};
+    const DcLayerForm lf{fs, ss, f.wgr, f.narrow, f.g1_tiles, f.upc, f.rec_stride, f.idle_path};
     if (f.fuse_embed || f.fuse_extra || c.embedded) {
         // (embedded by the FiLM launch, or by the previous step's last layer)
     } else if (c.dbg.first >= 0)
@@ -1628,6 +1629,12 @@ int dc_sampler_set_clip_aligned(dc_sampler* s, int32_t mode) {
     if (!s) return fail(DC_ERR_INVALID, "null sampler");
     if (mode < -1 || mode > 1) return fail(DC_ERR_INVALID, "clip-aligned units: 1 (always), 0 (flat units), -1 (the library's rule)");
     s->clip_aligned = mode;
+    return DC_OK;
+}
+
+int dc_sampler_set_idle_wave_path(dc_sampler* s, int32_t on) {
+    if (!s) return fail(DC_ERR_INVALID, "null sampler");
+    s->idle_wave_path = on != 0;
     return DC_OK;
 }
 

@@ -88,6 +88,7 @@ struct Settings {
     bool split_model = false;             // the model record with the split stage images exists (fp16 / bf16 precision, on a device)
     bool film_w16 = false, film_w16_tail = false;      // DcModel::film_w16 / film_w16_tail exist
     int l16_max_units = 0;                // dc_layer16_max_units()
+    bool idle_wave_path = true;           // dc_sampler_set_idle_wave_path: padding waves of the wide plain layer kernel pass it barrier-only
 };
 
 // Test hooks of one evaluation (dc_sampler_debug_denoise, dc_sampler_debug_layer); the defaults run the production evaluation
@@ -133,6 +134,8 @@ struct StepForm {
     bool shared_film = false;     // the FiLM GEMM covers film_groups < G groups (film_share): takes wrap, the guided shadow half reads group film_groups - 1
     int film_groups = 0;          // groups the FiLM GEMM computes = the e_groups of the layer kernels' tile reads (nothing shared: G)
     int film_period = 0, film_wrap = 0;      // token group g reads the tiles of group g < film_wrap ? g % film_period : film_groups - 1 (nothing shared: G, G)
+    bool idle_path = false;       // wide plain production layer launches: the padding waves of a clip's last workgroup (WgMap, !active) issue
+                                  // their shares of the image copies and pass the barriers, nothing else (k_layer, layer_idle_wave)
 };
 
 // The token groups the FiLM GEMM has to compute, and which of them a token group reads.  A loop's step has one timestep, so a FiLM tile
@@ -242,7 +245,8 @@ inline StepForm step_form(const Geometry& g, const Settings& s, const Switches& 
     // ... and for the wide (chip-full) form whenever the clip-aligned launch needs no more rounds of workgroups over the chip than the flat
     // one (bs = 32 x 1800: 256 workgroups instead of 228, one round either way): a clip's result is then bit-identical whatever the
     // batch around it - the reference's semantics (transformer.py:111: the key softmax is per clip) - for +1.6 ... +2.1 % per loop
-    // (profiles/r06_ab_align.txt).  Where it would cost a round (bs = 35 x 1800: 280 against 250 workgroups on 256 CUs) flat units stay -
+    // (profiles/r06_ab_align.txt) while the padding waves of a clip's last workgroup ran the whole layer, +0.1 % since they pass it
+    // barrier-only (idle_path below; profiles/idle_waves_ab.txt).  Where it would cost a round (bs = 35 x 1800: 280 against 250 workgroups on 256 CUs) flat units stay -
     // a clip then depends on its neighbours at the rounding level (4e-4).  dc_sampler_set_clip_aligned: 1 forces
     // aligned units, 0 flat ones; DC_ALIGN=1 / DC_FLAT_UNITS=1 in the environment do the same per process.
     const int nwg_flat = (G + 7) / 8, ncu = g.num_cu > 0 ? g.num_cu : 256;
@@ -279,6 +283,11 @@ inline StepForm step_form(const Geometry& g, const Settings& s, const Switches& 
     const bool wide_plain = wgr && !narrow && !ss && fuse_silu && ff == fs && quiet && !s.no_eff;
     // (a guided step's update runs in k_guided_update, behind the last layer: there is no x_{t-1} in that layer's registers to embed)
     f.embed_next = !w.no_embed_next && o.loop_mode && o.next_plain && wide_plain && !guided;
+    // The padding waves of that kernel (clip-aligned units at 1800 frames: 7 of the 8 waves of every clip's last workgroup, 11 % of the
+    // launch's waves) do a workgroup member's duties only; dc_sampler_set_idle_wave_path(s, 0) has them run the whole layer as before
+    // (results are bit-identical either way: nothing of theirs ever reached an output).  Only the instantiation without hooks and stamps
+    // has the path; the others ignore the flag.
+    f.idle_path = s.idle_wave_path && wgr && !narrow && !ss && quiet && !s.no_eff;
     if (o.embedded && !(o.loop_mode && wide_plain)) {
         f.error = "internal: a step whose front work was done by its predecessor changed its launch form";
         return f;
@@ -368,6 +377,7 @@ inline LoopTail loop_tail(const Settings& s, int tail_split, std::optional<int> 
 //   0 .. 15  the environment switches (Switches::bits: every switch step_form can see)
 //   16 .. 23 the loop's DC_UPD_* flags (the noise / known tensors' addresses are not baked in: the kernels read them from their slots)
 //   24       l16_own            25, 26  clip_aligned + 1            27, 28  guided_key_bits
+//   29       the padding waves' barrier-only path is OFF (Settings::idle_wave_path; set when off, so the default's key is what it was)
 //   39       the loop has a precise tail: its plain evaluations read G' scale tiles, those of a loop without one G' - 1 tiles
 //   40 ..    the split evaluations at the end of this graph
 using GraphKey = std::tuple<int, int, int, int, unsigned long long, int>;
@@ -404,7 +414,7 @@ inline LoopPlan loop_plan(const Geometry& g, const Settings& s, const Switches& 
     const FilmShare share = film_share(g.B, g.T, g.G, o.guided, o.takes, !s.fmt.split_film, w);
     const unsigned long long bits = w.bits() | (unsigned long long)(o.flags & 0xff) << 16 | (s.l16_own ? 1ull : 0ull) << 24 |
                                     (unsigned long long)((s.clip_aligned + 1) & 3) << 25 | guided_key_bits(o.guided, share.groups < g.G) |
-                                    (p.g1_loop ? 1ull : 0ull) << 39;
+                                    (s.idle_wave_path ? 0ull : 1ull) << 29 | (p.g1_loop ? 1ull : 0ull) << 39;
     const int K = steps_per_graph(o.S), replays = o.S / K;
     const auto part = [&](int split_n, int launches) {
         p.parts.push_back({K, split_n, launches, GraphKey{g.B, g.T, g.Tx, K, bits | (unsigned long long)split_n << 40, takes_key_period(share)}});

@@ -1359,6 +1359,127 @@ __global__ __launch_bounds__(512, 2) void k_film_embed(const v8<T16>* __restrict
 #ifndef DC_SPLIT_NW
 #define DC_SPLIT_NW 8      // waves per k_layer workgroup in the split modes (4: one wave per SIMD, round 1-2's form)
 #endif
+// The steps of one k_layer launch, in order.  A step is: the weight-image copies issued while it runs (every wave issues its own
+// share of each, stage_frags), then ONE workgroup barrier that closes it.  The body names its copies and its closing barriers by
+// step (LayerImages::issue, layer_barrier), and the barrier-only path of a clip's padding waves (layer_idle_wave) is generated from
+// this list: a step added to or taken from the body goes through the list, and the padding waves follow by construction.
+//   PROLOGUE   SA query image -> buf0 (per-group records: + the self-attention fragments); the workgroup's own combine
+//   SA_APPLY   SA out-projection -> buf1          SA_STYL   CA query -> buf0 + the cross-attention fragments
+//   CA_APPLY   CA out-projection -> buf1          CA_STYL   FFN W1 | W2 -> buf0
+//   FFN        FFN out-projection -> buf1         FFN_STYL  the next layer's key image (last layer: the output image) -> buf0
+//   EMBED_NEXT (last layer under DC_UPD_EMBED_NEXT only) layer 0's key image -> buf1, the embedding image -> the FiLM rings;
+//              closed by the barrier behind the output projection
+//   KEYS       the value image of the front half (-> buf1; embed_next: layer 0's -> buf0); closed by the column maxima's barrier
+//   VALUES     no copy; closed by the barrier in front of the record tail
+// A last layer without embed_next ends behind FFN_STYL.
+#define DC_LAYER_STEPS(X) X(PROLOGUE) X(SA_APPLY) X(SA_STYL) X(CA_APPLY) X(CA_STYL) X(FFN) X(FFN_STYL) X(EMBED_NEXT) X(KEYS) X(VALUES)
+enum LayerStep : int {
+#define X(s) LS_##s,
+    DC_LAYER_STEPS(X)
+#undef X
+};
+template <class T16, bool SPLIT, bool WGR, int NW>
+struct LayerImages {
+    static constexpr int WM = SPLIT ? 2 : 1, NFW = 32 * WM, WSZ = (NFW + 1) * 1024, OFF_AF = 2 * WSZ, OFF_ER = OFF_AF + 16384;
+    using W = v8<T16>;
+    const DcModel* dm;
+    int l;
+    bool last, embed_next, wg_lds;
+    char* lds;
+    const W *a_sa, *acl;         // attention fragments: self-attention (per-group records), this layer's cross-attention
+    int ub0, B, wave, lane;
+    DEV char* buf0() const { return lds; }
+    DEV char* buf1() const { return lds + WSZ; }
+    DEV void attn(const W* a) const {            // frags of clips ub0, ub0+1 -> AF region
+        if constexpr (SPLIT) {                   // (workgroup records, clip-aligned: hi + lo frags of the one clip)
+            stage_frags<NW>(a + (size_t)ub0 * 16 * 64, lds + OFF_AF, 16, wave, lane);
+        } else {
+            const int c1i = min(ub0 + 1, B - 1);
+            stage_frags<NW>(a + (size_t)ub0 * 16 * 64, lds + OFF_AF, 8, wave, lane);
+            stage_frags<NW>(a + (size_t)c1i * 16 * 64, lds + OFF_AF + 8192, 8, wave, lane);
+        }
+    }
+    DEV bool runs(LayerStep s) const { return s < LS_EMBED_NEXT || (s == LS_EMBED_NEXT ? embed_next : (!last || embed_next)); }
+    template <LayerStep S>
+    DEV void issue() const {
+        const DcLayer& L = dm->layer[l];
+        if constexpr (S == LS_PROLOGUE) {
+            stage_frags<NW>(L.img_sa_q, buf0(), NFW + 1, wave, lane);
+            if constexpr (!WGR)      // (workgroup records: the fragments come from the workgroup's own combine)
+                if (wg_lds) attn(a_sa);
+        } else if constexpr (S == LS_SA_APPLY) {
+            stage_frags<NW>(L.img_sa_o, buf1(), NFW + 1, wave, lane);
+        } else if constexpr (S == LS_SA_STYL) {
+            stage_frags<NW>(L.img_ca_q, buf0(), NFW + 1, wave, lane);
+            if (wg_lds) attn(acl);
+        } else if constexpr (S == LS_CA_APPLY) {
+            stage_frags<NW>(L.img_ca_o, buf1(), NFW + 1, wave, lane);
+        } else if constexpr (S == LS_CA_STYL) {
+            stage_frags<NW>(L.img_ffn_w1, buf0(), 16 * WM, wave, lane);
+            stage_frags<NW>(L.img_ffn_w2, buf0() + 16 * WM * 1024, 16 * WM + 1, wave, lane);
+        } else if constexpr (S == LS_FFN) {
+            stage_frags<NW>(L.img_ffn_o, buf1(), NFW + 1, wave, lane);
+        } else if constexpr (S == LS_FFN_STYL) {
+            if (!last)
+                stage_frags<NW>(dm->layer[l + 1].img_sa_k, buf0(), NFW + 1, wave, lane);
+            else
+                stage_frags<NW>(dm->img_out, buf0(), 17, wave, lane);      // 8 hi + 8 lo frags + bias: always runs split
+        } else if constexpr (S == LS_EMBED_NEXT) {      // layer 0's key image -> buf1 (the FFN out-projection image, consumed); the embedding image -> the idle FiLM rings
+            stage_frags<NW>(dm->layer[0].img_sa_k, buf1(), NFW + 1, wave, lane);
+            stage_frags<NW>(dm->img_je, lds + OFF_ER, 17, wave, lane);
+        } else if constexpr (S == LS_KEYS) {
+            if (embed_next)
+                stage_frags<NW>(dm->layer[0].img_sa_v, buf0(), NFW + 1, wave, lane);
+            else if (!last)
+                stage_frags<NW>(dm->layer[l + 1].img_sa_v, buf1(), NFW + 1, wave, lane);
+        }
+    }
+};
+// the workgroup barrier that closes step S (the wait in front of it is the caller's: the body's counted waits rest on its issue order)
+template <LayerStep S>
+DEV void layer_barrier() { __syncthreads(); }
+// stage_sync as the closer of step S (KEEP8, split formats: the 8 FiLM prefetch loads stay in flight, stage_sync_keep8)
+template <LayerStep S, bool KEEP8 = false>
+DEV void layer_close() {
+    if constexpr (KEEP8)
+        stage_sync_keep8();
+    else
+        stage_sync();
+}
+
+// A padding wave of a clip's last workgroup (WgMap: !active) in the wide plain production form: the duties of a workgroup member
+// and nothing else.  Its share of every weight-image copy (the shares stride by wave), the workgroup's combine (all 512 threads
+// share that work), every barrier the body passes, in the body's order - each behind vmcnt(0): the body's counted waits
+// (vmcnt(8), vmcnt(16)) rest on an issue order this path does not have -, -inf in its column of the maxima (wg_colmax reads all NW
+// entries) and its share of the record tail (wave w sums tile w & 3 of slot w >> 2, idle or not).  No residual-stream load, no
+// FiLM tiles, no pst / ss / xp / scw writes, no arithmetic: none of it has ever reached a result (wg_write_record skips v >= nact,
+// valid_rows_clip gives an idle wave an empty range, store_h and the x update are under `active`).
+template <class T16, int NW, class Img>
+DEV void layer_idle_wave(const Img& im, const float* __restrict__ recs_in, float* __restrict__ recs_out, const WgMap& wm, int tid, int wg) {
+    using W = v8<T16>;
+    float* mx = reinterpret_cast<float*>(im.lds + Img::OFF_AF);
+    sprio<3>();      // (a handful of instructions per step: the copies go out at once)
+#define X(s)                                                                                                                   \
+    if (im.runs(LS_##s)) {                                                                                                     \
+        im.template issue<LS_##s>();                                                                                           \
+        if constexpr (LS_##s == LS_PROLOGUE)      /* self-attention matrices from the previous layer's workgroup records (scratch: buf1) */ \
+            wg_combine_attn<T16, false>(recs_in, reinterpret_cast<W*>(im.lds + Img::OFF_AF), reinterpret_cast<float*>(im.buf1()), \
+                                        im.ub0, im.B, wm.Mu, wm.Tu, tid, wg);                                                    \
+        if constexpr (LS_##s == LS_KEYS) {        /* (the AF region's last reader is CA_APPLY: closed long ago) */              \
+            if (im.lane < 32)                                                                                                  \
+                for (int k = 0; k < 8; ++k) mx[(k * 32 + im.lane) * NW + im.wave] = -INFINITY;                                 \
+        }                                                                                                                      \
+        __builtin_amdgcn_sched_barrier(0);                                                                                     \
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                                       \
+        layer_barrier<LS_##s>();                                                                                               \
+        __builtin_amdgcn_sched_barrier(0);                                                                                     \
+    }
+    DC_LAYER_STEPS(X)
+#undef X
+    if (im.runs(LS_VALUES))
+        wg_write_record<NW>(recs_out, mx, reinterpret_cast<const f32x8*>(im.lds + Img::OFF_ER), reinterpret_cast<const f32x8*>(im.lds + Img::OFF_AF + 8192),
+                            reinterpret_cast<const float*>(im.lds + Img::OFF_ER + 8 * 8192), im.wave, im.lane, im.ub0, wm.nact, wm.Mu, wm.Tu, wg);
+}
 template <class T16, bool SPLIT, bool DBG, bool STAMP, bool WGR, bool NARROW = false, bool G1 = false /* FiLM scale tiles hold G' (film_affine) */>
 __global__ __launch_bounds__((NARROW || (SPLIT && DC_SPLIT_NW == 4)) ? 256 : 512, (SPLIT && DC_SPLIT_NW == 4) ? 1 : 2)      // (NARROW runs one wave per SIMD by its LDS; bounds of 2 keep hipcc off the AGPR half: 247 VGPRs instead of 247 + 112 and 1 400 accvgpr moves)
 void k_layer(const DcModel* __restrict__ dm, int l, float* __restrict__ hbuf, const f16x16* __restrict__ E, int NT,
@@ -1368,7 +1489,8 @@ void k_layer(const DcModel* __restrict__ dm, int l, float* __restrict__ hbuf, co
              float* __restrict__ snaps, int M, int T, int G, int B, int dbg,
              unsigned long long* __restrict__ stamps, size_t rec_stride, const int* __restrict__ iter_base,
              int Tx /* frames per clip of xin / xout / snaps (<= the clip stride T) */, int upc /* workgroups per clip (WgMap) or 0 */,
-             int e_groups /* groups of FiLM tiles behind E (DcLayerArgs) */, int e_period, int e_wrap, unsigned e_magic /* film_tile_group */, const DcUpdate upd) {
+             int e_groups /* groups of FiLM tiles behind E (DcLayerArgs) */, int e_period, int e_wrap, unsigned e_magic /* film_tile_group */,
+             int idle_path /* wide plain production form: padding waves take layer_idle_wave (DcLayerForm::idle_path) */, const DcUpdate upd) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     static_assert(!NARROW || (WGR && !SPLIT && !DBG), "narrow workgroups: workgroup-record form, non-split formats, no test hooks");
     constexpr int NW = NARROW ? 4 : (SPLIT ? DC_SPLIT_NW : 8);
@@ -1407,10 +1529,25 @@ void k_layer(const DcModel* __restrict__ dm, int l, float* __restrict__ hbuf, co
     // `dm` itself: a pointer that has been an asm input counts as escaped, and the LDS-DMA statements' memory clobbers then cover it.)
     {
         const unsigned grid_x = gridDim.x;
-        asm("" : "+s"(T) : "s"(l), "s"(hbuf), "s"(E), "s"(recs), "s"(a_ca), "s"(NT), "s"(M), "s"(Tx), "s"(G), "s"(B), "s"(rec_stride), "s"(upc), "s"(grid_x));
+        asm("" : "+s"(T) : "s"(l), "s"(hbuf), "s"(E), "s"(recs), "s"(a_ca), "s"(NT), "s"(M), "s"(Tx), "s"(G), "s"(B), "s"(rec_stride), "s"(upc), "s"(grid_x), "s"(idle_path));
     }
 #endif
     const int nl = dm->num_layers;
+    // Wide plain production form: a padding wave of a clip's last workgroup (clip-aligned units at 1800 frames: 7 of its 8 waves; flat
+    // units: the tail of the last workgroup) leaves here, before anything of the layer is live, and passes the launch as a workgroup
+    // member only (layer_idle_wave).  One wave-uniform branch; the active waves' code behind it is what it was.  idle_path == 0
+    // (dc_sampler_set_idle_wave_path(s, 0)): such a wave runs the whole layer on the clip's last group, for nobody.
+    if constexpr (WGR && !SPLIT && !NARROW && !DBG && !STAMP) {
+        const int wave_ = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), wg_ = wg_index();
+        const WgMap wm_ = wg_map(wg_, wave_, NW, G, M, T, B, upc);
+        if (idle_path && !wm_.active) {
+            const bool last_ = l + 1 >= nl;
+            const LayerImages<T16, SPLIT, WGR, NW> im_{dm, l, last_, last_ && out_mode == 1 && (upd.flags & DC_UPD_EMBED_NEXT) != 0, true, lds,
+                                                       a_sa, a_ca + (size_t)l * B * 16 * 64, wm_.ub0, B, wave_, (int)threadIdx.x & 63};
+            layer_idle_wave<T16, NW>(im_, recs + (size_t)(l & 1) * rec_stride, recs + (size_t)((l + 1) & 1) * rec_stride, wm_, (int)threadIdx.x, wg_);
+            return;
+        }
+    }
     f32x16 h[4];
     {
         const int g0 = wg_map(WGR ? wg_index() : (int)blockIdx.x, threadIdx.x >> 6, NW, G, M, T, B, WGR ? upc : 0).g;
@@ -1434,35 +1571,30 @@ void k_layer(const DcModel* __restrict__ dm, int l, float* __restrict__ hbuf, co
     const bool wg_lds = WGR || (!SPLIT && T >= NW * 32);       // WGR is only launched with T >= NW * 32
     const int ub0 = wm.ub0;
     char* ring = lds + OFF_ER + wave * 8192;
-    auto stage_attn = [&](const W* a) {          // frags of clips ub0, ub0+1 -> AF region
-        if constexpr (SPLIT) {                   // (workgroup records, clip-aligned: hi + lo frags of the one clip)
-            stage_frags<NW>(a + (size_t)ub0 * 16 * 64, lds + OFF_AF, 16, wave, lane);
-        } else {
-            const int c1i = min(ub0 + 1, B - 1);
-            stage_frags<NW>(a + (size_t)ub0 * 16 * 64, lds + OFF_AF, 8, wave, lane);
-            stage_frags<NW>(a + (size_t)c1i * 16 * 64, lds + OFF_AF + 8192, 8, wave, lane);
-        }
-    };
     const W* af = reinterpret_cast<const W*>(lds + OFF_AF);
-    const DcLayer& L = dm->layer[l];
     const bool last = l + 1 >= nl;
     const f16x8* Eg = reinterpret_cast<const f16x8*>(E) + ((size_t)film_tile_group(g, e_period, e_wrap, e_groups, e_magic) * NT + (size_t)l * 24) * 128;   // 3 blocks x 8 tiles
     const W* acl = a_ca + (size_t)l * B * 16 * 64;
     const float* recs_in = recs + (size_t)(l & 1) * rec_stride;
     float* recs_out = recs + (size_t)((l + 1) & 1) * rec_stride;
+    // The last layer of a step can also do the NEXT step's front work (dc_api.hip, DC_UPD_EMBED_NEXT; production form of the wide non-split
+    // kernel, captured and eager loops): see behind stage 6.
+    bool embed_next = false;
+    if constexpr (WGR && !SPLIT && !NARROW && !DBG) embed_next = last && out_mode == 1 && (upd.flags & DC_UPD_EMBED_NEXT) != 0;
+    // the weight-image copies of this launch, by step (DC_LAYER_STEPS: the list the padding waves' path is made from)
+    const LayerImages<T16, SPLIT, WGR, NW> im{dm, l, last, embed_next, wg_lds, lds, a_sa, acl, ub0, B, wave, lane};
+    static_assert(decltype(im)::WSZ == WSZ && decltype(im)::OFF_AF == OFF_AF && decltype(im)::OFF_ER == OFF_ER, "one LDS layout");
 
     DC_STAMP(0);
     if (STAMP && stamps && blockIdx.x == 3 && (threadIdx.x & 63) == 0 && l == 3) stamps[(threadIdx.x >> 6) * 32 + 26] = __builtin_amdgcn_s_memtime();
     DC_WGSTAMP(0);
     if (STAMP && stamps && threadIdx.x == 0 && (l == 3 || l == 4) && blockIdx.x < 256) stamps[2576 + (l - 3) * 256 + blockIdx.x] = t_first;
-    stage_frags<NW>(L.img_sa_q, buf0, NFW + 1, wave, lane);
+    im.template issue<LS_PROLOGUE>();       // SA query image -> buf0 (per-group records: + the self-attention fragments)
     if constexpr (NARROW)
         wg_combine_attn_narrow<T16>(recs_in, reinterpret_cast<W*>(lds + OFF_AF), reinterpret_cast<float*>(buf1), ub0, wm.Mu, wm.Tu, tid_, wg);
     else if constexpr (WGR)      // self-attention matrices from the previous layer's workgroup records (scratch: buf1)
         wg_combine_attn<T16, SPLIT>(recs_in, reinterpret_cast<W*>(lds + OFF_AF), reinterpret_cast<float*>(buf1), ub0, B, wm.Mu, wm.Tu, tid_, wg,
                                     (STAMP && stamps && blockIdx.x == 3 && l == 3) ? stamps : nullptr);
-    else if (wg_lds)
-        stage_attn(a_sa);
     DC_STAMP(14);
     constexpr bool use_ring = !SPLIT;             // FiLM tiles through the per-wave LDS ring (else: registers)
 #ifdef DC_PROLOGUE_WAIT_ALL
@@ -1472,7 +1604,7 @@ void k_layer(const DcModel* __restrict__ dm, int l, float* __restrict__ hbuf, co
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     DC_STAMP(15);
-    stage_sync();
+    layer_close<LS_PROLOGUE>();
 #else
     // The first two FiLM ring tiles are this wave's 8 youngest vector-memory operations and are first read in stage 2, behind
     // stage 1's closing vmcnt(0): the prologue waits for everything BUT them (vmcnt counts in issue order) - at kernel start
@@ -1491,7 +1623,7 @@ void k_layer(const DcModel* __restrict__ dm, int l, float* __restrict__ hbuf, co
     }
     DC_STAMP(15);
     __builtin_amdgcn_sched_barrier(0);
-    __syncthreads(); sprio<3>();
+    layer_barrier<LS_PROLOGUE>(); sprio<3>();
     __builtin_amdgcn_sched_barrier(0);
 #endif
 #ifdef DC_DIAG_HALF_SHIFT
@@ -1507,7 +1639,7 @@ void k_layer(const DcModel* __restrict__ dm, int l, float* __restrict__ hbuf, co
     DC_STAMP(1);
 
     // ---- stage 1: SA query + attention apply [buf0]; prefetch SA out-proj -> buf1
-    stage_frags<NW>(L.img_sa_o, buf1, NFW + 1, wave, lane);
+    im.template issue<LS_SA_APPLY>();
     EPre ep;
     constexpr bool split_pf = DC_SPLIT_STYL_PF && SPLIT && !DBG;      // split formats: FiLM tiles through registers, two k-tiles ahead
     EPf epf;
@@ -1529,20 +1661,18 @@ void k_layer(const DcModel* __restrict__ dm, int l, float* __restrict__ hbuf, co
         __builtin_amdgcn_sched_barrier(0);
         epf_fetch(epf, Eg, 0, 0, lane);
         epf_fetch(epf, Eg, 1, 1, lane);
-        stage_sync_keep8();
+        layer_close<LS_SA_APPLY, true>();
     } else
-        stage_sync();
+        layer_close<LS_SA_APPLY>();
     DC_STAMP(3);
     if constexpr (use_ring) epre_landed(ep);
     // ---- stage 2: SA stylization [buf1]; prefetch CA query -> buf0 (+ cross-attention frags)
     if constexpr (!use_ring) {
-        stage_frags<NW>(L.img_ca_q, buf0, NFW + 1, wave, lane);
-        if (wg_lds) stage_attn(acl);
+        im.template issue<LS_SA_STYL>();
         if (!(DBG && skip_blocks >= 1)) { if constexpr (split_pf) styl_accumulate_pf<T16, SPLIT, DC_SPLIT_STYL_PF == 2>(h, y, y_rstd, y_shift, Eg, epf, c1, w1, lane, cx.hh); else styl_accumulate<T16, SPLIT, G1>(h, y, y_rstd, y_shift, Eg, c1, w1, lane, cx.hh); }
     } else {
         auto next2 = [&]() {
-            stage_frags<NW>(L.img_ca_q, buf0, NFW + 1, wave, lane);
-            if (wg_lds) stage_attn(acl);
+            im.template issue<LS_SA_STYL>();
             ering_issue(Eg + 8 * 128, 0, ring, lane);
             ering_issue(Eg + 8 * 128, 1, ring + 4096, lane);
         };
@@ -1553,10 +1683,10 @@ void k_layer(const DcModel* __restrict__ dm, int l, float* __restrict__ hbuf, co
     }
     if constexpr (DBG) if ((dbg & 0xff) == 1) { if (active) store_h(h, hbuf, g, lane); return; }   // test hook: stop after self-attention
     DC_STAMP(4);
-    stage_sync();
+    layer_close<LS_SA_STYL>();
     DC_STAMP(5);
     // ---- stage 3: CA query + attention apply [buf0]; prefetch CA out-proj -> buf1
-    stage_frags<NW>(L.img_ca_o, buf1, NFW + 1, wave, lane);
+    im.template issue<LS_CA_APPLY>();
     if constexpr (use_ring) epre_load(ep, Eg + 8 * 128, lane);
     if (DBG && skip_blocks >= 2) {
     } else if (wg_lds)
@@ -1570,19 +1700,17 @@ void k_layer(const DcModel* __restrict__ dm, int l, float* __restrict__ hbuf, co
         __builtin_amdgcn_sched_barrier(0);
         epf_fetch(epf, Eg + 8 * 128, 0, 0, lane);
         epf_fetch(epf, Eg + 8 * 128, 1, 1, lane);
-        stage_sync_keep8();
+        layer_close<LS_CA_APPLY, true>();
     } else
-        stage_sync();
+        layer_close<LS_CA_APPLY>();
     if constexpr (use_ring) epre_landed(ep);
     // ---- stage 4: CA stylization [buf1]; prefetch FFN W1|W2 (+ b1|b2) -> buf0
     if constexpr (!use_ring) {
-        stage_frags<NW>(L.img_ffn_w1, buf0, 16 * WM, wave, lane);
-        stage_frags<NW>(L.img_ffn_w2, buf0 + 16 * WM * 1024, 16 * WM + 1, wave, lane);
+        im.template issue<LS_CA_STYL>();
         if (!(DBG && skip_blocks >= 2)) { if constexpr (split_pf) styl_accumulate_pf<T16, SPLIT, DC_SPLIT_STYL_PF == 2>(h, y, y_rstd, y_shift, Eg + 8 * 128, epf, c1, w1, lane, cx.hh); else styl_accumulate<T16, SPLIT, G1>(h, y, y_rstd, y_shift, Eg + 8 * 128, c1, w1, lane, cx.hh); }
     } else {
         auto next4 = [&]() {
-            stage_frags<NW>(L.img_ffn_w1, buf0, 16 * WM, wave, lane);
-            stage_frags<NW>(L.img_ffn_w2, buf0 + 16 * WM * 1024, 16 * WM + 1, wave, lane);
+            im.template issue<LS_CA_STYL>();
             ering_issue(Eg + 16 * 128, 0, ring, lane);
             ering_issue(Eg + 16 * 128, 1, ring + 4096, lane);
         };
@@ -1593,10 +1721,10 @@ void k_layer(const DcModel* __restrict__ dm, int l, float* __restrict__ hbuf, co
     }
     if constexpr (DBG) if ((dbg & 0xff) == 2) { if (active) store_h(h, hbuf, g, lane); return; }   // test hook: stop after cross-attention
     DC_STAMP(7);
-    stage_sync();
+    layer_close<LS_CA_STYL>();
     DC_STAMP(8);
     // ---- stage 5: FFN [buf0]; prefetch FFN out-proj -> buf1
-    stage_frags<NW>(L.img_ffn_o, buf1, NFW + 1, wave, lane);
+    im.template issue<LS_FFN>();
     if constexpr (use_ring) epre_load(ep, Eg + 16 * 128, lane);
     {
         f32x16 u[2];
@@ -1637,18 +1765,13 @@ void k_layer(const DcModel* __restrict__ dm, int l, float* __restrict__ hbuf, co
         __builtin_amdgcn_sched_barrier(0);
         epf_fetch(epf, Eg + 16 * 128, 0, 0, lane);
         epf_fetch(epf, Eg + 16 * 128, 1, 1, lane);
-        stage_sync_keep8();
+        layer_close<LS_FFN, true>();
     } else
-        stage_sync();
+        layer_close<LS_FFN>();
     if constexpr (use_ring) epre_landed(ep);
     // ---- stage 6: FFN stylization [buf1]; prefetch next layer's key projection (or the output projection) -> buf0
     {
-        auto next_w = [&]() {
-            if (!last)
-                stage_frags<NW>(dm->layer[l + 1].img_sa_k, buf0, NFW + 1, wave, lane);
-            else
-                stage_frags<NW>(dm->img_out, buf0, 17, wave, lane);      // 8 hi + 8 lo frags + bias: always runs split
-        };
+        auto next_w = [&]() { im.template issue<LS_FFN_STYL>(); };
         if constexpr (!use_ring) {
             next_w();
             { if constexpr (split_pf) styl_accumulate_pf<T16, SPLIT, DC_SPLIT_STYL_PF == 2>(h, y, y_rstd, y_shift, Eg + 16 * 128, epf, c1, w1, lane, cx.hh); else styl_accumulate<T16, SPLIT, G1>(h, y, y_rstd, y_shift, Eg + 16 * 128, c1, w1, lane, cx.hh); }
@@ -1658,7 +1781,7 @@ void k_layer(const DcModel* __restrict__ dm, int l, float* __restrict__ hbuf, co
     }
     if constexpr (DBG) if ((dbg & 0xff) == 3) { if (active) store_h(h, hbuf, g, lane); return; }   // test hook: stop after the FFN
     DC_STAMP(10);
-    stage_sync();
+    layer_close<LS_FFN_STYL>();
 #ifdef DC_DIAG_HALF_SHIFT
     if constexpr (WGR && !SPLIT && !NARROW && !DBG) {
         if (wave < NW / 2) { for (int i_ = 0; i_ < DC_DIAG_HALF_SHIFT; ++i_) __builtin_amdgcn_s_barrier(); }
@@ -1672,14 +1795,9 @@ void k_layer(const DcModel* __restrict__ dm, int l, float* __restrict__ hbuf, co
     // (joint_embed + sequence_embedding, the same split-operand GEMM in the same order as embed_front_body: h bit-identical) and layer 0's
     // self-attention front half (stage 7 below, with layer 0's images) follow at once - the next step's FiLM launch is then the bare GEMM.
     // What that saves is the front kernel's cold start (x, the embedding image and the sequence rows through a cold cache: 8 of its 22 us)
-    // and the difference between its record pass and this kernel's.
-    bool embed_next = false;
-    if constexpr (WGR && !SPLIT && !NARROW && !DBG) embed_next = last && out_mode == 1 && (upd.flags & DC_UPD_EMBED_NEXT) != 0;
+    // and the difference between its record pass and this kernel's.  (`embed_next` itself: at the head of the body, beside `im`)
     if (last) {
-    if (embed_next) {      // layer 0's key image -> buf1 (the FFN out-projection image, consumed); the embedding image -> the idle FiLM rings
-        stage_frags<NW>(dm->layer[0].img_sa_k, buf1, NFW + 1, wave, lane);
-        stage_frags<NW>(dm->img_je, lds + OFF_ER, 17, wave, lane);
-    }
+    if (embed_next) im.template issue<LS_EMBED_NEXT>();      // layer 0's key image -> buf1 (the FFN out-projection image, consumed); the embedding image -> the idle FiLM rings
     // ---- output projection [buf0, split] + DDIM update
     f32x16 x0[1];
     const int P = dm->input_feats;
@@ -1710,9 +1828,9 @@ void k_layer(const DcModel* __restrict__ dm, int l, float* __restrict__ hbuf, co
             // output image in buf0 any more: layer 0's value image goes there, ahead of everything the update and the embedding issue
             __builtin_amdgcn_sched_barrier(0);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads(); sprio<3>();
+            layer_barrier<LS_EMBED_NEXT>(); sprio<3>();
             __builtin_amdgcn_sched_barrier(0);
-            stage_frags<NW>(dm->layer[0].img_sa_v, buf0, NFW + 1, wave, lane);
+            im.template issue<LS_KEYS>();      // (embed_next: layer 0's value image -> buf0)
             const int xb = e_xb, xn = e_xn;
             const bool live = e_live;
             {
@@ -1808,7 +1926,6 @@ void k_layer(const DcModel* __restrict__ dm, int l, float* __restrict__ hbuf, co
     }          // (last)
     {
         // (embed_next: the front half of the NEXT STEP's layer 0 - key image in buf1, value image into buf0)
-        const DcLayer& Ln = dm->layer[last ? 0 : l + 1];
         char* const bufK = last ? buf1 : buf0;
         char* const bufV = last ? buf0 : buf1;
         const W* const wK = reinterpret_cast<const W*>(bufK);
@@ -1816,7 +1933,7 @@ void k_layer(const DcModel* __restrict__ dm, int l, float* __restrict__ hbuf, co
         const float* const cK = reinterpret_cast<const float*>(bufK + NFW * 1024);
         const float* const cV = reinterpret_cast<const float*>(bufV + NFW * 1024);
         // ---- stage 7: next layer's SA front half: K [buf0] and V [buf1], partial records
-        if (!last) stage_frags<NW>(Ln.img_sa_v, bufV, NFW + 1, wave, lane);      // (embed_next: requested behind the output projection)
+        if (!last) im.template issue<LS_KEYS>();      // the value image -> bufV (embed_next: requested behind the output projection)
         // h goes out right behind the value-image DMA: vmcnt counts in issue order, so waiting until only the 16
         // youngest operations (the 16 dwordx4 stores of h) are outstanding means "the image has landed" while the
         // stores keep draining behind the K/V projections.
@@ -1917,7 +2034,7 @@ void k_layer(const DcModel* __restrict__ dm, int l, float* __restrict__ hbuf, co
             else
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             DC_STAMP(21);
-            __syncthreads(); sprio<3>();
+            layer_barrier<LS_KEYS>(); sprio<3>();
             __builtin_amdgcn_sched_barrier(0);
             DC_STAMP(12);
             // rescale factors of this wave's columns, through its own LDS strip (each lane needs 8 of them as row factors)
@@ -1980,7 +2097,7 @@ void k_layer(const DcModel* __restrict__ dm, int l, float* __restrict__ hbuf, co
             }
             __builtin_amdgcn_sched_barrier(0);
             DC_STAMP(16);
-            __syncthreads(); sprio<3>();
+            layer_barrier<LS_VALUES>(); sprio<3>();
             DC_STAMP(17);
             wg_write_record<NW>(recs_out, mx, pst, xp, ss, wave, lane, ub0, wm.nact, wm.Mu, wm.Tu, wg);
         } else {
@@ -1995,7 +2112,7 @@ void k_layer(const DcModel* __restrict__ dm, int l, float* __restrict__ hbuf, co
                 asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
             else
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads(); sprio<3>();
+            layer_barrier<LS_KEYS>(); sprio<3>();      // (per-group records: the one barrier of the front half, no VALUES step)
             __builtin_amdgcn_sched_barrier(0);
             DC_STAMP(12);
             float* rec = recs + (size_t)cx.g * 2 * DC_REC_FLOATS;
@@ -3021,7 +3138,7 @@ hipError_t dc_launch_embed_front(hipStream_t st, const DcLayerForm& f, const DcM
 
 template <class T16, bool SP, bool DBG, bool STAMP, bool WGR, bool NARROW = false, bool G1 = false>
 static hipError_t launch_layer_t(hipStream_t st, const DcLayerArgs& a, int l, const void* a_sa, const void* a_ca, int dbg,
-                                 unsigned long long* stamps, size_t rec_stride, int upc) {
+                                 unsigned long long* stamps, size_t rec_stride, int upc, bool idle_path) {
     constexpr int NW = NARROW ? 4 : (SP ? DC_SPLIT_NW : 8);
     // two stage images (+1 KiB constants each); non-split adds the attention-frag region and the FiLM rings
     const size_t shm = SP ? 2 * 65 * 1024 + (WGR ? 16384 + 6144 : 0) : 2 * 33 * 1024 + 16384 + 8 * 8192 + 6144;
@@ -3029,7 +3146,8 @@ static hipError_t launch_layer_t(hipStream_t st, const DcLayerArgs& a, int l, co
     if (hipError_t e = lds_optin((const void*)k_layer<T16, SP, DBG, STAMP, WGR, NARROW, G1>, (int)shm, optin_done)) return e;
     k_layer<T16, SP, DBG, STAMP, WGR, NARROW, G1><<<dim3((WGR && upc) ? a.B * upc : (a.G + NW - 1) / NW), dim3(NW * 64), shm, st>>>(
         a.dm, l, a.hbuf, (const f16x16*)a.E, a.NT, (const v8<T16>*)a_sa, (const v8<T16>*)a_ca, a.recs, a.length, a.xin, a.xout, a.out_mode,
-        a.coef_cur, a.snap_cur, a.snaps, a.M, a.T, a.G, a.B, dbg, stamps, rec_stride, a.iter_base, a.Tx, WGR ? upc : 0, a.e_groups, a.e_period, a.e_wrap, a.e_magic, a.upd);
+        a.coef_cur, a.snap_cur, a.snaps, a.M, a.T, a.G, a.B, dbg, stamps, rec_stride, a.iter_base, a.Tx, WGR ? upc : 0, a.e_groups, a.e_period, a.e_wrap, a.e_magic,
+        idle_path ? 1 : 0, a.upd);
     return hipGetLastError();
 }
 
@@ -3050,7 +3168,7 @@ hipError_t dc_launch_layer(hipStream_t st, const DcLayerForm& f, const DcLayerAr
 #define X(SP, DBG, STAMP, WGR, NARROW, G1)                                                                      \
     if (f.split == SP && stop == DBG && stamp == STAMP && f.wgr == WGR && f.narrow == NARROW && f.g1 == G1)     \
         return (f.fmt == 1 ? launch_layer_t<_Float16, SP, DBG, STAMP, WGR, NARROW, G1> : launch_layer_t<__bf16, SP, DBG, STAMP, WGR, NARROW, G1>)( \
-            st, a, l, a_sa, a_ca, dbg, stamps, f.rec_stride, f.upc);
+            st, a, l, a_sa, a_ca, dbg, stamps, f.rec_stride, f.upc, f.idle_path);
     LAYER_FORMS(X)
 #undef X
     return hipErrorInvalidValue;

@@ -55,6 +55,8 @@ struct DcLayerForm {
     bool g1;             // the FiLM scale tiles hold G' (film_affine in dc_dev.h; plain-operand production forms of k_layer only)
     int upc;             // wgr: workgroups per clip (clip-aligned units, WgMap in dc_dev.h), grid = B * upc; else 0
     size_t rec_stride;   // floats between the two alternating unit-record buffers, in units of the form (0 = single buffer, non-wgr)
+    bool idle_path;      // k_layer, wide plain production form (wgr, non-split, 8 waves, no stop stage, no stamps): the padding waves of a
+                         // clip's last workgroup pass the launch on the barrier-only path (layer_idle_wave); every other form ignores it
 };
 hipError_t dc_launch_embed_front(hipStream_t st, const DcLayerForm& f, const DcModel* dm, const float* x, float* hbuf, float* recs,
                                  const int* length, int M, int T, int G, int B,

@@ -20,7 +20,7 @@ DC_PREC = {"bf16": 0, "mixed": 1, "bf16x3": 2, "fp16": 3}
 EXPORTS = [
     "dc_last_error", "dc_version", "dc_linear_beta_schedule", "dc_ddim_coefficients", "dc_pack_weight",
     "dc_sampler_create", "dc_sampler_destroy", "dc_sampler_set_param", "dc_sampler_finalize_params",
-    "dc_sampler_set_conditioning", "dc_sampler_encode_music", "dc_sampler_set_encoder_format", "dc_sampler_set_precise_tail", "dc_precise_tail_default", "dc_sampler_set_precise_forward", "dc_sampler_set_combine_exchange", "dc_sampler_set_clip_aligned", "dc_sampler_denoise", "dc_sampler_ddim_loop", "dc_sampler_profile_loop",
+    "dc_sampler_set_conditioning", "dc_sampler_encode_music", "dc_sampler_set_encoder_format", "dc_sampler_set_precise_tail", "dc_precise_tail_default", "dc_sampler_set_precise_forward", "dc_sampler_set_combine_exchange", "dc_sampler_set_clip_aligned", "dc_sampler_set_idle_wave_path", "dc_sampler_denoise", "dc_sampler_ddim_loop", "dc_sampler_profile_loop",
     "dc_kernel_name", "dc_kernel_count", "dc_sampler_workspace_bytes", "dc_sampler_clip_stride", "dc_sampler_debug_denoise",
     "dc_sampler_debug_read", "dc_sampler_debug_layer", "dc_savgol_coefficients", "dc_savgol_filter",
     "dc_ddim_coefficients_ex", "dc_sampler_ddim_loop_ex", "dc_sampler_status", "dc_sampler_set_smoothing",
@@ -136,6 +136,7 @@ def lib():
     L.dc_sampler_set_precise_tail.argtypes = [C.c_void_p, C.c_int32]
     L.dc_sampler_set_combine_exchange.argtypes = [C.c_void_p, C.c_int32]
     L.dc_sampler_set_clip_aligned.argtypes = [C.c_void_p, C.c_int32]
+    L.dc_sampler_set_idle_wave_path.argtypes = [C.c_void_p, C.c_int32]
     L.dc_precise_tail_default.argtypes = [C.c_int32]
     L.dc_precise_tail_default.restype = C.c_int32
     L.dc_sampler_set_precise_forward.argtypes = [C.c_void_p, C.c_int32]
@@ -540,6 +541,11 @@ class NativeSampler:
         """Units of the wide launch form: True clip-aligned (batch-invariant results), False flat (throughput), None the library's rule -
         aligned whenever that costs no extra round of workgroups (dc_ddim.h, dc_sampler_set_clip_aligned)."""
         _check(lib().dc_sampler_set_clip_aligned(self._h, -1 if mode is None else (1 if mode else 0)))
+
+    def set_idle_wave_path(self, on):
+        """Padding waves of a clip's last workgroup in the wide plain layer kernel: True (default) barrier-only, False the whole layer
+        as before - bit-identical results, the comparison form (dc_ddim.h, dc_sampler_set_idle_wave_path)."""
+        _check(lib().dc_sampler_set_idle_wave_path(self._h, 1 if on else 0))
 
     def set_precise_forward(self, on):
         """denoise() on split operands (the precise tail's evaluation form; dc_ddim.h, dc_sampler_set_precise_forward)."""

@@ -385,6 +385,13 @@ DC_EXPORT int dc_sampler_status(dc_sampler* s, int32_t* h_status, int32_t clear)
  * (dc_sampler_clip_stride) and T >= 256; ignored otherwise. */
 DC_EXPORT int dc_sampler_set_clip_aligned(dc_sampler* s, int32_t mode);
 
+/* Clip-aligned units pad a clip to whole 256-token workgroups: at 1800 frames the eighth workgroup of a clip has one wave with tokens
+ * and seven without.  on != 0 (default): in the wide plain layer kernel such a padding wave issues its shares of the weight-image copies,
+ * takes part in the workgroup's combine, barriers and record tail, and does nothing else.  on == 0: it runs the whole layer on the clip's
+ * last group, as it did before this setting existed - the comparison form.  Results are bit-identical either way (nothing a padding wave
+ * computes reaches an output); a change re-captures the loop's graph.  No reference counterpart. */
+DC_EXPORT int dc_sampler_set_idle_wave_path(dc_sampler* s, int32_t on);
+
 /* Small batches (B * ceil(T / 64) <= CUs): on != 0 (default) lets a clip's workgroups share the combine of the attention unit records
  * inside a layer launch (-8 % per layer launch at one clip per call; needs the launch's workgroups co-resident, see DC_STATUS_TIMEOUT);
  * on == 0 makes every workgroup combine alone - no in-launch wait, safe beside other work on the GPU.  No reference counterpart
