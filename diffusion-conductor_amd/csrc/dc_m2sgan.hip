@@ -224,7 +224,9 @@ struct dc_m2sgan {
     DcParams params;
     GanImage image;                      // offsets (the floats themselves are dropped after the upload)
     float* d_img = nullptr;
+    size_t img_bytes = 0;                // (the image's size follows the decoder choice)
     DcWorkspace ws;
+    int decoder = DC_M2SGAN_DECODER_TCN; // dc_m2sgan_set_decoder: NONE = features only (the pose decoder is another handle's)
     bool finalized = false;
 };
 
@@ -304,10 +306,14 @@ int features_run(dc_m2sgan* g, const GanPlan& pl, const float* mel, int nb, int 
     return DC_OK;
 }
 
-// the shape rules every entry point shares; Tm < 0: no mel (decode), Ln < 0: no latent
+// the shape rules every entry point shares; Tm < 0: no mel (decode), Ln < 0: no latent.  A features-only handle has no decoder
+// to call and no temporal block whose reflection bounds T.
 int check_shapes(const char* fn, const dc_m2sgan* g, int B, int Tm, int Ln, int T) {
     const std::string f(fn);
     if (!g->finalized) return dc_set_error(DC_ERR_INVALID, (f + " before dc_m2sgan_finalize").c_str());
+    const bool tcn = g->decoder == DC_M2SGAN_DECODER_TCN;
+    if (!tcn && f != "dc_m2sgan_features")
+        return dc_set_error(DC_ERR_INVALID, (f + ": this generator was finalized without a decoder (dc_m2sgan_set_decoder); it computes features only").c_str());
     if (B < 1) return dc_set_error(DC_ERR_INVALID, (f + ": B must be >= 1").c_str());
     if (Tm >= 0 && Tm < 4) return dc_set_error(DC_ERR_INVALID, (f + ": need at least 4 mel frames (the encoder's reflection padding)").c_str());
     if (Tm >= 0 && T != dc_music_frames(Tm))
@@ -316,7 +322,7 @@ int check_shapes(const char* fn, const dc_m2sgan* g, int B, int Tm, int Ln, int 
     if (Ln >= 0 && (Ln < 1 || T != 30 * Ln))
         return dc_set_error(DC_ERR_INVALID, (f + ": a latent of " + std::to_string(Ln) + " steps makes " + std::to_string(30 * (long long)Ln) +
                                              " frames, the music has " + std::to_string(T)).c_str());
-    if (T < G_MIN_T)
+    if (tcn && T < G_MIN_T)
         return dc_set_error(DC_ERR_INVALID, (f + ": " + std::to_string(T) + " frames; the last temporal block reflects 128 frames and needs T > 128").c_str());
     return DC_OK;
 }
@@ -349,22 +355,43 @@ int dc_m2sgan_set_param(dc_m2sgan* g, const char* name, const float* h_data, int
     const std::string given(name), k = unalias(given);
     bool changed = false;
     // a `net.N.*` alias (k != given) is the same tensor as its conv / bn twin, which is the parameter: checked and dropped
+    const DcParamList used = g->decoder == DC_M2SGAN_DECODER_TCN ? gan_required() : gan_required_features();
     const int rc = starts_with(k, "music_encoder.") ? g->music.take(kWhat, kGanC, k, h_data, numel, &changed)
-                                                    : dc_param_take(kWhat, gan_required(), {}, k, given, h_data, numel, k == given ? &g->params : nullptr, &changed);
+                                                    : dc_param_take(kWhat, used, {}, k, given, h_data, numel, k == given ? &g->params : nullptr, &changed);
     if (changed) g->finalized = false;
     return rc;
+}
+
+int dc_m2sgan_set_decoder(dc_m2sgan* g, int32_t decoder) {
+    if (!g) return dc_set_error(DC_ERR_INVALID, "dc_m2sgan_set_decoder: NULL handle");
+    if (decoder != DC_M2SGAN_DECODER_TCN && decoder != DC_M2SGAN_DECODER_NONE)
+        return dc_set_error(DC_ERR_INVALID, "dc_m2sgan_set_decoder: decoder must be DC_M2SGAN_DECODER_TCN or DC_M2SGAN_DECODER_NONE");
+    if (decoder != g->decoder) g->finalized = false;
+    g->decoder = decoder;
+    return DC_OK;
 }
 
 int dc_m2sgan_finalize(dc_m2sgan* g) {
     if (!g) return dc_set_error(DC_ERR_INVALID, "dc_m2sgan_finalize: NULL handle");
     g->finalized = false;
+    const bool tcn = g->decoder == DC_M2SGAN_DECODER_TCN;
+    if (!tcn)
+        for (const auto& e : g->params)
+            if (starts_with(e.first, "tcn."))
+                return dc_set_error(DC_ERR_PARAM, (std::string(kWhat) + " parameter " + e.first + " was set, but the generator has no decoder (dc_m2sgan_set_decoder)").c_str());
     if (const int rc = g->music.check(kWhat, kGanC)) return rc;
-    if (const int rc = dc_param_complete(kWhat, gan_required(), g->params)) return rc;
+    if (const int rc = dc_param_complete(kWhat, tcn ? gan_required() : gan_required_features(), g->params)) return rc;
     DC_HIP_TRY(hipSetDevice(g->device));
     if (const int rc = g->music.rebuild(kWhat, kGanC)) return rc;
-    g->image = gan_pack(g->params);
+    g->image = gan_pack(g->params, tcn);
     const size_t bytes = g->image.img.size() * sizeof(float);
+    if (g->d_img && g->img_bytes != bytes) {
+        DC_HIP_TRY(hipDeviceSynchronize());     // (work of earlier calls may still read the old image)
+        DC_HIP_TRY(hipFree(g->d_img));
+        g->d_img = nullptr;
+    }
     if (!g->d_img) DC_HIP_TRY(hipMalloc((void**)&g->d_img, bytes));
+    g->img_bytes = bytes;
     DC_HIP_TRY(hipMemcpy(g->d_img, g->image.img.data(), bytes, hipMemcpyHostToDevice));
     g->image.img = std::vector<float>();
     g->finalized = true;

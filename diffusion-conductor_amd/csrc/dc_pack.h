@@ -415,10 +415,19 @@ inline DcParamList gan_required() {
     return r;
 }
 
-// params: every entry of gan_required, with its size
-inline GanImage gan_pack(const DcParams& params) {
+// the entries of gan_required a features-only generator (decoder = none) computes with: everything but `tcn.*`
+inline DcParamList gan_required_features() {
+    DcParamList r;
+    for (const auto& e : gan_required())
+        if (e.first.rfind("tcn.", 0) != 0) r.push_back(e);
+    return r;
+}
+
+// params: every entry of gan_required (with_tcn) or of gan_required_features (the `tcn.*` offsets are then left unset), with its size
+inline GanImage gan_pack(const DcParams& params, bool with_tcn = true) {
     const auto P = [&](const std::string& n) -> const float* { return params.find(n)->second.data(); };
     GanImage I;
+    const int n_blocks = with_tcn ? kGanBlocks : 0, n_head = with_tcn ? 4 : 0;
     const auto conv = [&](const std::string& cv, const std::string& bn, int cin, size_t& w, size_t& b) {
         std::vector<float> W((size_t)kGanC * kGanTaps * cin), bias(kGanC), frags(W.size());
         gan_fold_conv(P(cv + ".weight_g"), P(cv + ".weight_v"), P(cv + ".bias"), P(bn + ".weight"), P(bn + ".bias"), P(bn + ".running_mean"),
@@ -427,17 +436,19 @@ inline GanImage gan_pack(const DcParams& params) {
         w = I.add(frags);
         b = I.add(bias);
     };
-    for (int i = 0; i < kGanBlocks; ++i) {
+    for (int i = 0; i < n_blocks; ++i) {
         const std::string p = gan_block(i);
         conv(p + "conv1", p + "bn1", i == 0 ? kGanIn : kGanC, I.block[i].w1, I.block[i].b1);
         conv(p + "conv2", p + "bn2", kGanC, I.block[i].w2, I.block[i].b2);
     }
-    std::vector<float> fd((size_t)kGanC * kGanIn);
-    gan_pack_frags2(P(gan_block(0) + "downsample.weight"), kGanIn, fd.data());
-    I.wd = I.add(fd);
-    I.bd = I.add(params.find(gan_block(0) + "downsample.bias")->second);
+    if (with_tcn) {
+        std::vector<float> fd((size_t)kGanC * kGanIn);
+        gan_pack_frags2(P(gan_block(0) + "downsample.weight"), kGanIn, fd.data());
+        I.wd = I.add(fd);
+        I.bd = I.add(params.find(gan_block(0) + "downsample.bias")->second);
+    }
     const std::string head[4] = {"tcn.TCN.tcn.linear", "tcn.fc.0", "tcn.fc.2", "tcn.fc.4"};
-    for (int i = 0; i < 4; ++i) {
+    for (int i = 0; i < n_head; ++i) {
         const int n = i == 3 ? kGanPose : kGanC;
         std::vector<float> f((size_t)cdiv(n, 32) * (kGanC / 2) * 64), b(kGanC, 0.f);
         head_pack_frags(P(head[i] + ".weight"), n, kGanC, f.data());
@@ -458,6 +469,94 @@ inline GanImage gan_pack(const DcParams& params) {
     }
     I.nscale = I.add(sc);
     I.nshift = I.add(sh);
+    return I;
+}
+
+// ---- BiLSTM pose decoder image (kernels: dc_bilstm.hip) -----------------------------------------------------------
+// PoseDecoderBiLSTM of Contrastive_Stage/models/Generator.py:7-31: nn.LSTM(In, 128, num_layers = 2, bidirectional) and the head
+// `out` = Linear(256, 64), ReLU, Linear(64, 64), ReLU, Linear(64, 26), Sigmoid.  Gate rows in torch's order i, f, g, o.
+constexpr int kLstmH = 128, kLstmGates = 4 * kLstmH, kLstmRows = 2 * kLstmGates, kLstmMaxIn = 128, kLstmPose = 26, kLstmHead = 64;
+inline std::string lstm_name(const char* leaf, int layer, int dir) {
+    return std::string("LSTM.") + leaf + "_l" + std::to_string(layer) + (dir ? "_reverse" : "");
+}
+
+// names and sizes of the decoder's state_dict entries for an input of `in` features, in the module's order
+inline DcParamList lstm_required(int in) {
+    DcParamList r;
+    for (int l = 0; l < 2; ++l)
+        for (int d = 0; d < 2; ++d) {
+            r.push_back({lstm_name("weight_ih", l, d), (size_t)kLstmGates * (l ? 2 * kLstmH : in)});
+            r.push_back({lstm_name("weight_hh", l, d), (size_t)kLstmGates * kLstmH});
+            r.push_back({lstm_name("bias_ih", l, d), kLstmGates});
+            r.push_back({lstm_name("bias_hh", l, d), kLstmGates});
+        }
+    const int n[3] = {kLstmHead, kLstmHead, kLstmPose}, k[3] = {2 * kLstmH, kLstmHead, kLstmHead};
+    for (int i = 0; i < 3; ++i) {
+        r.push_back({"out." + std::to_string(2 * i) + ".weight", (size_t)n[i] * k[i]});
+        r.push_back({"out." + std::to_string(2 * i) + ".bias", (size_t)n[i]});
+    }
+    return r;
+}
+
+// A layer's input projection for both directions as ONE 1024-row matrix (row 512 d + r = W_ih[d][r]) in sixteen 64-row groups,
+// each a gan_pack_frags2 image over k_pad columns (k_in, rounded up to even, the pad a zero weight): dst [16][k_pad / 2][64][2]
+inline void lstm_pack_proj(const float* w_fwd, const float* w_bwd, int k_in, int k_pad, float* dst) {
+    std::vector<float> W((size_t)64 * k_pad);
+    for (int rg = 0; rg < kLstmRows / 64; ++rg) {
+        const float* src = (rg < 8 ? w_fwd : w_bwd) + (size_t)(rg & 7) * 64 * k_in;
+        for (int r = 0; r < 64; ++r)
+            for (int k = 0; k < k_pad; ++k) W[(size_t)r * k_pad + k] = k < k_in ? src[(size_t)r * k_in + k] : 0.f;
+        gan_pack_frags2(W.data(), k_pad, dst + (size_t)rg * 64 * k_pad);
+    }
+}
+// b_ih + b_hh of both directions [1024], summed in fp64 and rounded once
+inline void lstm_fold_bias(const float* bih_f, const float* bhh_f, const float* bih_b, const float* bhh_b, float* dst) {
+    for (int r = 0; r < kLstmGates; ++r) {
+        dst[r] = (float)((double)bih_f[r] + (double)bhh_f[r]);
+        dst[kLstmGates + r] = (float)((double)bih_b[r] + (double)bhh_b[r]);
+    }
+}
+
+struct LstmImage {
+    std::vector<float> img;      // every entry at a multiple of 64 floats
+    int in = 0, k_pad[2] = {0, 2 * kLstmH};
+    size_t wih[2], bias[2];      // per layer: lstm_pack_proj image, lstm_fold_bias [1024]
+    size_t whh[2];               // per layer: W_hh of both directions as they are, [2][512][128]
+    size_t hw[3], hb[3];         // out.0, out.2, out.4: head_pack_frags images ([mt][ks][lane]), plain biases (padded to 64)
+    size_t add(const std::vector<float>& v) {
+        const size_t off = (img.size() + 63) & ~(size_t)63;
+        img.resize(off + v.size());
+        memcpy(img.data() + off, v.data(), v.size() * sizeof(float));
+        return off;
+    }
+};
+
+// params: every entry of lstm_required(in), with its size
+inline LstmImage lstm_pack(const DcParams& params, int in) {
+    const auto P = [&](const std::string& n) -> const float* { return params.find(n)->second.data(); };
+    LstmImage I;
+    I.in = in;
+    I.k_pad[0] = (in + 1) & ~1;
+    for (int l = 0; l < 2; ++l) {
+        const int k_in = l ? 2 * kLstmH : in;
+        std::vector<float> f((size_t)kLstmRows * I.k_pad[l]), b(kLstmRows), hh((size_t)2 * kLstmGates * kLstmH);
+        lstm_pack_proj(P(lstm_name("weight_ih", l, 0)), P(lstm_name("weight_ih", l, 1)), k_in, I.k_pad[l], f.data());
+        lstm_fold_bias(P(lstm_name("bias_ih", l, 0)), P(lstm_name("bias_hh", l, 0)), P(lstm_name("bias_ih", l, 1)), P(lstm_name("bias_hh", l, 1)),
+                       b.data());
+        for (int d = 0; d < 2; ++d) memcpy(hh.data() + (size_t)d * kLstmGates * kLstmH, P(lstm_name("weight_hh", l, d)), sizeof(float) * kLstmGates * kLstmH);
+        I.wih[l] = I.add(f);
+        I.bias[l] = I.add(b);
+        I.whh[l] = I.add(hh);
+    }
+    const int n[3] = {kLstmHead, kLstmHead, kLstmPose}, k[3] = {2 * kLstmH, kLstmHead, kLstmHead};
+    for (int i = 0; i < 3; ++i) {
+        const std::string p = "out." + std::to_string(2 * i);
+        std::vector<float> f((size_t)cdiv(n[i], 32) * (k[i] / 2) * 64), b(kLstmHead, 0.f);
+        head_pack_frags(P(p + ".weight"), n[i], k[i], f.data());
+        memcpy(b.data(), P(p + ".bias"), n[i] * sizeof(float));
+        I.hw[i] = I.add(f);
+        I.hb[i] = I.add(b);
+    }
     return I;
 }
 

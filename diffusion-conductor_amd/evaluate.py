@@ -489,6 +489,9 @@ def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed
         out.update(_rhythm_scores(rh_rows.numpy(), ids, T, rhythm, discriminator))
         if verbose:
             print("  ".join(f"{key}: {out[key]}" for key in ("rde", "sce", "sd_gen", "sd_real", "w_distance") if key in out))
+            if "sd_gen" in out:
+                from .metrics import standard_deviation_percentage
+                print(f"sdp: {standard_deviation_percentage(out['sd_gen'], out['sd_real']):.2f}%")
     return out
 
 
@@ -610,7 +613,8 @@ def _movement_scorers(args, dev):
 
 
 def _baseline_main(args, dev):
-    """--baseline_generator: evaluate_dataset on the M2S-GAN generator (generator.GeneratorBaseline), one JSON line."""
+    """--baseline_generator: evaluate_dataset on the M2S-GAN generator (generator.GeneratorBaseline), one JSON line.  The loader picks
+    the decoder - the TCN or the CNN-LSTM baseline's BiLSTM - from the checkpoint's keys."""
     import json
     from .generator import GeneratorBaseline, load_m2sgan_generator
     gen = load_m2sgan_generator(args.baseline_generator, dev)
@@ -657,7 +661,9 @@ def main(argv=None):
                                                           "W-distance D(real) - D(generated) (discriminator.py)")
     ap.add_argument("--baseline_generator", default=None, help="score the M2S-GAN generator of this checkpoint (a plain state_dict, "
                                                                "M2SGAN_eval.py:451) instead of the denoiser: the same evaluation, one JSON "
-                                                               "line with \"model\": \"m2sgan\" (generator.py)")
+                                                               "line with \"model\": \"m2sgan\" (generator.py).  Either flavour loads: the "
+                                                               "TCN decoder (tcn.TCN.* keys) or the CNN-LSTM baseline's BiLSTM decoder "
+                                                               "(tcn.LSTM.* keys)")
     args = ap.parse_args(argv)
     if args.baseline_generator:
         clash = [f for f, on in (("--model", args.model), ("--val_loss", args.val_loss), ("--guidance_scale", args.guidance_scale is not None),

@@ -222,3 +222,16 @@ def w_distance(d_real, d_gen):
     if r.shape != g.shape or not r.size:
         raise ValueError(f"w_distance: {r.shape} real and {g.shape} generated scores")
     return float((r - g).astype(np.float64).mean())
+
+
+def standard_deviation_percentage(sd_gen, sd_real):
+    """SDP of the competition's evaluation (Contrastive_Stage/ProspectiveCup/eval.py:78): the mean standard deviation of the generated
+    motion as a percentage of the real motion's, mean(SD_fake) / mean(SD_real) * 100.  `sd_gen`, `sd_real`: the per-clip standard
+    deviations (arrays or tensors), or their means - evaluate_dataset's "sd_gen" and "sd_real"."""
+    g = np.asarray(sd_gen.detach().cpu() if hasattr(sd_gen, "detach") else sd_gen, np.float64).reshape(-1)
+    r = np.asarray(sd_real.detach().cpu() if hasattr(sd_real, "detach") else sd_real, np.float64).reshape(-1)
+    if not g.size or not r.size:
+        raise ValueError(f"standard_deviation_percentage: {g.size} generated and {r.size} real standard deviations")
+    if not r.mean() > 0:
+        raise ValueError(f"standard_deviation_percentage: the real motion's mean standard deviation is {r.mean()}, not positive")
+    return float(g.mean() / r.mean() * 100.0)

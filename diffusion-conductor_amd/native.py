@@ -35,7 +35,9 @@ EXPORTS = [
     "dc_sampler_set_conditioning_takes",
     "dc_q_sample_coefficients", "dc_q_sample", "dc_motion_loss_terms", "dc_latent_l1",
     "dc_m2sgan_create", "dc_m2sgan_destroy", "dc_m2sgan_set_param", "dc_m2sgan_finalize", "dc_m2sgan_features", "dc_m2sgan_decode",
-    "dc_m2sgan_generate", "dc_m2sgan_debug_blocks", "dc_m2sgan_fold_conv",
+    "dc_m2sgan_generate", "dc_m2sgan_debug_blocks", "dc_m2sgan_fold_conv", "dc_m2sgan_set_decoder",
+    "dc_bilstm_create", "dc_bilstm_destroy", "dc_bilstm_set_param", "dc_bilstm_finalize", "dc_bilstm_input_size", "dc_bilstm_decode",
+    "dc_bilstm_hidden", "dc_bilstm_pass_clips",
     "dc_rhythm_create", "dc_rhythm_destroy", "dc_rhythm_psd", "dc_rhythm_contour",
     "dc_discriminator_create", "dc_discriminator_destroy", "dc_discriminator_set_param", "dc_discriminator_finalize",
     "dc_discriminator_features", "dc_discriminator_score",
@@ -58,7 +60,7 @@ class DcError(RuntimeError):
 
 
 SOURCES = ("dc_kernels.hip", "dc_api.hip", "dc_music.hip", "dc_layer16.hip", "dc_stgcn.hip", "dc_m2snet.hip", "dc_loss.hip", "dc_m2sgan.hip",
-           "dc_rhythm.hip")
+           "dc_rhythm.hip", "dc_bilstm.hip")
 HEADERS = ("dc_common.h", "dc_dev.h", "dc_form.h", "dc_handle.h", "dc_launch.h", "dc_mfma_f32.h", "dc_music.h", "dc_pack.h")
 EXTRA_FLAGS = {}      # per-source compiler flags
 
@@ -196,6 +198,18 @@ def lib():
     L.dc_m2sgan_generate.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     L.dc_m2sgan_debug_blocks.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     L.dc_m2sgan_fold_conv.argtypes = [fp] * 7 + [C.c_int32] * 3 + [fp, fp]
+    L.dc_m2sgan_set_decoder.argtypes = [C.c_void_p, C.c_int32]
+    L.dc_bilstm_create.argtypes = [C.c_int32, C.POINTER(C.c_void_p)]
+    L.dc_bilstm_destroy.argtypes = [C.c_void_p]
+    L.dc_bilstm_destroy.restype = None
+    L.dc_bilstm_set_param.argtypes = [C.c_void_p, C.c_char_p, fp, C.c_int64]
+    L.dc_bilstm_finalize.argtypes = [C.c_void_p]
+    L.dc_bilstm_input_size.argtypes = [C.c_void_p]
+    L.dc_bilstm_input_size.restype = C.c_int32
+    L.dc_bilstm_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    L.dc_bilstm_hidden.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    L.dc_bilstm_pass_clips.argtypes = [C.c_int32, C.c_int32]
+    L.dc_bilstm_pass_clips.restype = C.c_int32
     L.dc_rhythm_create.argtypes = [C.c_int32, C.POINTER(C.c_void_p)]
     L.dc_rhythm_destroy.argtypes = [C.c_void_p]
     L.dc_rhythm_destroy.restype = None
@@ -861,17 +875,27 @@ class NativeM2SNet(_NativeHandle):
 # the M2S-GAN generator (the baseline of the evaluation table)
 # ---------------------------------------------------------------------------------------
 class NativeM2SGAN(_NativeHandle):
-    """Owns one dc_m2sgan.  Shapes the library refuses (T <= 128, T != 30 Ln, T != (Tm-1)//3+1) raise ValueError before the call."""
+    """Owns one dc_m2sgan.  Shapes the library refuses (T <= 128, T != 30 Ln, T != (Tm-1)//3+1) raise ValueError before the call.
+    `decoder`: "tcn" (the reference's default), or "none" for a features-only generator whose poses come from a NativeBiLSTM."""
     _prefix = "dc_m2sgan"
+    DECODERS = {"tcn": 0, "none": 1}      # DC_M2SGAN_DECODER_*
+
+    def __init__(self, device=0, decoder="tcn"):
+        if decoder not in self.DECODERS:
+            raise ValueError(f"decoder must be one of {sorted(self.DECODERS)}, got {decoder!r}")
+        super().__init__(device)
+        self.decoder = decoder
+        if decoder != "tcn":
+            _check(lib().dc_m2sgan_set_decoder(self._h, self.DECODERS[decoder]))
 
     @staticmethod
-    def check_frames(T, Tm=None, Ln=None):
+    def check_frames(T, Tm=None, Ln=None, decoder="tcn"):
         """The library's shape rules (dc_ddim.h) as ValueErrors."""
         if Tm is not None and (Tm < 4 or T != (Tm - 1) // 3 + 1):
             raise ValueError(f"{Tm} mel frames make {(Tm - 1) // 3 + 1 if Tm >= 4 else 0} frames, not {T} (and at least 4 are needed)")
         if Ln is not None and T != 30 * Ln:
             raise ValueError(f"a latent of {Ln} steps makes {30 * Ln} frames, the music has {T}")
-        if T <= 128:
+        if T <= 128 and decoder == "tcn":
             raise ValueError(f"{T} frames: the generator's last temporal block reflects 128 frames and needs T > 128 (T >= 150)")
 
     def _inputs(self, mel, noise):
@@ -881,7 +905,7 @@ class NativeM2SGAN(_NativeHandle):
         B, Tm, Ln = int(mel.shape[0]), int(mel.shape[1]), int(noise.shape[1])
         self._ok(noise, (B, Ln, 8))
         T = (Tm - 1) // 3 + 1 if Tm >= 4 else 0
-        self.check_frames(T, Tm, Ln)
+        self.check_frames(T, Tm, Ln, self.decoder)
         return B, Tm, Ln, T
 
     def features(self, mel, noise):
@@ -896,6 +920,8 @@ class NativeM2SGAN(_NativeHandle):
     def generate(self, mel, noise):
         """mel fp32 [B, Tm, 128], noise fp32 [B, Ln, 8] on the device -> poses fp32 [B, T, 26]."""
         import torch
+        if self.decoder != "tcn":
+            raise ValueError("this generator was built without a decoder (decoder='none'): it computes features only")
         B, Tm, Ln, T = self._inputs(mel, noise)
         out = torch.empty((B, T, 26), dtype=torch.float32, device=mel.device)
         with torch.cuda.device(mel.device):
@@ -909,6 +935,8 @@ class NativeM2SGAN(_NativeHandle):
         self._ok(feat)
         assert feat.dim() == 3 and feat.shape[2] == 128, tuple(feat.shape)
         B, T = int(feat.shape[0]), int(feat.shape[1])
+        if self.decoder != "tcn":
+            raise ValueError("this generator was built without a decoder (decoder='none'): it computes features only")
         self.check_frames(T)
         out = torch.empty((B, T, 26 if n_blocks is None else 64), dtype=torch.float32, device=feat.device)
         with torch.cuda.device(feat.device):
@@ -917,6 +945,46 @@ class NativeM2SGAN(_NativeHandle):
             else:
                 _check(lib().dc_m2sgan_debug_blocks(self._h, feat.data_ptr(), B, T, int(n_blocks), out.data_ptr(), self._stream()))
         return out
+
+
+# ---------------------------------------------------------------------------------------
+# the BiLSTM pose decoder (the CNN-LSTM baselines of the evaluation table)
+# ---------------------------------------------------------------------------------------
+def bilstm_pass_clips(B, T):
+    """dc_bilstm_pass_clips: clips per pass of the BiLSTM decoder, min(B, 128, 2^28 // (1536 T)) and at least 1."""
+    return int(lib().dc_bilstm_pass_clips(int(B), int(T)))
+
+
+class NativeBiLSTM(_NativeHandle):
+    """Owns one dc_bilstm."""
+    _prefix = "dc_bilstm"
+
+    @property
+    def input_size(self):
+        return int(lib().dc_bilstm_input_size(self._h))
+
+    def _run(self, feat, layers):
+        import torch
+        self._ok(feat)
+        assert feat.dim() == 3, tuple(feat.shape)
+        B, T, In = (int(n) for n in feat.shape)
+        if In != self.input_size:
+            raise ValueError(f"features of {In} values per frame, the decoder was loaded for {self.input_size}")
+        out = torch.empty((B, T, 26 if layers is None else 256), dtype=torch.float32, device=feat.device)
+        with torch.cuda.device(feat.device):
+            if layers is None:
+                _check(lib().dc_bilstm_decode(self._h, feat.data_ptr(), B, T, out.data_ptr(), self._stream()))
+            else:
+                _check(lib().dc_bilstm_hidden(self._h, feat.data_ptr(), B, T, int(layers), out.data_ptr(), self._stream()))
+        return out
+
+    def decode(self, feat):
+        """features fp32 [B, T, In] on the device -> poses fp32 [B, T, 26]."""
+        return self._run(feat, None)
+
+    def hidden(self, feat, layers=2):
+        """Test hook: the LSTM's output fp32 [B, T, 256] after `layers` (1 or 2) layers."""
+        return self._run(feat, layers)
 
 
 # ---------------------------------------------------------------------------------------

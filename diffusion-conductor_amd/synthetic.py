@@ -340,6 +340,39 @@ def synthetic_m2sgan_state_dict(seed: int = 0):
     return out
 
 
+# gain of the seeded BiLSTM decoder over torch's default ranges: U(+-1 / sqrt(128)) for the LSTM, U(+-1 / sqrt(fan_in)) for a Linear of
+# the head (see synthetic_bilstm_state_dict)
+BILSTM_GAIN = 3.0
+BILSTM_HH_GAIN = 1.5      # on top of it for weight_hh: how far along a clip a frame is felt
+
+
+def synthetic_bilstm_state_dict(seed: int = 0, input_size: int = 128):
+    """name -> np.ndarray for every state_dict entry of PoseDecoderBiLSTM(input_size, 26) (generator.bilstm_shapes), in the reference
+    module's order.  Every entry is drawn from torch's default range - U(-1, 1) / sqrt(128) for the LSTM of 128 hidden units,
+    U(-1, 1) / sqrt(fan_in) for a Linear of the head - times BILSTM_GAIN, the recurrent weights times BILSTM_HH_GAIN more (at 1 the far end of a 30-frame clip moves a pose by
+    3e-4, at 2 by 0.2 - the recurrence stops contracting): at the default range the gates stay in their linear part and the poses near 0.5; at this one (tools/make_golden_bilstm.py asserts it)
+    every gate has pre-activations of both signs, the poses span more than [0.2, 0.8] and a frame's pose depends on the far end of
+    the clip in both directions."""
+    from .generator import bilstm_shapes
+    shapes = bilstm_shapes(input_size)
+    out = OrderedDict()
+    for name, shape in shapes.items():
+        g = _rng(seed, f"bilstm{input_size}:" + name)
+        fan_in = 128 if name.startswith("LSTM.") else shapes[name.rsplit(".", 1)[0] + ".weight"][1]
+        gain = BILSTM_GAIN * (BILSTM_HH_GAIN if "weight_hh" in name else 1.0)
+        out[name] = np.ascontiguousarray(g.uniform(-1.0, 1.0, shape) * (gain / np.sqrt(fan_in)), dtype=np.float32)
+    return out
+
+
+def synthetic_m2sgan_bilstm_state_dict(seed: int = 0):
+    """The CNN-LSTM baseline's Generator (generator.m2sgan_bilstm_shapes: `self.tcn = PoseDecoderBiLSTM(128, 26)`): the encoder and
+    noise branch entries of synthetic_m2sgan_state_dict(seed) - the same tensors, so its features equal the TCN generator's - and
+    synthetic_bilstm_state_dict(seed, 128) under `tcn.`, in the reference module's order."""
+    from .generator import m2sgan_bilstm_shapes
+    gan, dec = synthetic_m2sgan_state_dict(seed), synthetic_bilstm_state_dict(seed, 128)
+    return OrderedDict((k, dec[k[4:]] if k.startswith("tcn.") else gan[k]) for k in m2sgan_bilstm_shapes())
+
+
 # gains of the seeded critic over PyTorch's default initialiser bound, per convolution stage and per fc layer (see
 # synthetic_discriminator_state_dict)
 DISCRIMINATOR_CONV_GAIN = (6.0, 2.0, 2.0)

@@ -555,6 +555,49 @@ DC_EXPORT int dc_m2sgan_fold_conv(const float* weight_g, const float* weight_v, 
                                   const float* bn_bias, const float* bn_mean, const float* bn_var, int32_t cout, int32_t cin, int32_t k,
                                   float* h_w, float* h_b);
 
+/* Replaces the choice of `self.tcn` in Generator.__init__ (Generator.py:57-58: PoseDecoderTCN, or PoseDecoderBiLSTM for the
+ * CNN-LSTM baseline).  Call it before dc_m2sgan_finalize; a handle that never calls it decodes with the TCN, as before.
+ * DC_M2SGAN_DECODER_NONE makes a features-only generator whose pose decoder is a dc_bilstm: set_param and finalize then take the
+ * "music_encoder.*", "noise_convTranspose.*" and "noise_BN.*" entries only and refuse every "tcn.*" entry (DC_ERR_PARAM);
+ * dc_m2sgan_features works for every T = 30 Ln (no TemporalBlock bounds it from below); dc_m2sgan_decode, _generate and
+ * _debug_blocks return DC_ERR_INVALID.  Another value -> DC_ERR_INVALID. */
+enum { DC_M2SGAN_DECODER_TCN = 0, DC_M2SGAN_DECODER_NONE = 1 };
+DC_EXPORT int dc_m2sgan_set_decoder(dc_m2sgan* g, int32_t decoder);
+
+/* ---- BiLSTM pose decoder: the decoder of the CNN-LSTM baselines ---------------------------------------------------------------
+ * Replaces constructing PoseDecoderBiLSTM(In, 26) (Contrastive_Stage/models/Generator.py:7-25: nn.LSTM(In, 128, num_layers = 2,
+ * bidirectional, batch_first, dropout 0.5 - the identity in eval mode) and the head `out`) on the device `device`: the `tcn` of
+ * the CNN-LSTM Generator (:58, In = 128) and the `lstm` of Generator_CVPR_LSTM (:89-100, In = 20).  Implemented in
+ * csrc/dc_bilstm.hip; none of it is on the sampling path.  dc_bilstm_destroy frees on the handle's device and puts the caller's
+ * current device back. */
+typedef struct dc_bilstm dc_bilstm;
+DC_EXPORT int dc_bilstm_create(int32_t device, dc_bilstm** out);
+DC_EXPORT void dc_bilstm_destroy(dc_bilstm* m);
+
+/* Replaces PoseDecoderBiLSTM.load_state_dict: one call per entry with its key and contiguous fp32 data.  The keys are exactly the
+ * module's: "LSTM.{weight_ih,weight_hh,bias_ih,bias_hh}_l{0,1}" and the same with "_reverse" (Generator.py:20-21; gate rows in
+ * torch's order i, f, g, o) and "out.{0,2,4}.{weight,bias}" (:22-25).  "LSTM.weight_ih_l0[_reverse]" is [512, In] for any
+ * 1 <= In <= 128.  Unknown key or wrong numel -> DC_ERR_PARAM. */
+DC_EXPORT int dc_bilstm_set_param(dc_bilstm* m, const char* name, const float* h_data, int64_t numel);
+
+/* Replaces .eval() + .to(device): In = numel(LSTM.weight_ih_l0) / 512; sums b_ih + b_hh (fp64, rounded once), packs and uploads.
+ * A missing entry, or one whose size does not fit In -> DC_ERR_PARAM.  Synchronous.  The entry points below return DC_ERR_INVALID
+ * before it. */
+DC_EXPORT int dc_bilstm_finalize(dc_bilstm* m);
+/* In of a finalized handle (0 before). */
+DC_EXPORT int32_t dc_bilstm_input_size(const dc_bilstm* m);
+
+/* Replaces PoseDecoderBiLSTM.forward (Generator.py:27-31): d_feat fp32 [B, T, In] -> d_pose fp32 [B, T, 26], any B >= 1 and
+ * T >= 1 (else DC_ERR_INVALID, before anything is enqueued).  Everything is enqueued on `stream`; the only host wait is a
+ * workspace that has to grow.  Clips are processed in passes of dc_bilstm_pass_clips(B, T); a clip's poses do not depend on the
+ * batch it is in.  A handle serves one stream at a time, as a dc_m2sgan does; not thread-safe. */
+DC_EXPORT int dc_bilstm_decode(dc_bilstm* m, const float* d_feat, int32_t B, int32_t T, float* d_pose, void* stream);
+/* Test hook: the output of self.LSTM (Generator.py:28) cut after `layers` (1 or 2) layers, cat(forward, reverse) -> d_h fp32 [B, T, 256]. */
+DC_EXPORT int dc_bilstm_hidden(dc_bilstm* m, const float* d_feat, int32_t B, int32_t T, int32_t layers, float* d_h, void* stream);
+/* Host only: clips per pass = min(B, 128, floor(2^28 / (1536 T))), at least 1 - a pass's workspace of 1536 floats per frame (the
+ * gate pre-activations of both directions and the two layers' outputs) stays within 1 GiB.  0 for B < 1 or T < 1. */
+DC_EXPORT int32_t dc_bilstm_pass_clips(int32_t B, int32_t T);
+
 /* ---- Realism and rhythm: the Welch spectrum, the speed contour, the standard deviation and the M2S-GAN critic -------------------
  * The four scores of Contrastive_Stage/M2SGAN_eval.py:100-133 that look at how the motion moves.  Implemented in
  * csrc/dc_rhythm.hip; none of it is on the sampling path.  All arithmetic is fp32, every output is a fixed-order sum without
