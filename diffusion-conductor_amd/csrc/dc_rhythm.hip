@@ -22,8 +22,18 @@
 //                  conv frames of one clip x 64 channels, + bias, ReLU, and MaxPool1d(5, stride S) in the epilogue: lane S q takes the
 //                  maximum of lanes S q .. S q + 4 and writes pooled frame p0 + q; a wave advances by (27 / S + 1) pooled frames.
 //   k_disc_head    fc 64 -> 32 -> 32 -> 1 per pooled frame, chained in registers (as k_gan_head); k_disc_mean: mean over the frames.
+//
+// Beat consistency (BC) and Beat Align from supplied music beats:
+//   motion_peak_onehot     Diffusion_Stage/tools/eval_new_metrics.py:285-309 = Contrastive_Stage/M2SGAN_eval.py:310-332: the summed joint
+//                          speed and scipy.signal.argrelextrema(envelope, np.less, order=10) - strict minima over +-10 frames.
+//   alignment_score        eval_new_metrics.py:253-275 = M2SGAN_eval.py:345-367: per music beat a Gaussian of the distance to the nearest
+//                          motion beat.  (get_music_beat, librosa's tracker, is a function of the mel alone: its one-hot is an input.)
+//   k_beat_motion  one workgroup per clip: the envelope with numpy's float32 bits (envelope_frame), a barrier, the strict minima.
+//   k_beat_scores  one workgroup per clip: both one-hots compacted into sorted index lists (wave ballots, a running prefix), a binary
+//                  search per beat, expf, fixed-order sums.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -43,6 +53,8 @@ constexpr int R_POSE = 26;                 // pose channels
 constexpr int C_WIN = 60, C_HOP = 30;      // AvgPool1d(kernel_size=60, stride=30) of the strength contour
 constexpr int C_WPB = 7;                   // windows per workgroup: 30 * 6 + 60 = 240 frames
 constexpr int SD_LANES = 32;               // time lanes per channel of k_sd
+constexpr int B_THREADS = 256;             // threads of the beat kernels' one workgroup per clip
+constexpr int B_MAX_ORDER = 64;            // largest `order` of dc_rhythm_motion_beats
 
 // x [clips][T][26] -> part [clips][nw][32]: per wave and bin, the sum over the wave's columns of the column's periodogram
 __global__ __launch_bounds__(64 * R_WAVES) void k_psd_cols(const float* __restrict__ x, const float2* __restrict__ tab, float* __restrict__ part,
@@ -144,6 +156,150 @@ __global__ __launch_bounds__(R_POSE * SD_LANES) void k_sd(const float* __restric
         float m = 0.f;
         for (int i = 0; i < R_POSE; ++i) m += stat[i];
         sd[blockIdx.x] = m / (float)R_POSE;
+    }
+}
+
+// ---- beat consistency: the motion's beats and their alignment with supplied music beats ---------------------------------------------
+struct BeatLengths {
+    int len[R_CHUNK];                    // frames of each clip of a pass
+};
+
+// The summed joint speed of one frame with numpy's float32 bits: prev, cur = the 13 (x, y) pairs of frames t - 1 and t.  Every
+// operation is rounded on its own (the pragma: hipcc's default would fuse dx dx into the addition), sqrtf is correctly rounded
+// (hipcc's default for fp32), and the 13 norms are added in the order of numpy's pairwise reduction over 13 contiguous float32.
+DEV float envelope_frame(const float2* __restrict__ prev, const float2* __restrict__ cur) {
+#pragma clang fp contract(off)
+    float n[R_POSE / 2];
+#pragma unroll
+    for (int j = 0; j < R_POSE / 2; ++j) {
+        const float2 a = prev[j], b = cur[j];
+        const float dx = b.x - a.x, dy = b.y - a.y;
+        n[j] = sqrtf(dx * dx + dy * dy);
+    }
+    float s = ((n[0] + n[1]) + (n[2] + n[3])) + ((n[4] + n[5]) + (n[6] + n[7]));
+#pragma unroll
+    for (int j = 8; j < R_POSE / 2; ++j) s += n[j];
+    return s;
+}
+
+// x [clips][T][26] -> env [clips][T], beats [clips][T]; one workgroup per clip.  The envelope goes through global memory (the
+// caller's array or the workspace), so T is not bounded by LDS; the barrier between the two passes orders this workgroup's stores
+// before its own loads.
+__global__ __launch_bounds__(B_THREADS) void k_beat_motion(const float* __restrict__ x, float* env, uint8_t* __restrict__ beats, int T, int order,
+                                                          BeatLengths bl) {
+    const int L = bl.len[blockIdx.x];
+    const float* xb = x + (size_t)blockIdx.x * T * R_POSE;
+    float* e = env + (size_t)blockIdx.x * T;
+    uint8_t* o = beats + (size_t)blockIdx.x * T;
+    for (int t = threadIdx.x; t < T; t += B_THREADS) {
+        float v = 0.f;
+        if (t >= 1 && t < L)
+            v = envelope_frame(reinterpret_cast<const float2*>(xb + (size_t)(t - 1) * R_POSE), reinterpret_cast<const float2*>(xb + (size_t)t * R_POSE));
+        e[t] = v;
+    }
+    __syncthreads();
+    for (int t = threadIdx.x; t < T; t += B_THREADS) {
+        bool beat = t < L;
+        if (beat) {
+            const float v = e[t];
+            for (int s = 1; s <= order && beat; ++s) {      // argrelextrema's mode='clip': the index is clamped to the clip
+                const int lo = t - s < 0 ? 0 : t - s, hi = t + s > L - 1 ? L - 1 : t + s;
+                beat = v < e[lo] && v < e[hi];
+            }
+        }
+        o[t] = beat ? 1 : 0;
+    }
+}
+
+// idx[0 .. n): the positions of the nonzero bytes of v[0 .. N) in increasing order, n returned to every thread.  Tiles of B_THREADS
+// positions: a ballot per wave, the waves' counts through `cnt` (LDS, one int per wave), a running base.  Ends with a barrier.
+DEV int compact_beats(const uint8_t* __restrict__ v, int N, int* idx, int* cnt) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int base = 0;
+    for (int i0 = 0; i0 < N; i0 += B_THREADS) {      // (the trip count is the same for every thread: barriers inside)
+        const int i = i0 + (int)threadIdx.x;
+        const bool on = i < N && v[i] != 0;
+        const unsigned long long m = __ballot(on);
+        if (lane == 0) cnt[w] = __popcll(m);
+        __syncthreads();
+        int before = 0, total = 0;
+#pragma unroll
+        for (int k = 0; k < B_THREADS / 64; ++k) {
+            const int c = cnt[k];
+            before += k < w ? c : 0;
+            total += c;
+        }
+        if (on) idx[base + before + __popcll(m & ((1ull << lane) - 1ull))] = i;
+        base += total;
+        __syncthreads();                 // (cnt is rewritten by the next tile; the last one orders idx before its readers)
+    }
+    return base;
+}
+
+// exp(-d^2 / (2 sigma^2)) of the distance from position q to the nearest of the n >= 1 sorted positions scale * list[j], all in music
+// frames (integers); d = (float)distance / (float)music_stride is the only rounding in front of the square.
+DEV float beat_term(long long q, const int* list, int n, long long scale, float stride, float two_sigma2) {
+    int lo = 0, hi = n;                  // -> the first j with scale * list[j] >= q
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (scale * list[mid] < q) lo = mid + 1;
+        else hi = mid;
+    }
+    long long best = lo < n ? scale * list[lo] - q : q - scale * list[n - 1];
+    if (lo > 0) {
+        const long long below = q - scale * list[lo - 1];
+        best = below < best ? below : best;
+    }
+    const float d = (float)best / stride;
+    return expf(-(d * d) / two_sigma2);
+}
+
+// The sum of every thread's v in a fixed order: partial j + partial j + 128, then + 64, ... + 1 (a binary tree over the thread index).
+DEV float block_sum(float v, float* buf) {
+    buf[threadIdx.x] = v;
+    __syncthreads();
+#pragma unroll
+    for (int off = B_THREADS / 2; off >= 1; off >>= 1) {
+        if ((int)threadIdx.x < off) buf[threadIdx.x] += buf[threadIdx.x + off];
+        __syncthreads();
+    }
+    const float s = buf[0];
+    __syncthreads();                     // (buf is reused by the next sum)
+    return s;
+}
+
+// mot [clips][T], mus [clips][Lm] one-hots -> scores [clips][2] (BC, Beat Align), counts [clips][2] (music, motion); one workgroup
+// per clip, lists [clips][T + Lm] ints in the workspace.
+// Order of the sums (it depends on the positions alone, so on (Lm, T) at most): thread j of 256 adds the terms of the positions
+// j, j + 256, j + 512, ... in increasing order - a position without a beat adds nothing -, then block_sum's tree over the 256
+// partial sums.  Zeros behind a clip's last music beat therefore change nothing, bit for bit.
+__global__ __launch_bounds__(B_THREADS) void k_beat_scores(const uint8_t* __restrict__ mot, const uint8_t* __restrict__ mus, int* lists, int T, int Lm,
+                                                          int stride, float two_sigma2, float* __restrict__ scores, int* __restrict__ counts) {
+    __shared__ int cnt[B_THREADS / 64];
+    __shared__ float buf[B_THREADS];
+    const uint8_t* mo = mot + (size_t)blockIdx.x * T;
+    const uint8_t* mu = mus + (size_t)blockIdx.x * Lm;
+    int* mot_idx = lists + (size_t)blockIdx.x * ((size_t)T + Lm);
+    int* mus_idx = mot_idx + T;
+    const int n_mot = compact_beats(mo, T, mot_idx, cnt);
+    const int n_mus = compact_beats(mu, Lm, mus_idx, cnt);
+    const float fs = (float)stride;
+    float bc = 0.f, ba = 0.f;
+    if (n_mot > 0 && n_mus > 0) {        // (block-uniform)
+        for (int i = threadIdx.x; i < Lm; i += B_THREADS)
+            if (mu[i]) bc += beat_term(i, mot_idx, n_mot, stride, fs, two_sigma2);
+        for (int t = threadIdx.x; t < T; t += B_THREADS)
+            if (mo[t]) ba += beat_term((long long)stride * t, mus_idx, n_mus, 1, fs, two_sigma2);
+    }
+    bc = block_sum(bc, buf);
+    ba = block_sum(ba, buf);
+    if (threadIdx.x == 0) {
+        scores[2 * blockIdx.x] = n_mot == 0 ? 0.f : bc / (float)n_mus;            // 0 / 0 = NaN without music beats, as the reference
+        scores[2 * blockIdx.x + 1] = n_mus == 0 ? 0.f : ba / (float)n_mot;
+        if (counts) {
+            counts[2 * blockIdx.x] = n_mus;
+            counts[2 * blockIdx.x + 1] = n_mot;
+        }
     }
 }
 
@@ -395,6 +551,54 @@ int dc_rhythm_contour(dc_rhythm* h, const float* d_motion, int32_t B, int32_t T,
         const float* x = d_motion + (size_t)b0 * T * R_POSE;
         if (d_contour) k_contour<<<dim3((unsigned)((W + C_WPB - 1) / C_WPB), nb), 256, 0, st>>>(x, d_contour + (size_t)b0 * W, T, W);
         if (d_sd) k_sd<<<nb, R_POSE * SD_LANES, 0, st>>>(x, d_sd + b0, T);
+        DC_HIP_TRY(hipGetLastError());
+        return DC_OK;
+    });
+}
+
+int dc_rhythm_motion_beats(dc_rhythm* h, const float* d_motion, const int32_t* h_length, int32_t B, int32_t T, int32_t order, float* d_envelope,
+                           uint8_t* d_beats, void* stream) {
+    if (!h || !d_motion || !d_beats) return dc_set_error(DC_ERR_INVALID, "dc_rhythm_motion_beats: NULL argument");
+    if (const int rc = rhythm_check("dc_rhythm_motion_beats", B, T, 1, "T must be >= 1")) return rc;
+    if (order < 1 || order > B_MAX_ORDER)
+        return dc_set_error(DC_ERR_INVALID, ("dc_rhythm_motion_beats: order " + std::to_string(order) + " is outside 1 .. 64").c_str());
+    if (h_length)
+        for (int32_t b = 0; b < B; ++b)
+            if (h_length[b] < 1 || h_length[b] > T)
+                return dc_set_error(DC_ERR_INVALID, ("dc_rhythm_motion_beats: length " + std::to_string(h_length[b]) + " of clip " + std::to_string(b) +
+                                                     " is outside [1, " + std::to_string(T) + "]").c_str());
+    if (reinterpret_cast<uintptr_t>(d_motion) % 8) return dc_set_error(DC_ERR_INVALID, "dc_rhythm_motion_beats: the motion must be 8-byte aligned");
+    DC_HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    const int chunk = B < R_CHUNK ? B : R_CHUNK;
+    if (!d_envelope)
+        if (const int rc = h->ws.reserve((size_t)chunk * T, st)) return rc;
+    return dc_chunks(B, chunk, [&](int b0, int nb) -> int {
+        BeatLengths bl;
+        for (int i = 0; i < R_CHUNK; ++i) bl.len[i] = i < nb ? (h_length ? h_length[b0 + i] : T) : 0;
+        float* env = d_envelope ? d_envelope + (size_t)b0 * T : h->ws.p;
+        k_beat_motion<<<nb, B_THREADS, 0, st>>>(d_motion + (size_t)b0 * T * R_POSE, env, d_beats + (size_t)b0 * T, T, order, bl);
+        DC_HIP_TRY(hipGetLastError());
+        return DC_OK;
+    });
+}
+
+int dc_rhythm_beat_scores(dc_rhythm* h, const uint8_t* d_motion_beats, int32_t B, int32_t T, const uint8_t* d_music_beats, int32_t Lm,
+                          int32_t music_stride, float sigma, float* d_scores, int32_t* d_counts, void* stream) {
+    if (!h || !d_motion_beats || !d_music_beats || !d_scores) return dc_set_error(DC_ERR_INVALID, "dc_rhythm_beat_scores: NULL argument");
+    if (const int rc = rhythm_check("dc_rhythm_beat_scores", B, T, 1, "T must be >= 1")) return rc;
+    if (Lm < 1) return dc_set_error(DC_ERR_INVALID, "dc_rhythm_beat_scores: Lm must be >= 1");
+    if (music_stride < 1) return dc_set_error(DC_ERR_INVALID, "dc_rhythm_beat_scores: music_stride must be >= 1");
+    if (!std::isfinite(sigma) || !(sigma > 0.f)) return dc_set_error(DC_ERR_INVALID, "dc_rhythm_beat_scores: sigma must be finite and > 0");
+    DC_HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    const int chunk = B < R_CHUNK ? B : R_CHUNK;
+    const size_t per_clip = (size_t)T + (size_t)Lm;      // the two index lists (int32, in the float workspace)
+    if (const int rc = h->ws.reserve((size_t)chunk * per_clip, st)) return rc;
+    const float two_sigma2 = 2.f * sigma * sigma;
+    return dc_chunks(B, chunk, [&](int b0, int nb) -> int {
+        k_beat_scores<<<nb, B_THREADS, 0, st>>>(d_motion_beats + (size_t)b0 * T, d_music_beats + (size_t)b0 * Lm, reinterpret_cast<int*>(h->ws.p), T, Lm,
+                                               music_stride, two_sigma2, d_scores + (size_t)b0 * 2, d_counts ? d_counts + (size_t)b0 * 2 : nullptr);
         DC_HIP_TRY(hipGetLastError());
         return DC_OK;
     });

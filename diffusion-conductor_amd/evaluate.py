@@ -177,6 +177,17 @@ def _sync_predictions(m2snet, mel, pred, gts, dim_pose):
     return real, gen, mis
 
 
+def _ground_truth(pred, gts, dim_pose, ids, what):
+    """The batch's ground truth [B, T, dim_pose] fp32 on the poses' device (uploaded on the current stream); every clip must have the
+    poses' T frames (ValueError naming `what` scores otherwise)."""
+    T = pred.shape[1]
+    bad = [(cid, np.shape(g)) for cid, g in zip(ids, gts) if int(np.prod(np.shape(g))) != T * dim_pose]
+    if bad:
+        raise ValueError(f"the {what} scores compare clips of {T} frames, but these ground truths differ: {bad[:4]}")
+    gt = torch.from_numpy(np.ascontiguousarray(np.stack([np.reshape(g, (T, dim_pose)) for g in gts]), np.float32))
+    return gt.pin_memory().to(pred.device, non_blocking=True) if pred.is_cuda else gt
+
+
 def _rhythm_columns(rhythm, discriminator, T):
     """Floats per clip of _rhythm_arrays' rows: [psd generated 32 | psd real 32 | contour generated W | contour real W | sd generated |
     sd real] with `rhythm`, then [D(generated) | D(real)] with `discriminator`."""
@@ -188,12 +199,7 @@ def _rhythm_arrays(rhythm, discriminator, pred, gts, dim_pose, ids):
     """One row [B, _rhythm_columns] per clip of what RDE, SCE, SD and the W-distance are made of, for the sampled poses and the ground
     truth, enqueued on the current stream right behind the sampling (the ground truth is uploaded to the poses' device first)."""
     B, T = pred.shape[0], pred.shape[1]
-    bad = [(cid, np.shape(g)) for cid, g in zip(ids, gts) if int(np.prod(np.shape(g))) != T * dim_pose]
-    if bad:
-        raise ValueError(f"the rhythm scores compare clips of {T} frames, but these ground truths differ: {bad[:4]}")
-    gt = torch.from_numpy(np.ascontiguousarray(np.stack([np.reshape(g, (T, dim_pose)) for g in gts]), np.float32))
-    if pred.is_cuda:
-        gt = gt.pin_memory().to(pred.device, non_blocking=True)
+    gt = _ground_truth(pred, gts, dim_pose, ids, "rhythm")
     gen = pred.reshape(B, T, dim_pose).contiguous()
     cols = []
     if rhythm is not None:
@@ -220,6 +226,55 @@ def _rhythm_scores(rows, ids, T, rhythm, discriminator):
         at += 2
     if discriminator is not None:
         out["w_distance"] = w_distance(rows[:, at + 1], rows[:, at])
+    return out
+
+
+BEAT_COLUMNS = 8      # floats per clip of _beat_rows: [BC, Beat Align, music beats, motion beats] of the sampled poses, then of the ground truth
+
+
+def _check_music_beats(music_beats, ids):
+    """{clip id: 1-D one-hot} covers `ids`, every array 1-D with at least one beat (ValueError naming the clips otherwise) -> the
+    arrays as uint8, by clip id."""
+    missing = [cid for cid in ids if cid not in music_beats]
+    if missing:
+        raise ValueError(f"music_beats has no entry for {len(missing)} clip(s): {missing[:8]}{' ...' if len(missing) > 8 else ''}")
+    out = {cid: np.asarray(music_beats[cid]) for cid in ids}
+    bad = [(cid, a.shape) for cid, a in out.items() if a.ndim != 1 or a.size < 1]
+    if bad:
+        raise ValueError(f"music_beats holds one 1-D one-hot per clip, but these differ: {bad[:4]}")
+    out = {cid: (a != 0).astype(np.uint8) for cid, a in out.items()}
+    silent = [cid for cid, a in out.items() if not a.any()]
+    if silent:
+        raise ValueError(f"no music beat in {len(silent)} clip(s), beat consistency is undefined there: {silent[:8]}{' ...' if len(silent) > 8 else ''}")
+    return out
+
+
+def _beat_rows(beat_rhythm, pred, gts, dim_pose, ids, music_beats, stride):
+    """One row [B, BEAT_COLUMNS] per clip of dc_rhythm_motion_beats + dc_rhythm_beat_scores on the sampled poses and on the ground
+    truth, enqueued on the current stream right behind the sampling.  The batch's music beats are padded with zeros to its longest
+    and uploaded with it (zeros behind a clip's last beat change nothing: csrc/dc_rhythm.hip, k_beat_scores)."""
+    B, T = pred.shape[0], pred.shape[1]
+    gt = _ground_truth(pred, gts, dim_pose, ids, "beat")
+    mus = np.zeros((B, max(music_beats[cid].size for cid in ids)), np.uint8)
+    for i, cid in enumerate(ids):
+        mus[i, :music_beats[cid].size] = music_beats[cid]
+    mus = torch.from_numpy(mus)
+    if pred.is_cuda:
+        mus = mus.pin_memory().to(pred.device, non_blocking=True)
+    cols = []
+    for x in (pred.reshape(B, T, dim_pose).contiguous(), gt):
+        scores, counts = beat_rhythm.beat_scores(beat_rhythm.motion_beats(x), mus, music_stride=stride, counts=True)
+        cols += [scores, counts.to(torch.float32)]           # (counts are at most a clip's frames: exact in fp32)
+    return torch.cat(cols, dim=1)
+
+
+def _beat_results(rows, ids):
+    """The result keys of the beat scores from every clip's row (_beat_rows), in clip order."""
+    from .metrics import beat_consistency
+    out = {}
+    for name, at in (("gen", 0), ("real", 4)):
+        out[f"bc_{name}"], out[f"bc_{name}_per_clip"] = beat_consistency(rows[:, at:at + 2], rows[:, at + 2:at + 4], ids)
+        out[f"beat_align_{name}"] = beat_consistency(rows[:, at:at + 2], rows[:, at + 2:at + 4], ids, column=1)[0]
     return out
 
 
@@ -293,7 +348,7 @@ class _Scorer:
 
 def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed=0, smooth=False, verbose=True, motion_encoder=None,
                      diversity_seed=0, m2snet=None, guidance_scale=None, steps=None, spacing="uniform", solver="ddim", rhythm=None,
-                     discriminator=None):
+                     discriminator=None, music_beats=None, beat_stride=1):
     """Samples every clip under `root` and returns {"per_clip": {id: mse}, "total_loss", "final_mse", "clips",
     "seconds", "frames_per_s"}.  Clip i (in sorted order) starts from noise seeded with (seed, i), so the result
     does not depend on batch_size or on the number of ranks.
@@ -323,6 +378,18 @@ def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed
     with the latents, with `smooth` these are the scores of the SMOOTHED poses.  Without the two arguments the result and the work
     done are exactly what they were before these scores existed.
 
+    `music_beats` ({clip id: 1-D one-hot, nonzero = a beat}: metrics.load_music_beats): beat consistency as well, the BC column of
+    the paper's table (eval_new_metrics.py:253-317) - from SUPPLIED music beats: the reference's get_music_beat is librosa's tracker
+    on the clip's mel, a property of the dataset (tools/music_beats_librosa.py).  Each batch's one-hots are padded with zeros to its
+    longest and uploaded with it; the motion's beats and their alignment (rhythm.MotionRhythm.motion_beats, .beat_scores) run on the
+    sampled poses and on the ground truth right behind the sampling, on the same stream (on `rhythm` when one is given, else on a
+    MotionRhythm of the poses' device), and the [B, 2] scores and counts come back with the other per-clip rows.  Adds "bc_gen",
+    "bc_real" (the means over the clips of "bc_gen_per_clip", "bc_real_per_clip", {id: value}), "beat_align_gen" and
+    "beat_align_real" (the other direction; nan when a clip has no motion beat).  `beat_stride`: 1 compares the index lists as they
+    are, as the reference does (90-fps mel frames against 30-fps motion frames; the paper's numbers); 3 puts both on one clock.  A
+    clip id without an entry, an entry that is not 1-D or has no beat: ValueError before anything is sampled.  With `smooth` the
+    scores are those of the SMOOTHED poses.  Without the argument the result and the work done are exactly what they were.
+
     `guidance_scale`: None, or the classifier-free guidance scale every batch is sampled with (generate_music_motion).
     `steps`, `spacing`, `solver`: every batch is sampled on `steps` of the schedule's timesteps (generate_music_motion; the defaults
     walk every timestep, as before).
@@ -349,6 +416,11 @@ def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed
     if discriminator is not None and T < 41:
         raise ValueError(f"clips of {T} frames: the critic needs at least 41 (one pooled frame behind its third stage)")
     rh_rows = None                       # pinned [clips, _rhythm_columns]: every clip's row, read after the last batch's event
+    bt_rows = beat_rhythm = None         # pinned [clips, BEAT_COLUMNS] likewise, and the MotionRhythm that fills it (music_beats only)
+    if music_beats is not None:
+        if int(beat_stride) < 1:
+            raise ValueError(f"beat_stride must be >= 1, got {beat_stride}")
+        music_beats = _check_music_beats(music_beats, ids)
     pf = _Prefetcher(root, ids, batch_size, mel_shape, noise=(seed, T, dim_pose))
     pf.start(0)
     scorer = _Scorer(dim_pose)
@@ -362,6 +434,8 @@ def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed
     slot_free = [None, None]             # event: the GPU has consumed the slot's pinned mel / noise buffers
     results = {}
     sync = {}                            # batch -> (real, generated, mismatched | None) predictions [B, T] on the device (m2snet only)
+    if music_beats is not None and hasattr(rhythm, "motion_beats") and hasattr(rhythm, "beat_scores"):
+        beat_rhythm = rhythm
     exchange_before = getattr(enc, "combine_exchange", None)
     ev_first = ev_last = None            # completion events of the first and the last batch: the GPU's own steady-state period
     n_after_first = 0
@@ -408,6 +482,14 @@ def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed
                     rh_rows = torch.empty((len(ids), _rhythm_columns(rhythm, discriminator, T)), dtype=torch.float32, pin_memory=pred.is_cuda)
                 rh_rows[k * batch_size:k * batch_size + pred.shape[0]].copy_(_rhythm_arrays(rhythm, discriminator, pred, gts, dim_pose, bid),
                                                                              non_blocking=True)
+            if music_beats is not None:
+                if beat_rhythm is None:
+                    from .rhythm import MotionRhythm
+                    beat_rhythm = MotionRhythm(pred.device)
+                if bt_rows is None:
+                    bt_rows = torch.empty((len(ids), BEAT_COLUMNS), dtype=torch.float32, pin_memory=pred.is_cuda)
+                bt_rows[k * batch_size:k * batch_size + pred.shape[0]].copy_(_beat_rows(beat_rhythm, pred, gts, dim_pose, bid, music_beats, int(beat_stride)),
+                                                                             non_blocking=True)
             ph.copy_(pred, non_blocking=True)
             ev = None
             if pred.is_cuda:
@@ -436,6 +518,8 @@ def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed
                     sync[k] = _sync_predictions(m2snet, mel, pred_d, gts, dim_pose)
                 if moves:
                     rh_rows[k * batch_size:k * batch_size + pred_d.shape[0]].copy_(_rhythm_arrays(rhythm, discriminator, pred_d, gts, dim_pose, bid))
+                if music_beats is not None:
+                    bt_rows[k * batch_size:k * batch_size + pred_d.shape[0]].copy_(_beat_rows(beat_rhythm, pred_d, gts, dim_pose, bid, music_beats, int(beat_stride)))
                 pred = pred_d.cpu().numpy()
                 results[k] = [(cid, mse_loss(gts[i], pred[i].reshape([pred[i].shape[0], dim_pose // 2, 2]))) for i, cid in enumerate(bid)]
                 if lats is not None:
@@ -492,6 +576,10 @@ def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed
             if "sd_gen" in out:
                 from .metrics import standard_deviation_percentage
                 print(f"sdp: {standard_deviation_percentage(out['sd_gen'], out['sd_real']):.2f}%")
+    if music_beats is not None:
+        out.update(_beat_results(bt_rows.numpy(), ids))
+        if verbose:
+            print("  ".join(f"{key}: {out[key]}" for key in ("bc_gen", "bc_real", "beat_align_gen", "beat_align_real")))
     return out
 
 
@@ -612,6 +700,15 @@ def _movement_scorers(args, dev):
     return rh, disc
 
 
+def _music_beats(args):
+    """{clip id: one-hot} of --beats for the clips main is about to evaluate | None."""
+    if not args.beats:
+        return None
+    from .metrics import load_music_beats
+    ids = list_clips(args.data_root)
+    return load_music_beats(args.beats, ids if args.limit is None else ids[:int(args.limit)])
+
+
 def _baseline_main(args, dev):
     """--baseline_generator: evaluate_dataset on the M2S-GAN generator (generator.GeneratorBaseline), one JSON line.  The loader picks
     the decoder - the TCN or the CNN-LSTM baseline's BiLSTM - from the checkpoint's keys."""
@@ -621,7 +718,8 @@ def _baseline_main(args, dev):
     menc, m2s = _evaluation_encoders(args, dev)
     rh, disc = _movement_scorers(args, dev)
     r = evaluate_dataset(GeneratorBaseline(gen), args.data_root, 26, args.batch_size, args.limit, args.seed, args.smooth, verbose=False,
-                         motion_encoder=menc, diversity_seed=args.diversity_seed, m2snet=m2s, rhythm=rh, discriminator=disc)
+                         motion_encoder=menc, diversity_seed=args.diversity_seed, m2snet=m2s, rhythm=rh, discriminator=disc,
+                         music_beats=_music_beats(args), beat_stride=args.beat_stride)
     print(json.dumps({"model": "m2sgan", **r}))
     return 0
 
@@ -664,6 +762,11 @@ def main(argv=None):
                                                                "line with \"model\": \"m2sgan\" (generator.py).  Either flavour loads: the "
                                                                "TCN decoder (tcn.TCN.* keys) or the CNN-LSTM baseline's BiLSTM decoder "
                                                                "(tcn.LSTM.* keys)")
+    ap.add_argument("--beats", default=None, help=".npz of music beats, one 1-D one-hot per clip id (tools/music_beats_librosa.py): also "
+                                                  "beat consistency and Beat Align of the sampled and the real motion (rhythm.py, metrics.py)")
+    ap.add_argument("--beat_stride", type=int, default=1, help="music frames per motion frame for --beats: 1 compares the beat indices as "
+                                                               "they are, as the reference does; 3 puts 90-fps mel frames and 30-fps poses "
+                                                               "on one clock")
     args = ap.parse_args(argv)
     if args.baseline_generator:
         clash = [f for f, on in (("--model", args.model), ("--val_loss", args.val_loss), ("--guidance_scale", args.guidance_scale is not None),
@@ -675,6 +778,13 @@ def main(argv=None):
     if args.val_loss and (args.rhythm or args.discriminator):
         ap.error("--val_loss scores the checkpoint without sampling it: --rhythm and --discriminator score sampled motion and cannot be "
                  "combined with it")
+    if args.val_loss and (args.beats or args.beat_stride != 1):
+        ap.error("--val_loss scores the checkpoint without sampling it: --beats and --beat_stride score sampled motion and cannot be "
+                 "combined with it")
+    if args.beat_stride != 1 and not args.beats:
+        ap.error("--beat_stride places the music beats of --beats and says nothing without it")
+    if args.beat_stride < 1:
+        ap.error("--beat_stride must be >= 1")
     from . import DDPMTrainer, MotionTransformer
     dev = torch.device("cuda", args.gpu_id)
     torch.cuda.set_device(dev)
@@ -699,7 +809,8 @@ def main(argv=None):
     rh, disc = _movement_scorers(args, dev)
     r = evaluate_dataset(tr, args.data_root, 26, args.batch_size, args.limit, args.seed, args.smooth, motion_encoder=menc,
                          diversity_seed=args.diversity_seed, m2snet=m2s, guidance_scale=args.guidance_scale,
-                         steps=args.steps, spacing=args.spacing, solver=args.solver, rhythm=rh, discriminator=disc)
+                         steps=args.steps, spacing=args.spacing, solver=args.solver, rhythm=rh, discriminator=disc,
+                         music_beats=_music_beats(args), beat_stride=args.beat_stride)
     print(f"{r['clips']} clips in {r['seconds']:.2f} s = {r['frames_per_s']:.0f} frames/s")
     return 0
 

@@ -23,7 +23,13 @@ Host numpy / scipy over the ST-GCN latents of motion_encoder.py (``latent(x)`` =
 and discriminator.Discriminator_1DCNN compute on the device.  The reference evaluates at batch size 1 and averages the per-clip
 values; these do the same.
 
-Beat consistency (BC) is not here: its music side is librosa's onset / beat tracker.
+Beat consistency (BC) and Beat Align come from SUPPLIED music beats: the reference's calculate_beat_scores
+(eval_new_metrics.py:253-317) is librosa's beat tracker on the mel (get_music_beat - a function of the clip's mel alone, so a
+property of the dataset: tools/music_beats_librosa.py writes it once per clip, ``load_music_beats`` reads it), the motion's beats
+(motion_peak_onehot) and their alignment (alignment_score).  The last two run on the device (rhythm.MotionRhythm.motion_beats,
+.beat_scores); ``motion_beats_host`` and ``beat_alignment_host`` restate them in numpy float32 - the CPU path for tests and for a
+box without a GPU - and ``beat_consistency`` averages the per-clip scores.  The tracker itself is not built: it cannot be pinned
+without librosa.
 """
 from __future__ import annotations
 
@@ -235,3 +241,139 @@ def standard_deviation_percentage(sd_gen, sd_real):
     if not r.mean() > 0:
         raise ValueError(f"standard_deviation_percentage: the real motion's mean standard deviation is {r.mean()}, not positive")
     return float(g.mean() / r.mean() * 100.0)
+
+
+BEAT_ORDER, BEAT_SIGMA = 10, 3.0      # argrelextrema's order (eval_new_metrics.py:301) and alignment_score's sigma (:315)
+_BEAT_LANES = 256                     # threads of csrc/dc_rhythm.hip's k_beat_scores: the partial sums of its summation order
+
+
+def _motion_clips(motion):
+    x = np.asarray(motion.detach().cpu() if hasattr(motion, "detach") else motion, np.float32)
+    if x.ndim == 3 and x.shape[-1] == 2:              # one clip [T, 13, 2]
+        x = x[None]
+    if x.ndim not in (3, 4) or x.size != x.shape[0] * x.shape[1] * 26:
+        raise ValueError(f"motion must be [T, 13, 2], [B, T, 26] or [B, T, 13, 2], got {x.shape}")
+    return x.reshape(x.shape[0], x.shape[1], 13, 2)
+
+
+def motion_beats_host(motion, length=None, order=BEAT_ORDER):
+    """motion_peak_onehot (eval_new_metrics.py:285-309) as the device computes it (dc_rhythm_motion_beats), in numpy float32:
+    -> (beats bool [B, T], envelope float32 [B, T]).  The envelope is e[0] = 0, e[t] = the sum over the 13 joints of
+    sqrt(dx dx + dy dy), every operation rounded on its own and the 13 norms added as numpy's float32 reduction over 13 contiguous
+    values adds them - ((n0+n1)+(n2+n3)) + ((n4+n5)+(n6+n7)), then n8 .. n12 one by one -, written out so that it does not depend
+    on the numpy it runs under.  A beat is a strict minimum over +-`order` frames, the index clamped to the clip
+    (scipy.signal.argrelextrema's mode='clip').  `length`: None or the clips' frame counts; frames behind one are 0."""
+    x = _motion_clips(motion)
+    B, T = x.shape[:2]
+    if not 1 <= int(order) <= 64:
+        raise ValueError(f"order {order} is outside 1 .. 64")
+    ln = np.full(B, T, np.int64) if length is None else np.asarray(length, np.int64).reshape(-1)
+    if ln.shape != (B,) or ln.min() < 1 or ln.max() > T:
+        raise ValueError(f"length must hold {B} values in [1, {T}], got {ln.tolist()}")
+    env, beats = np.zeros((B, T), np.float32), np.zeros((B, T), bool)
+    for b in range(B):
+        L = int(ln[b])
+        v = x[b, 1:L] - x[b, :L - 1]
+        n = np.sqrt(v[..., 0] * v[..., 0] + v[..., 1] * v[..., 1])                   # [L - 1, 13] float32
+        s = ((n[:, 0] + n[:, 1]) + (n[:, 2] + n[:, 3])) + ((n[:, 4] + n[:, 5]) + (n[:, 6] + n[:, 7]))
+        for j in range(8, 13):
+            s = s + n[:, j]
+        e = env[b, :L]
+        e[1:] = s
+        t = np.arange(L)
+        ok = np.ones(L, bool)
+        for k in range(1, int(order) + 1):
+            ok &= (e < e[np.clip(t - k, 0, L - 1)]) & (e < e[np.clip(t + k, 0, L - 1)])
+        beats[b, :L] = ok
+    return beats, env
+
+
+def _onehots(a, what):
+    a = np.asarray(a.detach().cpu() if hasattr(a, "detach") else a)
+    if a.ndim == 1:
+        a = a[None]
+    if a.ndim != 2 or a.shape[1] < 1:
+        raise ValueError(f"{what}: expected one-hots [B, L], got {a.shape}")
+    return a != 0
+
+
+def _ordered_sum(terms):
+    """The float32 sum of `terms` (one per position, 0 where there is no beat) in k_beat_scores' order: partial j adds the positions
+    j, j + 256, ... in increasing order, then the partials are added as a binary tree (j with j + 128, then + 64, ...)."""
+    pad = np.zeros(-len(terms) % _BEAT_LANES, np.float32)
+    rows = np.concatenate([terms.astype(np.float32), pad]).reshape(-1, _BEAT_LANES)
+    acc = np.zeros(_BEAT_LANES, np.float32)
+    for r in rows:
+        acc = acc + r
+    while acc.size > 1:
+        acc = acc[:acc.size // 2] + acc[acc.size // 2:]
+    return acc[0]
+
+
+def _nearest_terms(query, keys, stride, sigma):
+    """float32 exp(-d^2 / (2 sigma^2)), d = (float)min |query - keys| / (float)stride, for every query; integers in music frames."""
+    j = np.searchsorted(keys, query)
+    above = np.abs(keys[np.minimum(j, len(keys) - 1)] - query)
+    below = np.abs(query - keys[np.maximum(j - 1, 0)])
+    d = np.minimum(above, below).astype(np.float32) / np.float32(stride)
+    return np.exp(-(d * d) / (np.float32(2) * np.float32(sigma) * np.float32(sigma)))
+
+
+def beat_alignment_host(music_onehot, motion_onehot, sigma=BEAT_SIGMA, music_stride=1):
+    """alignment_score (eval_new_metrics.py:253-275) as the device computes it (dc_rhythm_beat_scores), in numpy float32: one-hots
+    [Lm] and [T], or [B, Lm] and [B, T] (nonzero = a beat) -> float32 [2] or [B, 2]: BC - the mean over the music beats of
+    exp(-d^2 / (2 sigma^2)), d the distance to the nearest motion beat; 0 without motion beats, NaN with motion beats and no music
+    beat - and Beat Align, the other direction (0 without music beats, NaN with music beats and no motion beat).  Music beat i sits
+    at i / music_stride motion frames: 1 is the reference (the index lists compared as they are), 3 puts 90-fps music frames and
+    30-fps motion frames on one clock."""
+    single = np.ndim(music_onehot) == 1
+    mus, mot = _onehots(music_onehot, "music_onehot"), _onehots(motion_onehot, "motion_onehot")
+    if mus.shape[0] != mot.shape[0]:
+        raise ValueError(f"{mus.shape[0]} clips of music beats and {mot.shape[0]} of motion beats")
+    if int(music_stride) < 1 or not (np.isfinite(sigma) and sigma > 0):
+        raise ValueError(f"music_stride {music_stride} must be >= 1 and sigma {sigma} finite and > 0")
+    s = int(music_stride)
+    out = np.zeros((mus.shape[0], 2), np.float32)
+    for b in range(mus.shape[0]):
+        i, m = np.flatnonzero(mus[b]).astype(np.int64), np.flatnonzero(mot[b]).astype(np.int64)
+        bc, ba = np.zeros(mus.shape[1], np.float32), np.zeros(mot.shape[1], np.float32)
+        if i.size and m.size:
+            bc[i] = _nearest_terms(i, s * m, s, sigma)
+            ba[m] = _nearest_terms(s * m, i, s, sigma)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            out[b, 0] = 0 if not m.size else _ordered_sum(bc) / np.float32(i.size)
+            out[b, 1] = 0 if not i.size else _ordered_sum(ba) / np.float32(m.size)
+    return out[0] if single else out
+
+
+def beat_consistency(scores, counts, ids, column=0):
+    """The mean over the clips of the per-clip scores [n, 2] of dc_rhythm_beat_scores (`column` 0: BC, 1: Beat Align) and
+    {clip id: score}.  `counts` [n, 2]: the clips' music and motion beat counts.  A clip without a music beat has no BC (the
+    reference divides by zero there): ValueError naming those clips.  (Beat Align of a clip without a motion beat is NaN, and so is
+    its mean: that is a finding about the motion, not about the input.)"""
+    s = np.asarray(scores.detach().cpu() if hasattr(scores, "detach") else scores, np.float32).reshape(-1, 2)
+    c = np.asarray(counts.detach().cpu() if hasattr(counts, "detach") else counts).reshape(-1, 2)
+    ids = list(ids)
+    if not (len(ids) == s.shape[0] == c.shape[0]) or not ids:
+        raise ValueError(f"beat_consistency: {s.shape[0]} scores, {c.shape[0]} counts and {len(ids)} clip ids")
+    silent = [cid for cid, n in zip(ids, c[:, 0]) if n == 0]
+    if silent:
+        raise ValueError(f"beat_consistency: no music beat in {len(silent)} clip(s): {silent[:8]}{' ...' if len(silent) > 8 else ''}")
+    return float(s[:, column].astype(np.float64).mean()), {cid: float(v) for cid, v in zip(ids, s[:, column])}
+
+
+def load_music_beats(path, ids):
+    """{clip id: uint8 one-hot [Lm]} for `ids` from an .npz whose keys are clip ids and whose values are 1-D one-hots (bool, uint8 or
+    float; nonzero = a beat) - the `beat_onehot` the reference's get_music_beat returns, one entry per mel frame
+    (tools/music_beats_librosa.py writes it).  ValueError for a clip id the file lacks or an array that is not 1-D."""
+    out = {}
+    with np.load(path) as z:
+        missing = [cid for cid in ids if cid not in z.files]
+        if missing:
+            raise ValueError(f"{path} has no music beats for {len(missing)} clip(s): {missing[:8]}{' ...' if len(missing) > 8 else ''}")
+        for cid in ids:
+            a = z[cid]
+            if a.ndim != 1 or a.size < 1:
+                raise ValueError(f"{path}: the music beats of clip {cid} have shape {a.shape}, expected a 1-D one-hot")
+            out[cid] = (a != 0).astype(np.uint8)
+    return out

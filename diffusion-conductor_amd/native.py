@@ -38,7 +38,7 @@ EXPORTS = [
     "dc_m2sgan_generate", "dc_m2sgan_debug_blocks", "dc_m2sgan_fold_conv", "dc_m2sgan_set_decoder",
     "dc_bilstm_create", "dc_bilstm_destroy", "dc_bilstm_set_param", "dc_bilstm_finalize", "dc_bilstm_input_size", "dc_bilstm_decode",
     "dc_bilstm_hidden", "dc_bilstm_pass_clips",
-    "dc_rhythm_create", "dc_rhythm_destroy", "dc_rhythm_psd", "dc_rhythm_contour",
+    "dc_rhythm_create", "dc_rhythm_destroy", "dc_rhythm_psd", "dc_rhythm_contour", "dc_rhythm_motion_beats", "dc_rhythm_beat_scores",
     "dc_discriminator_create", "dc_discriminator_destroy", "dc_discriminator_set_param", "dc_discriminator_finalize",
     "dc_discriminator_features", "dc_discriminator_score",
 ]
@@ -215,6 +215,9 @@ def lib():
     L.dc_rhythm_destroy.restype = None
     L.dc_rhythm_psd.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     L.dc_rhythm_contour.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.dc_rhythm_motion_beats.argtypes = [C.c_void_p, C.c_void_p, ip, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.dc_rhythm_beat_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]
     L.dc_discriminator_create.argtypes = [C.c_int32, C.POINTER(C.c_void_p)]
     L.dc_discriminator_destroy.argtypes = [C.c_void_p]
     L.dc_discriminator_destroy.restype = None
@@ -1002,7 +1005,7 @@ class NativeRhythm(_NativeHandle):
     """Owns one dc_rhythm (no parameters: the handle is ready after create).  Shapes the library refuses raise ValueError before
     the call."""
     _prefix = "dc_rhythm"
-    PSD_BINS, MIN_PSD_T, MIN_CONTOUR_T = 32, 256, 60
+    PSD_BINS, MIN_PSD_T, MIN_CONTOUR_T, MAX_ORDER = 32, 256, 60, 64
 
     @staticmethod
     def windows(T):
@@ -1032,6 +1035,44 @@ class NativeRhythm(_NativeHandle):
             _check(lib().dc_rhythm_contour(self._h, motion.data_ptr(), B, T, c.data_ptr() if contour else None,
                                            s.data_ptr() if sd else None, self._stream()))
         return c, s
+
+    def motion_beats(self, motion, length=None, order=10, envelope=False):
+        """motion fp32 [B, T, 26] on the device, `length` None or B host ints -> (beats uint8 [B, T], envelope fp32 [B, T] | None):
+        dc_rhythm_motion_beats, the strict minima over +-`order` frames of the summed joint speed."""
+        import torch
+        B, T = _motion26(self, motion)
+        if not 1 <= int(order) <= self.MAX_ORDER:
+            raise ValueError(f"order {order} is outside 1 .. {self.MAX_ORDER}")
+        lp = None
+        if length is not None:
+            ln = np.ascontiguousarray(np.asarray(length).reshape(-1), np.int32)
+            if ln.shape != (B,) or ln.min() < 1 or ln.max() > T:
+                raise ValueError(f"length must hold {B} values in [1, {T}], got {ln.tolist()}")
+            lp = _iptr(ln)
+        beats = torch.empty((B, T), dtype=torch.uint8, device=motion.device)
+        env = torch.empty((B, T), dtype=torch.float32, device=motion.device) if envelope else None
+        with torch.cuda.device(motion.device):
+            _check(lib().dc_rhythm_motion_beats(self._h, motion.data_ptr(), lp, B, T, int(order), env.data_ptr() if envelope else None,
+                                                beats.data_ptr(), self._stream()))
+        return beats, env
+
+    def beat_scores(self, motion_beats, music_beats, music_stride=1, sigma=3.0):
+        """one-hots uint8 [B, T] and [B, Lm] on the device (nonzero = a beat) -> (scores fp32 [B, 2]: BC and Beat Align, counts int32
+        [B, 2]: music beats and motion beats): dc_rhythm_beat_scores."""
+        import torch
+        for t in (motion_beats, music_beats):
+            assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and t.dim() == 2, (t.dtype, tuple(t.shape))
+        B, T, Lm = int(motion_beats.shape[0]), int(motion_beats.shape[1]), int(music_beats.shape[1])
+        if int(music_beats.shape[0]) != B or B < 1 or T < 1 or Lm < 1:
+            raise ValueError(f"motion beats {tuple(motion_beats.shape)} and music beats {tuple(music_beats.shape)}: one non-empty row per clip each")
+        if int(music_stride) < 1 or not (np.isfinite(sigma) and sigma > 0):
+            raise ValueError(f"music_stride {music_stride} must be >= 1 and sigma {sigma} finite and > 0")
+        scores = torch.empty((B, 2), dtype=torch.float32, device=motion_beats.device)
+        counts = torch.empty((B, 2), dtype=torch.int32, device=motion_beats.device)
+        with torch.cuda.device(motion_beats.device):
+            _check(lib().dc_rhythm_beat_scores(self._h, motion_beats.data_ptr(), B, T, music_beats.data_ptr(), Lm, int(music_stride),
+                                               C.c_float(float(sigma)), scores.data_ptr(), counts.data_ptr(), self._stream()))
+        return scores, counts
 
 
 class NativeDiscriminator(_NativeHandle):

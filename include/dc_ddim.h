@@ -628,6 +628,44 @@ DC_EXPORT int dc_rhythm_psd(dc_rhythm* h, const float* d_motion, int32_t B, int3
  * Either output may be NULL.  DC_ERR_INVALID before anything is enqueued: B < 1, T < 60, a NULL handle or motion. */
 DC_EXPORT int dc_rhythm_contour(dc_rhythm* h, const float* d_motion, int32_t B, int32_t T, float* d_contour, float* d_sd, void* stream);
 
+/* Replaces motion_peak_onehot (Diffusion_Stage/tools/eval_new_metrics.py:285-309, Contrastive_Stage/M2SGAN_eval.py:310-332), the
+ * motion half of beat consistency: d_motion fp32 [B, T, 26] (13 joints x (x, y)), h_length host int32 [B] or NULL (every clip T
+ * frames) ->
+ *   d_envelope fp32 [B, T] or NULL: the summed joint speed with the reference's float32 BITS.  e[0] = 0; for t >= 1 the sum over
+ *             the 13 joints of sqrt(dx dx + dy dy), dx = x[t] - x[t-1] - every difference, product, sum and the (correctly
+ *             rounded) square root rounded on its own, nothing contracted into an FMA -, the 13 norms added in the order of
+ *             numpy's float32 reduction over 13 contiguous values: ((n0+n1)+(n2+n3)) + ((n4+n5)+(n6+n7)), then + n8 ... + n12 one
+ *             after the other.  0 at frames >= the clip's length.  NULL: the envelope lives in the handle's workspace;
+ *   d_beats uint8 [B, T]: 1 where scipy.signal.argrelextrema(e, np.less, order=`order`) - mode='clip', the default the reference
+ *             relies on - finds a minimum: e[t] < e[clip(t - s)] and e[t] < e[clip(t + s)] for every s = 1 .. order, clip clamping
+ *             to [0, L - 1], L the clip's length.  Strict: no plateau minimum, never frame 0, no frame <= order (e[0] = 0), never
+ *             frame L - 1; 0 at frames >= L, whatever the motion holds there.
+ * `order` is 10 in the reference; 1 .. 64 are accepted.  T is not bounded by LDS.  One workgroup per clip, no atomics: bit-identical
+ * on a rerun, in any batch and at any place in it.  DC_ERR_INVALID before anything is enqueued: B < 1, T < 1, `order` outside
+ * 1 .. 64, a length outside [1, T], a NULL handle, motion or beats pointer, a motion that is not 8-byte aligned. */
+DC_EXPORT int dc_rhythm_motion_beats(dc_rhythm* h, const float* d_motion, const int32_t* h_length, int32_t B, int32_t T, int32_t order,
+                                     float* d_envelope, uint8_t* d_beats, void* stream);
+
+/* Replaces alignment_score (eval_new_metrics.py:253-275, M2SGAN_eval.py:345-367) with the music beats as an INPUT - get_music_beat
+ * (librosa's tracker, a function of the clip's mel alone) stays outside: d_motion_beats uint8 [B, T] and d_music_beats uint8
+ * [B, Lm], nonzero = a beat.  Music beat i sits at i / music_stride motion frames; its distance to motion beat m is
+ * d = (float)|i - music_stride m| / (float)music_stride (integers until the one division).  music_stride = 1 is the reference, which
+ * compares the two index lists as they are (90-fps mel frames against 30-fps motion frames, eval_new_metrics.py:312-315); 3 puts
+ * both on one clock.
+ *   d_scores[b, 0]  BC: the mean over the clip's music beats of expf(-d^2 / (2 sigma^2)), d to the NEAREST motion beat; 0 when the
+ *                   clip has no motion beat (:255-256, tested first), NaN when it has motion beats and no music beat (the reference
+ *                   divides by zero there);
+ *   d_scores[b, 1]  Beat Align, the AIST++ direction the reference keeps commented out at :262-267: the mean over the motion beats
+ *                   of the same Gaussian of the distance to the nearest music beat; 0 without music beats (tested first), NaN with
+ *                   music beats and no motion beat;
+ *   d_counts int32 [B, 2] or NULL: the number of music beats and of motion beats.
+ * Sums are fp32 in a fixed order that depends on the positions alone (csrc/dc_rhythm.hip, k_beat_scores): a clip's scores are
+ * bit-identical on a rerun, in any batch, at any place in it and behind any zero padding of its music beats.  The two sorted index
+ * lists live in the handle's workspace.  DC_ERR_INVALID before anything is enqueued: B, T or Lm < 1, music_stride < 1, sigma not
+ * finite or <= 0, a NULL handle, beats or scores pointer. */
+DC_EXPORT int dc_rhythm_beat_scores(dc_rhythm* h, const uint8_t* d_motion_beats, int32_t B, int32_t T, const uint8_t* d_music_beats,
+                                    int32_t Lm, int32_t music_stride, float sigma, float* d_scores, int32_t* d_counts, void* stream);
+
 /* Replaces constructing Discriminator_1DCNN (Contrastive_Stage/models/Discriminator.py:5-27), the M2S-GAN critic whose
  * D(real) - D(fake) is the W-distance of M2SGAN_eval.py:107-109, on the device `device`. */
 typedef struct dc_discriminator dc_discriminator;
