@@ -40,9 +40,9 @@ int fail(int code, const char* fmt, ...) {
         if (e_ != hipSuccess) return fail(DC_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
     } while (0)
 
-enum KernelId { K_BEGIN = 0, K_SILU, K_FILM, K_EMBED, K_COMBINE, K_LAYER, K_NOISE, K_GUIDE, K_COUNT };
+enum KernelId { K_BEGIN = 0, K_SILU, K_FILM, K_EMBED, K_COMBINE, K_LAYER, K_NOISE, K_GUIDE, K_WINDOWS, K_COUNT };
 const char* kKernelNames[K_COUNT] = {"k_begin_step", "k_silu_emb", "k_film_gemm", "k_embed_front", "k_attn_combine", "k_layer", "k_step_noise",
-                                     "k_guided_update"};
+                                     "k_guided_update", "k_windows_update"};
 
 struct Prof {                       // per-kernel profile (dc_sampler_profile_loop): events around every launch
     std::vector<hipEvent_t> ev;     // pairs
@@ -129,9 +129,12 @@ struct dc_sampler : Formats {     // (set_precision(cfg.precision))
         int user_B = 0, Tx = 0;   // in another take order are another geometry): a loop over any other conditioning clears the tensors
         bool guided = false;
         int takes = 1;
-        bool operator==(const KnownFor& o) const { return user_B == o.user_B && Tx == o.Tx && guided == o.guided && takes == o.takes; }
+        int win_W = 0, win_L = 0; // windows: the caller's tensors are [pieces][L][P]
+        bool operator==(const KnownFor& o) const {
+            return user_B == o.user_B && Tx == o.Tx && guided == o.guided && takes == o.takes && win_W == o.win_W && win_L == o.win_L;
+        }
     } known_set_for;
-    KnownFor known_for() const { return {user_B(), Tx, guided, takes}; }      // ... of the current conditioning
+    KnownFor known_for() const { return {user_B(), Tx, guided, takes, win_W, win_L}; }      // ... of the current conditioning
     const float** d_kslot = nullptr;
     // Savitzky-Golay smoothing applied by the loop's final write (dc_sampler_set_smoothing; window 0 = off)
     int smooth_window = 0, smooth_order = 0, smooth_table_window = 0;     // (table_window: the hat matrix d_smooth_coef holds)
@@ -145,7 +148,19 @@ struct dc_sampler : Formats {     // (set_precision(cfg.precision))
     size_t cap_raw = 0;
     float *d_xf2_proj = nullptr, *d_xf2_out = nullptr;      // feature images [B][Tx][64] of the internal batch (second half: the null pair)
     size_t cap_xf2_proj = 0, cap_xf2_out = 0;
-    int user_B() const { return guided ? B / 2 : B; }       // clips of the caller's tensors (takes x the musics)
+    int user_B() const { return (guided ? B / 2 : B) / (win_W > 0 ? win_W : 1); }       // clips of the caller's tensors (takes x the musics; windows: pieces)
+    // Windows of longer pieces (dc_sampler_set_conditioning_windows): B is win_W windows x the caller's pieces, window-major (x 2 guided);
+    // the caller's tensors and the loop's state d_xp are [pieces][win_L][P], d_x holds the windows' slots for the model to read.
+    // d_win_start / d_win_weight: the plan's tables, d_winslot the slot that names them (k_windows_gather, k_windows_update)
+    int win_W = 0, win_L = 0;
+    int user_frames() const { return win_W > 0 ? win_L : Tx; }       // frames per clip of the caller's tensors
+    size_t user_elems() const { return (size_t)user_B() * user_frames() * cfg.input_feats; }
+    float* d_xp = nullptr;
+    size_t cap_xp = 0;
+    int* d_win_start = nullptr;
+    float* d_win_weight = nullptr;
+    size_t cap_win_start = 0, cap_win_weight = 0;
+    DcWindows* d_winslot = nullptr;
     // Takes (dc_sampler_set_conditioning_takes): the conditional clips are `takes` runs of the same musics, take-major; the feature images of
     // the internal batch live in d_xf2_* as they do for guidance
     int takes = 1;
@@ -838,7 +853,7 @@ int enqueue_step(dc_sampler* s, hipStream_t st, const Step& c, const Switches& w
         LAUNCH(K_BEGIN, dc_launch_begin_step(st, s->d_iter, s->d_t_of_iter, s->d_coef_of_iter, s->d_snap_of_iter,
                                              s->d_t_clip, s->d_coef_cur, s->d_snap_cur, B));
     if (c.loop_mode && (s->upd_flags & DC_UPD_ZSTEP))       // this iteration's draws (eta > 0, library-generated): consumed by the last layer's epilogue
-        LAUNCH(K_NOISE, dc_launch_step_noise(st, s->d_zstep, (size_t)s->user_B() * Tx * s->cfg.input_feats, 0, reinterpret_cast<const unsigned long long*>(s->d_zslot) + 1,
+        LAUNCH(K_NOISE, dc_launch_step_noise(st, s->d_zstep, s->user_elems(), 0, reinterpret_cast<const unsigned long long*>(s->d_zslot) + 1,
                                              iter_base, folded ? graph_step : 0,
                                              folded ? nullptr : s->d_snap_cur, 0));
     if (!f.fuse_silu)
@@ -870,9 +885,10 @@ int enqueue_step(dc_sampler* s, hipStream_t st, const Step& c, const Switches& w
     const int nl_run = f.nl_run;
     DcLayerArgs la{};
     la.dm = dmod, la.hbuf = s->d_h, la.E = s->d_E, la.NT = s->NT, la.recs = s->d_recs, la.length = s->d_length, la.xin = c.x_src, la.xout = c.x_dst;
-    la.out_mode = (c.loop_mode && !f.guided) ? 1 : 0, la.coef_cur = coef_src, la.snap_cur = snap_src, la.snaps = s->d_snaps, la.iter_base = iter_base;
+    la.out_mode = (c.loop_mode && !f.guided && !f.windows) ? 1 : 0, la.coef_cur = coef_src, la.snap_cur = snap_src, la.snaps = s->d_snaps, la.iter_base = iter_base;
     la.M = M, la.T = T, la.G = G, la.B = B, la.Tx = Tx, la.e_groups = f.film_groups, la.e_period = f.film_period, la.e_wrap = f.film_wrap, la.e_magic = film_magic(f.film_period, f.film_wrap);
     if (f.guided) la.xout = s->d_raw;      // the raw output of all 2 B clips; k_guided_update (below) combines the halves and updates x
+    if (f.windows) la.xout = s->d_raw;     // ... of all windows; k_windows_update (below) blends them and updates x in piece space
     la.upd = DcUpdate{s->d_zslot, s->d_status, (c.loop_mode ? s->upd_flags : 0) | f.upd_flags, folded ? graph_step : -1, nullptr, s->d_kslot, s->d_x0_prev};
     DcLayerArgs la_stamps = la;      // (stage stamps of layer 3 in diagnostic builds: DcUpdate::stamps carries the buffer)
     la_stamps.upd.stamps = s->d_stamps;
@@ -881,7 +897,10 @@ int enqueue_step(dc_sampler* s, hipStream_t st, const Step& c, const Switches& w
         for (int l = 0; l < nl_run; ++l)        // (stage stamps: tools/stage_stamps_full.py + a -DDC_FULL_STAMPS build)
             LAUNCH(K_LAYER, dc_launch_layer_full(st, fs, ss, (want_stamps && l == 3) ? la_stamps : la, l, s->d_kv_sa[l & 1], s->d_kv_sa[(l + 1) & 1],
                                                  s->d_kv_ca, s->KT, (l == nl_run - 1) ? f.stop_stage : 0));
-        if (f.guided)
+        if (f.windows)
+            LAUNCH(K_WINDOWS, dc_launch_windows_update(st, s->d_raw, c.x_dst, s->d_xp, f.guided ? 2 : 1, s->user_B(), s->win_W, Tx, s->win_L, s->cfg.input_feats,
+                                                       s->d_winslot, coef_src, snap_src, s->d_snaps, iter_base, s->d_wslot, la.upd));
+        else if (f.guided)
             LAUNCH(K_GUIDE, dc_launch_guided_update(st, s->d_raw, c.x_dst, (size_t)s->user_B() * Tx * s->cfg.input_feats, coef_src, snap_src,
                                                     s->d_snaps, iter_base, s->d_wslot, la.upd));
         return DC_OK;
@@ -906,7 +925,10 @@ int enqueue_step(dc_sampler* s, hipStream_t st, const Step& c, const Switches& w
         LAUNCH(K_LAYER, dc_launch_layer(st, lf, la, l, s->d_a_sa, s->d_a_ca, (l == nl_run - 1) ? f.stop_stage : 0,
                                         ((l == 3 || l == 4) && want_stamps) ? s->d_stamps : nullptr));
     }
-    if (f.guided)
+    if (f.windows)
+        LAUNCH(K_WINDOWS, dc_launch_windows_update(st, s->d_raw, c.x_dst, s->d_xp, f.guided ? 2 : 1, s->user_B(), s->win_W, Tx, s->win_L, s->cfg.input_feats,
+                                                   s->d_winslot, coef_src, snap_src, s->d_snaps, iter_base, s->d_wslot, la.upd));
+    else if (f.guided)
         LAUNCH(K_GUIDE, dc_launch_guided_update(st, s->d_raw, c.x_dst, (size_t)s->user_B() * Tx * s->cfg.input_feats, coef_src, snap_src,
                                                 s->d_snaps, iter_base, s->d_wslot, la.upd));
     return DC_OK;
@@ -966,8 +988,8 @@ int loop_validate(dc_sampler* s, const LoopCall& c, int& flags) {
         return fail(DC_ERR_INVALID, "known values are set: the loop needs the [S][8] table of dc_ddim_coefficients_known (slot 5 = sqrt(1 - abar_prev))");
     if (known && profile) return fail(DC_ERR_UNSUPPORTED, "dc_sampler_profile_loop does not run with known values set");
     if (known) flags |= DC_UPD_KNOWN;
-    if (s->smooth_window > 0 && s->Tx < s->smooth_window)       // (before anything is enqueued: a failed call leaves no work and no half-ordered streams)
-        return fail(DC_ERR_INVALID, "smoothing window %d exceeds the %d frames of a clip", s->smooth_window, s->Tx);
+    if (s->smooth_window > 0 && s->user_frames() < s->smooth_window)       // (before anything is enqueued: a failed call leaves no work and no half-ordered streams)
+        return fail(DC_ERR_INVALID, "smoothing window %d exceeds the %d frames of a clip", s->smooth_window, s->user_frames());
     return DC_OK;
 }
 
@@ -1024,16 +1046,18 @@ int loop_prepare(dc_sampler* s, const LoopCall& c, int& flags, size_t MP) {
     }
     HIP_TRY(hipMemsetAsync(s->d_iter, 0, 16, st));
     if (flags & DC_UPD_MULTISTEP) HIP_TRY(hipMemsetAsync(s->d_x0_prev, 0, MP * 4, st));      // (kappa is 0 in the first step: the zeros are read, never used)
-    HIP_TRY(hipMemcpyAsync(s->d_x, c.d_noise, MP * 4, hipMemcpyDeviceToDevice, st));
+    float* x0 = s->win_W > 0 ? s->d_xp : s->d_x;      // the loop's state in the caller's layout (windows: piece space)
+    HIP_TRY(hipMemcpyAsync(x0, c.d_noise, MP * 4, hipMemcpyDeviceToDevice, st));
     if (flags & DC_UPD_KNOWN) {      // x_T of the known elements at the loop's starting level (slots 6, 7 of the first step's row)
         const float* c0 = h_coef;
         HIP_TRY(dc_launch_set_known(st, s->d_kslot, s->known_val, s->known_mask, s->known_noise));
-        HIP_TRY(dc_launch_known_blend(st, s->d_x, s->known_val, s->known_mask, s->known_noise, c0[6], c0[7], MP));
+        HIP_TRY(dc_launch_known_blend(st, x0, s->known_val, s->known_mask, s->known_noise, c0[6], c0[7], MP));
     }
-    if (s->guided) {      // both halves of x start equal (behind the blend), and the scale goes into its slot
+    if (s->win_W > 0)     // every window's slot of x (both halves of a guided loop) starts from its rows of the piece, behind the blend
+        HIP_TRY(dc_launch_windows_gather(st, s->d_xp, s->d_x, s->guided ? 2 : 1, s->user_B(), s->win_W, s->Tx, s->win_L, s->cfg.input_feats, s->d_winslot));
+    else if (s->guided)   // both halves of x start equal (behind the blend)
         HIP_TRY(hipMemcpyAsync(s->d_x + MP, s->d_x, MP * 4, hipMemcpyDeviceToDevice, st));
-        HIP_TRY(dc_launch_set_scale(st, s->d_wslot, s->guide_w));
-    }
+    if (s->guided) HIP_TRY(dc_launch_set_scale(st, s->d_wslot, s->guide_w));      // ... and the scale goes into its slot
     return DC_OK;
 }
 
@@ -1075,12 +1099,12 @@ int find_or_capture(dc_sampler* s, hipStream_t st, const GraphKey& key, hipGraph
 int loop_common(dc_sampler* s, const LoopCall& c, int flags) {
     int rc;
     if ((rc = loop_validate(s, c, flags))) return rc;
-    const size_t MP = (size_t)s->user_B() * s->Tx * s->cfg.input_feats;
+    const size_t MP = s->user_elems();
     if ((rc = loop_prepare(s, c, flags, MP))) return rc;
     hipStream_t st = s->stream;
     const char* env_tail = getenv("DC_PRECISE_TAIL");      // (DC_PRECISE_TAIL=k overrides the sampler's precise tail: loop_tail)
     LoopOpts lo;
-    lo.S = c.n, lo.flags = flags, lo.guided = s->guided, lo.takes = s->takes, lo.profile = c.profile;
+    lo.S = c.n, lo.flags = flags, lo.guided = s->guided, lo.takes = s->takes, lo.windows = s->win_W, lo.win_L = s->win_L, lo.profile = c.profile;
     lo.no_graph = getenv("DC_DISABLE_GRAPH") != nullptr, lo.tail_split = s->tail_split;
     if (env_tail) lo.env_tail = atoi(env_tail);
     const Switches sw = Switches::read();
@@ -1111,10 +1135,11 @@ int loop_common(dc_sampler* s, const LoopCall& c, int flags) {
     }
     // the final write x0 -> the caller's tensor: a copy, or (dc_sampler_set_smoothing) the Savitzky-Golay filter along time
     // (tools/visualization.py:20-26,126) reading the loop's x0 and writing the caller's tensor directly - no pass of its own
+    const float* x_end = s->win_W > 0 ? s->d_xp : s->d_x;      // (guided: the first half; windows: the piece)
     if (s->smooth_window > 0) {
-        HIP_TRY(dc_launch_savgol(st, s->d_x, c.d_out, s->d_smooth_coef, s->user_B(), s->Tx, s->cfg.input_feats, s->smooth_window));      // (guided: the first half)
+        HIP_TRY(dc_launch_savgol(st, x_end, c.d_out, s->d_smooth_coef, s->user_B(), s->user_frames(), s->cfg.input_feats, s->smooth_window));
     } else {
-        HIP_TRY(hipMemcpyAsync(c.d_out, s->d_x, MP * 4, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hipMemcpyAsync(c.d_out, x_end, MP * 4, hipMemcpyDeviceToDevice, st));
     }
     if (c.n_snap > 0 && c.d_snaps)
         HIP_TRY(hipMemcpyAsync(c.d_snaps, s->d_snaps, (size_t)c.n_snap * MP * 4, hipMemcpyDeviceToDevice, st));
@@ -1208,6 +1233,9 @@ int denoise(dc_sampler* s, const float* d_x, const int32_t* h_timesteps, float* 
     if (s->guided)
         return fail(DC_ERR_INVALID, "the conditioning is guided (dc_sampler_set_conditioning_guided): single evaluations are not guided - per-clip "
                                     "timesteps break the unconditional half's shared FiLM column; call dc_sampler_set_conditioning and combine on your side");
+    if (s->win_W > 0)
+        return fail(DC_ERR_INVALID, "the conditioning holds the windows of longer pieces (dc_sampler_set_conditioning_windows): single evaluations "
+                                    "have no piece to blend into; call dc_sampler_set_conditioning on the windows' features");
     if (s->takes > 1)
         return fail(DC_ERR_INVALID, "the conditioning holds %d takes per music (dc_sampler_set_conditioning_takes): single evaluations take per-clip "
                                     "timesteps, which break the takes' shared FiLM tiles; call dc_sampler_set_conditioning on tiled features", s->takes);
@@ -1387,7 +1415,7 @@ void dc_sampler_destroy(dc_sampler* s) {
                     s->d_a_ca, s->d_x, s->d_snaps, s->d_recs_ca, s->d_nh_hi, s->d_nh_lo, s->d_iter,
                     s->d_t_clip, s->d_snap_cur, s->d_t_of_iter, s->d_snap_of_iter, s->d_coef_cur, s->d_x0_prev, s->d_coef_of_iter,
                     s->d_kv_sa[0], s->d_kv_sa[1], s->d_kv_ca, s->d_stamps, s->d_film_rate, s->d_status, s->d_smooth_coef, s->d_zslot, s->d_kslot, s->d_zstep, s->d_a_ca16, s->d_gran,
-                    s->d_wslot, s->d_raw, s->d_xf2_proj, s->d_xf2_out, s->d_pp_share};
+                    s->d_wslot, s->d_raw, s->d_xf2_proj, s->d_xf2_out, s->d_pp_share, s->d_xp, s->d_win_start, s->d_win_weight, s->d_winslot};
     for (void* p : ptrs)
         if (p) hipFree(p);
     dc_music_destroy(s->music);
@@ -1527,7 +1555,7 @@ int dc_sampler_set_conditioning(dc_sampler* s, const float* d_xf_proj, const flo
     const int rc = set_conditioning(s, d_xf_proj, d_xf_out, h_length, B, T, stream);
     // a plain conditioning switches guidance and takes off (a failed call on such a sampler leaves no conditioning set: the internal
     // batch may be half rebuilt)
-    if (s && (s->guided || s->takes > 1)) s->guided = false, s->takes = 1, s->cond_set = rc == DC_OK;
+    if (s && (s->guided || s->takes > 1 || s->win_W > 0)) s->guided = false, s->takes = 1, s->win_W = s->win_L = 0, s->cond_set = rc == DC_OK;
     return rc;      // (known values set on the guided / takes conditioning are dropped by the next loop: known_set_for)
 }
 
@@ -1543,7 +1571,7 @@ static int set_conditioning_images(dc_sampler* s, const float* d_xf_proj, const 
     if (Bi > (1 << 30)) return fail(DC_ERR_INVALID, "B=%d, takes=%d: the internal batch holds %lld clips", B, takes, Bi);
     if (s->host_only) return fail(DC_ERR_NO_DEVICE, "host-only sampler (sanitizer build without a device)");
     HIP_TRY(hipSetDevice(s->cfg.device));
-    s->guided = false, s->takes = 1, s->cond_set = false;
+    s->guided = false, s->takes = 1, s->win_W = s->win_L = 0, s->cond_set = false;
     // the feature images of the internal clips: the caller's B, `takes` times, then every frame of the shadows carrying the null pair
     const size_t rows = (size_t)B * T, crows = rows * takes, irows = (size_t)Bi * T;
     int rc;
@@ -1604,6 +1632,48 @@ int dc_sampler_set_conditioning_takes(dc_sampler* s, const float* d_xf_proj, con
         return fail(DC_ERR_INVALID, "takes: the null pair is both vectors (guided) or neither (unguided); one of h_null_proj, h_null_out is NULL");
     if (takes == 1 && !h_null_proj) return dc_sampler_set_conditioning(s, d_xf_proj, d_xf_out, h_length, B, T, stream);
     return set_conditioning_images(s, d_xf_proj, d_xf_out, h_length, B, T, takes, h_null_proj, h_null_out, stream);
+}
+
+int dc_windows_check(const int32_t* h_start, const float* h_weight, int32_t W, int32_t T, int32_t L, const int32_t* h_length) {
+    if (h_length) return fail(DC_ERR_INVALID, "windows are full: a conditioning over windows takes no h_length");
+    const std::string why = windows_plan_error(h_start, h_weight, W, T, L);
+    return why.empty() ? DC_OK : fail(DC_ERR_INVALID, "%s", why.c_str());
+}
+
+int dc_sampler_set_conditioning_windows(dc_sampler* s, const float* d_xf_proj, const float* d_xf_out, const int32_t* h_length,
+                                        const int32_t* h_start, const float* h_weight, int32_t B, int32_t W, int32_t T, int32_t L,
+                                        const float* h_null_proj, const float* h_null_out, void* stream) {
+    if (!s || !s->finalized) return fail(DC_ERR_INVALID, "sampler not finalized");
+    if (B < 1) return fail(DC_ERR_INVALID, "bad conditioning arguments (need B >= 1, T >= 1)");
+    if ((h_null_proj != nullptr) != (h_null_out != nullptr))
+        return fail(DC_ERR_INVALID, "windows: the null pair is both vectors (guided) or neither (unguided); one of h_null_proj, h_null_out is NULL");
+    int rc;      // the plan, on the host, before anything is enqueued or allocated
+    if ((rc = dc_windows_check(h_start, h_weight, W, T, L, h_length))) return rc;
+    const bool guided = h_null_proj != nullptr;
+    if ((long long)B * W > (1 << 29)) return fail(DC_ERR_INVALID, "B=%d, W=%d: the internal batch holds %lld windows", B, W, (long long)B * W);
+    // the internal batch: W B clips of T frames, window-major as the caller's features are (+ their shadows)
+    if (guided)
+        rc = set_conditioning_images(s, d_xf_proj, d_xf_out, nullptr, B * W, T, 1, h_null_proj, h_null_out, stream);
+    else
+        rc = dc_sampler_set_conditioning(s, d_xf_proj, d_xf_out, nullptr, B * W, T, stream);
+    if (rc) return rc;
+    s->cond_set = false;
+    const size_t irows = (size_t)s->B * T, P = (size_t)s->cfg.input_feats;
+    if ((rc = grow(s, s->d_raw, s->cap_raw, irows * P, 4, true))) return rc;
+    if ((rc = grow(s, s->d_xp, s->cap_xp, (size_t)B * L * P, 4, true))) return rc;
+    if ((rc = grow(s, s->d_win_start, s->cap_win_start, (size_t)W, 4, false))) return rc;       // (captured launches read the slot, not these)
+    if ((rc = grow(s, s->d_win_weight, s->cap_win_weight, (size_t)W * T, 4, false))) return rc;
+    if (!s->d_winslot && (rc = dev_alloc(s, s->d_winslot, sizeof(DcWindows)))) return rc;
+    // the tables go up behind the sampler's earlier loops, which may still read the previous plan's (synchronous: host arrays)
+    hipStream_t st = s->stream;
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipMemcpyAsync(s->d_win_start, h_start, (size_t)W * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(s->d_win_weight, h_weight, (size_t)W * T * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(dc_launch_set_windows(st, s->d_winslot, s->d_win_start, s->d_win_weight));
+    HIP_TRY(hipStreamSynchronize(st));
+    s->win_W = W, s->win_L = L;
+    s->cond_set = true;
+    return DC_OK;
 }
 
 int dc_sampler_set_guidance_scale(dc_sampler* s, float w) {
@@ -1912,6 +1982,7 @@ int dc_sampler_debug_layer(dc_sampler* s, const float* h_h, const int32_t* h_tim
     if (!h_h || !h_timesteps) return fail(DC_ERR_INVALID, "null pointer argument");
     if (s->guided) return fail(DC_ERR_INVALID, "the conditioning is guided (dc_sampler_set_conditioning_guided): the debug entry points run plain conditionings");
     if (s->takes > 1) return fail(DC_ERR_INVALID, "the conditioning holds %d takes per music (dc_sampler_set_conditioning_takes): the debug entry points run plain conditionings", s->takes);
+    if (s->win_W > 0) return fail(DC_ERR_INVALID, "the conditioning holds the windows of longer pieces (dc_sampler_set_conditioning_windows): the debug entry points run plain conditionings");
     if (layer < 0 || layer >= s->cfg.num_layers || first_stage < 1 || stage > 3 || first_stage > stage)
         return fail(DC_ERR_INVALID, "layer / stage out of range (need 1 <= first_stage <= last_stage <= 3)");
     if (s->cfg.no_eff) return fail(DC_ERR_UNSUPPORTED, "dc_sampler_debug_layer covers the linear-attention layers");

@@ -136,6 +136,13 @@ struct DcNull64 {
     float v[64];
 };
 
+// the device slot of a loop over windows (dc_sampler_set_conditioning_windows): where the plan's tables are.  k_windows_gather and
+// k_windows_update read the slot, not the addresses, so a captured graph serves every plan of its (Bp, W, T, L)
+struct DcWindows {
+    const int* start;       // [W] first frame of each window, ascending
+    const float* weight;    // [W][T] blend weights, summing to 1 over the windows that cover a frame
+};
+
 // k_embed_front's arguments when it rides in the FiLM GEMM's launch (the first `ne` workgroups embed one 256-token unit each, flat units)
 struct DcEmbedArgs {
     const DcModel* dm;

@@ -2,7 +2,8 @@
 // launch form of one evaluation from the geometry, the sampler's settings, the environment switches and the step's options;
 // clip_stride, steps_per_graph and loop_tail decide the workspace stride, the graph size and the precise tail of a loop; loop_plan
 // decides a whole loop - eager or captured, its graphs, their keys and replays - and loop_step the options of each of its steps.
-// dc_api.hip launches what they say; tests/form_probe.cpp checks the rules on the CPU (tests/test_host_form.py, _known, _guided, _takes).
+// dc_api.hip launches what they say; tests/form_probe.cpp checks the rules on the CPU (tests/test_host_form.py, _known, _guided, _takes),
+// tests/form_probe_windows.cpp those of the windows option (tests/test_host_windows.py).
 #pragma once
 #include <algorithm>
 #include <cstdio>
@@ -77,6 +78,44 @@ inline unsigned long long guided_key_bits(bool guided, bool shared_film) {
     return (guided ? 1ull << 27 : 0ull) | ((guided && shared_film) ? 1ull << 28 : 0ull);
 }
 
+// Overlapping windows of a long piece in one loop (dc_sampler_set_conditioning_windows; include/dc_ddim.h states the semantics): the
+// geometry's B clips are W windows of Bp pieces each, window-major (twice that under guidance), and the loop's state is one tensor in
+// piece space [Bp][L][P].  What such a loop adds to the key of its captured graph (loop_plan): bit 30 - another store in the last
+// layer, k_windows_update behind it -, the window count in bits 47 .. 62 and the piece length in the key's last element (the takes'
+// wrap period otherwise; windows refuse takes, so the two never meet).  Starts and weights are NOT in the key: the kernels read them
+// from device tables, so another plan of the same (Bp, W, T, L) replays the graph.
+constexpr int DC_WINDOWS_MAX = 65535;      // windows per piece: what the key's 16 bits hold
+constexpr int DC_WINDOWS_COVER = 4;        // windows over one frame, at most
+inline unsigned long long windows_key_bits(int W) { return W > 0 ? (1ull << 30 | (unsigned long long)(W & 0xffff) << 47) : 0ull; }
+
+// The plan of such a loop, checked on the host before anything is enqueued: "" or why dc_sampler_set_conditioning_windows refuses it.
+// starts[W] ascending from 0 to L - T without a gap (s_{k+1} <= s_k + T), at most DC_WINDOWS_COVER windows over a frame; weight[W][T]
+// finite, >= 0, and summing to 1 over the covering windows of every frame within 4 ulp of fp32 (summed in fp64, ascending k).
+inline std::string windows_plan_error(const int* start, const float* weight, int W, int T, int L) {
+    char buf[200];
+    const auto say = [&](const char* fmt, auto... a) { snprintf(buf, sizeof buf, fmt, a...); return std::string(buf); };
+    if (!start || !weight) return "windows: the starts h_start[W] or the weights h_weight[W][T] are NULL";
+    if (W < 1 || W > DC_WINDOWS_MAX || T < 1 || L < T) return say("windows: need 1 <= W <= %d and L >= T >= 1 (W=%d, T=%d, L=%d)", DC_WINDOWS_MAX, W, T, L);
+    if (start[0] != 0) return say("windows: the first window starts at frame %d, not 0", start[0]);
+    if (start[W - 1] != L - T) return say("windows: the last window starts at frame %d, not L - T = %d", start[W - 1], L - T);
+    for (int k = 1; k < W; ++k) {
+        if (start[k] <= start[k - 1]) return say("windows: starts must ascend (window %d starts at %d, window %d at %d)", k - 1, start[k - 1], k, start[k]);
+        if (start[k] > start[k - 1] + T) return say("windows: frames [%d, %d) lie in no window", start[k - 1] + T, start[k]);
+        if (k >= DC_WINDOWS_COVER && start[k - DC_WINDOWS_COVER] + T > start[k])
+            return say("windows: frame %d lies in more than %d windows", start[k], DC_WINDOWS_COVER);
+    }
+    for (size_t i = 0; i < (size_t)W * T; ++i)
+        if (!(weight[i] >= 0.f && weight[i] <= 3.0e38f)) return say("windows: weight[%d][%d] is negative or not finite", (int)(i / T), (int)(i % T));
+    int lo = 0;      // the first window that reaches frame f
+    for (int f = 0; f < L; ++f) {
+        while (start[lo] + T <= f) ++lo;
+        double sum = 0.0;
+        for (int k = lo; k < W && start[k] <= f; ++k) sum += (double)weight[(size_t)k * T + (f - start[k])];
+        if (!(sum >= 1.0 - 4 * 0x1p-23 && sum <= 1.0 + 4 * 0x1p-23)) return say("windows: the weights over frame %d sum to %.9g, not 1 (4 ulp)", f, sum);
+    }
+    return "";
+}
+
 // what the rule reads of a sampler
 struct Settings {
     int precision = DCF_FP16;
@@ -113,6 +152,9 @@ struct StepOpts {
     bool guided = false;          // loops: classifier-free guidance (dc_sampler_set_conditioning_guided): the geometry's B clips are B / 2 conditional
                                   // clips followed by their B / 2 unconditional shadows; the last layer stores the raw model output and
                                   // k_guided_update combines the halves and updates x (no embed_next: x_{t-1} is not in the last layer's registers)
+    bool windows = false;         // loops: the clips are overlapping windows of longer pieces (dc_sampler_set_conditioning_windows): the last layer
+                                  // stores the raw model output and k_windows_update blends the windows, combines the guided halves when there
+                                  // are any, and updates x in piece space (no embed_next, as for `guided`; no takes)
     Hooks dbg;
 };
 
@@ -131,6 +173,7 @@ struct StepForm {
     int upd_flags = 0;            // DC_UPD_* bits the form adds to the loop's (TEST_DROP_SLICE, EMBED_NEXT, KNOWN)
     int nl_run = 0, stop_stage = 0;      // layers to run; the stop stage handed to the last of them (0 = the whole layer)
     bool guided = false;          // the last layer writes the raw output of all clips; k_guided_update follows it
+    bool windows = false;         // ... k_windows_update follows it (guided or not)
     bool shared_film = false;     // the FiLM GEMM covers film_groups < G groups (film_share): takes wrap, the guided shadow half reads group film_groups - 1
     int film_groups = 0;          // groups the FiLM GEMM computes = the e_groups of the layer kernels' tile reads (nothing shared: G)
     int film_period = 0, film_wrap = 0;      // token group g reads the tiles of group g < film_wrap ? g % film_period : film_groups - 1 (nothing shared: G, G)
@@ -201,6 +244,15 @@ inline StepForm step_form(const Geometry& g, const Settings& s, const Switches& 
         return f;
     }
     const bool guided = f.guided = o.guided;
+    if (o.windows && !(o.loop_mode && dbg.production())) {
+        f.error = "internal: an evaluation over windows is a loop step";
+        return f;
+    }
+    if (o.windows && o.takes != 1) {
+        f.error = "windows do not combine with takes";
+        return f;
+    }
+    f.windows = o.windows;
     // "no test hook, no stamps": what the production-only forms below ask for.  Conditions that name single hooks instead are meant
     // as they stand, and say why.
     const bool quiet = dbg.production() && !stamps;
@@ -282,7 +334,8 @@ inline StepForm step_form(const Geometry& g, const Settings& s, const Switches& 
     // and it has no front launch.  DC_NO_EMBED_NEXT=1 keeps the front work in every step's own FiLM launch.
     const bool wide_plain = wgr && !narrow && !ss && fuse_silu && ff == fs && quiet && !s.no_eff;
     // (a guided step's update runs in k_guided_update, behind the last layer: there is no x_{t-1} in that layer's registers to embed)
-    f.embed_next = !w.no_embed_next && o.loop_mode && o.next_plain && wide_plain && !guided;
+    // (nor a step's over windows: its update runs in k_windows_update, in piece space)
+    f.embed_next = !w.no_embed_next && o.loop_mode && o.next_plain && wide_plain && !guided && !o.windows;
     // The padding waves of that kernel (clip-aligned units at 1800 frames: 7 of the 8 waves of every clip's last workgroup, 11 % of the
     // launch's waves) do a workgroup member's duties only; dc_sampler_set_idle_wave_path(s, 0) has them run the whole layer as before
     // (results are bit-identical either way: nothing of theirs ever reached an output).  Only the instantiation without hooks and stamps
@@ -378,6 +431,7 @@ inline LoopTail loop_tail(const Settings& s, int tail_split, std::optional<int> 
 //   16 .. 23 the loop's DC_UPD_* flags (the noise / known tensors' addresses are not baked in: the kernels read them from their slots)
 //   24       l16_own            25, 26  clip_aligned + 1            27, 28  guided_key_bits
 //   29       the padding waves' barrier-only path is OFF (Settings::idle_wave_path; set when off, so the default's key is what it was)
+//   30       the clips are windows of longer pieces (windows_key_bits; their count in bits 47 .. 62, the piece length in the last element)
 //   39       the loop has a precise tail: its plain evaluations read G' scale tiles, those of a loop without one G' - 1 tiles
 //   40 ..    the split evaluations at the end of this graph
 using GraphKey = std::tuple<int, int, int, int, unsigned long long, int>;
@@ -387,6 +441,7 @@ struct LoopOpts {
     int flags = 0;                // DC_UPD_* of the loop, the internal NOISY / ZSTEP / MULTISTEP / KNOWN bits resolved
     bool guided = false;          // the conditioning (StepOpts::guided, ::takes)
     int takes = 1;
+    int windows = 0, win_L = 0;   // windows per piece and frames per piece (dc_sampler_set_conditioning_windows); 0: none (StepOpts::windows)
     bool profile = false;         // events around every launch: an eager loop
     bool no_graph = false;        // DC_DISABLE_GRAPH: an eager loop
     int tail_split = -1;          // loop_tail's arguments
@@ -414,10 +469,11 @@ inline LoopPlan loop_plan(const Geometry& g, const Settings& s, const Switches& 
     const FilmShare share = film_share(g.B, g.T, g.G, o.guided, o.takes, !s.fmt.split_film, w);
     const unsigned long long bits = w.bits() | (unsigned long long)(o.flags & 0xff) << 16 | (s.l16_own ? 1ull : 0ull) << 24 |
                                     (unsigned long long)((s.clip_aligned + 1) & 3) << 25 | guided_key_bits(o.guided, share.groups < g.G) |
-                                    (s.idle_wave_path ? 0ull : 1ull) << 29 | (p.g1_loop ? 1ull : 0ull) << 39;
+                                    (s.idle_wave_path ? 0ull : 1ull) << 29 | windows_key_bits(o.windows) | (p.g1_loop ? 1ull : 0ull) << 39;
     const int K = steps_per_graph(o.S), replays = o.S / K;
     const auto part = [&](int split_n, int launches) {
-        p.parts.push_back({K, split_n, launches, GraphKey{g.B, g.T, g.Tx, K, bits | (unsigned long long)split_n << 40, takes_key_period(share)}});
+        p.parts.push_back({K, split_n, launches, GraphKey{g.B, g.T, g.Tx, K, bits | (unsigned long long)split_n << 40,
+                                                                  o.windows > 0 ? o.win_L : takes_key_period(share)}});
     };
     // (with a precise tail and several replays per loop - S > 64 - the LAST replay runs a second graph whose final steps are split)
     if (lt.tail && replays > 1) {
@@ -433,6 +489,6 @@ inline StepOpts loop_step(const LoopPlan& p, const LoopPart& part, const LoopOpt
     StepOpts c;
     c.loop_mode = true, c.graph_step = p.eager ? -1 : i, c.split = i >= part.steps - part.split_n, c.g1_loop = p.g1_loop;
     c.next_plain = i + 1 < part.steps - part.split_n, c.profile = o.profile, c.known = (o.flags & DC_UPD_KNOWN) != 0;
-    c.guided = o.guided, c.takes = o.takes;
+    c.guided = o.guided, c.takes = o.takes, c.windows = o.windows > 0;
     return c;
 }

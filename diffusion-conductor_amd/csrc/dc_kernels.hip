@@ -142,6 +142,152 @@ __global__ __launch_bounds__(256) void k_guided_update(const float* __restrict__
 }
 
 // ------------------------------------------------------------------------------------
+// Overlapping windows of a long piece in one loop (dc_sampler_set_conditioning_windows; include/dc_ddim.h states the semantics; no
+// counterpart in the reference, which samples one window).  The internal batch is W windows of Bp pieces, window-major - clip k Bp + b
+// is frames [s_k, s_k + T) of piece b - followed, under guidance, by as many unconditional shadows; the loop's state is xp [Bp][L][P].
+// k_windows_gather copies piece x_T into every window's slot of the internal x before the first evaluation.  k_windows_update runs
+// behind the step's last layer, which has stored the raw model output of all clips (out_mode 0), on one thread per 4 consecutive PIECE
+// elements:   out = sum_k w[k][f - s_k] raw_k[f - s_k]   over the windows that cover frame f, ascending k, fp32 without contraction,
+// the accumulator starting from the first product (a frame under one window, whose weight is exactly 1, keeps its raw value bit for
+// bit); guided: the two halves are blended each, then combined as k_guided_update combines them; then ddim_update, the multistep term
+// and known_replace exactly as there, every tensor of the update in piece space.  x_{t-1} goes to xp and to every covering window's
+// slot of the internal x (both halves).  Starts and weights come from the device tables *win names: another plan of the same
+// (Bp, W, T, L) replays the captured graph.  16-byte accesses where counts, bases and a window's offset allow, scalar ones elsewhere.
+// ------------------------------------------------------------------------------------
+__global__ void k_set_windows(DcWindows* slot, const int* start, const float* weight) { slot->start = start, slot->weight = weight; }
+DEV float win_accumulate(float acc, float w, float v, bool first) {
+#pragma clang fp contract(off)
+    const float p = w * v;
+    return first ? p : acc + p;
+}
+__global__ __launch_bounds__(256) void k_windows_gather(const float* __restrict__ xp /*[Bp][L][P]*/, float* __restrict__ xw /*[halves W Bp][T][P]*/,
+                                                        size_t n_win /* halves W Bp T P */, int Bp, int W, int T, int L, int P,
+                                                        const DcWindows* __restrict__ win) {
+    const size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i >= n_win) return;
+    const int cnt = (int)(n_win - i < 4 ? n_win - i : 4);
+    const int* __restrict__ start = win->start;
+    const size_t TP = (size_t)T * P, LP = (size_t)L * P;
+    const auto a16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    const size_t clip = i / TP, q = i - clip * TP, c2 = clip % ((size_t)W * Bp);
+    const size_t src = (c2 % Bp) * LP + (size_t)start[c2 / Bp] * P + q;
+    float v[4];
+    if (cnt == 4 && q + 3 < TP) {      // one clip: four consecutive piece elements
+        guide_ld4(v, xp, src, 4, (src & 3) == 0 && a16(xp));
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (j >= cnt) continue;
+            const size_t e = i + j, cj = e / TP, qj = e - cj * TP, cc = cj % ((size_t)W * Bp);
+            v[j] = xp[(cc % Bp) * LP + (size_t)start[cc / Bp] * P + qj];
+        }
+    }
+    guide_st4(xw, i, v, cnt, (n_win & 3) == 0 && a16(xw));
+}
+__global__ __launch_bounds__(256) void k_windows_update(const float* __restrict__ raw /*[halves W Bp][T][P]*/, float* __restrict__ xw /*the same*/,
+                                                        float* __restrict__ xp /*[Bp][L][P]*/, size_t n /* Bp L P */, int Bp, int W, int T, int L,
+                                                        int P, int halves, const DcWindows* __restrict__ win,
+                                                        const float* __restrict__ coef_cur, const int* __restrict__ snap_cur,
+                                                        float* __restrict__ snaps, const int* __restrict__ iter_base,
+                                                        const float* __restrict__ wslot, const DcUpdate upd) {
+    const size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    if (i >= n) return;
+    const int cnt = (int)(n - i < 4 ? n - i : 4);
+    const int ib = iter_base ? *iter_base : 0;
+    const float* cc = coef_cur + DC_COEF * ib;
+    const int snap = snap_cur[ib];
+    const bool noisy = (upd.flags & DC_UPD_NOISY) != 0;
+    const float* zrow = nullptr;
+    if (noisy) zrow = *upd.zslot + ((upd.flags & DC_UPD_ZSTEP) ? (size_t)0 : (size_t)(iter_base ? upd.step + ib : snap_cur[1]) * n);
+    const KnownPtrs kn = known_ptrs(upd);
+    const bool guided = halves == 2;
+    const float wm1 = guided ? *wslot - 1.f : 0.f;
+    const int* __restrict__ start = win->start;
+    const float* __restrict__ weight = win->weight;
+    const auto a16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    const bool multi = (upd.flags & DC_UPD_MULTISTEP) != 0;
+    const bool vec = (n & 3) == 0 && a16(xp) && a16(snaps) && a16(zrow) && a16(upd.x0_prev);      // the piece-space tensors
+    const bool vec_w = a16(raw) && a16(xw);                                                       // the window-space ones, offset permitting
+    const size_t TP = (size_t)T * P, LP = (size_t)L * P, half = (size_t)W * Bp * TP;
+    // this thread's elements: piece b, offsets r .. r + cnt - 1 inside it (the last quad of a piece whose size is no multiple of 4 runs
+    // into piece b + 1: element j then sits at pb[j], pr[j])
+    const size_t b = i / LP, r = i - b * LP;
+    size_t pb[4], pr[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) pb[j] = r + j < LP ? b : b + 1, pr[j] = r + j < LP ? r + j : r + j - LP;
+    const bool one_piece = r + cnt - 1 < LP;
+    float c[4] = {0.f, 0.f, 0.f, 0.f}, u[4] = {0.f, 0.f, 0.f, 0.f};
+    unsigned seen = 0;      // bit j: element j has its first product
+    for (int k = 0; k < W; ++k) {
+        const size_t row0 = (size_t)start[k] * P, row1 = row0 + TP;
+        // (starts ascend: past the last element of a quad inside one piece no later window covers any of it)
+        if (one_piece && row0 > r + cnt - 1) break;
+        const float* __restrict__ wk = weight + (size_t)k * T;
+        if (one_piece && cnt == 4 && row0 <= r && r + 3 < row1) {      // the window covers the quad
+            const size_t o = ((size_t)k * Bp + b) * TP + (r - row0);
+            const bool v4 = vec_w && (o & 3) == 0;
+            float rc[4], ru[4];
+            guide_ld4(rc, raw, o, 4, v4);
+            if (guided) guide_ld4(ru, raw + half, o, 4, v4);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float wj = wk[(r + j - row0) / P];
+                c[j] = win_accumulate(c[j], wj, rc[j], !(seen >> j & 1));
+                if (guided) u[j] = win_accumulate(u[j], wj, ru[j], !(seen >> j & 1));
+            }
+            seen = 15;
+            continue;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (j >= cnt || pr[j] < row0 || pr[j] >= row1) continue;
+            const size_t o = ((size_t)k * Bp + pb[j]) * TP + (pr[j] - row0);
+            const float wj = wk[(pr[j] - row0) / P];
+            c[j] = win_accumulate(c[j], wj, raw[o], !(seen >> j & 1));
+            if (guided) u[j] = win_accumulate(u[j], wj, raw[half + o], !(seen >> j & 1));
+            seen |= 1u << j;
+        }
+    }
+    float xt[4], z[4] = {0.f, 0.f, 0.f, 0.f}, xn[4], pred[4], prev[4] = {0.f, 0.f, 0.f, 0.f};
+    if (multi) guide_ld4(prev, upd.x0_prev, i, cnt, vec);
+    guide_ld4(xt, xp, i, cnt, vec);
+    if (noisy) guide_ld4(z, zrow, i, cnt, vec);
+    bool bad = false;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        bad = bad || (j < cnt && !(fabsf(c[j]) <= 3.0e38f && fabsf(u[j]) <= 3.0e38f));
+        bool badj = false;
+        xn[j] = ddim_update(guided ? guide_combine(c[j], u[j], wm1) : c[j], xt[j], cc, upd.flags, noisy, z[j], badj, pred[j]);
+        if (multi) xn[j] += cc[8] * (pred[j] - prev[j]);      // (multistep_update, dc_dev.h, on this thread's four elements)
+        bad = bad || (j < cnt && badj);
+        if (j < cnt) xn[j] = known_replace(xn[j], kn, i + j, cc);
+    }
+    guide_st4(xp, i, xn, cnt, vec);
+    if (multi) guide_st4(upd.x0_prev, i, pred, cnt, vec);
+    if (snap >= 0) guide_st4(snaps + (size_t)snap * n, i, xn, cnt, vec);
+    // x_{t-1} into every covering window's slot of the internal x: the walk above, storing
+    for (int k = 0; k < W; ++k) {
+        const size_t row0 = (size_t)start[k] * P, row1 = row0 + TP;
+        if (one_piece && row0 > r + cnt - 1) break;
+        if (one_piece && cnt == 4 && row0 <= r && r + 3 < row1) {
+            const size_t o = ((size_t)k * Bp + b) * TP + (r - row0);
+            const bool v4 = vec_w && (o & 3) == 0;
+            guide_st4(xw, o, xn, 4, v4);
+            if (guided) guide_st4(xw + half, o, xn, 4, v4);
+            continue;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (j >= cnt || pr[j] < row0 || pr[j] >= row1) continue;
+            const size_t o = ((size_t)k * Bp + pb[j]) * TP + (pr[j] - row0);
+            xw[o] = xn[j];
+            if (guided) xw[half + o] = xn[j];
+        }
+    }
+    if (bad && upd.status) atomicOr(upd.status, DC_STATUS_NONFINITE);
+}
+
+// ------------------------------------------------------------------------------------
 // eta > 0 without a caller-supplied noise tensor: the N(0, 1) draws of ONE iteration (the reference's th.randn_like(x),
 // gaussian_diffusion.py:822), generated at the head of the step that consumes them - a [B][Tx][P] buffer instead of the
 // [S][B][Tx][P] tensor (6 GB at S = 1000, bs = 32).  Philox4x32-10 keyed by the seed, counter = (element quad, iteration);
@@ -2929,6 +3075,23 @@ hipError_t dc_launch_guided_update(hipStream_t st, const float* raw, float* x, s
                                    const int* iter_base, const float* wslot, const DcUpdate& upd) {
     const size_t threads = (n + 3) / 4;
     k_guided_update<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st>>>(raw, x, n, coef_cur, snap_cur, snaps, iter_base, wslot, upd);
+    return hipGetLastError();
+}
+hipError_t dc_launch_set_windows(hipStream_t st, DcWindows* slot, const int* start, const float* weight) {
+    k_set_windows<<<1, 1, 0, st>>>(slot, start, weight);
+    return hipGetLastError();
+}
+hipError_t dc_launch_windows_gather(hipStream_t st, const float* xp, float* xw, int halves, int Bp, int W, int T, int L, int P, const DcWindows* slot) {
+    const size_t n_win = (size_t)halves * W * Bp * T * P, threads = (n_win + 3) / 4;
+    k_windows_gather<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st>>>(xp, xw, n_win, Bp, W, T, L, P, slot);
+    return hipGetLastError();
+}
+hipError_t dc_launch_windows_update(hipStream_t st, const float* raw, float* xw, float* xp, int halves, int Bp, int W, int T, int L, int P,
+                                    const DcWindows* slot, const float* coef_cur, const int* snap_cur, float* snaps, const int* iter_base,
+                                    const float* wslot, const DcUpdate& upd) {
+    const size_t n = (size_t)Bp * L * P, threads = (n + 3) / 4;
+    k_windows_update<<<dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st>>>(raw, xw, xp, n, Bp, W, T, L, P, halves, slot, coef_cur, snap_cur,
+                                                                                   snaps, iter_base, wslot, upd);
     return hipGetLastError();
 }
 hipError_t dc_launch_set_ptr(hipStream_t st, const float** slot, const float* p, unsigned long long seed, unsigned long long first) {

@@ -121,6 +121,16 @@ hipError_t dc_launch_fill_rows64(hipStream_t st, float* dst, size_t rows, const 
 hipError_t dc_launch_set_scale(hipStream_t st, float* slot, float w);
 hipError_t dc_launch_guided_update(hipStream_t st, const float* raw, float* x, size_t n, const float* coef_cur, const int* snap_cur, float* snaps,
                                    const int* iter_base, const float* wslot, const DcUpdate& upd);
+// Windows of a long piece (dc_sampler_set_conditioning_windows).  xw, raw = the internal x and the last layer's raw output
+// [halves][W][Bp][T][P] (halves = 2: the guided shadows behind the conditional clips), xp = the loop's state in piece space [Bp][L][P].
+// dc_launch_set_windows: the tables' addresses into the slot.  dc_launch_windows_gather: xw = every window's rows of xp.
+// dc_launch_windows_update: blend raw over the covering windows, combine the halves (wslot: the guidance scale), update xp as
+// dc_launch_guided_update updates x - noise, known values, x0_prev and snapshots in piece space - and write x_{t-1} to xp and xw.
+hipError_t dc_launch_set_windows(hipStream_t st, DcWindows* slot, const int* start, const float* weight);
+hipError_t dc_launch_windows_gather(hipStream_t st, const float* xp, float* xw, int halves, int Bp, int W, int T, int L, int P, const DcWindows* slot);
+hipError_t dc_launch_windows_update(hipStream_t st, const float* raw, float* xw, float* xp, int halves, int Bp, int W, int T, int L, int P,
+                                    const DcWindows* slot, const float* coef_cur, const int* snap_cur, float* snaps, const int* iter_base,
+                                    const float* wslot, const DcUpdate& upd);
 // N(0, 1) draws of one DDIM iteration (Philox keyed by *seed_slot when given, else seed; iteration = step + *iter_base, else snap_cur[1],
 // else step) into z[0..n); z[0] is element `first` (seed_slot[1] when a slot is given) of the whole batch's draw
 hipError_t dc_launch_step_noise(hipStream_t st, float* z, size_t n, unsigned long long seed, const unsigned long long* seed_slot, const int* iter_base,

@@ -254,10 +254,18 @@ class MotionTransformer(nn.Module):
         proj.bias.  The reference has no sampling counterpart."""
         return self.get_parameter("proj.bias").detach().float().cpu().reshape(64), torch.zeros(64)
 
-    def set_conditioning(self, xf_proj, xf_out, length=None, guided=False, takes=1):
+    def set_conditioning(self, xf_proj, xf_out, length=None, guided=False, takes=1, windows=None):
         """`guided`: the conditioning of a guided loop (include/dc_ddim.h, dc_sampler_set_conditioning_guided) with null_conditioning().
-        `takes`: samples per music (dc_sampler_set_conditioning_takes): the loops then run takes x the musics, take-major."""
+        `takes`: samples per music (dc_sampler_set_conditioning_takes): the loops then run takes x the musics, take-major.
+        `windows`: (starts [W], weights fp32 [W, T], L) - the features are the W x B windows of B pieces of L frames, window-major, and
+        the loops run over the pieces (dc_sampler_set_conditioning_windows); set on every call (the plan is part of it)."""
         nat = self._ensure_native(xf_proj.device)
+        if windows is not None:
+            self._cond_key = None
+            starts, weights, L = windows
+            nat.set_conditioning_windows(xf_proj.contiguous().float(), xf_out.contiguous().float(), starts, weights, L,
+                                         null=self.null_conditioning() if guided else None)
+            return nat
         T = xf_proj.shape[1]
         if length is None:
             length = [T] * xf_proj.shape[0]

@@ -37,6 +37,34 @@ def plan_windows(L, T, overlap):
     return [(s, 0 if k == 0 else starts[k - 1] + T - s) for k, s in enumerate(starts)]
 
 
+def window_weights(L, T, starts, blend="tent"):
+    """The blend weights of a piece of L frames sampled JOINTLY over windows of T frames at `starts` (ascending, from 0 to L - T, no
+    gap): fp32 [W, T], row k the weight of window k's local frames.  A window's raw weight at local frame j is min(j + 1, T - j)
+    (blend="tent": 1 at the window's edges, rising linearly to its middle, so a window hands a frame over to its neighbour across
+    their overlap) or 1 (blend="uniform": the plain mean); the raw weights are normalised over the windows that cover a frame in
+    fp64 and rounded to fp32 once, so they sum to 1 within an fp32 ulp, and a frame under a single window gets exactly 1.0.
+    Pure; ValueError for starts that are not such a cover or an unknown blend.  (dc_sampler_set_conditioning_windows checks the
+    cover count - at most 4 windows over a frame - and the sums again.)"""
+    L, T = int(L), int(T)
+    st = [int(s) for s in np.asarray(starts).reshape(-1)]
+    if blend not in ("tent", "uniform"):
+        raise ValueError(f"blend must be 'tent' or 'uniform', got {blend!r}")
+    if T < 1 or L < T or not st or st[0] != 0 or st[-1] != L - T or any(b <= a or b > a + T for a, b in zip(st, st[1:])):
+        raise ValueError(f"starts must ascend from 0 to L - T = {L - T} without leaving a gap between windows of {T} frames, got {st}")
+    j = np.arange(T)
+    raw = np.minimum(j + 1, T - j).astype(np.float64) if blend == "tent" else np.ones(T, np.float64)
+    total, cover = np.zeros(L, np.float64), np.zeros(L, np.int64)
+    for s in st:
+        total[s:s + T] += raw
+        cover[s:s + T] += 1
+    w = np.empty((len(st), T), np.float32)
+    for k, s in enumerate(st):
+        wk = raw / total[s:s + T]
+        wk[cover[s:s + T] == 1] = 1.0
+        w[k] = wk.astype(np.float32)
+    return w
+
+
 class DDPMTrainer(object):
     def __init__(self, args, encoder):
         self.opt = args
@@ -209,7 +237,8 @@ class DDPMTrainer(object):
             return self._validation_batch(xf_proj, xf_out, x0, lengths, t, noise, noise_seed, motion_encoder)
 
     def generate_long_music_motion(self, music_mel, dim_pose, overlap=LONG_OVERLAP, noise=None, seed=None, smooth=None, window=None,
-                                   guidance_scale=None, steps=None, spacing="uniform", solver="ddim"):
+                                   guidance_scale=None, steps=None, spacing="uniform", solver="ddim", joint=False, blend="tent",
+                                   known=None, known_mask=None, known_noise=None):
         """Conduct music LONGER than one window: music_mel [Tm,128] or [B,Tm,128] (pieces of one length), Tm at least one window
         (3 * window mel frames; ValueError below that - generate_music_motion serves those) -> tensor [B, L, dim_pose] with
         L = (Tm-1)//3 + 1.
@@ -228,11 +257,22 @@ class DDPMTrainer(object):
 
         `overlap` (frames, default LONG_OVERLAP = 300: 10 s); `smooth`: the Savitzky-Golay kernel size (order 5), applied ONCE
         over the whole piece with dc_savgol_filter (per window it would break the seams).  Every window runs the same captured
-        graph (the first with an all-zero mask) - also with `guidance_scale` (classifier-free guidance of every window's loop) and with `steps`, `spacing`, `solver` (every window's loop on that sub-sequence of timesteps, generate_music_motion; the solver's table carries the known slots and its last step lands on abar = 1, so the seams stay exact).  Not built: sharding pieces over the ranks of a torch.distributed group."""
+        graph (the first with an all-zero mask) - also with `guidance_scale` (classifier-free guidance of every window's loop) and with `steps`, `spacing`, `solver` (every window's loop on that sub-sequence of timesteps, generate_music_motion; the solver's table carries the known slots and its last step lands on abar = 1, so the seams stay exact).  Not built: sharding pieces over the ranks of a torch.distributed group.
+
+        `joint` (default False: the sequential path above, untouched): True samples ALL windows in ONE loop whose state is the whole
+        piece [B, L, dim_pose] - at every step the model is evaluated on the W * B windows as one batch and its predictions are
+        blended over the overlaps with window_weights(L, window, starts, `blend`) before the update (include/dc_ddim.h,
+        dc_sampler_set_conditioning_windows; GaussianDiffusion.ddim_sample_loop, window_starts=).  Same plan_windows, same single
+        encode_music call, same [B, L, dim_pose] noise.  No seam is causal any more, and `known`, `known_mask`, `known_noise` (as
+        ddim_sample_loop takes them, over the whole piece) may hold any frames of the piece, its middle included; `smooth` is then
+        folded into the loop's final write.  Needs overlap <= window / 2 (ValueError: beyond it a frame's weight is no longer a
+        hand-over between two neighbours).  known= without joint=True is a ValueError."""
         from . import native
         _, world = dist_info()
         if world > 1:
             raise NotImplementedError("generate_long_music_motion does not shard pieces over the ranks of a torch.distributed group yet")
+        if not joint and (known is not None or known_mask is not None or known_noise is not None):
+            raise ValueError("known= over a whole piece needs joint=True: the sequential path gives every window's known frames itself")
         mel = torch.as_tensor(np.asarray(music_mel) if not torch.is_tensor(music_mel) else music_mel)
         if mel.dim() == 2:
             mel = mel.unsqueeze(0)
@@ -244,6 +284,8 @@ class DDPMTrainer(object):
             raise ValueError(f"music of {Tm} mel frames is shorter than one window of {Tw}: use generate_music_motion")
         plan = plan_windows(L, T, overlap)
         W = len(plan)
+        if joint and 2 * int(overlap) > T:
+            raise ValueError(f"joint=True needs overlap <= window / 2 = {T // 2} frames, got {overlap}")
         if noise is None:
             g = None
             if seed is not None:
@@ -256,6 +298,14 @@ class DDPMTrainer(object):
         with torch.no_grad():
             mel_w = torch.stack([mel[:, min(3 * s, Tm - Tw):min(3 * s, Tm - Tw) + Tw] for s, _ in plan]).reshape(W * B, Tw, mel.shape[2])
             xf_proj, xf_out = self.encoder.encode_music(mel_w, self.device)
+            if joint:      # one loop over the W * B windows (window-major, as encoded), its state the whole piece
+                starts = [s for s, _ in plan]
+                return self.diffusion.ddim_sample_loop(
+                    self.encoder, (B, L, dim_pose), noise=noise, clip_denoised=False, progress=False,
+                    model_kwargs={"xf_proj": xf_proj, "xf_out": xf_out}, window_starts=starts,
+                    window_weights=window_weights(L, T, starts, blend), smooth=(int(smooth), 5) if smooth else None,
+                    known=known, known_mask=known_mask, known_noise=known_noise, guidance_scale=guidance_scale,
+                    **self._solver_kwargs(steps, spacing, solver))
             xf_proj, xf_out = xf_proj.view(W, B, T, -1), xf_out.view(W, B, T, -1)
             out = torch.zeros(B, L, dim_pose, dtype=torch.float32, device=self.device)
             length = torch.LongTensor([T] * B)

@@ -33,6 +33,7 @@ EXPORTS = [
     "dc_m2snet_score",
     "dc_solver_table", "dc_sampler_solver_loop", "dc_sampler_solver_profile_loop",
     "dc_sampler_set_conditioning_takes",
+    "dc_sampler_set_conditioning_windows", "dc_windows_check",
     "dc_q_sample_coefficients", "dc_q_sample", "dc_motion_loss_terms", "dc_latent_l1",
     "dc_m2sgan_create", "dc_m2sgan_destroy", "dc_m2sgan_set_param", "dc_m2sgan_finalize", "dc_m2sgan_features", "dc_m2sgan_decode",
     "dc_m2sgan_generate", "dc_m2sgan_debug_blocks", "dc_m2sgan_fold_conv", "dc_m2sgan_set_decoder",
@@ -159,6 +160,9 @@ def lib():
     L.dc_sampler_set_conditioning_guided.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, ip, C.c_int32, C.c_int32, fp, fp, C.c_void_p]
     L.dc_sampler_set_guidance_scale.argtypes = [C.c_void_p, C.c_float]
     L.dc_sampler_set_conditioning_takes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, ip, C.c_int32, C.c_int32, C.c_int32, fp, fp, C.c_void_p]
+    L.dc_sampler_set_conditioning_windows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, ip, ip, fp, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                      fp, fp, C.c_void_p]
+    L.dc_windows_check.argtypes = [ip, fp, C.c_int32, C.c_int32, C.c_int32, ip]
     L.dc_sampler_set_step_noise_seed.argtypes = [C.c_void_p, C.c_uint64]
     L.dc_sampler_set_step_noise_seed_at.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64]
     L.dc_step_noise_fill.argtypes = [C.c_void_p, C.c_int64, C.c_uint64, C.c_int32, C.c_void_p]
@@ -295,6 +299,19 @@ def savgol_coefficients(window: int, order: int) -> np.ndarray:
     out = np.empty((window, window), np.float32)
     _check(lib().dc_savgol_coefficients(int(window), int(order), _fptr(out)))
     return out
+
+
+def windows_check(starts, weights, T: int, L: int, length=None):
+    """dc_windows_check: the host's check of a plan of overlapping windows (starts [W], weights fp32 [W, T], pieces of L frames);
+    ValueError with the library's reason for a plan dc_sampler_set_conditioning_windows refuses (DC_ERR_INVALID)."""
+    st = np.ascontiguousarray(np.asarray(starts).reshape(-1), np.int32)
+    wt = np.ascontiguousarray(np.asarray(weights), np.float32).reshape(-1)
+    if wt.shape[0] != st.shape[0] * int(T):
+        raise ValueError(f"weights must be {(st.shape[0], int(T))}")
+    ln = None if length is None else np.ascontiguousarray(np.asarray(length).reshape(-1), np.int32)
+    rc = lib().dc_windows_check(_iptr(st), _fptr(wt), st.shape[0], int(T), int(L), None if ln is None else _iptr(ln))
+    if rc != 0:
+        raise ValueError(lib().dc_last_error().decode())
 
 
 def savgol_filter(poses, window: int = 19, order: int = 5):
@@ -484,6 +501,7 @@ class NativeSampler:
         self.B = self.T = 0
         self.guided = False
         self.takes = 1
+        self.windows = None      # (W, T) while the conditioning holds the windows of longer pieces (set_conditioning_windows)
 
     def close(self):
         if getattr(self, "_h", None) and self._h.value:
@@ -543,6 +561,35 @@ class NativeSampler:
         self.takes = int(takes)
         self.B, self.T = B * self.takes, T
         self.guided = null is not None
+        self.windows = None
+
+    def set_conditioning_windows(self, xf_proj, xf_out, starts, weights, L, null=None):
+        """dc_sampler_set_conditioning_windows: xf_proj, xf_out [W * B, T, 64], window-major (row k * B + b: window k of piece b),
+        `starts` [W], `weights` fp32 [W, T] (harness.window_weights), pieces of L frames; `null`: the pair that makes the loops guided.
+        Every tensor handed to the loops and to set_known is then [B, L, P]: self.B is the pieces, self.T is L.  A bad plan raises
+        ValueError here, before the library is called (windows_check)."""
+        import torch
+        assert xf_proj.is_cuda and xf_proj.dtype == torch.float32 and xf_proj.is_contiguous()
+        assert xf_out.is_cuda and xf_out.dtype == torch.float32 and xf_out.is_contiguous()
+        st = np.ascontiguousarray(np.asarray(starts).reshape(-1), np.int32)
+        W = int(st.shape[0])
+        WB, T, Cc = xf_proj.shape
+        if W < 1 or WB % W:
+            raise ValueError(f"{WB} feature rows are not {W} windows of whole pieces")
+        assert Cc == 64 and tuple(xf_out.shape) == (WB, T, 64)
+        wt = np.ascontiguousarray(np.asarray(weights), np.float32)
+        if wt.shape != (W, T):
+            raise ValueError(f"weights must be {(W, T)}, got {wt.shape}")
+        windows_check(st, wt, T, int(L))
+        nv = [None, None]
+        if null is not None:
+            nv = [np.ascontiguousarray(np.asarray(v.detach().cpu() if hasattr(v, "detach") else v), np.float32).reshape(-1) for v in null]
+            assert len(nv) == 2 and all(v.shape == (64,) for v in nv), "null = (null_proj[64], null_out[64])"
+        _check(lib().dc_sampler_set_conditioning_windows(self._h, xf_proj.data_ptr(), xf_out.data_ptr(), None, _iptr(st), _fptr(wt), WB // W, W,
+                                                         T, int(L), *[None if v is None else _fptr(v) for v in nv], self._stream()))
+        self.takes, self.guided = 1, null is not None
+        self.B, self.T = WB // W, int(L)
+        self.windows = (W, T)
 
     def set_guidance_scale(self, w):
         """dc_sampler_set_guidance_scale: out = c + (w - 1)(c - u) in the loops of a guided conditioning; another scale replays the same
@@ -598,6 +645,8 @@ class NativeSampler:
 
     def denoise(self, x, timesteps):
         import torch
+        if self.windows is not None:
+            raise ValueError("the conditioning holds the windows of longer pieces: a single evaluation has no piece to blend into")
         assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
         assert tuple(x.shape) == (self.B, self.T, self.cfg.input_feats)
         ta = np.ascontiguousarray(np.asarray(timesteps.cpu() if hasattr(timesteps, "cpu") else timesteps), np.int32)

@@ -467,6 +467,37 @@ class GaussianDiffusion:
             raise ValueError(f"shape[0]={shape[0]} must be takes x musics = {takes} x {int(ref.shape[0])}")
         return takes
 
+    def _check_windows(self, model, window_starts, window_weights, shape, model_kwargs, takes, denoised_fn, cond_fn, stepped=False):
+        """window_starts= / window_weights= blend the windows of longer pieces inside the native loop: None when neither was given
+        (today's loop), else (starts, weights fp32 [W, T], L) after the checks the host can make; ValueError where the call would step
+        through ddim_sample, with takes, and for features or a plan that do not fit `shape` = (B, L, P)."""
+        if window_starts is None and window_weights is None:
+            return None
+        if window_starts is None or window_weights is None:
+            raise ValueError("window_starts= and window_weights= come together (harness.window_weights makes the weights of a plan)")
+        if stepped or not self._fast_path_ok(model, denoised_fn, cond_fn):
+            raise ValueError("window_starts= blends the windows inside the native loop's update; "
+                             f"{'the progressive generator' if stepped else 'this call'} steps through ddim_sample, where there is no such step")
+        if takes != 1:
+            raise ValueError("windows do not combine with takes")
+        starts = [int(s) for s in np.asarray(window_starts).reshape(-1)]
+        weights = np.ascontiguousarray(np.asarray(window_weights.cpu() if th.is_tensor(window_weights) else window_weights), np.float32)
+        B, L = int(shape[0]), int(shape[1])
+        mk = model_kwargs or {}
+        ref = mk.get("xf_proj") if mk.get("xf_proj") is not None else mk.get("text")
+        if weights.ndim != 2 or weights.shape[0] != len(starts):
+            raise ValueError(f"window_weights must be [W, T] for the {len(starts)} window_starts, got {weights.shape}")
+        T = int(weights.shape[1])
+        if ref is not None and int(ref.shape[0]) != len(starts) * B:
+            raise ValueError(f"the features hold {int(ref.shape[0])} rows, not W x B = {len(starts)} x {B} windows (window-major)")
+        if mk.get("xf_proj") is not None and int(mk["xf_proj"].shape[1]) != T:
+            raise ValueError(f"the features hold windows of {int(mk['xf_proj'].shape[1])} frames, the weights of {T}")
+        ln = mk.get("length")
+        if ln is not None and any(int(v) != T for v in (ln.tolist() if hasattr(ln, "tolist") else ln)):
+            raise ValueError("windows are full: model_kwargs['length'] must be left out (or all T) with window_starts=")
+        native.windows_check(starts, weights, T, L)
+        return starts, weights, L
+
     def _solver_timesteps(self, model, steps, spacing, timesteps, solver, eta, denoised_fn, cond_fn, stepped=False):
         """The list of a loop on a sub-sequence (steps= / timesteps= / solver=), or None when none of them was given (today's loop).
         Such a loop runs natively only: ValueError where the call would step through ddim_sample, as for guidance_scale=."""
@@ -493,7 +524,7 @@ class GaussianDiffusion:
         return ts
 
     def _native_loop(self, model, img, mk, clip_denoised, eta, snap, step_noise, smooth=None, step_noise_seed=None, known=None,
-                     guidance_scale=None, timesteps=None, solver="ddim", takes=1):
+                     guidance_scale=None, timesteps=None, solver="ddim", takes=1, windows=None):
         """The captured loop on `model`'s sampler; returns (out, snaps).  Numeric health is checked once per call
         (`model.check_numerics`): a non-finite x0 under precision="auto" falls back to the bf16-range mode in a fresh sampler.
         `timesteps` (a list) runs dc_sampler_solver_loop on it with `solver`'s table; None the loop over every timestep."""
@@ -524,7 +555,11 @@ class GaussianDiffusion:
         retried = False
         while True:
             tk = {} if takes == 1 else {"takes": takes}      # (one take: the model is called as before)
-            if guidance_scale is None:
+            if windows is not None:      # (_check_windows: the windows are full, the lengths stay out)
+                nat = model.set_conditioning(mk["xf_proj"], mk["xf_out"], None, guided=guidance_scale is not None, windows=windows)
+                if guidance_scale is not None:
+                    nat.set_guidance_scale(guidance_scale)
+            elif guidance_scale is None:
                 nat = model.set_conditioning(mk["xf_proj"], mk["xf_out"], mk.get("length"), **tk)
             else:        # (inside the retry loop: precision="auto"'s re-run on a fresh sampler keeps the scale)
                 nat = model.set_conditioning(mk["xf_proj"], mk["xf_out"], mk.get("length"), guided=True, **tk)
@@ -553,7 +588,8 @@ class GaussianDiffusion:
     def ddim_sample_loop(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None, cond_fn=None,
                          model_kwargs=None, device=None, progress=False, eta=0.0, idxs=[], step_noise=None, smooth=None,
                          step_noise_seed=None, known=None, known_mask=None, known_noise=None, known_noise_seed=None,
-                         guidance_scale=None, steps=None, spacing="uniform", timesteps=None, solver="ddim", takes=1):
+                         guidance_scale=None, steps=None, spacing="uniform", timesteps=None, solver="ddim", takes=1,
+                         window_starts=None, window_weights=None):
         """gaussian_diffusion.py:871-915.  Returns the final sample, or when `idxs` is non-empty a
         dict {iteration: sample} for the listed iterations plus {num_timesteps: final}.
         `steps`, `spacing`, `timesteps`, `solver` (extension, native loop only; none given = today's loop over every timestep, bit for
@@ -581,9 +617,17 @@ class GaussianDiffusion:
         `takes` (extension, native loop only; 1 = today's loop): samples per music.  `model_kwargs` holds B musics and `shape[0]` must be
         takes * B (ValueError otherwise): clip j * B + b of `noise`, of the result and of every other [.., T, P] argument is take j of
         music b.  The takes share each step's FiLM tiles (include/dc_ddim.h, dc_sampler_set_conditioning_takes); the result equals the
-        loop over the music tiled `takes` times, bit for bit.  ValueError where the loop would step through ddim_sample."""
+        loop over the music tiled `takes` times, bit for bit.  ValueError where the loop would step through ddim_sample.
+        `window_starts`, `window_weights` (extension, native loop only; neither given = today's loop): sample pieces LONGER than the
+        model's window in one loop.  `shape` is (B, L, P) - and so are `noise`, the result, `idxs` snapshots, `step_noise` per
+        iteration and the known tensors -; `model_kwargs` holds the features of the W x B windows, [W * B, T, 64], window-major (row
+        k * B + b: window k of piece b, frames [window_starts[k], window_starts[k] + T) of it); `window_weights` fp32 [W, T] are the
+        blend weights (harness.window_weights).  At every step the model's predictions are blended over the windows that cover a
+        frame before the update (include/dc_ddim.h, dc_sampler_set_conditioning_windows).  ValueError for a plan the library
+        refuses, with takes, and where the loop would step through ddim_sample."""
         self._check_guidance(model, guidance_scale, denoised_fn, cond_fn)
         takes = self._check_takes(model, takes, shape, model_kwargs, denoised_fn, cond_fn)
+        windows = self._check_windows(model, window_starts, window_weights, shape, model_kwargs, takes, denoised_fn, cond_fn)
         ts = self._solver_timesteps(model, steps, spacing, timesteps, solver, eta, denoised_fn, cond_fn)
         n_iter = self.num_timesteps if ts is None else len(ts)
         self._refuse_epsilon_full_attention(model, eta)
@@ -600,7 +644,7 @@ class GaussianDiffusion:
             snap = sorted(int(i) for i in set(idxs) if 0 <= int(i) < n_iter)
             kn = self._known_tensors(img, known, known_mask, known_noise, known_noise_seed)
             out, snaps = self._native_loop(model, img, mk, bool(clip_denoised), float(eta), snap, step_noise, smooth, step_noise_seed, kn,
-                                            guidance_scale, ts, solver, takes)
+                                            guidance_scale, ts, solver, takes, windows)
             if len(idxs) == 0:
                 return out
             result = {it: snaps[k] for k, it in enumerate(snap)}
@@ -631,12 +675,13 @@ class GaussianDiffusion:
     def ddim_sample_loop_progressive(self, model, shape, noise=None, clip_denoised=True, denoised_fn=None,
                                      cond_fn=None, model_kwargs=None, device=None, progress=False, eta=0.0,
                                      step_noise=None, guidance_scale=None, steps=None, spacing="uniform", timesteps=None, solver="ddim",
-                                     takes=1):
+                                     takes=1, window_starts=None, window_weights=None):
         """gaussian_diffusion.py:917-965: yields {"sample","pred_xstart"} after every step.  `guidance_scale`, `steps`, `timesteps`,
-        `solver`, `takes`: the defaults only - this generator steps through ddim_sample (ValueError otherwise; ddim_sample_loop guides, and
+        `solver`, `takes`, `window_starts`, `window_weights`: the defaults only - this generator steps through ddim_sample (ValueError otherwise; ddim_sample_loop guides, and
         samples on a sub-sequence, inside the captured loop)."""
         self._check_guidance(model, guidance_scale, denoised_fn, cond_fn, stepped=True)
         self._check_takes(model, takes, shape, model_kwargs, denoised_fn, cond_fn, stepped=True)
+        self._check_windows(model, window_starts, window_weights, shape, model_kwargs, takes, denoised_fn, cond_fn, stepped=True)
         self._solver_timesteps(model, steps, spacing, timesteps, solver, eta, denoised_fn, cond_fn, stepped=True)
         self._refuse_epsilon_full_attention(model, eta)
         if device is None:

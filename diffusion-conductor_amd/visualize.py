@@ -123,6 +123,10 @@ def make_parser():
     parser.add_argument('--full_length', action='store_true',
                         help="conduct mels longer than one window (5400 frames = 60 s) whole, window by window around the frames "
                              "already generated (DDPMTrainer.generate_long_music_motion); without it only the first window is sampled")
+    parser.add_argument('--joint', action='store_true',
+                        help="with --full_length: sample all windows of a longer mel in ONE loop, blending their predictions over the "
+                             "overlaps at every step (generate_long_music_motion, joint=True) instead of window by window")
+    parser.add_argument('--blend', type=str, default="tent", choices=["tent", "uniform"], help="blend weights of --joint across an overlap")
     parser.add_argument('--precision', type=str, default="fp16", choices=["fp16", "mixed", "bf16x3", "bf16", "auto"])
     parser.add_argument('--steps', type=int, default=None, help="sample on this many of the schedule's timesteps (omitted: all of them)")
     parser.add_argument('--spacing', type=str, default="uniform", choices=["uniform", "logsnr"], help="how --steps picks them (use logsnr with dpmpp2m)")
@@ -162,8 +166,11 @@ def main(argv=None):
                 raise SystemExit("--takes samples one window per take: it does not combine with --full_length on a longer mel")
             gkw["takes"] = args.takes
         # [B, T, 26] on the device; --smooth: smooth_motion(kernel=19) (:126) happens in the loop's final write
+        if args.joint and not args.full_length:
+            raise SystemExit("--joint blends the windows of a longer mel: it goes with --full_length")
         if args.full_length and mel.shape[-2] > 3 * opt.max_motion_length:
-            pred_motions = trainer.generate_long_music_motion(mel, opt.dim_pose, seed=args.seed, smooth=19 if args.smooth else None, **gkw)
+            jkw = {"joint": True, "blend": args.blend} if args.joint else {}      # (without --joint the trainer is called as before)
+            pred_motions = trainer.generate_long_music_motion(mel, opt.dim_pose, seed=args.seed, smooth=19 if args.smooth else None, **gkw, **jkw)
         else:
             pred_motions = trainer.generate_music_motion(mel, opt.dim_pose, seed=args.seed, smooth=19 if args.smooth else None, **gkw)
         B, T = pred_motions.shape[0], pred_motions.shape[1]

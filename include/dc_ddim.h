@@ -328,6 +328,37 @@ DC_EXPORT int dc_sampler_set_conditioning_takes(dc_sampler* s, const float* d_xf
                                                 int32_t B, int32_t T, int32_t takes, const float* h_null_proj, const float* h_null_out,
                                                 void* stream);
 
+/* Overlapping WINDOWS of a longer piece in ONE loop, blended at every step (no counterpart in the reference, which samples one window;
+ * the scheme is MultiDiffusion's).  A piece has L frames and is covered by W windows of T frames at ascending starts
+ * s_0 = 0 < ... < s_{W-1} = L - T, without gaps (s_{k+1} <= s_k + T) and with at most 4 windows over a frame.  The loop's state is ONE
+ * tensor in piece space, x [B, L, P].  At every step
+ *   1. window k's frames are rows [s_k, s_k + T) of x: overlapping windows read the same x_t;
+ *   2. the model is evaluated on the W B windows, window-major - internal clip k B + b is window k of piece b, with its own music
+ *      features (d_xf_proj, d_xf_out: fp32 [W B, T, 64] in that order) - and the last layer stores the raw output;
+ *   3. for every piece element,  out = sum_k w[k][f - s_k] raw_k[f - s_k]  over the windows that cover frame f, in ascending k: fp32,
+ *      no contraction, the accumulator starting from the first product, w = h_weight, fp32 [W][T];
+ *   4. the update of dc_sampler_ddim_loop_ex / dc_sampler_solver_loop and the replacement of known values are applied to `out`
+ *      exactly as a guided loop applies them: eta noise, clipping, EPSILON, the multistep term, snapshots, DC_STATUS_NONFINITE;
+ *      noise, step noise, known values, the multistep history and snapshots are all [B, L, P];
+ *   5. x_{t-1} is written to piece space and to every covering window's slot of the internal x.
+ * With the null pair given the conditioning is guided as dc_sampler_set_conditioning_guided: the conditional and the unconditional raw
+ * outputs are blended each (step 3), combined as c + (w - 1)(c - u), then updated; 2 W B internal clips.
+ * The loop entry points then take and return [B, L, P] (d_noise, d_out, d_snaps, d_step_noise per iteration, seeded step noise, the
+ * tensors of dc_sampler_set_known, smoothing runs over the L frames).  A frame under one window, whose weight is then exactly 1, takes
+ * that window's output bit for bit: W = 1 (L = T), and windows that do not overlap, give the bits of the plain loop on those clips
+ * in the same launch form.  Starts and weights reach the kernels through device tables: another plan of the same (B, W, T, L) replays
+ * the captured hipGraph.  dc_sampler_denoise and the debug entry points return DC_ERR_INVALID on such a conditioning; a plain
+ * dc_sampler_set_conditioning switches windows off; known values belong to the (B, W, T, L) they were set on.  Windows do not combine
+ * with takes.  Synchronous (the tables are host arrays).
+ * DC_ERR_INVALID, on the host before anything is enqueued (dc_windows_check is that check alone, no sampler or GPU needed): starts that
+ * are unordered or leave a gap, s_0 != 0, s_{W-1} != L - T, more than 4 windows over a frame, W > 65535, a weight that is negative or
+ * not finite, weights over a frame that do not sum to 1 within 4 ulp of fp32 (summed in fp64), an h_length (windows are full: must be
+ * NULL), exactly one vector of the null pair. */
+DC_EXPORT int dc_sampler_set_conditioning_windows(dc_sampler* s, const float* d_xf_proj, const float* d_xf_out, const int32_t* h_length,
+                                                  const int32_t* h_start, const float* h_weight, int32_t B, int32_t W, int32_t T, int32_t L,
+                                                  const float* h_null_proj, const float* h_null_out, void* stream);
+DC_EXPORT int dc_windows_check(const int32_t* h_start, const float* h_weight, int32_t W, int32_t T, int32_t L, const int32_t* h_length);
+
 /* The guidance scale w of the loops on a guided conditioning (same reference lines: transformer.py:389,451-459 train for it, no sampling
  * counterpart).  1 after every dc_sampler_set_conditioning_guided.  Must be finite (DC_ERR_INVALID), and a guided conditioning must be
  * set.  The scale reaches the kernels through a device slot: another scale replays the same hipGraph. */
