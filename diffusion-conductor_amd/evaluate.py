@@ -13,7 +13,9 @@ copy behind an event and are scored on a third thread - the GPU's queue never ru
 :126) on the GPU.
 
 ``validation_dataset`` (``--val_loss``) scores a checkpoint WITHOUT sampling it: the held-out value of the denoising objective it was
-trained on (models/gaussian_diffusion.py:1002-1090, trainers/ddpm_trainer.py:223-268), per noise level.
+trained on (models/gaussian_diffusion.py:1002-1090, trainers/ddpm_trainer.py:223-268), per noise level.  ``bound_dataset``
+(``--bpd``) scores it by its variational bound in bits per dimension (calc_bpd_loop, models/gaussian_diffusion.py:1110-1165): one
+model evaluation per clip and timestep, as a per-timestep table.
 """
 from __future__ import annotations
 
@@ -664,6 +666,68 @@ def validation_dataset(trainer, root, timesteps=None, batch_size=32, seed=0, mot
     return {"clips": len(ids), "timesteps": grid, "per_timestep": rows, "average": avg, "evaluations": n_levels, "seconds": dt}
 
 
+def bound_grid(num_timesteps, k):
+    """The `k` evenly spaced timesteps of a --bpd table, decreasing; 0 and S - 1 are always among them (k >= 2; k = 1 gives [S - 1])."""
+    S, k = int(num_timesteps), int(k)
+    if not 1 <= k:
+        raise ValueError(f"the table needs at least one timestep, got {k}")
+    if k == 1:
+        return [S - 1]
+    return sorted({int(v) for v in np.floor(np.linspace(0, S - 1, k) + 0.5)} | {0, S - 1}, reverse=True)
+
+
+def bound_dataset(trainer, root, timesteps=None, batch_size=32, seed=0, limit=None):
+    """Scores a checkpoint by its VARIATIONAL BOUND in bits per dimension (DDPMTrainer.bound_bpd, GaussianDiffusion.calc_bpd_loop) over
+    every clip under `root`: one model evaluation per clip and timestep, no sampling loop.
+    `timesteps`: an int K - the table bound_grid(S, K); a list - those timesteps; None - every timestep of the schedule, which is what
+    the total needs.  Each batch's music is encoded once.  Step t's noise is the library's device draw (seed + batch index,
+    iteration = t).
+    Returns {"clips", "timesteps" (decreasing), "total_bpd" (mean over the clips; None for a subset), "prior_bpd",
+    "per_timestep": [{"t", "vb", "xstart_mse", "mse"}] (means over the clips), "evaluations" (model evaluations per clip), "seconds"}."""
+    ids = list_clips(root)
+    if limit is not None:
+        ids = ids[:int(limit)]
+    if not ids:
+        raise FileNotFoundError(f"no <id>/mel.npy + <id>/motion.npy pairs under {root}")
+    S = int(trainer.diffusion.num_timesteps)
+    grid = None
+    if timesteps is not None:
+        grid = bound_grid(S, timesteps) if np.ndim(timesteps) == 0 else sorted({int(v) for v in timesteps}, reverse=True)
+        if not grid or any(not 0 <= v < S for v in grid):
+            raise ValueError(f"timesteps must be inside [0, {S}), got {grid}")
+    mel_shape = tuple(np.load(pjoin(root, ids[0], "mel.npy"), mmap_mode="r").shape)
+    T = (mel_shape[0] - 1) // 3 + 1
+    nb = (len(ids) + batch_size - 1) // batch_size
+    pf = _Prefetcher(root, ids, batch_size, mel_shape)
+    pf.start(0)
+    dev = trainer.device
+    slot_free = [None, None]
+    rows = []
+    t0 = time.perf_counter()
+    for k in range(nb):
+        bid, mel, gts = pf.take()
+        if k + 1 < nb:
+            pf.start(k + 1, after=slot_free[(k + 1) & 1])
+        bad = [(cid, np.shape(g)) for cid, g in zip(bid, gts) if int(np.prod(np.shape(g))) != T * 26]
+        if bad:
+            raise ValueError(f"the music gives {T} frames, but these motions differ: {bad[:4]}")
+        x0 = torch.from_numpy(np.ascontiguousarray(np.stack([np.reshape(g, (T, 26)) for g in gts]), np.float32)).to(dev)
+        with torch.no_grad():
+            xf_proj, xf_out = trainer.encoder.encode_music(mel, dev)
+        if torch.device(dev).type == "cuda":
+            slot_free[k & 1] = torch.cuda.Event()
+            slot_free[k & 1].record()
+        rows.append(trainer._bound_batch(xf_proj, xf_out, x0, np.full(len(bid), T, np.int64), grid, int(seed) + k))
+    dt = time.perf_counter() - t0
+    ts = rows[0]["timesteps"]
+    cat = {key: np.concatenate([r[key] for r in rows]) for key in ("vb", "xstart_mse", "mse", "prior_bpd")}
+    total = None if grid is not None else float(np.concatenate([r["total_bpd"] for r in rows]).mean())
+    return {"clips": len(ids), "timesteps": ts, "total_bpd": total, "prior_bpd": float(cat["prior_bpd"].mean()),
+            "per_timestep": [{"t": t, "vb": float(cat["vb"][:, i].mean()), "xstart_mse": float(cat["xstart_mse"][:, i].mean()),
+                              "mse": float(cat["mse"][:, i].mean())} for i, t in enumerate(ts)],
+            "evaluations": len(ts), "seconds": dt}
+
+
 def _evaluation_encoders(args, dev):
     """(motion encoder for --metrics | None, M2SNet for --sync | None) as main's flags ask for them."""
     menc = None
@@ -753,6 +817,10 @@ def main(argv=None):
                                                             "one JSON line, no sampling loop (validation_dataset)")
     ap.add_argument("--val_timesteps", type=int, default=None, help="--val_loss on a grid of this many noise levels (omitted: one uniform "
                                                                     "timestep per clip, the training protocol)")
+    ap.add_argument("--bpd", action="store_true", help="score the checkpoint by its variational bound in bits per dimension instead of "
+                                                       "sampling it: one JSON line, one model evaluation per clip and timestep (bound_dataset)")
+    ap.add_argument("--bpd_timesteps", type=int, default=None, help="--bpd on this many evenly spaced timesteps, 0 and S - 1 among them "
+                                                                    "(omitted: every timestep, which the total needs)")
     ap.add_argument("--rhythm", action="store_true", help="also RDE, SCE and the standard deviations of the sampled and the real motion "
                                                           "(M2SGAN_eval.py:100-133; rhythm.py, metrics.py)")
     ap.add_argument("--discriminator", default=None, help="M2S-GAN critic checkpoint (a plain state_dict, M2SGAN_eval.py:453): also the "
@@ -781,6 +849,18 @@ def main(argv=None):
     if args.val_loss and (args.beats or args.beat_stride != 1):
         ap.error("--val_loss scores the checkpoint without sampling it: --beats and --beat_stride score sampled motion and cannot be "
                  "combined with it")
+    if args.bpd_timesteps is not None and not args.bpd:
+        ap.error("--bpd_timesteps picks the timesteps of --bpd and says nothing without it")
+    if args.bpd:
+        clash = [f for f, on in (("--val_loss", args.val_loss), ("--baseline_generator", args.baseline_generator), ("--rhythm", args.rhythm),
+                                 ("--discriminator", args.discriminator), ("--beats", args.beats), ("--beat_stride", args.beat_stride != 1),
+                                 ("--metrics", args.metrics), ("--sync", args.sync), ("--smooth", args.smooth),
+                                 ("--guidance_scale", args.guidance_scale is not None), ("--steps", args.steps is not None),
+                                 ("--solver", args.solver != "ddim"), ("--spacing", args.spacing != "uniform")) if on]
+        if clash:
+            ap.error(f"--bpd scores the checkpoint without sampling it: {', '.join(clash)} cannot be combined with it")
+        if args.bpd_timesteps is not None and args.bpd_timesteps < 1:
+            ap.error("--bpd_timesteps must be >= 1")
     if args.beat_stride != 1 and not args.beats:
         ap.error("--beat_stride places the music beats of --beats and says nothing without it")
     if args.beat_stride < 1:
@@ -800,6 +880,10 @@ def main(argv=None):
         from .synthetic import synthetic_state_dict
         enc.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in synthetic_state_dict().items()}, strict=True)
     tr.eval_mode()
+    if args.bpd:
+        import json
+        print(json.dumps(bound_dataset(tr, args.data_root, args.bpd_timesteps, args.batch_size, args.seed, limit=args.limit)))
+        return 0
     menc, m2s = _evaluation_encoders(args, dev)
     if args.val_loss:
         import json

@@ -236,6 +236,51 @@ class DDPMTrainer(object):
                 raise ValueError(f"the music gives {xf_proj.shape[1]} frames, the motions have {T}")
             return self._validation_batch(xf_proj, xf_out, x0, lengths, t, noise, noise_seed, motion_encoder)
 
+    def bound_bpd(self, music_mel, motions, m_lens=None, timesteps=None, seed=None):
+        """The variational bound of the checkpoint on held-out clips, in bits per dimension (GaussianDiffusion.calc_bpd_loop,
+        gaussian_diffusion.py:1110-1165): music_mel [B, 5400, 128] and motions [B, T, 13, 2] (or [B, T, 26]), or one clip of each; m_lens
+        [B] frame counts for the model's mask (None: all T).  ONE encode_music call, then one model evaluation per timestep.
+        timesteps: a list - only those (the sum is then left out); None - every timestep of the schedule.
+        seed: of the library's device draws, step t's noise being (seed, iteration = t); None draws one from torch's generator.
+        Returns the per-clip arrays "vb" [B, K], "xstart_mse" [B, K], "mse" [B, K] (columns by descending "timesteps"), "prior_bpd" [B],
+        "total_bpd" [B] (None for a subset), and their means over the clips: "mean_total_bpd" (or None), "mean_prior_bpd", "mean_vb" [K],
+        "mean_xstart_mse" [K], "mean_mse" [K]."""
+        mel = torch.as_tensor(np.asarray(music_mel) if not torch.is_tensor(music_mel) else music_mel)
+        x0 = torch.as_tensor(np.asarray(motions) if not torch.is_tensor(motions) else motions)
+        if mel.dim() == 2:
+            mel = mel.unsqueeze(0)
+        if x0.dim() == 3 and x0.shape[-1] == 2:
+            x0 = x0.unsqueeze(0)
+        B, T = int(x0.shape[0]), int(x0.shape[1])
+        if mel.shape[0] != B:
+            raise ValueError(f"{mel.shape[0]} musics for {B} motions")
+        x0 = x0.to(self.device, dtype=torch.float32).reshape(B, T, -1).contiguous()
+        lengths = np.full(B, T, np.int64) if m_lens is None else np.minimum(np.asarray(m_lens, np.int64).reshape(B), T)
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        with torch.no_grad():
+            xf_proj, xf_out = self.encoder.encode_music(mel if mel.is_cuda else mel.to(self.device, dtype=torch.float32), self.device)
+            if xf_proj.shape[1] != T:
+                raise ValueError(f"the music gives {xf_proj.shape[1]} frames, the motions have {T}")
+            return self._bound_batch(xf_proj, xf_out, x0, lengths, timesteps, seed)
+
+    def _bound_batch(self, xf_proj, xf_out, x0, lengths, timesteps, seed):
+        """bound_bpd on music that is already encoded: x0 [B, T, 26] on the device, lengths a host int array [B]."""
+        S = int(self.diffusion.num_timesteps)
+        r = self.diffusion.calc_bpd_loop(self.encoder, x0, clip_denoised=True, noise_seed=seed, timesteps=timesteps,
+                                         model_kwargs={"xf_proj": xf_proj, "xf_out": xf_out, "length": torch.as_tensor(np.asarray(lengths, np.int64))})
+        K = int(r["vb"].shape[1])
+        full = r["total_bpd"] is not None
+        # the one wait: every array below is a slice of this [B, 3 K + 2] host tensor
+        flat = torch.cat([r["vb"], r["xstart_mse"], r["mse"], r["prior_bpd"][:, None],
+                          (r["total_bpd"] if full else r["prior_bpd"])[:, None]], dim=1).cpu().numpy()
+        out = {"timesteps": list(range(S))[::-1] if timesteps is None else sorted({int(v) for v in np.asarray(timesteps).reshape(-1)}, reverse=True),
+               "vb": flat[:, :K], "xstart_mse": flat[:, K:2 * K], "mse": flat[:, 2 * K:3 * K], "prior_bpd": flat[:, 3 * K],
+               "total_bpd": flat[:, 3 * K + 1] if full else None}
+        out.update(mean_total_bpd=float(out["total_bpd"].mean()) if full else None, mean_prior_bpd=float(out["prior_bpd"].mean()),
+                   mean_vb=out["vb"].mean(axis=0), mean_xstart_mse=out["xstart_mse"].mean(axis=0), mean_mse=out["mse"].mean(axis=0))
+        return out
+
     def generate_long_music_motion(self, music_mel, dim_pose, overlap=LONG_OVERLAP, noise=None, seed=None, smooth=None, window=None,
                                    guidance_scale=None, steps=None, spacing="uniform", solver="ddim", joint=False, blend="tent",
                                    known=None, known_mask=None, known_noise=None):

@@ -35,6 +35,7 @@ EXPORTS = [
     "dc_sampler_set_conditioning_takes",
     "dc_sampler_set_conditioning_windows", "dc_windows_check",
     "dc_q_sample_coefficients", "dc_q_sample", "dc_motion_loss_terms", "dc_latent_l1",
+    "dc_vb_coefficients", "dc_vb_workspace_floats", "dc_vb_terms", "dc_prior_kl",
     "dc_m2sgan_create", "dc_m2sgan_destroy", "dc_m2sgan_set_param", "dc_m2sgan_finalize", "dc_m2sgan_features", "dc_m2sgan_decode",
     "dc_m2sgan_generate", "dc_m2sgan_debug_blocks", "dc_m2sgan_fold_conv", "dc_m2sgan_set_decoder",
     "dc_bilstm_create", "dc_bilstm_destroy", "dc_bilstm_set_param", "dc_bilstm_finalize", "dc_bilstm_input_size", "dc_bilstm_decode",
@@ -49,6 +50,10 @@ STATUS_NONFINITE, STATUS_F16_SATURATED, STATUS_TIMEOUT = 1, 2, 4        # bits o
 SOLVER_ROW = 12                                       # DC_SOLVER_ROW: floats per row of dc_solver_table
 SOLVER_ORDER = {"ddim": 1, "dpmpp2m": 2}              # solver= of the Python surfaces -> order of dc_solver_table
 LOSS_TERMS = 8                                        # DC_LOSS_TERMS: floats per clip of dc_motion_loss_terms
+VB_TERMS = 8                                          # DC_VB_TERMS: floats per clip of dc_vb_terms
+VB_COEF = 12                                          # DC_VB_COEF: floats per clip of dc_vb_coefficients
+VB_MEAN = {"PREVIOUS_X": 1, "START_X": 2, "EPSILON": 3}                                  # DC_VB_MEAN_*
+VB_VAR = {"LEARNED": 1, "FIXED_SMALL": 2, "FIXED_LARGE": 3, "LEARNED_RANGE": 4}          # DC_VB_VAR_*
 
 
 class DcConfig(C.Structure):
@@ -192,6 +197,11 @@ def lib():
                               C.c_void_p, C.c_void_p, C.c_void_p]
     L.dc_motion_loss_terms.argtypes = [C.c_void_p, C.c_void_p, ip, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     L.dc_latent_l1.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    L.dc_vb_coefficients.argtypes = [C.c_int32, dp, C.c_int32, ip, C.c_int32, fp]
+    L.dc_vb_workspace_floats.restype = C.c_int64
+    L.dc_vb_workspace_floats.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    L.dc_vb_terms.argtypes = [C.c_void_p] * 5 + [fp] + [C.c_int32] * 6 + [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.dc_prior_kl.argtypes = [C.c_void_p, fp, fp, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     L.dc_m2sgan_create.argtypes = [C.c_int32, C.POINTER(C.c_void_p)]
     L.dc_m2sgan_destroy.argtypes = [C.c_void_p]
     L.dc_m2sgan_destroy.restype = None
@@ -413,6 +423,67 @@ def latent_l1(a, b):
     with torch.cuda.device(a.device):
         _check(lib().dc_latent_l1(a.data_ptr(), b.data_ptr(), int(a.shape[0]), int(a.shape[2]), out.data_ptr(),
                                   C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    return out
+
+
+def _vb_type(table, v, what):
+    """A DC_VB_MEAN_* / DC_VB_VAR_* number from an enum member (by name), a name or the number itself."""
+    name = getattr(v, "name", v)
+    if isinstance(name, str):
+        if name not in table:
+            raise ValueError(f"{what} must be one of {sorted(table)}, got {name!r}")
+        return table[name]
+    return int(name)
+
+
+def vb_coefficients(betas: np.ndarray, var_type, timesteps):
+    """dc_vb_coefficients: fp32 [B, VB_COEF] per clip - posterior_mean_coef1 / coef2, posterior_log_variance_clipped, the model's fixed
+    log-variance (LEARNED_RANGE: max_log), sqrt_recip / sqrt_recipm1_alphas_cumprod, the t == 0 flag, 1 / coef1, coef2 / coef1 - each
+    (float) of the float64 table entry (host only).  DcError for a timestep outside the schedule."""
+    be = np.ascontiguousarray(betas, np.float64).reshape(-1)
+    ts = np.ascontiguousarray(np.asarray(timesteps.cpu() if hasattr(timesteps, "cpu") else timesteps).reshape(-1), np.int32)
+    out = np.zeros((max(ts.shape[0], 1), VB_COEF), np.float32)
+    _check(lib().dc_vb_coefficients(be.shape[0], be.ctypes.data_as(C.POINTER(C.c_double)), _vb_type(VB_VAR, var_type, "var_type"),
+                                    _iptr(ts), ts.shape[0], _fptr(out)))
+    return out
+
+
+def vb_terms(x_start, x_t, model_out, coef, mean_type, var_type, clip_denoised=True, var_values=None, noise=None):
+    """dc_vb_terms on fp32 device tensors [B, T, ...]: per clip [B, VB_TERMS] - output (t == 0 ? decoder_nll : kl), kl, decoder_nll (bits),
+    xstart_mse, mse ((eps - noise)^2; 0 without `noise`), 0, 0, 0 - from `coef` of vb_coefficients.  `var_values`: the variance half of a
+    LEARNED / LEARNED_RANGE model's output."""
+    import torch
+    x = _loss_tensor(x_start, "x_start")
+    B, T = int(x.shape[0]), int(x.shape[1])
+    P = x.numel() // max(B * T, 1)
+    xt, mo = _loss_tensor(x_t, "x_t", x.shape), _loss_tensor(model_out, "model_out", x.shape)
+    vv = None if var_values is None else _loss_tensor(var_values, "var_values", x.shape)
+    nz = None if noise is None else _loss_tensor(noise, "noise", x.shape)
+    cf = np.ascontiguousarray(coef, np.float32)
+    assert cf.shape == (B, VB_COEF), "one row of vb_coefficients per clip"
+    L = lib()
+    work = torch.empty((max(int(L.dc_vb_workspace_floats(B, T, P)), 1),), dtype=torch.float32, device=x.device)
+    out = torch.empty((B, VB_TERMS), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _check(L.dc_vb_terms(x.data_ptr(), xt.data_ptr(), mo.data_ptr(), None if vv is None else vv.data_ptr(),
+                             None if nz is None else nz.data_ptr(), _fptr(cf), _vb_type(VB_MEAN, mean_type, "mean_type"),
+                             _vb_type(VB_VAR, var_type, "var_type"), int(bool(clip_denoised)), B, T, P, work.data_ptr(), out.data_ptr(),
+                             C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    return out
+
+
+def prior_kl(x_start, a, logvar):
+    """dc_prior_kl: x_start fp32 [B, T, ...] on the device, host arrays a, logvar [B] -> the prior term of the bound per clip, bits, [B]."""
+    import torch
+    x = _loss_tensor(x_start, "x_start")
+    B, T = int(x.shape[0]), int(x.shape[1])
+    P = x.numel() // max(B * T, 1)
+    a, lv = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(logvar, np.float32)
+    assert a.shape == (B,) and lv.shape == (B,), "one (a, logvar) pair per clip"
+    out = torch.empty((B,), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _check(lib().dc_prior_kl(x.data_ptr(), _fptr(a), _fptr(lv), B, T, P, out.data_ptr(),
+                                 C.c_void_p(torch.cuda.current_stream().cuda_stream)))
     return out
 
 

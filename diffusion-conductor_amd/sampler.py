@@ -19,9 +19,17 @@ call still going through the native denoiser; ``p_mean_variance`` (:442-536) is 
 The FORWARD VALUE of the training objective is here as an evaluator: ``q_sample`` (:398-416) and
 ``training_losses`` (:1002-1090) for the MSE loss types, under ``no_grad`` - with this package's
 MotionTransformer on a GPU the noising and the reductions are the kernels of csrc/dc_loss.hip, with
-any other callable or device the same definitions in plain torch.  Gradients, the optimiser, the
-variational bound (``LossType.KL`` / ``RESCALED_KL``, learned variances), ancestral ``p_sample``
-and the loss-aware schedule samplers stay out of scope and are not provided.
+any other callable or device the same definitions in plain torch.
+
+So is the VARIATIONAL BOUND as a score: ``normal_kl`` (:162-188), ``approx_standard_normal_cdf``,
+``discretized_gaussian_log_likelihood`` (:191-225), ``mean_flat``, ``q_mean_variance`` (:381-396),
+``_vb_terms_bpd`` (:967-1000), ``_prior_bpd`` (:1092-1108) and ``calc_bpd_loop`` (:1110-1165), for all
+three mean types and all four variance types.  On GPU tensors what follows each model evaluation is
+one fused pass (dc_vb_terms); on the host, or with ``denoised_fn``, the same definitions in plain torch.
+
+Gradients, the optimiser, the bound as a TRAINING objective (``LossType.KL`` / ``RESCALED_KL`` and the
+learned-variance term of ``training_losses``), ancestral ``p_sample`` and the loss-aware schedule
+samplers stay out of scope and are not provided.
 """
 from __future__ import annotations
 
@@ -113,14 +121,53 @@ class LossType(enum.Enum):
         return self == LossType.KL or self == LossType.RESCALED_KL
 
 
-def _extract(arr, timesteps, broadcast_shape):
+def _extract(arr, timesteps, broadcast_shape, device=None):
     """_extract_into_tensor (gaussian_diffusion.py:1168-1181) without the per-call H2D copy of the
-    whole table: the needed scalars are gathered on the host."""
+    whole table: the needed scalars are gathered on the host.  `device` (default: the timesteps' own): where the result goes -
+    timesteps kept on the host then cost no wait for the device."""
     t = timesteps.detach().cpu().numpy()
-    res = th.from_numpy(np.asarray(arr)[t]).float().to(timesteps.device)
+    res = th.from_numpy(np.asarray(arr)[t]).float().to(timesteps.device if device is None else device)
     while len(res.shape) < len(broadcast_shape):
         res = res[..., None]
     return res.expand(broadcast_shape)
+
+
+def mean_flat(tensor):
+    """gaussian_diffusion.py:155-159: the mean over all non-batch dimensions."""
+    return tensor.mean(dim=list(range(1, len(tensor.shape))))
+
+
+def normal_kl(mean1, logvar1, mean2, logvar2):
+    """gaussian_diffusion.py:162-188: the KL divergence between two gaussians; shapes broadcast, scalars are accepted."""
+    tensor = None
+    for obj in (mean1, logvar1, mean2, logvar2):
+        if isinstance(obj, th.Tensor):
+            tensor = obj
+            break
+    assert tensor is not None, "at least one argument must be a Tensor"
+    logvar1, logvar2 = [x if isinstance(x, th.Tensor) else th.tensor(x).to(tensor) for x in (logvar1, logvar2)]
+    return 0.5 * (-1.0 + logvar2 - logvar1 + th.exp(logvar1 - logvar2) + ((mean1 - mean2) ** 2) * th.exp(-logvar2))
+
+
+def approx_standard_normal_cdf(x):
+    """gaussian_diffusion.py:191-196: the tanh approximation of the standard normal's cumulative distribution function."""
+    return 0.5 * (1.0 + th.tanh(np.sqrt(2.0 / np.pi) * (x + 0.044715 * th.pow(x, 3))))
+
+
+def discretized_gaussian_log_likelihood(x, *, means, log_scales):
+    """gaussian_diffusion.py:199-225: the log-likelihood (nats) of a Gaussian discretised to bins of 2/255 around `x` in [-1, 1]; the
+    two outermost bins are open-ended, and a probability is clamped at 1e-12."""
+    assert x.shape == means.shape == log_scales.shape
+    centered_x = x - means
+    inv_stdv = th.exp(-log_scales)
+    cdf_plus = approx_standard_normal_cdf(inv_stdv * (centered_x + 1.0 / 255.0))
+    cdf_min = approx_standard_normal_cdf(inv_stdv * (centered_x - 1.0 / 255.0))
+    log_cdf_plus = th.log(cdf_plus.clamp(min=1e-12))
+    log_one_minus_cdf_min = th.log((1.0 - cdf_min).clamp(min=1e-12))
+    cdf_delta = cdf_plus - cdf_min
+    log_probs = th.where(x < -0.999, log_cdf_plus, th.where(x > 0.999, log_one_minus_cdf_min, th.log(cdf_delta.clamp(min=1e-12))))
+    assert log_probs.shape == x.shape
+    return log_probs
 
 
 class GaussianDiffusion:
@@ -140,6 +187,7 @@ class GaussianDiffusion:
         self.alphas_cumprod_next = np.append(self.alphas_cumprod[1:], 0.0)
         self.sqrt_alphas_cumprod = np.sqrt(self.alphas_cumprod)
         self.sqrt_one_minus_alphas_cumprod = np.sqrt(1.0 - self.alphas_cumprod)
+        self.log_one_minus_alphas_cumprod = np.log(1.0 - self.alphas_cumprod)
         self.sqrt_recip_alphas_cumprod = np.sqrt(1.0 / self.alphas_cumprod)
         self.sqrt_recipm1_alphas_cumprod = np.sqrt(1.0 / self.alphas_cumprod - 1)
         # posterior q(x_{t-1} | x_t, x_0) (gaussian_diffusion.py:363-379): read by the PREVIOUS_X parameterisation, the learned-range
@@ -158,18 +206,18 @@ class GaussianDiffusion:
         return t
 
     def _predict_eps_from_xstart(self, x_t, t, pred_xstart):
-        return (_extract(self.sqrt_recip_alphas_cumprod, t, x_t.shape) * x_t - pred_xstart) / \
-            _extract(self.sqrt_recipm1_alphas_cumprod, t, x_t.shape)
+        return (_extract(self.sqrt_recip_alphas_cumprod, t, x_t.shape, x_t.device) * x_t - pred_xstart) / \
+            _extract(self.sqrt_recipm1_alphas_cumprod, t, x_t.shape, x_t.device)
 
     def _predict_xstart_from_eps(self, x_t, t, eps):
-        return _extract(self.sqrt_recip_alphas_cumprod, t, x_t.shape) * x_t - \
-            _extract(self.sqrt_recipm1_alphas_cumprod, t, x_t.shape) * eps
+        return _extract(self.sqrt_recip_alphas_cumprod, t, x_t.shape, x_t.device) * x_t - \
+            _extract(self.sqrt_recipm1_alphas_cumprod, t, x_t.shape, x_t.device) * eps
 
     def _predict_xstart_from_xprev(self, x_t, t, xprev):
         """gaussian_diffusion.py:545-553: (xprev - coef2 * x_t) / coef1."""
         assert x_t.shape == xprev.shape
-        return _extract(1.0 / self.posterior_mean_coef1, t, x_t.shape) * xprev - \
-            _extract(self.posterior_mean_coef2 / self.posterior_mean_coef1, t, x_t.shape) * x_t
+        return _extract(1.0 / self.posterior_mean_coef1, t, x_t.shape, x_t.device) * xprev - \
+            _extract(self.posterior_mean_coef2 / self.posterior_mean_coef1, t, x_t.shape, x_t.device) * x_t
 
     def q_posterior_mean_variance(self, x_start, x_t, t):
         """gaussian_diffusion.py:418-440."""
@@ -304,7 +352,8 @@ class GaussianDiffusion:
         The target is x_start (START_X), the noise (EPSILON) or the posterior mean (PREVIOUS_X).
         `noise_seed` (extension, GPU only): as q_sample.  With this package's MotionTransformer on a GPU the noising and the
         reductions are libdc_ddim's kernels; with any other callable or device the same definitions in plain torch.
-        NotImplementedError: LossType.KL / RESCALED_KL and learned variances (the variational bound is out of scope).
+        NotImplementedError: LossType.KL / RESCALED_KL and learned variances (the variational bound as a training objective is out of
+        scope; calc_bpd_loop scores it).
         ValueError: T < 2 - the velocity means run over no elements there and the reference returns NaN."""
         if self.loss_type.is_vb():
             raise NotImplementedError(f"{self.loss_type}: the variational bound is out of scope; LossType.MSE / RESCALED_MSE only")
@@ -350,6 +399,105 @@ class GaussianDiffusion:
             terms = native.motion_loss_terms(pred, target, length) if on_gpu else self.loss_terms_torch(pred, target, length)
         return {"mse": terms[:, 0], "velocity_body": terms[:, 2].mean(), "velocity_elbow": terms[:, 3].mean(),
                 "velocity_head": terms[:, 4].mean(), "velocity": terms[:, 5].mean(), "target": target, "pred": pred, "terms": terms}
+
+    # ---- the variational bound, as a score ------------------------------------------------
+    def q_mean_variance(self, x_start, t):
+        """gaussian_diffusion.py:381-396: (mean, variance, log_variance) of q(x_t | x_0)."""
+        mean = _extract(self.sqrt_alphas_cumprod, t, x_start.shape) * x_start
+        return mean, _extract(1.0 - self.alphas_cumprod, t, x_start.shape), _extract(self.log_one_minus_alphas_cumprod, t, x_start.shape)
+
+    def vb_terms_torch(self, x_start, x_t, t, out, noise=None):
+        """native.vb_terms in plain torch (fp32, any device) from `out` = p_mean_variance's dict: [B, 8] per clip - output, kl,
+        decoder_nll (bits), xstart_mse, mse (0 without `noise`), 0, 0, 0 (include/dc_ddim.h, dc_vb_terms)."""
+        true_mean, _, true_log_variance_clipped = self.q_posterior_mean_variance(x_start=x_start, x_t=x_t, t=t)
+        kl = mean_flat(normal_kl(true_mean, true_log_variance_clipped, out["mean"], out["log_variance"])) / np.log(2.0)
+        decoder_nll = -discretized_gaussian_log_likelihood(x_start, means=out["mean"], log_scales=0.5 * out["log_variance"])
+        assert decoder_nll.shape == x_start.shape
+        decoder_nll = mean_flat(decoder_nll) / np.log(2.0)
+        cols = [th.where((t == 0), decoder_nll, kl), kl, decoder_nll, mean_flat((out["pred_xstart"] - x_start) ** 2)]
+        zero = th.zeros_like(kl)
+        cols.append(zero if noise is None else mean_flat((self._predict_eps_from_xstart(x_t, t, out["pred_xstart"]) - noise) ** 2))
+        return th.stack(cols + [zero, zero, zero], dim=1)
+
+    def _vb_terms_bpd(self, model, x_start, x_t, t, clip_denoised=True, model_kwargs=None, *, denoised_fn=None, noise=None):
+        """gaussian_diffusion.py:967-1000: {"output": [N] NLLs (t == 0) or KLs in bits, "pred_xstart"}, plus the extension key "terms"
+        [N, 8] (include/dc_ddim.h, dc_vb_terms: output, kl, decoder_nll, xstart_mse, mse, 0, 0, 0).  On GPU tensors the model call is
+        followed by ONE fused pass over x_start, x_t and the model's output (native.vb_terms); on the host, or with `denoised_fn`
+        (extension: p_mean_variance's), the same definitions in plain torch.  `noise` (extension): the draw x_t was noised with - fills
+        "terms"[:, 4], calc_bpd_loop's epsilon error.  `t` may stay on the host beside GPU tensors: nothing then waits for the device."""
+        x = th.as_tensor(x_start)
+        t = th.as_tensor(t).long()
+        with th.no_grad():
+            if not x.is_cuda or denoised_fn is not None:
+                t = t.to(x.device)
+                out = self.p_mean_variance(model, x_t, t, clip_denoised=clip_denoised, denoised_fn=denoised_fn, model_kwargs=model_kwargs)
+                terms = self.vb_terms_torch(x, x_t, t, out, noise)
+                return {"output": terms[:, 0], "pred_xstart": out["pred_xstart"], "terms": terms}
+            x = x.to(th.float32).contiguous()
+            xt = th.as_tensor(x_t).to(device=x.device, dtype=th.float32).contiguous()
+            t_host = t.cpu()
+            # (this package's denoiser reads its timesteps on the host; any other callable gets them where the reference puts them)
+            model_output, var_values = self._model_output(model, xt, t_host if isinstance(model, MotionTransformer) else t.to(x.device),
+                                                          model_kwargs)
+            model_output = th.as_tensor(model_output).to(th.float32).contiguous()
+            coef = native.vb_coefficients(self.betas, self.model_var_type, t_host)
+            terms = native.vb_terms(x, xt, model_output.reshape(x.shape), coef, self.model_mean_type, self.model_var_type, clip_denoised,
+                                    var_values=None if var_values is None else var_values.to(th.float32).contiguous().reshape(x.shape),
+                                    noise=None if noise is None else th.as_tensor(noise).to(device=x.device, dtype=th.float32).contiguous())
+            pred_xstart = self._xstart_of(model_output.reshape(xt.shape), xt, t_host, clip_denoised, None)
+        return {"output": terms[:, 0], "pred_xstart": pred_xstart, "terms": terms}
+
+    def _prior_bpd(self, x_start):
+        """gaussian_diffusion.py:1092-1108: the prior term of the bound, KL(q(x_T | x_0) || N(0, I)) in bits per dimension, [N]."""
+        x = th.as_tensor(x_start)
+        B = int(x.shape[0])
+        if x.is_cuda:
+            S = self.num_timesteps
+            return native.prior_kl(x.to(th.float32).contiguous(), np.full(B, np.float32(self.sqrt_alphas_cumprod[S - 1])),
+                                   np.full(B, np.float32(self.log_one_minus_alphas_cumprod[S - 1])))
+        t = th.tensor([self.num_timesteps - 1] * B, device=x.device)
+        qt_mean, _, qt_log_variance = self.q_mean_variance(x, t)
+        return mean_flat(normal_kl(mean1=qt_mean, logvar1=qt_log_variance, mean2=0.0, logvar2=0.0)) / np.log(2.0)
+
+    def calc_bpd_loop(self, model, x_start, clip_denoised=True, model_kwargs=None, *, noise_seed=None, timesteps=None):
+        """gaussian_diffusion.py:1110-1165: the whole variational bound in bits per dimension - ONE model evaluation per timestep of the
+        schedule, from S - 1 down to 0.  Returns "total_bpd" [N], "prior_bpd" [N], "vb" [N, S], "xstart_mse" [N, S], "mse" [N, S]
+        (columns in the loop's order: column 0 is t = S - 1).  With GPU tensors the noising is dc_q_sample and what follows each
+        evaluation is dc_vb_terms; nothing in the loop waits for the device.
+        `noise_seed` (extension, GPU only): step t's noise is the library's draw (seed, iteration = t) in place of th.randn_like.
+        `timesteps` (extension): evaluate only these timesteps; the K columns are in descending order of t, and "total_bpd" is None -
+        the sum needs every term."""
+        x = th.as_tensor(x_start)
+        B, S = int(x.shape[0]), self.num_timesteps
+        if timesteps is None:
+            ts = list(range(S))[::-1]
+        else:
+            ts = sorted({int(v) for v in np.asarray(timesteps).reshape(-1)}, reverse=True)
+            if not ts or ts[0] >= S or ts[-1] < 0:
+                raise ValueError(f"timesteps must be inside [0, {S}), got {ts}")
+        if noise_seed is not None and not x.is_cuda:
+            raise ValueError("noise_seed= draws on the device; on the host the noise is th.randn_like's")
+        if x.is_cuda:
+            x = x.to(th.float32).contiguous()
+        terms = []
+        for t in ts:
+            t_batch = th.full((B,), t, dtype=th.long)      # on the host: the tables are gathered there
+            if x.is_cuda:
+                a, s = native.q_sample_coefficients(self.alphas_cumprod, t_batch)
+                if noise_seed is not None:
+                    x_t, noise = native.q_sample(x, a, s, noise_seed=(noise_seed, t, 0), return_noise=True)
+                else:
+                    noise = th.randn_like(x)
+                    x_t = native.q_sample(x, a, s, noise=noise)
+            else:
+                noise = th.randn_like(x)
+                x_t = self.q_sample(x_start=x, t=t_batch, noise=noise)
+            terms.append(self._vb_terms_bpd(model, x_start=x, x_t=x_t, t=t_batch, clip_denoised=clip_denoised, model_kwargs=model_kwargs,
+                                            noise=noise)["terms"])
+        terms = th.stack(terms, dim=1)      # [N, K, 8]
+        vb, prior_bpd = terms[:, :, 0], self._prior_bpd(x)
+        return {"total_bpd": vb.sum(dim=1) + prior_bpd if timesteps is None else None, "prior_bpd": prior_bpd, "vb": vb,
+                "xstart_mse": terms[:, :, 3], "mse": terms[:, :, 4]}
 
     # ---- DDIM ---------------------------------------------------------------------------
     def ddim_sample(self, model, x, t, clip_denoised=True, denoised_fn=None, cond_fn=None, model_kwargs=None,

@@ -771,6 +771,66 @@ DC_EXPORT int dc_motion_loss_terms(const float* d_pred, const float* d_target, c
  * The reference's scalar is the plain mean over the clips.  Same reduction rules as dc_motion_loss_terms.  B, T >= 1. */
 DC_EXPORT int dc_latent_l1(const float* d_a, const float* d_b, int32_t B, int32_t T, float* d_out, void* stream);
 
+/* ---- The variational bound: scoring a checkpoint in bits per dimension ---------------------------------------------------------
+ * GaussianDiffusion.calc_bpd_loop (models/gaussian_diffusion.py:1110-1165) evaluates the model at EVERY timestep and, behind each
+ * evaluation, _vb_terms_bpd (:967-1000) with normal_kl (:162-188) and discretized_gaussian_log_likelihood (:199-225), the x0 error
+ * (:1149) and the epsilon error (:1150-1151); _prior_bpd (:1092-1108) closes the sum.  The model evaluation is dc_sampler_denoise, the
+ * noising dc_q_sample; what follows an evaluation is ONE fused pass here.  Implemented in csrc/dc_loss.hip; not on the sampling path. */
+
+/* The reference's enums (:275-308, enum.auto() in their order). */
+#define DC_VB_MEAN_PREVIOUS_X 1
+#define DC_VB_MEAN_START_X 2
+#define DC_VB_MEAN_EPSILON 3
+#define DC_VB_VAR_LEARNED 1
+#define DC_VB_VAR_FIXED_SMALL 2
+#define DC_VB_VAR_FIXED_LARGE 3
+#define DC_VB_VAR_LEARNED_RANGE 4
+
+/* The per-clip scalars of one step, from the tables GaussianDiffusion.__init__ builds of h_betas fp64 [n_train] (:328-379), each
+ * (float) of the fp64 entry - what _extract_into_tensor(...).float() (:1168-1181) yields.  h_coef fp32 [B][DC_VB_COEF]:
+ *   [0] [1]  posterior_mean_coef1 / coef2 [t]                                   (:373-379)
+ *   [2]      posterior_log_variance_clipped [t]  (= min_log of LEARNED_RANGE)   (:368-372)
+ *   [3]      the model's log-variance: FIXED_SMALL the same entry, FIXED_LARGE log(append(posterior_variance[1], betas[1:]))[t]
+ *            (:488-503), LEARNED_RANGE max_log = log(betas)[t] (:479-480), LEARNED 0 (not read)
+ *   [4] [5]  sqrt_recip_alphas_cumprod [t], sqrt_recipm1_alphas_cumprod [t]     (:357-358)
+ *   [6]      1 where t == 0 (the step whose term is the decoder NLL, :999), else 0
+ *   [7] [8]  (1 / posterior_mean_coef1) [t], (posterior_mean_coef2 / posterior_mean_coef1) [t]: PREVIOUS_X's pred_xstart (:545-553)
+ *   [9..11]  0
+ * DC_ERR_INVALID: a timestep outside [0, n_train), a beta outside (0, 1], an unknown var_type, FIXED_LARGE with n_train < 2.
+ * Host only. */
+#define DC_VB_COEF 12
+DC_EXPORT int dc_vb_coefficients(int32_t n_train, const double* h_betas, int32_t var_type, const int32_t* h_timesteps, int32_t B,
+                                 float* h_coef);
+
+/* _vb_terms_bpd (:967-1000) behind p_mean_variance (:442-536), and the two errors of calc_bpd_loop (:1149-1151), PER CLIP: d_x0, d_xt,
+ * d_model_out (the mean-parameter half of the model's output), d_var_values (the other half of a LEARNED / LEARNED_RANGE model, NULL
+ * for a fixed variance), d_noise (the draw d_xt was noised with; NULL: slot 4 is not computed) fp32 [B, T, P], h_coef of
+ * dc_vb_coefficients -> d_terms fp32 [B][DC_VB_TERMS]:
+ *   [0]  output = t == 0 ? decoder_nll : kl                                     (:999)
+ *   [1]  kl = mean normal_kl(true_mean, true_log_variance_clipped, mean, log_variance) / log 2          (:986-989)
+ *   [2]  decoder_nll = - mean discretized_gaussian_log_likelihood(x0, mean, 0.5 log_variance) / log 2   (:991-995)
+ *   [3]  xstart_mse = mean (pred_xstart - x0)^2                                 (:1149)
+ *   [4]  mse = mean (eps - noise)^2, eps = _predict_eps_from_xstart(x_t, t, pred_xstart)   (:1150-1151; 0 without d_noise)
+ *   [5..7]  0
+ * The per-element expressions are the reference's fp32 expressions in the reference's order, never contracted, with tanhf / logf /
+ * expf: where fp32 tanh saturates the clamp at 1e-12 gives log 1e-12, as in the reference.  mean_type DC_VB_MEAN_*, var_type
+ * DC_VB_VAR_*, clip_denoised as p_mean_variance's.  Any P >= 1.  Deterministic and batch-independent: a clip is reduced by a number
+ * of workgroups that depends on T * P only, their partial sums (d_workspace, dc_vb_workspace_floats(B, T, P) floats) are added in
+ * index order by a second launch; no floating-point atomics (orders and rounding counts: csrc/dc_loss.hip).
+ * DC_ERR_INVALID before any device call: a NULL pointer, B, T or P < 1, T * P >= 2^31 - 1, an unknown type, d_var_values missing for a
+ * learned variance or given beside a fixed one. */
+#define DC_VB_TERMS 8
+DC_EXPORT int64_t dc_vb_workspace_floats(int32_t B, int32_t T, int32_t P);
+DC_EXPORT int dc_vb_terms(const float* d_x0, const float* d_xt, const float* d_model_out, const float* d_var_values, const float* d_noise,
+                          const float* h_coef, int32_t mean_type, int32_t var_type, int32_t clip_denoised, int32_t B, int32_t T,
+                          int32_t P, float* d_workspace, float* d_terms, void* stream);
+
+/* _prior_bpd (:1092-1108): d_out[b] = mean over (T, P) of normal_kl(h_a[b] * x0, h_logvar[b], 0, 0) / log 2, with h_a[b] =
+ * (float)sqrt_alphas_cumprod[S - 1] and h_logvar[b] = (float)log_one_minus_alphas_cumprod[S - 1] (host arrays [B]).  One workgroup per
+ * clip, same reduction rules. */
+DC_EXPORT int dc_prior_kl(const float* d_x0, const float* h_a, const float* h_logvar, int32_t B, int32_t T, int32_t P, float* d_out,
+                          void* stream);
+
 /* Introspection used by tests: bytes of device workspace currently held; frames per clip of the sampler's internal token space
  * (the T of dc_sampler_set_conditioning, padded to whole 32-frame groups where the clip-aligned kernels run): the layout of the
  * buffers dc_sampler_debug_read returns. */
