@@ -50,6 +50,16 @@ DEV void split8(const float (&v)[8], bf16x8& hi, bf16x8& lo) {
         lo[j] = (__bf16)(v[j] - (float)h);
     }
 }
+// torch.relu and max_pool2d: NaN stays NaN (fmaxf is v_max_f32, which returns the non-NaN operand; dc_mfma_f32.h has the same rule)
+DEV float relu(float y) { return y < 0.f ? 0.f : y; }
+// ... as two pinned instructions: in k_me_stem's phase A at 128 registers the compiler's own pair costs 12 more spilled registers
+// (k_me_stem<8, 64, false>: 752 -> 847 us per 32 clips; pinned: the parent's 10 spills)
+DEV float relu_pinned(float y) {
+    float r;
+    asm("v_cmp_gt_f32 vcc, 0, %1\n\tv_cndmask_b32_e64 %0, %1, 0, vcc" : "=v"(r) : "v"(y) : "vcc");
+    return r;
+}
+DEV float nanmax(float m, float v) { return (v > m || v != v) ? v : m; }
 DEV f32x16 zero16() {
     f32x16 x;
 #pragma unroll
@@ -179,7 +189,7 @@ __global__ __launch_bounds__(256) void k_me_conv(const float* __restrict__ mel, 
             const int c0 = 8 * q + 4 * kh;          // this lane's 4 consecutive output channels of register group q
             float v[4];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = fmaxf(acc[4 * q + e] + bias[4 * q + e], 0.f);
+            for (int e = 0; e < 4; ++e) v[e] = relu(acc[4 * q + e] + bias[4 * q + e]);
             if constexpr (RES == 1) {
                 const __bf16* ph = reinterpret_cast<const __bf16*>(in_hi) + pix * CIN + c0;
                 const __bf16* pl = reinterpret_cast<const __bf16*>(in_lo) + pix * CIN + c0;
@@ -302,7 +312,7 @@ __global__ __launch_bounds__(256, 2) void k_me_conv_t(const typename PL<SP>::v8*
                 const int c0 = 8 * q + 4 * kh;          // this lane's 4 consecutive output channels of register group q
                 float v[4];
 #pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = fmaxf(acc[i][4 * q + e] + bias[4 * q + e], 0.f);
+                for (int e = 0; e < 4; ++e) v[e] = relu(acc[i][4 * q + e] + bias[4 * q + e]);
                 if constexpr (RES == 1) {               // input channels c0 .. c0+3 of the centre pixel: half kh of piece (q >> 1, q & 1)
                     const int pc = ((q >> 1) * 2 + (q & 1)) * SEL + (r + 1) * PXW + seg * 32 + n + 1;
                     const V4 xh = reinterpret_cast<const V4*>(tl + pc)[kh];
@@ -456,7 +466,7 @@ __global__ __launch_bounds__(512, SP ? 2 : 4) void k_me_stem(const float* __rest
                 }
                 float v[4];
 #pragma unroll
-                for (int c = 0; c < 4; ++c) v[c] = fmaxf(acc[c], 0.f);
+                for (int c = 0; c < 4; ++c) v[c] = relu_pinned(acc[c]);
                 char* dst = TA + (size_t)(((quad >> 1) * NA + p) * 16 + (quad & 1) * 8);
                 put4(v, reinterpret_cast<E*>(dst), reinterpret_cast<E*>(dst + 2 * NA * 16));
                 px += 128 - RAW;
@@ -486,7 +496,7 @@ __global__ __launch_bounds__(512, SP ? 2 : 4) void k_me_stem(const float* __rest
                 const V4 rl = *reinterpret_cast<const V4*>(ctr + (LO * 2 + hp) * NA * 16 + ho);
                 float v[4];
 #pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = fmaxf(acc[e] + bb[e], 0.f) + val4(rh, rl, e);
+                for (int e = 0; e < 4; ++e) v[e] = relu(acc[e] + bb[e]) + val4(rh, rl, e);
                 if (f < NB) {
                     char* dst = TB + (size_t)((hp * NBP + f) * 16 + ho);
                     put4(v, reinterpret_cast<E*>(dst), reinterpret_cast<E*>(dst + 2 * NBP * 16));
@@ -520,7 +530,7 @@ __global__ __launch_bounds__(512, SP ? 2 : 4) void k_me_stem(const float* __rest
                 const V4 rl = *reinterpret_cast<const V4*>(ctr + (LO * 2 + hp) * NBP * 16 + ho);
                 float v[4];
 #pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = fmaxf(acc[e] + bc[e], 0.f) + val4(rh, rl, e);
+                for (int e = 0; e < 4; ++e) v[e] = relu(acc[e] + bc[e]) + val4(rh, rl, e);
                 if (y0 + row0 + 2 * k < H) put4(v, out_hi + pix * 16 + 4 * q4, out_lo + pix * 16 + 4 * q4);
                 org += 2 * RBW * 16;
                 pix += 2 * (size_t)W;
@@ -633,7 +643,7 @@ __global__ __launch_bounds__(512, SP ? 2 : 4) void k_me_mid(const typename PL<SP
             for (int q = 0; q < 4; ++q) {           // output channels 8 q + 4 kh .. + 3: chunk q >> 1, half q & 1, byte offset 8 kh
                 float v[4];
 #pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] = fmaxf(acc[4 * q + e] + bias0[4 * q + e], 0.f) + res[4 * q + e] + rbias0[4 * q + e];
+                for (int e = 0; e < 4; ++e) v[e] = relu(acc[4 * q + e] + bias0[4 * q + e]) + res[4 * q + e] + rbias0[4 * q + e];
                 if (f < NB) {
                     V8* dst = TB + ((q >> 1) * 2 + (q & 1)) * NBP + f;
                     put4(v, reinterpret_cast<E*>(dst) + 4 * kh, reinterpret_cast<E*>(dst + 4 * NBP) + 4 * kh);
@@ -665,7 +675,7 @@ __global__ __launch_bounds__(512, SP ? 2 : 4) void k_me_mid(const typename PL<SP
                     const V4 xl = reinterpret_cast<const V4*>(ctr + (LO * 4 + (q >> 1) * 2 + (q & 1)) * NBP)[kh];
                     float v[4];
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = fmaxf(acc[4 * q + e] + bias1[4 * q + e], 0.f) + val4(xh, xl, e);
+                    for (int e = 0; e < 4; ++e) v[e] = relu(acc[4 * q + e] + bias1[4 * q + e]) + val4(xh, xl, e);
                     put4(v, out_hi + pix * 32 + 8 * q + 4 * kh, out_lo + pix * 32 + 8 * q + 4 * kh);
                 }
             }
@@ -674,7 +684,7 @@ __global__ __launch_bounds__(512, SP ? 2 : 4) void k_me_mid(const typename PL<SP
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// max_pool2d on the plane pair; padding never wins (torch pads with -inf).  One thread per (pixel, 8 channels).
+// max_pool2d on the plane pair; padding never wins (torch pads with -inf) and a NaN always does (nanmax).  One thread per (pixel, 8 channels).
 // hi + lo is exact in fp32 (<= 17 significant bits), so the maximum re-splits into the very planes it came from.
 // ---------------------------------------------------------------------------------------------------------
 // Sliding window along time: a thread owns (clip, output column, 8 channels) and walks NY consecutive output rows,
@@ -713,7 +723,7 @@ __global__ __launch_bounds__(256) void k_me_pool(const bf16x8* __restrict__ in_h
             for (int i = 0; i < XO; ++i)
                 if (c >= i * SW && c < i * SW + KW) {
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) m[i][j] = fmaxf(m[i][j], (float)h[j] + (float)l[j]);
+                    for (int j = 0; j < 8; ++j) m[i][j] = nanmax(m[i][j], (float)h[j] + (float)l[j]);
                 }
         }
     };
@@ -729,7 +739,7 @@ __global__ __launch_bounds__(256) void k_me_pool(const bf16x8* __restrict__ in_h
             for (int j = 0; j < 8; ++j) {
                 m[j] = ring[0][i][j];
 #pragma unroll
-                for (int k = 1; k < KH; ++k) m[j] = fmaxf(m[j], ring[k][i][j]);
+                for (int k = 1; k < KH; ++k) m[j] = nanmax(m[j], ring[k][i][j]);
             }
             bf16x8 oh, ol;
             split8(m, oh, ol);
@@ -751,6 +761,27 @@ __global__ __launch_bounds__(256) void k_me_pool(const bf16x8* __restrict__ in_h
 }
 // The same sliding window on ONE fp16 plane: the maximum of fp16 values is one of them, so the window works on the packed values
 // (v_pk_max_f16: 4 instructions per 8 channels and tap, 4 registers per row maximum) and the output is exact.
+// v_pk_max_f16 drops a NaN like fmaxf, and max_pool2d keeps it: beside the maximum the window carries a = fma(x, 0, a), +0 until a
+// value is NaN (v_pk_fma_f16: one more instruction per tap; the magnitude bits through v_pk_max_u16 cost two and 46 us per 32 clips),
+// and the output is m | a: the maximum's own bits, or a NaN.  An infinity in the window gives NaN as well (inf x 0) where max_pool2d
+// returns it or, for -inf, a finite maximum: the plane holds one only after an fp16 overflow, and either way the output is not finite.
+typedef __attribute__((ext_vector_type(8))) short i16x8;
+struct PoolWin {
+    f16x8 m;           // maximum of the non-NaN values
+    f16x8 a;           // +0, or NaN
+};
+DEV void pool_take(PoolWin& w, f16x8 x) {
+    f16x8 z;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) z[j] = (_Float16)0.f;
+    w.m = __builtin_elementwise_max(w.m, x);
+    w.a = __builtin_elementwise_fma(x, z, w.a);
+}
+DEV void pool_merge(PoolWin& w, const PoolWin& o) {
+    w.m = __builtin_elementwise_max(w.m, o.m);
+    w.a = w.a + o.a;
+}
+DEV f16x8 pool_value(const PoolWin& w) { return __builtin_bit_cast(f16x8, __builtin_bit_cast(i16x8, w.m) | __builtin_bit_cast(i16x8, w.a)); }
 template <int KH, int KW, int SH, int SW, int PH, int PW>
 __global__ __launch_bounds__(256) void k_me_pool16(const f16x8* __restrict__ in, f16x8* __restrict__ out, int Bc, int H, int W, int C8, int Ho,
                                                    int Wo, int NY) {
@@ -762,18 +793,21 @@ __global__ __launch_bounds__(256) void k_me_pool16(const f16x8* __restrict__ in,
     const int xo = (int)((idx / C8) % Wo);
     const int sy = (int)((idx / ((long long)C8 * Wo)) % strips);
     const int b = (int)(idx / ((long long)C8 * Wo * strips));
-    f16x8 ninf;
+    PoolWin none;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) ninf[j] = (_Float16)(-INFINITY);
-    f16x8 ring[KH];
+    for (int j = 0; j < 8; ++j) {
+        none.m[j] = (_Float16)(-INFINITY);
+        none.a[j] = (_Float16)0.f;
+    }
+    PoolWin ring[KH];
     auto row_max = [&](int yy) {
-        f16x8 m = ninf;
+        PoolWin m = none;
         if (yy < 0 || yy >= H) return m;
 #pragma unroll
         for (int c = 0; c < KW; ++c) {
             const int xx = xo * SW - PW + c;
             if (xx < 0 || xx >= W) continue;
-            m = __builtin_elementwise_max(m, in[(((size_t)b * H + yy) * W + xx) * C8 + c8]);
+            pool_take(m, in[(((size_t)b * H + yy) * W + xx) * C8 + c8]);
         }
         return m;
     };
@@ -781,10 +815,10 @@ __global__ __launch_bounds__(256) void k_me_pool16(const f16x8* __restrict__ in,
 #pragma unroll
     for (int k = 0; k < KH; ++k) ring[k] = row_max(yo0 * SH - PH + k);
     for (int yo = yo0; yo < yo1; ++yo) {
-        f16x8 m = ring[0];
+        PoolWin m = ring[0];
 #pragma unroll
-        for (int k = 1; k < KH; ++k) m = __builtin_elementwise_max(m, ring[k]);
-        out[(((size_t)b * Ho + yo) * Wo + xo) * C8 + c8] = m;
+        for (int k = 1; k < KH; ++k) pool_merge(m, ring[k]);
+        out[(((size_t)b * Ho + yo) * Wo + xo) * C8 + c8] = pool_value(m);
         if (yo + 1 < yo1) {
 #pragma unroll
             for (int k = 0; k + SH < KH; ++k) ring[k] = ring[k + SH];

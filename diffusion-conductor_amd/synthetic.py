@@ -219,6 +219,50 @@ def motion_encoder_weight_variant(kind: str, seed: int = 1):
     return sd
 
 
+MUSIC_ENCODER_VARIANTS = ("seeded", "bn_stress", "dead_channels", "identity")
+MUSIC_ENCODER_DEAD_BIAS = -100.0          # BatchNorm bias of a dead channel: its pre-activation stays negative for any mel in [0, 1]
+
+
+def music_encoder_weight_variant(kind: str, seed: int = 1):
+    """synthetic_state_dict() (the seeded denoiser checkpoint, seed 0) with only its `music_encoder.*` entries replaced:
+      seeded         those of synthetic_state_dict(seed=seed);
+      bn_stress      ... and every BatchNorm (`residual.1` and `conv4.1` included) with gains of both signs, running_var log-uniform in
+                     [1e-4, 2] (the gain scales with sqrt(var) so activations stay O(1)) and running_mean ~ 2 N(0, 1);
+      dead_channels  ... and channels c % 4 == 1 of every ReLU layer pinned to zero by a BatchNorm bias of MUSIC_ENCODER_DEAD_BIAS (the
+                     1x1 residual's BatchNorm of conv2.0 zeroed on the same channels, so the sum is 0 as well): the same channels in
+                     every layer, so they are exactly 0 in every pool window - ties with each other and with the other channels' zeros;
+      identity       ... and identity BatchNorms (the control)."""
+    if kind not in MUSIC_ENCODER_VARIANTS:
+        raise ValueError(f"unknown music encoder weight variant {kind!r}")
+    sd = synthetic_state_dict(seed=0)
+    for k, v in synthetic_state_dict(seed=seed).items():
+        if k.startswith("music_encoder."):
+            sd[k] = v.copy()
+    g = _rng(seed, "music_encoder_variant:" + kind)
+    bns = sorted({k.rsplit(".", 1)[0] + "." for k in sd if k.startswith("music_encoder.") and k.endswith("running_var")})
+    if kind == "bn_stress":
+        for p in bns:
+            c = sd[p + "running_var"].shape[0]
+            var = np.exp(g.uniform(np.log(1e-4), np.log(2.0), c))
+            sd[p + "running_var"] = var.astype(np.float32)
+            sd[p + "weight"] = (np.where(g.random(c) < 0.5, -1.0, 1.0) * g.uniform(0.7, 1.3, c) * np.sqrt(var)).astype(np.float32)
+            sd[p + "running_mean"] = (2.0 * g.standard_normal(c)).astype(np.float32)
+    elif kind == "dead_channels":
+        for p in bns:
+            dead = np.arange(sd[p + "bias"].shape[0]) % 4 == 1
+            if ".conv2d_layer.1." in p:
+                sd[p + "bias"][dead] = MUSIC_ENCODER_DEAD_BIAS
+            elif ".residual.1." in p:
+                sd[p + "weight"][dead] = 0.0
+                sd[p + "bias"][dead] = 0.0
+    elif kind == "identity":
+        for p in bns:
+            c = sd[p + "running_var"].shape[0]
+            sd[p + "weight"], sd[p + "running_var"] = np.ones(c, np.float32), np.ones(c, np.float32)
+            sd[p + "bias"], sd[p + "running_mean"] = np.zeros(c, np.float32), np.zeros(c, np.float32)
+    return sd
+
+
 def synthetic_motion(B, T, seed=5, first=0):
     """[B, T, 13, 2] fp32 smooth pose-like tracks (random walks around a random rest pose, in [-1, 1]-ish units)."""
     out = np.empty((B, T, 13, 2), np.float32)
