@@ -161,10 +161,11 @@ def _encode_pair(motion_encoder, pred, gts, dim_pose, ids):
     return gen_lat, real_lat
 
 
-def _sync_predictions(m2snet, mel, pred, gts, dim_pose):
+def _sync_predictions(m2snet, mel, pred, gts, dim_pose, keep=None):
     """M2SNet's per-frame predictions [B, T] for a batch, the music encoded once and fused with three motions: the ground truth,
     the sampled poses, and the sampled poses of the NEXT clip of the batch (rolled by one: the mismatched control; None for a batch
-    of one clip).  Enqueued on the current stream; the tensors stay on the poses' device."""
+    of one clip).  Enqueued on the current stream; the tensors stay on the poses' device.  `keep` (a list, for the retrieval
+    scores): the batch's three latents - music [B, T, 64], real and generated motion [B, 64, T] - are put into it."""
     B, T = pred.shape[0], pred.shape[1]
     gt = torch.from_numpy(np.ascontiguousarray(np.stack(gts), np.float32))
     mel = torch.as_tensor(mel)
@@ -172,11 +173,43 @@ def _sync_predictions(m2snet, mel, pred, gts, dim_pose):
         gt = gt.pin_memory().to(pred.device, non_blocking=True)
         mel = mel.to(pred.device, non_blocking=True)
     mus = m2snet.music_latent(mel)
-    real = m2snet.fuse(mus, m2snet.motion_latent(gt))
+    real_lat = m2snet.motion_latent(gt)
+    real = m2snet.fuse(mus, real_lat)
     gen_lat = m2snet.motion_latent(pred.reshape(B, T, dim_pose // 2, 2))
     gen = m2snet.fuse(mus, gen_lat)
     mis = m2snet.fuse(mus, torch.roll(gen_lat, -1, 0).contiguous()) if B > 1 else None
+    if keep is not None:
+        keep[:] = [mus, real_lat, gen_lat]
     return real, gen, mis
+
+
+RETRIEVAL_TOP_K = (1, 2, 3)            # the reference's R-precision columns (Diffusion_Stage/utils/metrics.py calculate_R_precision, top_k = 3)
+
+
+def _retrieval_scores(m2snet, kept, ids, batch_size, top_k=RETRIEVAL_TOP_K):
+    """The m2s_* retrieval keys of evaluate_dataset from every batch's kept latents ({batch: [music, real, generated]}): all clips'
+    music against all clips' real and generated motion (M2SNet.fuse_pairs), ranked on the host (metrics.retrieval_stats,
+    metrics.pair_accuracy)."""
+    from .metrics import pair_accuracy, retrieval_stats
+    nb = len(kept)
+    T = int(kept[0][0].shape[1])
+    for k in range(nb):
+        Tk = int(kept[k][0].shape[1])
+        if Tk != T or any(int(kept[k][i].shape[2]) != T for i in (1, 2)):
+            raise ValueError(f"the retrieval scores pair every music with every motion and need one latent length: clip {ids[0]} has {T} "
+                             f"frames, clip {ids[k * batch_size]} has {Tk}")
+    mus, real, gen = (torch.cat([kept[k][i] for k in range(nb)]) for i in range(3))
+    out = {}
+    for name, mot in (("real", real), ("gen", gen)):
+        r = m2snet.fuse_pairs(mus, mot)
+        st = retrieval_stats(r["mean"].cpu().numpy(), top_k)
+        out[f"m2s_r_precision_{name}"] = [float(v) for v in st["r_precision"]]
+        out[f"m2s_mean_rank_{name}"] = st["mean_rank"]
+        out[f"m2s_margin_{name}"] = st["margin"]
+        out[f"m2s_pair_accuracy_{name}"] = pair_accuracy(r["above"].cpu().numpy(), r["below"].cpu().numpy(), r["count"].cpu().numpy())
+        if name == "gen":
+            out["m2s_sync_offdiag_gen"] = st["offdiag_mean"]
+    return out
 
 
 def _ground_truth(pred, gts, dim_pose, ids, what):
@@ -350,7 +383,7 @@ class _Scorer:
 
 def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed=0, smooth=False, verbose=True, motion_encoder=None,
                      diversity_seed=0, m2snet=None, guidance_scale=None, steps=None, spacing="uniform", solver="ddim", rhythm=None,
-                     discriminator=None, music_beats=None, beat_stride=1):
+                     discriminator=None, music_beats=None, beat_stride=1, retrieval=False):
     """Samples every clip under `root` and returns {"per_clip": {id: mse}, "total_loss", "final_mse", "clips",
     "seconds", "frames_per_s"}.  Clip i (in sorted order) starts from noise seeded with (seed, i), so the result
     does not depend on batch_size or on the number of ranks.
@@ -370,6 +403,19 @@ def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed
     batch of one clip, so the control depends on `batch_size`).  Adds "m2s_sync_real", "m2s_sync_gen", "m2s_sync_mismatched" (mean
     per-frame predictions over all clips; nan when no batch had two clips) and "m2s_accuracy_gen" (metrics.sync_stats: matched =
     generated, mismatched = rolled).  Without it the result is unchanged.
+
+    `retrieval` (needs `m2snet`, which must have `fuse_pairs`): the question the rolled control cannot ask - does a motion follow its
+    own music better than it follows the other pieces of the set?  The music latents and the real and generated motion latents of
+    ALL clips stay on the device (3 x 64 T floats per clip); after the last batch every music is scored against every real and every
+    generated motion (two M2SNet.fuse_pairs, N^2 pairs each; a pair's score is the mean per-frame probability) and the N x N matrices
+    are ranked on the host (metrics.retrieval_stats, the reference's calculate_R_precision / calculate_top_k of
+    Diffusion_Stage/utils/metrics.py on scores instead of distances).  Adds "m2s_r_precision_real" / "_gen" (lists over top-1, 2, 3:
+    the share of musics whose own motion is among the k best), "m2s_mean_rank_real" / "_gen" (1 = best), "m2s_margin_real" / "_gen"
+    (mean matched score minus mean mismatched score), "m2s_sync_offdiag_gen" (the mean mismatched score: every other clip, not the
+    next one of the batch), "m2s_pair_accuracy_real" / "_gen" (metrics.pair_accuracy: M2SNet_eval.py:65-68 with matched and
+    mismatched frames weighted equally) and "m2s_retrieval_s".  None of them depends on `batch_size` or on the order of the clips
+    (ties go to the lower clip index).  The clips must share one latent length (ValueError naming two that differ).  The existing
+    keys, the rolled control among them, are what they are without it.
 
     `rhythm` (a rhythm.MotionRhythm, or anything with its `psd` and `contour_and_std`): the scores of the M2S-GAN evaluation that look
     at how the motion moves (Contrastive_Stage/M2SGAN_eval.py:100-133, metrics.py) - "rde" and "sce" (the means over the clips of
@@ -404,6 +450,8 @@ def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed
     gkw = {} if guidance_scale is None else {"guidance_scale": float(guidance_scale)}      # (None: the trainer is called as before)
     if steps is not None or solver != "ddim":
         gkw.update(steps=steps, spacing=spacing, solver=solver)
+    if retrieval and (m2snet is None or not hasattr(m2snet, "fuse_pairs")):
+        raise ValueError("retrieval=True ranks M2SNet's scores of every pair: pass m2snet= (an m2snet.M2SNet, with fuse_pairs)")
     ids = list_clips(root)
     if limit is not None:
         ids = ids[:int(limit)]
@@ -412,6 +460,7 @@ def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed
     mel_shape = tuple(np.load(pjoin(root, ids[0], "mel.npy"), mmap_mode="r").shape)
     T = (mel_shape[0] - 1) // 3 + 1
     nb = (len(ids) + batch_size - 1) // batch_size
+    kept = {} if retrieval else None     # batch -> [music latent, real motion latent, generated motion latent] on the device
     moves = rhythm is not None or discriminator is not None
     if rhythm is not None and T < 256:
         raise ValueError(f"clips of {T} frames: the rhythm scores need at least 256 (Welch's segment)")
@@ -478,7 +527,7 @@ def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed
                 lat_h[0].copy_(lats[0], non_blocking=True)
                 lat_h[1].copy_(lats[1], non_blocking=True)
             if m2snet is not None:
-                sync[k] = _sync_predictions(m2snet, mel, pred, gts, dim_pose)
+                sync[k] = _sync_predictions(m2snet, mel, pred, gts, dim_pose, None if kept is None else kept.setdefault(k, []))
             if moves:
                 if rh_rows is None:
                     rh_rows = torch.empty((len(ids), _rhythm_columns(rhythm, discriminator, T)), dtype=torch.float32, pin_memory=pred.is_cuda)
@@ -517,7 +566,7 @@ def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed
                 pred_d = trainer.generate_music_motion(mel, dim_pose, noise=pf2.noise, smooth=19 if smooth else None, **gkw)
                 lats = _encode_pair(motion_encoder, pred_d, gts, dim_pose, bid) if motion_encoder is not None else None
                 if m2snet is not None:
-                    sync[k] = _sync_predictions(m2snet, mel, pred_d, gts, dim_pose)
+                    sync[k] = _sync_predictions(m2snet, mel, pred_d, gts, dim_pose, None if kept is None else kept.setdefault(k, []))
                 if moves:
                     rh_rows[k * batch_size:k * batch_size + pred_d.shape[0]].copy_(_rhythm_arrays(rhythm, discriminator, pred_d, gts, dim_pose, bid))
                 if music_beats is not None:
@@ -571,6 +620,12 @@ def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed
         if verbose:
             print(f"m2s_sync_real: {out['m2s_sync_real']}  m2s_sync_gen: {out['m2s_sync_gen']}  "
                   f"m2s_sync_mismatched: {out['m2s_sync_mismatched']}  m2s_accuracy_gen: {out['m2s_accuracy_gen']}")
+        if retrieval:
+            tm = time.perf_counter()
+            out.update(_retrieval_scores(m2snet, kept, ids, batch_size))
+            out["m2s_retrieval_s"] = time.perf_counter() - tm
+            if verbose:
+                print("  ".join(f"{key}: {out[key]}" for key in sorted(out) if key.startswith(("m2s_r_", "m2s_mean_rank", "m2s_margin", "m2s_pair"))))
     if moves:
         out.update(_rhythm_scores(rh_rows.numpy(), ids, T, rhythm, discriminator))
         if verbose:
@@ -582,6 +637,67 @@ def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed
         out.update(_beat_results(bt_rows.numpy(), ids))
         if verbose:
             print("  ".join(f"{key}: {out[key]}" for key in ("bc_gen", "bc_real", "beat_align_gen", "beat_align_real")))
+    return out
+
+
+NEGATIVE_STRATEGIES = {"easy": 1, "hard": 2, "super_hard": 2}      # strategy -> uniform draws PairBuilder.build_pairs takes for it
+
+
+def negative_windows(strategy, u, sample_length, clip_length):
+    """The index ranges PairBuilder.build_pairs (Contrastive_Stage/utils/train_utils.py:27-89) cuts for `strategy` from the uniform
+    draws `u` (its np.random.rand() values, in its order): {"music_1", "motion_1", "music_2", "motion_2"} -> (start, end), music at
+    90 Hz, motion at 30 Hz, with the reference's float64 expressions and int() truncations.  `sample_length`, `clip_length`: seconds.
+    For "easy" the second window is the first (the negative is the batch flipped)."""
+    if strategy not in NEGATIVE_STRATEGIES:
+        raise ValueError(f"strategy must be one of {sorted(NEGATIVE_STRATEGIES)}, got {strategy!r}")
+    if clip_length > sample_length / 3:
+        raise ValueError(f"clip_length {clip_length} must be at most sample_length / 3 = {sample_length / 3} (PairBuilder's condition)")
+    u = [float(v) for v in np.atleast_1d(np.asarray(u, np.float64))]
+    if len(u) != NEGATIVE_STRATEGIES[strategy]:
+        raise ValueError(f"{strategy} takes {NEGATIVE_STRATEGIES[strategy]} uniform draw(s), got {len(u)}")
+    L, c = sample_length, clip_length
+    if strategy == "easy":
+        start_1 = u[0] * (L - c)
+        start_2 = start_1
+    elif strategy == "hard":
+        start_1 = u[0] * (L - c - 10)
+        start_2 = start_1 + 10 + u[1] * (L - c - start_1 - 10)
+    else:
+        start_1 = u[0] * (L - c - 5)
+        start_2 = u[1] * (5 - 0.5) + start_1
+    end_1, end_2 = start_1 + c, start_2 + c
+    return {"music_1": (int(start_1 * 90), int(end_1 * 90)), "motion_1": (int(start_1 * 30), int(end_1 * 30)),
+            "music_2": (int(start_2 * 90), int(end_2 * 90)), "motion_2": (int(start_2 * 30), int(end_2 * 30))}
+
+
+def sync_negatives(m2snet, mel, motion, sample_length, clip_length, draws):
+    """The reference's own protocol for one batch (Contrastive_Stage/M2SNet_eval.py:58-92): for each of "easy", "hard" and
+    "super_hard", PairBuilder's windows (negative_windows) from the caller's uniform draws, `m2snet(mel_1, motion_1)` as the matched and
+    `m2snet(mel_1, motion_2)` as the mismatched predictions, and metrics.sync_stats of the two:
+    {strategy: {"sync", "non_sync", "accuracy"}}.  mel [B, >= 90 sample_length, 128], motion [B, >= 30 sample_length, 13, 2] (or
+    [.., 26]); `draws`: {strategy: its draws} (one for easy, two for the others; strategies left out are not scored).  For "easy" the
+    negative is the batch flipped.  Where the windows' frame counts are ones the reference's torch.cat fails on (the music window's
+    latent frames differ from the motion window's frames), ValueError.
+
+        u = np.random.RandomState(0).rand(5)
+        sync_negatives(net, mel, motion, 60, 20, {"easy": u[:1], "hard": u[1:3], "super_hard": u[3:]})
+    """
+    from .metrics import sync_stats
+    mel, motion = torch.as_tensor(mel), torch.as_tensor(motion)
+    out = {}
+    for strategy in NEGATIVE_STRATEGIES:
+        if strategy not in draws:
+            continue
+        w = negative_windows(strategy, draws[strategy], sample_length, clip_length)
+        mel_1 = mel[:, w["music_1"][0]:w["music_1"][1]]
+        motion_1 = motion[:, w["motion_1"][0]:w["motion_1"][1]]
+        motion_2 = motion_1.flip(0) if strategy == "easy" else motion[:, w["motion_2"][0]:w["motion_2"][1]]
+        Tm = int(mel_1.shape[1])
+        for what, x in (("motion_1", motion_1), ("motion_2", motion_2)):
+            if Tm < 1 or (Tm - 1) // 3 + 1 != int(x.shape[1]):
+                raise ValueError(f"{strategy}: the music window {w['music_1']} has {Tm} mel frames = {(Tm - 1) // 3 + 1 if Tm else 0} latent "
+                                 f"frames, {what} has {int(x.shape[1])} (the reference's torch.cat fails on this draw)")
+        out[strategy] = sync_stats(m2snet(mel_1.contiguous(), motion_1.contiguous()), m2snet(mel_1.contiguous(), motion_2.contiguous()))
     return out
 
 
@@ -783,7 +899,7 @@ def _baseline_main(args, dev):
     rh, disc = _movement_scorers(args, dev)
     r = evaluate_dataset(GeneratorBaseline(gen), args.data_root, 26, args.batch_size, args.limit, args.seed, args.smooth, verbose=False,
                          motion_encoder=menc, diversity_seed=args.diversity_seed, m2snet=m2s, rhythm=rh, discriminator=disc,
-                         music_beats=_music_beats(args), beat_stride=args.beat_stride)
+                         music_beats=_music_beats(args), beat_stride=args.beat_stride, retrieval=args.retrieval)
     print(json.dumps({"model": "m2sgan", **r}))
     return 0
 
@@ -813,6 +929,8 @@ def main(argv=None):
     ap.add_argument("--solver", default="ddim", choices=["ddim", "dpmpp2m"], help="first-order DDIM or the second-order multistep update")
     ap.add_argument("--sync", action="store_true", help="also M2SNet's synchronisation score of the sampled poses against the music "
                                                         "(m2snet.py; every entry of --m2snet, or seeded synthetic weights)")
+    ap.add_argument("--retrieval", action="store_true", help="also rank every clip's music against every clip's real and generated motion "
+                                                             "with M2SNet: R-precision, mean rank, margin and pair accuracy (implies --sync)")
     ap.add_argument("--val_loss", action="store_true", help="score the checkpoint by its held-out denoising losses instead of sampling it: "
                                                             "one JSON line, no sampling loop (validation_dataset)")
     ap.add_argument("--val_timesteps", type=int, default=None, help="--val_loss on a grid of this many noise levels (omitted: one uniform "
@@ -836,6 +954,8 @@ def main(argv=None):
                                                                "they are, as the reference does; 3 puts 90-fps mel frames and 30-fps poses "
                                                                "on one clock")
     args = ap.parse_args(argv)
+    if args.retrieval:
+        args.sync = True
     if args.baseline_generator:
         clash = [f for f, on in (("--model", args.model), ("--val_loss", args.val_loss), ("--guidance_scale", args.guidance_scale is not None),
                                  ("--steps", args.steps is not None), ("--solver", args.solver != "ddim"), ("--spacing", args.spacing != "uniform"),
@@ -894,7 +1014,7 @@ def main(argv=None):
     r = evaluate_dataset(tr, args.data_root, 26, args.batch_size, args.limit, args.seed, args.smooth, motion_encoder=menc,
                          diversity_seed=args.diversity_seed, m2snet=m2s, guidance_scale=args.guidance_scale,
                          steps=args.steps, spacing=args.spacing, solver=args.solver, rhythm=rh, discriminator=disc,
-                         music_beats=_music_beats(args), beat_stride=args.beat_stride)
+                         music_beats=_music_beats(args), beat_stride=args.beat_stride, retrieval=args.retrieval)
     print(f"{r['clips']} clips in {r['seconds']:.2f} s = {r['frames_per_s']:.0f} frames/s")
     return 0
 

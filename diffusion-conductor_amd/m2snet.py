@@ -125,6 +125,24 @@ class M2SNet:
         encodes a piece once and scores it against several motions."""
         return self._net().fuse(self._tensor(music_latent), self._tensor(motion_latent), logits=return_logits)
 
+    def fuse_pairs(self, music_latent, motion_latent, len_music=None, len_motion=None, return_frames=False):
+        """The fuse head on EVERY pair of `music_latent` [Bm, T, 64] and `motion_latent` [Bn, 64, T], without the Bm x Bn
+        concatenation (M2SNet.py:31-36 per pair, reduced as M2SNet_eval.py:58-68 reduces a batch): a dict of device tensors [Bm, Bn] -
+        "mean" (fp32, the mean probability over the pair's valid frames), "sum" (fp32), "above" and "below" (int32, the valid frames
+        with p > 0.5 and with p < 0.5) and "count" (int32, the valid frames: min(len_music[i], len_motion[j]); a length of None is T) -
+        and, with `return_frames`, "prob" [Bm, Bn, T], every frame's probability, bit-identical to `fuse` on that pair.  A pair's
+        numbers do not depend on the other pairs of the call.  Runs on the current stream, like `fuse`."""
+        import torch
+        mus, mot = self._tensor(music_latent), self._tensor(motion_latent)
+        total, above, below, prob = self._net().fuse_pairs(mus, mot, len_music, len_motion, frames=return_frames)
+        T = int(mus.shape[1])
+        lm, ln = (np.full(n, T, np.int32) if a is None else np.asarray(a, np.int32) for a, n in ((len_music, mus.shape[0]), (len_motion, mot.shape[0])))
+        count = torch.from_numpy(np.minimum(lm[:, None], ln[None, :])).to(self.device)
+        out = {"mean": total / count.to(torch.float32), "sum": total, "above": above, "below": below, "count": count}
+        if return_frames:
+            out["prob"] = prob
+        return out
+
     def logits(self, mel, motion):
         """The value in front of the sigmoid, [B, T]."""
         return self._net().score(self._mel(mel), self._motion_input(motion), logits=True)[1]

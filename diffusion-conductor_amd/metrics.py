@@ -145,6 +145,55 @@ def sync_stats(pred_matched, pred_mismatched=None):
             "accuracy": ((tp + tf) / (m.numel() + n.numel())).item()}
 
 
+def retrieval_stats(score, top_k=(1, 2, 3)):
+    """Ranks a square score matrix [N, N] whose entry (i, j) scores music i against motion j (higher = better matched) and whose
+    diagonal holds the matched pairs - calculate_R_precision / calculate_top_k of Diffusion_Stage/utils/metrics.py:21-43 on scores
+    instead of distances.  Row i's order is np.argsort(-score[i], kind="stable"): ties go to the lower column.  Returns
+      "r_precision"   list over `top_k`: the share of rows whose own column is among the k best
+      "top_k_table"   bool [N, max(top_k)]: column k - 1 = the own column is among the k best (calculate_top_k's cumulative table;
+                      k > N, where the reference would index past the matrix, is True)
+      "rank"          float [N]: the 1-based position of the own column in the row's order
+      "mean_rank", "diag_mean", "offdiag_mean" (nan for N = 1), "margin" = diag_mean - offdiag_mean
+    in float64.  A row holding a NaN has no order: its "rank" is nan, its table row False, and "r_precision" and "mean_rank", which
+    average over every row, are nan - the NaN is never sorted into a place."""
+    s = np.asarray(score, np.float64)
+    if s.ndim != 2 or s.shape[0] != s.shape[1] or s.shape[0] < 1:
+        raise ValueError(f"retrieval_stats: the scores must be a square [N, N] matrix with N >= 1, got {s.shape}")
+    ks = [int(k) for k in top_k]
+    if not ks or min(ks) < 1:
+        raise ValueError(f"retrieval_stats: top_k must be positive integers, got {tuple(top_k)}")
+    n = s.shape[0]
+    bad = np.isnan(s).any(axis=1)
+    order = np.argsort(-np.where(bad[:, None], 0.0, s), axis=1, kind="stable")
+    hit = order == np.arange(n)[:, None]                 # calculate_top_k's bool_mat: one True per row
+    rank = np.where(bad, np.nan, np.argmax(hit, axis=1) + 1.0)
+    kmax = max(ks)
+    table = np.logical_or.accumulate(np.concatenate([hit, np.zeros((n, max(0, kmax - n)), bool)], axis=1)[:, :kmax], axis=1)
+    table &= ~bad[:, None]
+    rp = [float("nan") if bad.any() else float(table[:, k - 1].mean()) for k in ks]
+    eye = np.eye(n, dtype=bool)
+    diag_mean = float(s[eye].mean())
+    off_mean = float(s[~eye].mean()) if n > 1 else float("nan")
+    return {"r_precision": rp, "top_k_table": table, "rank": rank, "mean_rank": float(rank.mean()), "diag_mean": diag_mean,
+            "offdiag_mean": off_mean, "margin": diag_mean - off_mean}
+
+
+def pair_accuracy(above, below, count):
+    """The 0.5-threshold accuracy of Contrastive_Stage/M2SNet_eval.py:65-68 over an [N, N] pair matrix (M2SNet.fuse_pairs' "above",
+    "below", "count": per pair, the valid frames with p > 0.5, with p < 0.5, and all of them), matched pairs on the diagonal:
+    1/2 (sum_diag above / sum_diag count + sum_off below / sum_off count) - the reference's (TP + TF) / frames whenever matched and
+    mismatched frames are equally many, as in its protocol; balanced, because here there are N - 1 mismatched pairs per matched one.
+    N = 1 has no mismatched pair: the matched side alone.  float."""
+    a, b, c = (np.asarray(x, np.int64) for x in (above, below, count))
+    if a.ndim != 2 or a.shape[0] != a.shape[1] or a.shape[0] < 1 or b.shape != a.shape or c.shape != a.shape:
+        raise ValueError(f"pair_accuracy: above, below and count must be one square shape, got {a.shape}, {b.shape}, {c.shape}")
+    eye = np.eye(a.shape[0], dtype=bool)
+    matched = a[eye].sum() / c[eye].sum()
+    if a.shape[0] == 1:
+        return float(matched)
+    return float(0.5 * (matched + b[~eye].sum() / c[~eye].sum()))
+
+
 # the weights of DDPMTrainer.backward_G (ddpm_trainer.py:252-256) and the clamp of its elbow term (:245)
 LAMBDA_REC, LAMBDA_FEAT, LAMBDA_VELOCITY, LAMBDA_ELBOW, LAMBDA_HEAD = 1.0, 1e-6, 0.1, 0.1, 0.1
 ELBOW_CLAMP = 2e-4

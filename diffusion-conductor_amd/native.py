@@ -30,7 +30,7 @@ EXPORTS = [
     "dc_ddim_coefficients_known", "dc_sampler_set_known",
     "dc_sampler_set_conditioning_guided", "dc_sampler_set_guidance_scale",
     "dc_m2snet_create", "dc_m2snet_destroy", "dc_m2snet_set_param", "dc_m2snet_finalize", "dc_m2snet_encode_music", "dc_m2snet_fuse",
-    "dc_m2snet_score",
+    "dc_m2snet_score", "dc_m2snet_fuse_pairs", "dc_m2snet_pairs_share",
     "dc_solver_table", "dc_sampler_solver_loop", "dc_sampler_solver_profile_loop",
     "dc_sampler_set_conditioning_takes",
     "dc_sampler_set_conditioning_windows", "dc_windows_check",
@@ -192,6 +192,10 @@ def lib():
     L.dc_m2snet_fuse.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.dc_m2snet_score.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                   C.c_void_p]
+    L.dc_m2snet_fuse_pairs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, ip, ip, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p]
+    L.dc_m2snet_pairs_share.restype = C.c_int32
+    L.dc_m2snet_pairs_share.argtypes = []
     L.dc_q_sample_coefficients.argtypes = [C.c_int32, dp, ip, C.c_int32, fp, fp]
     L.dc_q_sample.argtypes = [C.c_void_p, C.c_void_p, fp, fp, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_uint64,
                               C.c_void_p, C.c_void_p, C.c_void_p]
@@ -977,6 +981,41 @@ class NativeM2SNet(_NativeHandle):
             _check(lib().dc_m2snet_fuse(self._h, music_latent.data_ptr(), motion_latent.data_ptr(), B, T, prob.data_ptr(),
                                         logit.data_ptr() if logits else None, self._stream()))
         return (prob, logit) if logits else prob
+
+    @staticmethod
+    def pairs_share():
+        """The number of motions one wave of `fuse_pairs` walks per launch."""
+        return int(lib().dc_m2snet_pairs_share())
+
+    def fuse_pairs(self, music_latent, motion_latent, len_music=None, len_motion=None, frames=False):
+        """Every music [Bm, T, 64] against every motion [Bn, 64, T] (fp32, on the device) -> (sum fp32 [Bm, Bn], above int32 [Bm, Bn],
+        below int32 [Bm, Bn], prob fp32 [Bm, Bn, T] | None) over the frames t < min(len_music[i], len_motion[j]) (int arrays on the
+        host, None = T)."""
+        import torch
+        self._ok(music_latent)
+        self._ok(motion_latent)
+        assert music_latent.dim() == 3 and motion_latent.dim() == 3, (tuple(music_latent.shape), tuple(motion_latent.shape))
+        Bm, T, Bn = int(music_latent.shape[0]), int(music_latent.shape[1]), int(motion_latent.shape[0])
+        self._ok(music_latent, (Bm, T, 64))
+        self._ok(motion_latent, (Bn, 64, T))
+        lens = []
+        for a, n, what in ((len_music, Bm, "len_music"), (len_motion, Bn, "len_motion")):
+            if a is not None:
+                a = np.ascontiguousarray(np.asarray(a).astype(np.int32, casting="same_kind"))
+                if a.shape != (n,):
+                    raise ValueError(f"{what} must have shape ({n},), got {a.shape}")
+            lens.append(a)
+        dev = music_latent.device
+        total = torch.empty((Bm, Bn), dtype=torch.float32, device=dev)
+        above = torch.empty((Bm, Bn), dtype=torch.int32, device=dev)
+        below = torch.empty((Bm, Bn), dtype=torch.int32, device=dev)
+        prob = torch.empty((Bm, Bn, T), dtype=torch.float32, device=dev) if frames else None
+        with torch.cuda.device(dev):
+            _check(lib().dc_m2snet_fuse_pairs(self._h, music_latent.data_ptr(), motion_latent.data_ptr(), Bm, Bn, T,
+                                              None if lens[0] is None else _iptr(lens[0]), None if lens[1] is None else _iptr(lens[1]),
+                                              total.data_ptr(), above.data_ptr(), below.data_ptr(), prob.data_ptr() if frames else None,
+                                              self._stream()))
+        return total, above, below, prob
 
     def score(self, mel, motion, logits=False):
         """mel [B, Tm, 128] and motion [B, T, 13, 2] (or [B, T, 26]) -> probability [B, T] (or (probability, logit))."""

@@ -536,6 +536,27 @@ DC_EXPORT int dc_m2snet_fuse(dc_m2snet* n, const float* d_music_latent, const fl
 DC_EXPORT int dc_m2snet_score(dc_m2snet* n, const float* d_mel, const float* d_motion, int32_t B, int32_t Tm, int32_t T,
                               float* d_prob, float* d_logit, void* stream);
 
+/* Every music against every motion: replaces M2SNet.forward's torch.cat + fuse_layer (M2SNet.py:31-36) on all Bm x Bn pairs and
+ * the per-pair reductions of Contrastive_Stage/M2SNet_eval.py:58-68 (torch.mean(pred), np.sum(pred > 0.5), np.sum(pred < 0.5)).
+ * d_music_latent fp32 [Bm, T, 64] (16-byte aligned) and d_motion_latent fp32 [Bn, 64, T], as dc_m2snet_fuse takes them.  The valid
+ * frames of pair (i, j) are t < min(h_len_music[i], h_len_motion[j]); either array (int32, on the host) may be NULL, meaning T; a
+ * length outside [1, T] is DC_ERR_INVALID.  Outputs, caller-allocated on the device:
+ *   d_sum   fp32  [Bm, Bn]     the sum of the per-frame probabilities over the pair's valid frames
+ *   d_above int32 [Bm, Bn]     the number of valid frames with p > 0.5
+ *   d_below int32 [Bm, Bn]     the number of valid frames with p < 0.5 (a frame at exactly 0.5, or NaN, counts in neither)
+ *   d_prob  fp32  [Bm, Bn, T]  unless NULL: every frame's probability (valid or not)
+ * Every probability is bit-identical to what dc_m2snet_fuse returns for that pair: layer 0's chain runs k = 0 .. 63 over the music
+ * once per 32-frame tile and a copy of it is continued with each motion, in dc_m2snet_fuse's order.  The sum is taken in one fixed
+ * order that depends on T alone (a 32-lane tree per tile, then the tiles ascending; no atomics), so a pair's three numbers do not
+ * depend on Bm, Bn, the pair's position or the internal passes.  Partials live in the handle's workspace.  With a length array the
+ * call waits for the stream once (the upload of the lengths); without, it only enqueues.  Nothing is written on an error. */
+DC_EXPORT int dc_m2snet_fuse_pairs(dc_m2snet* n, const float* d_music_latent, const float* d_motion_latent, int32_t Bm, int32_t Bn,
+                                   int32_t T, const int32_t* h_len_music, const int32_t* h_len_motion, float* d_sum, int32_t* d_above,
+                                   int32_t* d_below, float* d_prob, void* stream);
+
+/* The number of motions one wave of dc_m2snet_fuse_pairs walks per launch (a test straddles it). */
+DC_EXPORT int32_t dc_m2snet_pairs_share(void);
+
 /* ---- M2S-GAN generator: the baseline the diffusion denoiser is compared against ----------------------------------------------
  * Replaces constructing Generator (Contrastive_Stage/models/Generator.py:52-65: a MusicEncoder, the noise branch's four
  * ConvTranspose1d + noise_BN, and PoseDecoderTCN on the DialtedCNN of models/TCN.py) on the device `device`.  Implemented in
