@@ -19,6 +19,7 @@ model evaluation per clip and timestep, as a per-timestep table.
 """
 from __future__ import annotations
 
+import functools
 import os
 import threading
 import time
@@ -134,137 +135,248 @@ class _Prefetcher:
         return self.result
 
 
-def _with_latents(res, gen_lat, real_lat):
-    """[(clip id, mse)] -> [(clip id, mse, latent_mse, generated latent [64, T], real latent [64, T])] (metrics.py)."""
-    from .metrics import latent_mse
-    out = []
-    for i, (cid, cur) in enumerate(res):
-        g, r = np.array(gen_lat[i]), np.array(real_lat[i])
-        out.append((cid, cur, latent_mse(g, r), g, r))
-    return out
+def _open_dataset(root, limit, batch_size):
+    """(clip ids, a mel's shape, the frames T it gives, the number of batches) of the first `limit` clips under `root`."""
+    ids = list_clips(root)
+    if limit is not None:
+        ids = ids[:int(limit)]
+    if not ids:
+        raise FileNotFoundError(f"no <id>/mel.npy + <id>/motion.npy pairs under {root}")
+    mel_shape = tuple(np.load(pjoin(root, ids[0], "mel.npy"), mmap_mode="r").shape)
+    return ids, mel_shape, (mel_shape[0] - 1) // 3 + 1, (len(ids) + batch_size - 1) // batch_size
 
 
-def _encode_pair(motion_encoder, pred, gts, dim_pose, ids):
-    """Latents [B, 64, T] of the sampled poses and of the ground truth, enqueued on the current stream right behind the sampling
-    (the ground truth is uploaded to the poses' device first)."""
-    T = pred.shape[1]
-    bad = [(cid, np.shape(g)) for cid, g in zip(ids, gts) if tuple(np.shape(g)) != (T, dim_pose // 2, 2)]
-    if bad:
-        raise ValueError(f"the latent metrics compare clips of {T} frames ([T, {dim_pose // 2}, 2] motions; the reference stacks the "
-                         f"latents with np.vstack), but these ground truths differ: {bad[:4]}")
-    gt = torch.from_numpy(np.ascontiguousarray(np.stack(gts), np.float32))
-    if pred.is_cuda:
-        gt = gt.pin_memory().to(pred.device, non_blocking=True)
-    B = pred.shape[0]
-    gen_lat = motion_encoder.latent(pred.reshape(B, T, dim_pose // 2, 2))
-    real_lat = motion_encoder.latent(gt)
-    return gen_lat, real_lat
+def _clip_mses(ids, gts, pred, dim_pose):
+    """[(clip id, mse)] of a batch's poses (numpy [B, T, dim_pose]) against its ground truths (eval_new.py:124-131)."""
+    return [(cid, mse_loss(gts[i], pred[i].reshape([pred[i].shape[0], dim_pose // 2, 2]))) for i, cid in enumerate(ids)]
 
 
-def _sync_predictions(m2snet, mel, pred, gts, dim_pose, keep=None):
-    """M2SNet's per-frame predictions [B, T] for a batch, the music encoded once and fused with three motions: the ground truth,
-    the sampled poses, and the sampled poses of the NEXT clip of the batch (rolled by one: the mismatched control; None for a batch
-    of one clip).  Enqueued on the current stream; the tensors stay on the poses' device.  `keep` (a list, for the retrieval
-    scores): the batch's three latents - music [B, T, 64], real and generated motion [B, 64, T] - are put into it."""
-    B, T = pred.shape[0], pred.shape[1]
-    gt = torch.from_numpy(np.ascontiguousarray(np.stack(gts), np.float32))
-    mel = torch.as_tensor(mel)
-    if pred.is_cuda:
-        gt = gt.pin_memory().to(pred.device, non_blocking=True)
-        mel = mel.to(pred.device, non_blocking=True)
-    mus = m2snet.music_latent(mel)
-    real_lat = m2snet.motion_latent(gt)
-    real = m2snet.fuse(mus, real_lat)
-    gen_lat = m2snet.motion_latent(pred.reshape(B, T, dim_pose // 2, 2))
-    gen = m2snet.fuse(mus, gen_lat)
-    mis = m2snet.fuse(mus, torch.roll(gen_lat, -1, 0).contiguous()) if B > 1 else None
-    if keep is not None:
-        keep[:] = [mus, real_lat, gen_lat]
-    return real, gen, mis
+class _Batch:
+    """One sampled batch on its way to the score families: its number `k`, the index `first` of its first clip, its `ids`, `mel`
+    (host) and `gts` (the motions as loaded), the sampled `pred` [B, T, dim_pose] on its device, and `slot` - which of the two pinned
+    host slots the pipelined loop gave it, None for a batch that is sampled again: later batches may still be queued on the scoring
+    thread and read those slots, so nothing of such a batch may be written there."""
+
+    def __init__(self, k, first, ids, mel, gts, pred, slot):
+        self.k, self.first, self.ids, self.mel, self.gts, self.pred, self.slot = k, first, ids, mel, gts, pred, slot
+
+    @functools.cached_property
+    def _truth(self):
+        gt = torch.from_numpy(np.ascontiguousarray(np.stack([np.reshape(g, -1) for g in self.gts]), np.float32))
+        return gt.pin_memory().to(self.pred.device, non_blocking=True) if self.pred.is_cuda else gt
+
+    def ground_truth(self, *shape):
+        """The ground truth fp32 [B, *shape] on the poses' device: stacked, pinned and uploaded on the current stream by the first
+        family that asks, and viewed by the others.  (Each family refuses the clips it cannot score before it asks.)"""
+        return self._truth.view(len(self.gts), *shape)
+
+
+class _LatentScores:
+    """`motion_encoder` (a motion_encoder.MotionEncoder_STGCN, or anything with its `latent(x)` -> [B, 64, T]): the latent-space
+    scores of the paper's table (metrics.py), added as "latent_mse" ({id: the clip's Sync Error term}, eval_old_metrics.py:90-100),
+    "final_latent_mse" (SE), "fgd", "feat_dist" (eval_new_metrics.py:169-199), "diversity" (:159-166, permutation drawn with
+    `diversity_seed`) and "metrics_s" (host seconds spent on FGD, feat_dist and diversity after the last batch).  The sampled poses
+    and the ground truth are encoded on the device right after each batch's sampling, on the same stream, and the latents come back
+    with the poses, into a pinned double buffer; the scoring thread takes them from there.  Every clip must have the poses' T frames
+    (ValueError otherwise).  With `smooth` the latents are those of the SMOOTHED poses - the reference scores the unsmoothed output."""
+
+    def __init__(self, motion_encoder, diversity_seed, ids, T, dim_pose, batch_size):
+        self.encoder, self.diversity_seed, self.ids, self.dim_pose, self.batch_size = motion_encoder, diversity_seed, ids, dim_pose, batch_size
+        self.slots = [None, None]        # pinned [2 (generated, real), batch_size, 64, T]
+        self.clips = {}                  # batch -> [(latent_mse, generated latent [64, T], real latent [64, T])], filled once it has landed
+
+    def enqueue(self, batch, pred):
+        B, T, J = pred.shape[0], pred.shape[1], self.dim_pose // 2
+        bad = [(cid, np.shape(g)) for cid, g in zip(batch.ids, batch.gts) if tuple(np.shape(g)) != (T, J, 2)]
+        if bad:
+            raise ValueError(f"the latent metrics compare clips of {T} frames ([T, {J}, 2] motions; the reference stacks the "
+                             f"latents with np.vstack), but these ground truths differ: {bad[:4]}")
+        gt = batch.ground_truth(T, J, 2)
+        lats = self.encoder.latent(pred.reshape(B, T, J, 2)), self.encoder.latent(gt)
+        s = batch.slot
+        if s is None:                    # (a batch sampled again: pageable memory and blocking copies)
+            host = torch.empty((2, B) + tuple(lats[0].shape[1:]), dtype=torch.float32)
+        else:
+            if self.slots[s] is None or self.slots[s].shape[1] < B or self.slots[s].shape[2:] != lats[0].shape[1:]:
+                self.slots[s] = torch.empty((2, self.batch_size) + tuple(lats[0].shape[1:]), dtype=torch.float32, pin_memory=pred.is_cuda)
+            host = self.slots[s][:, :B]
+        host[0].copy_(lats[0], non_blocking=s is not None)
+        host[1].copy_(lats[1], non_blocking=s is not None)
+        k = batch.k                      # (the callable holds the host tensor, not the batch and its device tensors)
+        return lambda: self._landed(k, host.numpy())
+
+    def _landed(self, k, lats):
+        from .metrics import latent_mse
+        pairs = [(np.array(g), np.array(r)) for g, r in zip(lats[0], lats[1])]      # (copies: the pinned slot is reused two batches later)
+        self.clips[k] = [(latent_mse(g, r), g, r) for g, r in pairs]
+
+    def finish(self, out, verbose):
+        from .metrics import diversity_score, frechet_gesture_distance, sync_error
+        tm = time.perf_counter()
+        clips = [c for k in sorted(self.clips) for c in self.clips[k]]
+        out["latent_mse"] = {cid: float(c[0]) for cid, c in zip(self.ids, clips)}
+        out["final_latent_mse"] = float(sync_error([c[0] for c in clips]))
+        gen, real = [c[1] for c in clips], [c[2] for c in clips]
+        fgd, feat_dist = frechet_gesture_distance(gen, real)
+        out["fgd"], out["feat_dist"], out["diversity"] = float(fgd), float(feat_dist), float(diversity_score(gen, self.diversity_seed))
+        out["metrics_s"] = time.perf_counter() - tm
+        if verbose:
+            print("final_latent_mse: ", out["final_latent_mse"])
+            print(f"fgd: {out['fgd']}  feat_dist: {out['feat_dist']}  diversity: {out['diversity']}")
 
 
 RETRIEVAL_TOP_K = (1, 2, 3)            # the reference's R-precision columns (Diffusion_Stage/utils/metrics.py calculate_R_precision, top_k = 3)
 
 
-def _retrieval_scores(m2snet, kept, ids, batch_size, top_k=RETRIEVAL_TOP_K):
-    """The m2s_* retrieval keys of evaluate_dataset from every batch's kept latents ({batch: [music, real, generated]}): all clips'
-    music against all clips' real and generated motion (M2SNet.fuse_pairs), ranked on the host (metrics.retrieval_stats,
-    metrics.pair_accuracy)."""
-    from .metrics import pair_accuracy, retrieval_stats
-    nb = len(kept)
-    T = int(kept[0][0].shape[1])
-    for k in range(nb):
-        Tk = int(kept[k][0].shape[1])
-        if Tk != T or any(int(kept[k][i].shape[2]) != T for i in (1, 2)):
-            raise ValueError(f"the retrieval scores pair every music with every motion and need one latent length: clip {ids[0]} has {T} "
-                             f"frames, clip {ids[k * batch_size]} has {Tk}")
-    mus, real, gen = (torch.cat([kept[k][i] for k in range(nb)]) for i in range(3))
-    out = {}
-    for name, mot in (("real", real), ("gen", gen)):
-        r = m2snet.fuse_pairs(mus, mot)
-        st = retrieval_stats(r["mean"].cpu().numpy(), top_k)
-        out[f"m2s_r_precision_{name}"] = [float(v) for v in st["r_precision"]]
-        out[f"m2s_mean_rank_{name}"] = st["mean_rank"]
-        out[f"m2s_margin_{name}"] = st["margin"]
-        out[f"m2s_pair_accuracy_{name}"] = pair_accuracy(r["above"].cpu().numpy(), r["below"].cpu().numpy(), r["count"].cpu().numpy())
-        if name == "gen":
-            out["m2s_sync_offdiag_gen"] = st["offdiag_mean"]
-    return out
+class _SyncScores:
+    """`m2snet` (an m2snet.M2SNet, or anything with its `music_latent`, `motion_latent` and `fuse`): the learned synchronisation
+    score - the one number here that looks at the music.  Each batch's music is encoded once and scored against the ground truth,
+    the sampled poses and, as the mismatched control, the sampled poses of the next clip of the batch (rolled by one; left out for a
+    batch of one clip, so the control depends on `batch_size`); the per-frame predictions [B, T] stay on the poses' device until the
+    end.  Adds "m2s_sync_real", "m2s_sync_gen", "m2s_sync_mismatched" (mean per-frame predictions over all clips; nan when no batch had
+    two clips) and "m2s_accuracy_gen" (metrics.sync_stats: matched = generated, mismatched = rolled).
+
+    `retrieval` (needs `m2snet`, which must have `fuse_pairs`): the question the rolled control cannot ask - does a motion follow its
+    own music better than it follows the other pieces of the set?  The music latents [B, T, 64] and the real and generated motion
+    latents [B, 64, T] of ALL clips stay on the device (3 x 64 T floats per clip); after the last batch every music is scored against
+    every real and every generated motion (two M2SNet.fuse_pairs, N^2 pairs each; a pair's score is the mean per-frame probability) and
+    the N x N matrices are ranked on the host (metrics.retrieval_stats, the reference's calculate_R_precision / calculate_top_k of
+    Diffusion_Stage/utils/metrics.py on scores instead of distances).  Adds "m2s_r_precision_real" / "_gen" (lists over top-1, 2, 3:
+    the share of musics whose own motion is among the k best), "m2s_mean_rank_real" / "_gen" (1 = best), "m2s_margin_real" / "_gen"
+    (mean matched score minus mean mismatched score), "m2s_sync_offdiag_gen" (the mean mismatched score: every other clip, not the
+    next one of the batch), "m2s_pair_accuracy_real" / "_gen" (metrics.pair_accuracy: M2SNet_eval.py:65-68 with matched and
+    mismatched frames weighted equally) and "m2s_retrieval_s".  None of them depends on `batch_size` or on the order of the clips
+    (ties go to the lower clip index).  The clips must share one latent length (ValueError naming two that differ).  The other
+    keys, the rolled control among them, are what they are without it.
+
+    (Built before the dataset is opened - its refusal has always come first - so it takes none of the dataset's facts.)"""
+
+    def __init__(self, m2snet, retrieval, dim_pose):
+        if retrieval and (m2snet is None or not hasattr(m2snet, "fuse_pairs")):
+            raise ValueError("retrieval=True ranks M2SNet's scores of every pair: pass m2snet= (an m2snet.M2SNet, with fuse_pairs)")
+        self.net, self.dim_pose = m2snet, dim_pose
+        self.preds = {}                  # batch -> (real, generated, mismatched | None) predictions [B, T] on the device
+        self.kept = {} if retrieval else None      # batch -> (its first clip's id, music latent, real motion latent, generated motion latent)
+
+    def enqueue(self, batch, pred):
+        B, T, net = pred.shape[0], pred.shape[1], self.net
+        gt = batch.ground_truth(-1, self.dim_pose // 2, 2)
+        mel = torch.as_tensor(batch.mel)
+        if pred.is_cuda:
+            mel = mel.to(pred.device, non_blocking=True)
+        mus = net.music_latent(mel)
+        real_lat = net.motion_latent(gt)
+        real = net.fuse(mus, real_lat)
+        gen_lat = net.motion_latent(pred.reshape(B, T, self.dim_pose // 2, 2))
+        gen = net.fuse(mus, gen_lat)
+        mis = net.fuse(mus, torch.roll(gen_lat, -1, 0).contiguous()) if B > 1 else None
+        self.preds[batch.k] = (real, gen, mis)
+        if self.kept is not None:
+            self.kept[batch.k] = (batch.ids[0], mus, real_lat, gen_lat)
+
+    def finish(self, out, verbose):
+        from .metrics import sync_stats
+        real, gen, mis = ([torch.as_tensor(self.preds[k][i]).cpu().reshape(-1) for k in sorted(self.preds) if self.preds[k][i] is not None]
+                          for i in range(3))
+        st = sync_stats(torch.cat(gen), torch.cat(mis) if mis else None)
+        out["m2s_sync_real"] = sync_stats(torch.cat(real))["sync"]
+        out["m2s_sync_gen"], out["m2s_sync_mismatched"], out["m2s_accuracy_gen"] = st["sync"], st["non_sync"], st["accuracy"]
+        if verbose:
+            print(f"m2s_sync_real: {out['m2s_sync_real']}  m2s_sync_gen: {out['m2s_sync_gen']}  "
+                  f"m2s_sync_mismatched: {out['m2s_sync_mismatched']}  m2s_accuracy_gen: {out['m2s_accuracy_gen']}")
+        if self.kept is not None:
+            tm = time.perf_counter()
+            self._retrieval(out)
+            out["m2s_retrieval_s"] = time.perf_counter() - tm
+            if verbose:
+                print("  ".join(f"{key}: {out[key]}" for key in sorted(out) if key.startswith(("m2s_r_", "m2s_mean_rank", "m2s_margin", "m2s_pair"))))
+
+    def _retrieval(self, out, top_k=RETRIEVAL_TOP_K):
+        """All clips' music against all clips' real and generated motion (M2SNet.fuse_pairs), ranked on the host."""
+        from .metrics import pair_accuracy, retrieval_stats
+        kept = [self.kept[k] for k in sorted(self.kept)]
+        T = int(kept[0][1].shape[1])
+        for cid, mus, real, gen in kept:
+            if int(mus.shape[1]) != T or int(real.shape[2]) != T or int(gen.shape[2]) != T:
+                raise ValueError(f"the retrieval scores pair every music with every motion and need one latent length: clip {kept[0][0]} has "
+                                 f"{T} frames, clip {cid} has {int(mus.shape[1])}")
+        mus, real, gen = (torch.cat([b[i] for b in kept]) for i in (1, 2, 3))
+        for name, mot in (("real", real), ("gen", gen)):
+            r = self.net.fuse_pairs(mus, mot)
+            st = retrieval_stats(r["mean"].cpu().numpy(), top_k)
+            out[f"m2s_r_precision_{name}"] = [float(v) for v in st["r_precision"]]
+            out[f"m2s_mean_rank_{name}"] = st["mean_rank"]
+            out[f"m2s_margin_{name}"] = st["margin"]
+            out[f"m2s_pair_accuracy_{name}"] = pair_accuracy(r["above"].cpu().numpy(), r["below"].cpu().numpy(), r["count"].cpu().numpy())
+            if name == "gen":
+                out["m2s_sync_offdiag_gen"] = st["offdiag_mean"]
 
 
-def _ground_truth(pred, gts, dim_pose, ids, what):
-    """The batch's ground truth [B, T, dim_pose] fp32 on the poses' device (uploaded on the current stream); every clip must have the
-    poses' T frames (ValueError naming `what` scores otherwise)."""
+def _same_frames(batch, pred, dim_pose, what):
+    """The batch's ground truth [B, T, dim_pose] on the poses' device; every clip must have the poses' T frames (ValueError naming
+    `what` scores otherwise)."""
     T = pred.shape[1]
-    bad = [(cid, np.shape(g)) for cid, g in zip(ids, gts) if int(np.prod(np.shape(g))) != T * dim_pose]
+    bad = [(cid, np.shape(g)) for cid, g in zip(batch.ids, batch.gts) if int(np.prod(np.shape(g))) != T * dim_pose]
     if bad:
         raise ValueError(f"the {what} scores compare clips of {T} frames, but these ground truths differ: {bad[:4]}")
-    gt = torch.from_numpy(np.ascontiguousarray(np.stack([np.reshape(g, (T, dim_pose)) for g in gts]), np.float32))
-    return gt.pin_memory().to(pred.device, non_blocking=True) if pred.is_cuda else gt
+    return batch.ground_truth(T, dim_pose)
 
 
-def _rhythm_columns(rhythm, discriminator, T):
-    """Floats per clip of _rhythm_arrays' rows: [psd generated 32 | psd real 32 | contour generated W | contour real W | sd generated |
-    sd real] with `rhythm`, then [D(generated) | D(real)] with `discriminator`."""
-    W = (T - 60) // 30 + 1
-    return (2 * 32 + 2 * W + 2 if rhythm is not None else 0) + (2 if discriminator is not None else 0)
+class _MovementScores:
+    """`rhythm` (a rhythm.MotionRhythm, or anything with its `psd` and `contour_and_std`): the scores of the M2S-GAN evaluation that look
+    at how the motion moves (Contrastive_Stage/M2SGAN_eval.py:100-133, metrics.py) - "rde" and "sce" (the means over the clips of
+    "rde_per_clip" and "sce_per_clip", {id: value}; the reference evaluates clip by clip), "sd_gen" and "sd_real".  Needs clips of
+    at least 256 frames.  `discriminator` (a discriminator.Discriminator_1DCNN, or anything with its `forward`): "w_distance", the
+    mean of D(real) - D(generated); at least 41 frames.  Both run on the device right behind each batch's sampling, on the same
+    stream; only the per-clip arrays come back, with the poses, into one pinned row per clip: [psd generated 32 | psd real 32 |
+    contour generated W | contour real W | sd generated | sd real] with `rhythm`, then [D(generated) | D(real)] with `discriminator`.
+    As with the latents, with `smooth` these are the scores of the SMOOTHED poses."""
+
+    def __init__(self, rhythm, discriminator, ids, T, dim_pose, batch_size):
+        if rhythm is not None and T < 256:
+            raise ValueError(f"clips of {T} frames: the rhythm scores need at least 256 (Welch's segment)")
+        if discriminator is not None and T < 41:
+            raise ValueError(f"clips of {T} frames: the critic needs at least 41 (one pooled frame behind its third stage)")
+        self.rhythm, self.critic, self.ids, self.dim_pose, self.W = rhythm, discriminator, ids, dim_pose, (T - 60) // 30 + 1
+        self.rows = None                 # pinned [clips, columns]: every clip's row, read after the last batch's event
+
+    def enqueue(self, batch, pred):
+        B, T = pred.shape[0], pred.shape[1]
+        gt = _same_frames(batch, pred, self.dim_pose, "rhythm")
+        gen = pred.reshape(B, T, self.dim_pose).contiguous()
+        cols = []
+        if self.rhythm is not None:
+            cg, sg = self.rhythm.contour_and_std(gen)
+            cr, sr = self.rhythm.contour_and_std(gt)
+            cols += [self.rhythm.psd(gen), self.rhythm.psd(gt), cg, cr, sg.reshape(B, 1), sr.reshape(B, 1)]
+        if self.critic is not None:
+            cols += [self.critic.forward(gen).reshape(B, 1), self.critic.forward(gt).reshape(B, 1)]
+        rows = torch.cat(cols, dim=1)
+        if self.rows is None:
+            self.rows = torch.empty((len(self.ids), rows.shape[1]), dtype=torch.float32, pin_memory=pred.is_cuda)
+        self.rows[batch.first:batch.first + B].copy_(rows, non_blocking=True)
+
+    def finish(self, out, verbose):
+        from .metrics import rhythm_density_error, standard_deviation_percentage, strength_contour_error, w_distance
+        rows, ids, W, at = self.rows.numpy(), self.ids, self.W, 0
+        if self.rhythm is not None:
+            psd_g, psd_r, c_g, c_r = rows[:, 0:32], rows[:, 32:64], rows[:, 64:64 + W], rows[:, 64 + W:64 + 2 * W]
+            at = 64 + 2 * W
+            rde, out["rde"] = rhythm_density_error(psd_r, psd_g)
+            sce, out["sce"] = strength_contour_error(c_r, c_g)
+            out["rde_per_clip"] = {cid: float(v) for cid, v in zip(ids, rde)}
+            out["sce_per_clip"] = {cid: float(v) for cid, v in zip(ids, sce)}
+            out["sd_gen"], out["sd_real"] = float(rows[:, at].astype(np.float64).mean()), float(rows[:, at + 1].astype(np.float64).mean())
+            at += 2
+        if self.critic is not None:
+            out["w_distance"] = w_distance(rows[:, at + 1], rows[:, at])
+        if verbose:
+            print("  ".join(f"{key}: {out[key]}" for key in ("rde", "sce", "sd_gen", "sd_real", "w_distance") if key in out))
+            if "sd_gen" in out:
+                print(f"sdp: {standard_deviation_percentage(out['sd_gen'], out['sd_real']):.2f}%")
 
 
-def _rhythm_arrays(rhythm, discriminator, pred, gts, dim_pose, ids):
-    """One row [B, _rhythm_columns] per clip of what RDE, SCE, SD and the W-distance are made of, for the sampled poses and the ground
-    truth, enqueued on the current stream right behind the sampling (the ground truth is uploaded to the poses' device first)."""
-    B, T = pred.shape[0], pred.shape[1]
-    gt = _ground_truth(pred, gts, dim_pose, ids, "rhythm")
-    gen = pred.reshape(B, T, dim_pose).contiguous()
-    cols = []
-    if rhythm is not None:
-        cg, sg = rhythm.contour_and_std(gen)
-        cr, sr = rhythm.contour_and_std(gt)
-        cols += [rhythm.psd(gen), rhythm.psd(gt), cg, cr, sg.reshape(B, 1), sr.reshape(B, 1)]
-    if discriminator is not None:
-        cols += [discriminator.forward(gen).reshape(B, 1), discriminator.forward(gt).reshape(B, 1)]
-    return torch.cat(cols, dim=1)
-
-
-def _rhythm_scores(rows, ids, T, rhythm, discriminator):
-    """The result keys of the rhythm scores from every clip's row (_rhythm_columns), in clip order."""
-    from .metrics import rhythm_density_error, strength_contour_error, w_distance
-    out, W, at = {}, (T - 60) // 30 + 1, 0
-    if rhythm is not None:
-        psd_g, psd_r, c_g, c_r = rows[:, 0:32], rows[:, 32:64], rows[:, 64:64 + W], rows[:, 64 + W:64 + 2 * W]
-        at = 64 + 2 * W
-        rde, out["rde"] = rhythm_density_error(psd_r, psd_g)
-        sce, out["sce"] = strength_contour_error(c_r, c_g)
-        out["rde_per_clip"] = {cid: float(v) for cid, v in zip(ids, rde)}
-        out["sce_per_clip"] = {cid: float(v) for cid, v in zip(ids, sce)}
-        out["sd_gen"], out["sd_real"] = float(rows[:, at].astype(np.float64).mean()), float(rows[:, at + 1].astype(np.float64).mean())
-        at += 2
-    if discriminator is not None:
-        out["w_distance"] = w_distance(rows[:, at + 1], rows[:, at])
-    return out
-
-
-BEAT_COLUMNS = 8      # floats per clip of _beat_rows: [BC, Beat Align, music beats, motion beats] of the sampled poses, then of the ground truth
+BEAT_COLUMNS = 8      # floats per clip of _BeatScores' rows: [BC, Beat Align, music beats, motion beats] of the sampled poses, then of the ground truth
 
 
 def _check_music_beats(music_beats, ids):
@@ -284,47 +396,67 @@ def _check_music_beats(music_beats, ids):
     return out
 
 
-def _beat_rows(beat_rhythm, pred, gts, dim_pose, ids, music_beats, stride):
-    """One row [B, BEAT_COLUMNS] per clip of dc_rhythm_motion_beats + dc_rhythm_beat_scores on the sampled poses and on the ground
-    truth, enqueued on the current stream right behind the sampling.  The batch's music beats are padded with zeros to its longest
-    and uploaded with it (zeros behind a clip's last beat change nothing: csrc/dc_rhythm.hip, k_beat_scores)."""
-    B, T = pred.shape[0], pred.shape[1]
-    gt = _ground_truth(pred, gts, dim_pose, ids, "beat")
-    mus = np.zeros((B, max(music_beats[cid].size for cid in ids)), np.uint8)
-    for i, cid in enumerate(ids):
-        mus[i, :music_beats[cid].size] = music_beats[cid]
-    mus = torch.from_numpy(mus)
-    if pred.is_cuda:
-        mus = mus.pin_memory().to(pred.device, non_blocking=True)
-    cols = []
-    for x in (pred.reshape(B, T, dim_pose).contiguous(), gt):
-        scores, counts = beat_rhythm.beat_scores(beat_rhythm.motion_beats(x), mus, music_stride=stride, counts=True)
-        cols += [scores, counts.to(torch.float32)]           # (counts are at most a clip's frames: exact in fp32)
-    return torch.cat(cols, dim=1)
+class _BeatScores:
+    """`music_beats` ({clip id: 1-D one-hot, nonzero = a beat}: metrics.load_music_beats): beat consistency, the BC column of the
+    paper's table (eval_new_metrics.py:253-317) - from SUPPLIED music beats: the reference's get_music_beat is librosa's tracker on
+    the clip's mel, a property of the dataset (tools/music_beats_librosa.py).  Each batch's one-hots are padded with zeros to its
+    longest and uploaded with it (zeros behind a clip's last beat change nothing: csrc/dc_rhythm.hip, k_beat_scores); the motion's
+    beats and their alignment (rhythm.MotionRhythm.motion_beats, .beat_scores) run on the sampled poses and on the ground truth right
+    behind the sampling, on the same stream (on `rhythm` when it can, else on a MotionRhythm of the poses' device), and the [B, 2]
+    scores and counts come back with the poses, into one pinned row of BEAT_COLUMNS per clip.  Adds "bc_gen", "bc_real" (the means
+    over the clips of "bc_gen_per_clip", "bc_real_per_clip", {id: value}), "beat_align_gen" and "beat_align_real" (the other
+    direction; nan when a clip has no motion beat).  `beat_stride`: 1 compares the index lists as they are, as the reference does
+    (90-fps mel frames against 30-fps motion frames; the paper's numbers); 3 puts both on one clock.  A clip id without an entry, an
+    entry that is not 1-D or has no beat: ValueError before anything is sampled.  With `smooth` the scores are those of the SMOOTHED
+    poses."""
+
+    def __init__(self, music_beats, beat_stride, rhythm, ids, T, dim_pose, batch_size):
+        if int(beat_stride) < 1:
+            raise ValueError(f"beat_stride must be >= 1, got {beat_stride}")
+        self.beats, self.stride, self.ids, self.dim_pose = _check_music_beats(music_beats, ids), int(beat_stride), ids, dim_pose
+        self.rhythm = rhythm if hasattr(rhythm, "motion_beats") and hasattr(rhythm, "beat_scores") else None
+        self.rows = None                 # pinned [clips, BEAT_COLUMNS]: every clip's row, read after the last batch's event
+
+    def enqueue(self, batch, pred):
+        B, T = pred.shape[0], pred.shape[1]
+        if self.rhythm is None:
+            from .rhythm import MotionRhythm
+            self.rhythm = MotionRhythm(pred.device)
+        if self.rows is None:
+            self.rows = torch.empty((len(self.ids), BEAT_COLUMNS), dtype=torch.float32, pin_memory=pred.is_cuda)
+        gt = _same_frames(batch, pred, self.dim_pose, "beat")
+        mus = np.zeros((B, max(self.beats[cid].size for cid in batch.ids)), np.uint8)
+        for i, cid in enumerate(batch.ids):
+            mus[i, :self.beats[cid].size] = self.beats[cid]
+        mus = torch.from_numpy(mus)
+        if pred.is_cuda:
+            mus = mus.pin_memory().to(pred.device, non_blocking=True)
+        cols = []
+        for x in (pred.reshape(B, T, self.dim_pose).contiguous(), gt):
+            scores, counts = self.rhythm.beat_scores(self.rhythm.motion_beats(x), mus, music_stride=self.stride, counts=True)
+            cols += [scores, counts.to(torch.float32)]           # (counts are at most a clip's frames: exact in fp32)
+        self.rows[batch.first:batch.first + B].copy_(torch.cat(cols, dim=1), non_blocking=True)
+
+    def finish(self, out, verbose):
+        from .metrics import beat_consistency
+        rows = self.rows.numpy()
+        for name, at in (("gen", 0), ("real", 4)):
+            out[f"bc_{name}"], out[f"bc_{name}_per_clip"] = beat_consistency(rows[:, at:at + 2], rows[:, at + 2:at + 4], self.ids)
+            out[f"beat_align_{name}"] = beat_consistency(rows[:, at:at + 2], rows[:, at + 2:at + 4], self.ids, column=1)[0]
+        if verbose:
+            print("  ".join(f"{key}: {out[key]}" for key in ("bc_gen", "bc_real", "beat_align_gen", "beat_align_real")))
 
 
-def _beat_results(rows, ids):
-    """The result keys of the beat scores from every clip's row (_beat_rows), in clip order."""
-    from .metrics import beat_consistency
-    out = {}
-    for name, at in (("gen", 0), ("real", 4)):
-        out[f"bc_{name}"], out[f"bc_{name}_per_clip"] = beat_consistency(rows[:, at:at + 2], rows[:, at + 2:at + 4], ids)
-        out[f"beat_align_{name}"] = beat_consistency(rows[:, at:at + 2], rows[:, at + 2:at + 4], ids, column=1)[0]
-    return out
-
-
-def _latent_scores(results, nb, diversity_seed):
-    """FGD, feat_dist and diversity (metrics.py) over every clip's latents in clip order."""
-    from .metrics import diversity_score, frechet_gesture_distance
-    gen = [r[3] for k in range(nb) for r in results[k]]
-    real = [r[4] for k in range(nb) for r in results[k]]
-    fgd, feat_dist = frechet_gesture_distance(gen, real)
-    return float(fgd), float(feat_dist), float(diversity_score(gen, diversity_seed))
+def _enqueue_scores(families, batch):
+    """Every active family's device work for `batch`, on the current stream and in the families' order -> what they left to do on
+    the host once the batch has landed (zero-argument callables)."""
+    return [fn for fn in [f.enqueue(batch, batch.pred) for f in families] if fn is not None]
 
 
 class _Scorer:
     """Per-clip MSE of a batch (eval_new.py:124-131) on a background thread, behind the event that says the batch's poses have
-    landed in the pinned buffer - the main thread is enqueueing the next batch meanwhile."""
+    landed in the pinned buffer - the main thread is enqueueing the next batch meanwhile.  `landed`: what the score families left
+    to do on the host once the batch is there (their `enqueue`'s return values), run behind the MSEs."""
 
     def __init__(self, dim_pose):
         import queue
@@ -340,27 +472,24 @@ class _Scorer:
             job = self.q.get()
             if job is None:
                 return
-            k, bid, gts, pred_h, event, _keep, lat_h = job
+            k, bid, gts, pred_h, event, _keep, landed = job
             try:
                 if event is not None:
                     event.synchronize()
                 pred = pred_h.numpy()
                 if not np.isfinite(pred).all():
                     raise FloatingPointError(f"non-finite poses in batch {k}")
-                res = []
-                for i, cid in enumerate(bid):
-                    pm = pred[i].reshape([pred[i].shape[0], self.dim_pose // 2, 2])          # eval_new.py:124-125
-                    res.append((cid, mse_loss(gts[i], pm)))
-                if lat_h is not None:           # (copies: the pinned slot is reused two batches later)
-                    res = _with_latents(res, lat_h[0].numpy(), lat_h[1].numpy())
+                res = _clip_mses(bid, gts, pred, self.dim_pose)
+                for fn in landed:
+                    fn()
             except BaseException as e:
                 res = e
             with self.cv:
                 self.done[k] = res
                 self.cv.notify_all()
 
-    def submit(self, k, bid, gts, pred_h, event, keep, lat_h=None):
-        self.q.put((k, bid, gts, pred_h, event, keep, lat_h))
+    def submit(self, k, bid, gts, pred_h, event, keep, landed=()):
+        self.q.put((k, bid, gts, pred_h, event, keep, landed))
 
     def wait_for(self, k, reraise=True):
         """Blocks until batch k has been scored (k < 0: nothing to wait for); returns its [(clip id, mse)] or raises its error.
@@ -388,90 +517,34 @@ def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed
     "seconds", "frames_per_s"}.  Clip i (in sorted order) starts from noise seeded with (seed, i), so the result
     does not depend on batch_size or on the number of ranks.
 
-    `motion_encoder` (a motion_encoder.MotionEncoder_STGCN, or anything with its `latent(x)` -> [B, 64, T]): the latent-space
-    scores of the paper's table as well (metrics.py), added as "latent_mse" ({id: the clip's Sync Error term},
-    eval_old_metrics.py:90-100), "final_latent_mse" (SE), "fgd", "feat_dist" (eval_new_metrics.py:169-199), "diversity"
-    (:159-166, permutation drawn with `diversity_seed`) and "metrics_s" (host seconds spent on FGD, feat_dist and diversity after
-    the last batch).  The sampled poses and the ground truth are encoded on the device right after each batch's sampling, on the
-    same stream, and the latents come back with the poses.  Every clip must have the poses' T frames (ValueError otherwise).
-    With `smooth` the latents are those of the SMOOTHED poses - the reference scores the unsmoothed output.  Without an encoder
-    the result is exactly what it was before these scores existed.
-
-    `m2snet` (an m2snet.M2SNet, or anything with its `music_latent`, `motion_latent` and `fuse`): the learned synchronisation
-    score as well - the one number here that looks at the music.  Each batch's music is encoded once and scored against the
-    ground truth, the sampled poses and, as the mismatched control, the sampled poses of the next clip of the batch (left out for a
-    batch of one clip, so the control depends on `batch_size`).  Adds "m2s_sync_real", "m2s_sync_gen", "m2s_sync_mismatched" (mean
-    per-frame predictions over all clips; nan when no batch had two clips) and "m2s_accuracy_gen" (metrics.sync_stats: matched =
-    generated, mismatched = rolled).  Without it the result is unchanged.
-
-    `retrieval` (needs `m2snet`, which must have `fuse_pairs`): the question the rolled control cannot ask - does a motion follow its
-    own music better than it follows the other pieces of the set?  The music latents and the real and generated motion latents of
-    ALL clips stay on the device (3 x 64 T floats per clip); after the last batch every music is scored against every real and every
-    generated motion (two M2SNet.fuse_pairs, N^2 pairs each; a pair's score is the mean per-frame probability) and the N x N matrices
-    are ranked on the host (metrics.retrieval_stats, the reference's calculate_R_precision / calculate_top_k of
-    Diffusion_Stage/utils/metrics.py on scores instead of distances).  Adds "m2s_r_precision_real" / "_gen" (lists over top-1, 2, 3:
-    the share of musics whose own motion is among the k best), "m2s_mean_rank_real" / "_gen" (1 = best), "m2s_margin_real" / "_gen"
-    (mean matched score minus mean mismatched score), "m2s_sync_offdiag_gen" (the mean mismatched score: every other clip, not the
-    next one of the batch), "m2s_pair_accuracy_real" / "_gen" (metrics.pair_accuracy: M2SNet_eval.py:65-68 with matched and
-    mismatched frames weighted equally) and "m2s_retrieval_s".  None of them depends on `batch_size` or on the order of the clips
-    (ties go to the lower clip index).  The clips must share one latent length (ValueError naming two that differ).  The existing
-    keys, the rolled control among them, are what they are without it.
-
-    `rhythm` (a rhythm.MotionRhythm, or anything with its `psd` and `contour_and_std`): the scores of the M2S-GAN evaluation that look
-    at how the motion moves (Contrastive_Stage/M2SGAN_eval.py:100-133, metrics.py) - "rde" and "sce" (the means over the clips of
-    "rde_per_clip" and "sce_per_clip", {id: value}; the reference evaluates clip by clip), "sd_gen" and "sd_real".  Needs clips of
-    at least 256 frames.  `discriminator` (a discriminator.Discriminator_1DCNN, or anything with its `forward`): "w_distance", the
-    mean of D(real) - D(generated); at least 41 frames.  Both run on the device right behind each batch's sampling, on the same
-    stream; only the per-clip arrays ([B, 32] spectra, [B, W] contours, [B] deviations and scores) come back, with the poses.  As
-    with the latents, with `smooth` these are the scores of the SMOOTHED poses.  Without the two arguments the result and the work
-    done are exactly what they were before these scores existed.
-
-    `music_beats` ({clip id: 1-D one-hot, nonzero = a beat}: metrics.load_music_beats): beat consistency as well, the BC column of
-    the paper's table (eval_new_metrics.py:253-317) - from SUPPLIED music beats: the reference's get_music_beat is librosa's tracker
-    on the clip's mel, a property of the dataset (tools/music_beats_librosa.py).  Each batch's one-hots are padded with zeros to its
-    longest and uploaded with it; the motion's beats and their alignment (rhythm.MotionRhythm.motion_beats, .beat_scores) run on the
-    sampled poses and on the ground truth right behind the sampling, on the same stream (on `rhythm` when one is given, else on a
-    MotionRhythm of the poses' device), and the [B, 2] scores and counts come back with the other per-clip rows.  Adds "bc_gen",
-    "bc_real" (the means over the clips of "bc_gen_per_clip", "bc_real_per_clip", {id: value}), "beat_align_gen" and
-    "beat_align_real" (the other direction; nan when a clip has no motion beat).  `beat_stride`: 1 compares the index lists as they
-    are, as the reference does (90-fps mel frames against 30-fps motion frames; the paper's numbers); 3 puts both on one clock.  A
-    clip id without an entry, an entry that is not 1-D or has no beat: ValueError before anything is sampled.  With `smooth` the
-    scores are those of the SMOOTHED poses.  Without the argument the result and the work done are exactly what they were.
+    Each further score is a family of its own, switched on by its argument(s) and described at its class; without them the result
+    and the work done are exactly what they were before the family existed, and each family refuses what it cannot score before
+    anything is sampled:
+    `motion_encoder`, `diversity_seed`: the latent scores SE, FGD, feat_dist and diversity (_LatentScores).
+    `m2snet`, `retrieval`: M2SNet's synchronisation score, and every music ranked against every motion (_SyncScores).
+    `rhythm`, `discriminator`: RDE, SCE, SD and the critic's W-distance (_MovementScores).
+    `music_beats`, `beat_stride`: beat consistency and Beat Align from supplied music beats (_BeatScores).
 
     `guidance_scale`: None, or the classifier-free guidance scale every batch is sampled with (generate_music_motion).
     `steps`, `spacing`, `solver`: every batch is sampled on `steps` of the schedule's timesteps (generate_music_motion; the defaults
     walk every timestep, as before).
 
     The host stays out of the GPU's way: batch k + 1's files and noise are prepared, and batch k - 1's MSEs computed, on
-    background threads while batch k is sampled; the poses come back through a pinned double buffer behind an event, not a stream
-    synchronisation; the sampler's per-loop numeric check (a status read that waits for the GPU) is replaced by a finiteness check
-    of the poses on the scoring thread, and a batch that fails it is sampled again the checked way (which is where
-    precision="auto" falls back to the bf16-range mode).  At most two batches are in flight."""
+    background threads while batch k is sampled; the active families enqueue their device work right behind the batch's sampling, in
+    the order above, and the poses come back behind it through a pinned double buffer and an event, not a stream synchronisation;
+    the sampler's per-loop numeric check (a status read that waits for the GPU) is replaced by a finiteness check of the poses on
+    the scoring thread, and a batch that fails it is sampled again the checked way (which is where precision="auto" falls back to
+    the bf16-range mode) and handed to the same families again, whose rows for it are overwritten.  At most two batches are in
+    flight."""
     gkw = {} if guidance_scale is None else {"guidance_scale": float(guidance_scale)}      # (None: the trainer is called as before)
     if steps is not None or solver != "ddim":
         gkw.update(steps=steps, spacing=spacing, solver=solver)
-    if retrieval and (m2snet is None or not hasattr(m2snet, "fuse_pairs")):
-        raise ValueError("retrieval=True ranks M2SNet's scores of every pair: pass m2snet= (an m2snet.M2SNet, with fuse_pairs)")
-    ids = list_clips(root)
-    if limit is not None:
-        ids = ids[:int(limit)]
-    if not ids:
-        raise FileNotFoundError(f"no <id>/mel.npy + <id>/motion.npy pairs under {root}")
-    mel_shape = tuple(np.load(pjoin(root, ids[0], "mel.npy"), mmap_mode="r").shape)
-    T = (mel_shape[0] - 1) // 3 + 1
-    nb = (len(ids) + batch_size - 1) // batch_size
-    kept = {} if retrieval else None     # batch -> [music latent, real motion latent, generated motion latent] on the device
-    moves = rhythm is not None or discriminator is not None
-    if rhythm is not None and T < 256:
-        raise ValueError(f"clips of {T} frames: the rhythm scores need at least 256 (Welch's segment)")
-    if discriminator is not None and T < 41:
-        raise ValueError(f"clips of {T} frames: the critic needs at least 41 (one pooled frame behind its third stage)")
-    rh_rows = None                       # pinned [clips, _rhythm_columns]: every clip's row, read after the last batch's event
-    bt_rows = beat_rhythm = None         # pinned [clips, BEAT_COLUMNS] likewise, and the MotionRhythm that fills it (music_beats only)
-    if music_beats is not None:
-        if int(beat_stride) < 1:
-            raise ValueError(f"beat_stride must be >= 1, got {beat_stride}")
-        music_beats = _check_music_beats(music_beats, ids)
+    sync = _SyncScores(m2snet, retrieval, dim_pose) if m2snet is not None or retrieval else None
+    ids, mel_shape, T, nb = _open_dataset(root, limit, batch_size)
+    facts = (ids, T, dim_pose, batch_size)
+    families = [f for f in (_LatentScores(motion_encoder, diversity_seed, *facts) if motion_encoder is not None else None, sync,
+                            _MovementScores(rhythm, discriminator, *facts) if rhythm is not None or discriminator is not None else None,
+                            _BeatScores(music_beats, beat_stride, rhythm, *facts) if music_beats is not None else None) if f is not None]
     pf = _Prefetcher(root, ids, batch_size, mel_shape, noise=(seed, T, dim_pose))
     pf.start(0)
     scorer = _Scorer(dim_pose)
@@ -481,12 +554,8 @@ def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed
     dev = getattr(trainer, "device", None)
     on_gpu = dev is not None and torch.device(dev).type == "cuda"
     out_h = [None, None]
-    lat_buf = [None, None]               # pinned [2 (generated, real), batch_size, 64, T] latent slots (motion_encoder only)
     slot_free = [None, None]             # event: the GPU has consumed the slot's pinned mel / noise buffers
     results = {}
-    sync = {}                            # batch -> (real, generated, mismatched | None) predictions [B, T] on the device (m2snet only)
-    if music_beats is not None and hasattr(rhythm, "motion_beats") and hasattr(rhythm, "beat_scores"):
-        beat_rhythm = rhythm
     exchange_before = getattr(enc, "combine_exchange", None)
     ev_first = ev_last = None            # completion events of the first and the last batch: the GPU's own steady-state period
     n_after_first = 0
@@ -518,29 +587,7 @@ def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed
             if out_h[s] is None or out_h[s].shape[0] < pred.shape[0] or out_h[s].shape[1:] != pred.shape[1:]:
                 out_h[s] = torch.empty((batch_size,) + tuple(pred.shape[1:]), dtype=pred.dtype, pin_memory=pred.is_cuda)     # pageable D2H costs ~3x the copy
             ph = out_h[s][:pred.shape[0]]
-            lat_h = None
-            if motion_encoder is not None:
-                lats = _encode_pair(motion_encoder, pred, gts, dim_pose, bid)
-                if lat_buf[s] is None or lat_buf[s].shape[1] < pred.shape[0] or lat_buf[s].shape[2:] != lats[0].shape[1:]:
-                    lat_buf[s] = torch.empty((2, batch_size) + tuple(lats[0].shape[1:]), dtype=torch.float32, pin_memory=pred.is_cuda)
-                lat_h = lat_buf[s][:, :pred.shape[0]]
-                lat_h[0].copy_(lats[0], non_blocking=True)
-                lat_h[1].copy_(lats[1], non_blocking=True)
-            if m2snet is not None:
-                sync[k] = _sync_predictions(m2snet, mel, pred, gts, dim_pose, None if kept is None else kept.setdefault(k, []))
-            if moves:
-                if rh_rows is None:
-                    rh_rows = torch.empty((len(ids), _rhythm_columns(rhythm, discriminator, T)), dtype=torch.float32, pin_memory=pred.is_cuda)
-                rh_rows[k * batch_size:k * batch_size + pred.shape[0]].copy_(_rhythm_arrays(rhythm, discriminator, pred, gts, dim_pose, bid),
-                                                                             non_blocking=True)
-            if music_beats is not None:
-                if beat_rhythm is None:
-                    from .rhythm import MotionRhythm
-                    beat_rhythm = MotionRhythm(pred.device)
-                if bt_rows is None:
-                    bt_rows = torch.empty((len(ids), BEAT_COLUMNS), dtype=torch.float32, pin_memory=pred.is_cuda)
-                bt_rows[k * batch_size:k * batch_size + pred.shape[0]].copy_(_beat_rows(beat_rhythm, pred, gts, dim_pose, bid, music_beats, int(beat_stride)),
-                                                                             non_blocking=True)
+            landed = _enqueue_scores(families, _Batch(k, k * batch_size, bid, mel, gts, pred, s))
             ph.copy_(pred, non_blocking=True)
             ev = None
             if pred.is_cuda:
@@ -549,7 +596,7 @@ def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed
                 slot_free[s] = ev
                 ev_first = ev_first or ev
                 ev_last, n_after_first = ev, (n_after_first + len(bid) if ev_first is not ev else 0)
-            scorer.submit(k, bid, gts, ph, ev, (pred, lat_h), lat_h)
+            scorer.submit(k, bid, gts, ph, ev, pred, landed)
             if serial:
                 scorer.wait_for(k, reraise=False)
         for k in range(nb):
@@ -563,18 +610,13 @@ def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed
                 pf2 = _Prefetcher(root, ids, batch_size, mel_shape, noise=(seed, T, dim_pose))
                 pf2._load_batch(k, 0)
                 bid, mel, gts = pf2.result
-                pred_d = trainer.generate_music_motion(mel, dim_pose, noise=pf2.noise, smooth=19 if smooth else None, **gkw)
-                lats = _encode_pair(motion_encoder, pred_d, gts, dim_pose, bid) if motion_encoder is not None else None
-                if m2snet is not None:
-                    sync[k] = _sync_predictions(m2snet, mel, pred_d, gts, dim_pose, None if kept is None else kept.setdefault(k, []))
-                if moves:
-                    rh_rows[k * batch_size:k * batch_size + pred_d.shape[0]].copy_(_rhythm_arrays(rhythm, discriminator, pred_d, gts, dim_pose, bid))
-                if music_beats is not None:
-                    bt_rows[k * batch_size:k * batch_size + pred_d.shape[0]].copy_(_beat_rows(beat_rhythm, pred_d, gts, dim_pose, bid, music_beats, int(beat_stride)))
-                pred = pred_d.cpu().numpy()
-                results[k] = [(cid, mse_loss(gts[i], pred[i].reshape([pred[i].shape[0], dim_pose // 2, 2]))) for i, cid in enumerate(bid)]
-                if lats is not None:
-                    results[k] = _with_latents(results[k], lats[0].cpu().numpy(), lats[1].cpu().numpy())
+                pred = trainer.generate_music_motion(mel, dim_pose, noise=pf2.noise, smooth=19 if smooth else None, **gkw)
+                # no pinned slot for this batch: later ones may still be queued on the scoring thread and read both.  What the families
+                # enqueue goes to their per-clip rows and per-batch entries, and the poses' blocking copy waits for all of it
+                landed = _enqueue_scores(families, _Batch(k, k * batch_size, bid, mel, gts, pred, None))
+                results[k] = _clip_mses(bid, gts, pred.cpu().numpy(), dim_pose)
+                for fn in landed:
+                    fn()
                 enc.check_numerics = False
     finally:
         scorer.close()
@@ -584,7 +626,7 @@ def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed
     dt = time.perf_counter() - t0
     per_clip, total_loss = {}, 0.0
     for k in range(nb):
-        for cid, cur, *_ in results[k]:
+        for cid, cur in results[k]:
             per_clip[cid] = float(cur)
             total_loss += cur
             if verbose:
@@ -600,43 +642,8 @@ def evaluate_dataset(trainer, root, dim_pose=26, batch_size=32, limit=None, seed
         # clips of batches 2 .. n over the time between the completion of batch 1 and of batch n ON THE GPU: the pipeline's rate
         # without the two things nothing can hide (the first batch's load before any GPU work, the last batch's scoring after it)
         out["steady_frames_per_s"] = n_after_first * T / (ev_first.elapsed_time(ev_last) * 1e-3)
-    if motion_encoder is not None:
-        from .metrics import sync_error
-        tm = time.perf_counter()
-        lmse = [(r[0], r[2]) for k in range(nb) for r in results[k]]
-        out["latent_mse"] = {cid: float(v) for cid, v in lmse}
-        out["final_latent_mse"] = float(sync_error([v for _, v in lmse]))
-        out["fgd"], out["feat_dist"], out["diversity"] = _latent_scores(results, nb, diversity_seed)
-        out["metrics_s"] = time.perf_counter() - tm
-        if verbose:
-            print("final_latent_mse: ", out["final_latent_mse"])
-            print(f"fgd: {out['fgd']}  feat_dist: {out['feat_dist']}  diversity: {out['diversity']}")
-    if m2snet is not None:
-        from .metrics import sync_stats
-        real, gen, mis = ([torch.as_tensor(sync[k][i]).cpu().reshape(-1) for k in range(nb) if sync[k][i] is not None] for i in range(3))
-        st = sync_stats(torch.cat(gen), torch.cat(mis) if mis else None)
-        out["m2s_sync_real"] = sync_stats(torch.cat(real))["sync"]
-        out["m2s_sync_gen"], out["m2s_sync_mismatched"], out["m2s_accuracy_gen"] = st["sync"], st["non_sync"], st["accuracy"]
-        if verbose:
-            print(f"m2s_sync_real: {out['m2s_sync_real']}  m2s_sync_gen: {out['m2s_sync_gen']}  "
-                  f"m2s_sync_mismatched: {out['m2s_sync_mismatched']}  m2s_accuracy_gen: {out['m2s_accuracy_gen']}")
-        if retrieval:
-            tm = time.perf_counter()
-            out.update(_retrieval_scores(m2snet, kept, ids, batch_size))
-            out["m2s_retrieval_s"] = time.perf_counter() - tm
-            if verbose:
-                print("  ".join(f"{key}: {out[key]}" for key in sorted(out) if key.startswith(("m2s_r_", "m2s_mean_rank", "m2s_margin", "m2s_pair"))))
-    if moves:
-        out.update(_rhythm_scores(rh_rows.numpy(), ids, T, rhythm, discriminator))
-        if verbose:
-            print("  ".join(f"{key}: {out[key]}" for key in ("rde", "sce", "sd_gen", "sd_real", "w_distance") if key in out))
-            if "sd_gen" in out:
-                from .metrics import standard_deviation_percentage
-                print(f"sdp: {standard_deviation_percentage(out['sd_gen'], out['sd_real']):.2f}%")
-    if music_beats is not None:
-        out.update(_beat_results(bt_rows.numpy(), ids))
-        if verbose:
-            print("  ".join(f"{key}: {out[key]}" for key in ("bc_gen", "bc_real", "beat_align_gen", "beat_align_real")))
+    for f in families:
+        f.finish(out, verbose)
     return out
 
 
@@ -701,6 +708,33 @@ def sync_negatives(m2snet, mel, motion, sample_length, clip_length, draws):
     return out
 
 
+def _encoded_batches(trainer, root, ids, batch_size, mel_shape, T, nb):
+    """The walk of the drivers that score without sampling: starts loading batch 0 at once and returns a generator of (k, the batch's
+    clip ids, x0 [B, T, 26] on the trainer's device, xf_proj, xf_out) - the batch's music encoded once (encode_music) while batch
+    k + 1's files are read into the other pinned slot, which is free once the GPU has consumed it."""
+    pf = _Prefetcher(root, ids, batch_size, mel_shape)
+    pf.start(0)
+    dev = trainer.device
+
+    def walk():
+        slot_free = [None, None]
+        for k in range(nb):
+            bid, mel, gts = pf.take()
+            if k + 1 < nb:
+                pf.start(k + 1, after=slot_free[(k + 1) & 1])
+            bad = [(cid, np.shape(g)) for cid, g in zip(bid, gts) if int(np.prod(np.shape(g))) != T * 26]
+            if bad:
+                raise ValueError(f"the music gives {T} frames, but these motions differ: {bad[:4]}")
+            x0 = torch.from_numpy(np.ascontiguousarray(np.stack([np.reshape(g, (T, 26)) for g in gts]), np.float32)).to(dev)
+            with torch.no_grad():
+                xf_proj, xf_out = trainer.encoder.encode_music(mel, dev)
+            if torch.device(dev).type == "cuda":
+                slot_free[k & 1] = torch.cuda.Event()
+                slot_free[k & 1].record()
+            yield k, bid, x0, xf_proj, xf_out
+    return walk()
+
+
 def validation_grid(num_timesteps, k):
     """The noise levels of a `k`-point loss curve: unique(round(linspace(0, S - 1, k))), increasing."""
     S, k = int(num_timesteps), int(k)
@@ -727,11 +761,7 @@ def validation_dataset(trainer, root, timesteps=None, batch_size=32, seed=0, mot
     "loss_velocity_body", "velocity_elbow", "mse", "feat_included"}], "average": the same scalars averaged over the grid,
     "evaluations" (model evaluations per clip), "seconds"}."""
     from .metrics import denoising_loss_scalars
-    ids = list_clips(root)
-    if limit is not None:
-        ids = ids[:int(limit)]
-    if not ids:
-        raise FileNotFoundError(f"no <id>/mel.npy + <id>/motion.npy pairs under {root}")
+    ids, mel_shape, T, nb = _open_dataset(root, limit, batch_size)
     S = int(trainer.diffusion.num_timesteps)
     if timesteps is None:
         grid, drawn = None, np.random.RandomState(int(seed) & 0xffffffff).choice(S, size=(len(ids),), p=np.ones(S) / S)
@@ -739,32 +769,13 @@ def validation_dataset(trainer, root, timesteps=None, batch_size=32, seed=0, mot
         grid = validation_grid(S, timesteps) if np.ndim(timesteps) == 0 else [int(v) for v in timesteps]
         if not grid or any(not 0 <= v < S for v in grid):
             raise ValueError(f"timesteps must be inside [0, {S}), got {grid}")
-    mel_shape = tuple(np.load(pjoin(root, ids[0], "mel.npy"), mmap_mode="r").shape)
-    T = (mel_shape[0] - 1) // 3 + 1
-    nb = (len(ids) + batch_size - 1) // batch_size
-    pf = _Prefetcher(root, ids, batch_size, mel_shape)
-    pf.start(0)
-    dev = trainer.device
-    slot_free = [None, None]
+    batches = _encoded_batches(trainer, root, ids, batch_size, mel_shape, T, nb)
     n_levels = 1 if grid is None else len(grid)
     terms = [[] for _ in range(n_levels)]
     feats = [[] for _ in range(n_levels)]
     t0 = time.perf_counter()
-    for k in range(nb):
-        bid, mel, gts = pf.take()
-        if k + 1 < nb:
-            pf.start(k + 1, after=slot_free[(k + 1) & 1])
-        bad = [(cid, np.shape(g)) for cid, g in zip(bid, gts) if int(np.prod(np.shape(g))) != T * 26]
-        if bad:
-            raise ValueError(f"the music gives {T} frames, but these motions differ: {bad[:4]}")
-        B = len(bid)
-        x0 = torch.from_numpy(np.ascontiguousarray(np.stack([np.reshape(g, (T, 26)) for g in gts]), np.float32)).to(dev)
-        with torch.no_grad():
-            xf_proj, xf_out = trainer.encoder.encode_music(mel, dev)
-        if torch.device(dev).type == "cuda":
-            slot_free[k & 1] = torch.cuda.Event()
-            slot_free[k & 1].record()
-        first = k * batch_size
+    for k, bid, x0, xf_proj, xf_out in batches:
+        B, first = len(bid), k * batch_size
         for gi in range(n_levels):
             t = drawn[first:first + B] if grid is None else np.full(B, grid[gi], np.int64)
             r = trainer._validation_batch(xf_proj, xf_out, x0, np.full(B, T, np.int64), t, noise_seed=(seed, gi, first * T * 26),
@@ -800,39 +811,17 @@ def bound_dataset(trainer, root, timesteps=None, batch_size=32, seed=0, limit=No
     iteration = t).
     Returns {"clips", "timesteps" (decreasing), "total_bpd" (mean over the clips; None for a subset), "prior_bpd",
     "per_timestep": [{"t", "vb", "xstart_mse", "mse"}] (means over the clips), "evaluations" (model evaluations per clip), "seconds"}."""
-    ids = list_clips(root)
-    if limit is not None:
-        ids = ids[:int(limit)]
-    if not ids:
-        raise FileNotFoundError(f"no <id>/mel.npy + <id>/motion.npy pairs under {root}")
+    ids, mel_shape, T, nb = _open_dataset(root, limit, batch_size)
     S = int(trainer.diffusion.num_timesteps)
     grid = None
     if timesteps is not None:
         grid = bound_grid(S, timesteps) if np.ndim(timesteps) == 0 else sorted({int(v) for v in timesteps}, reverse=True)
         if not grid or any(not 0 <= v < S for v in grid):
             raise ValueError(f"timesteps must be inside [0, {S}), got {grid}")
-    mel_shape = tuple(np.load(pjoin(root, ids[0], "mel.npy"), mmap_mode="r").shape)
-    T = (mel_shape[0] - 1) // 3 + 1
-    nb = (len(ids) + batch_size - 1) // batch_size
-    pf = _Prefetcher(root, ids, batch_size, mel_shape)
-    pf.start(0)
-    dev = trainer.device
-    slot_free = [None, None]
+    batches = _encoded_batches(trainer, root, ids, batch_size, mel_shape, T, nb)
     rows = []
     t0 = time.perf_counter()
-    for k in range(nb):
-        bid, mel, gts = pf.take()
-        if k + 1 < nb:
-            pf.start(k + 1, after=slot_free[(k + 1) & 1])
-        bad = [(cid, np.shape(g)) for cid, g in zip(bid, gts) if int(np.prod(np.shape(g))) != T * 26]
-        if bad:
-            raise ValueError(f"the music gives {T} frames, but these motions differ: {bad[:4]}")
-        x0 = torch.from_numpy(np.ascontiguousarray(np.stack([np.reshape(g, (T, 26)) for g in gts]), np.float32)).to(dev)
-        with torch.no_grad():
-            xf_proj, xf_out = trainer.encoder.encode_music(mel, dev)
-        if torch.device(dev).type == "cuda":
-            slot_free[k & 1] = torch.cuda.Event()
-            slot_free[k & 1].record()
+    for k, bid, x0, xf_proj, xf_out in batches:
         rows.append(trainer._bound_batch(xf_proj, xf_out, x0, np.full(len(bid), T, np.int64), grid, int(seed) + k))
     dt = time.perf_counter() - t0
     ts = rows[0]["timesteps"]

@@ -288,6 +288,68 @@ def test_through_the_evaluator(rhythm, critic, weights, tmp_path):
     assert e["sd_gen"] <= SD_TOL and e["sd_real"] <= SD_TOL, e
 
 
+def test_a_resampled_batch_scores_as_the_clean_run_with_every_family_on(rhythm, critic, tmp_path):
+    """evaluate_dataset with the ST-GCN encoder, M2SNet (+ retrieval), MotionRhythm, the critic and beats on the M2S-GAN generator,
+    4 clips at T = 270 in batches of 2: batch 0's poses come back with one inf from the unchecked pass, the batch is generated again
+    the checked way and scored by the same per-family code - every key but the timings is exactly the clean run's (deterministic
+    kernels on the same noise and mel)."""
+    from diffusion_conductor_amd import evaluate as ev
+    from diffusion_conductor_amd.generator import Generator, GeneratorBaseline
+    from diffusion_conductor_amd.m2snet import M2SNet
+    from diffusion_conductor_amd.motion_encoder import MotionEncoder_STGCN
+    from diffusion_conductor_amd.synthetic import (smooth_mel, synthetic_m2sgan_state_dict, synthetic_m2snet_state_dict, synthetic_motion,
+                                                   synthetic_motion_encoder_state_dict)
+    T, n, seed = 270, 4, 6
+    gts = synthetic_motion(n, T, seed=24) + np.float32(0.5)
+    beats = {}
+    for i in range(n):
+        d = tmp_path / f"{i:03d}"
+        d.mkdir()
+        np.save(d / "mel.npy", smooth_mel(700 + i, 3 * T - 2, seed=7))
+        np.save(d / "motion.npy", gts[i])
+        beats[f"{i:03d}"] = (np.arange(3 * T - 2 - 5 * i) % (44 + i) == 7).astype(np.uint8)
+    gen = Generator(DEV).load_state_dict(synthetic_m2sgan_state_dict(0), strict=True)
+    menc = MotionEncoder_STGCN(DEV).load_state_dict(synthetic_motion_encoder_state_dict())
+    m2s = M2SNet(DEV).load_state_dict(synthetic_m2snet_state_dict())
+
+    class Checks:                                                    # a stub of the denoiser's switches: what evaluate_dataset saves and restores
+        check_numerics = True
+        combine_exchange = True
+
+    class Poisoned(GeneratorBaseline):
+        def __init__(self, generator, poison):
+            super().__init__(generator)
+            self.encoder, self.poison, self.calls, self.checked_calls = Checks(), poison, 0, 0
+
+        def generate_music_motion(self, *a, **kw):
+            k = self.calls
+            self.calls += 1
+            out = super().generate_music_motion(*a, **kw)
+            if self.encoder.check_numerics:
+                self.checked_calls += 1
+            elif k == self.poison:
+                out = out.clone()
+                out[0, 5, 3] = float("inf")                           # (one overwritten element of the result: the kernels ran as always)
+            return out
+
+    def run(poison):
+        tr = Poisoned(gen, poison)
+        r = ev.evaluate_dataset(tr, str(tmp_path), 26, batch_size=2, seed=seed, verbose=False, motion_encoder=menc, m2snet=m2s,
+                                retrieval=True, rhythm=rhythm, discriminator=critic, music_beats=beats, beat_stride=3)
+        return tr, r
+
+    timing = {"seconds", "frames_per_s", "steady_frames_per_s", "main_thread_s", "metrics_s", "m2s_retrieval_s"}
+    _, clean = run(-1)
+    assert {"fgd", "m2s_sync_gen", "m2s_mean_rank_gen", "rde", "w_distance", "bc_gen", "beat_align_real"} <= set(clean)
+    tr, got = run(0)
+    assert tr.checked_calls == 1 and tr.calls == 3 and tr.encoder.check_numerics is True and tr.encoder.combine_exchange is True
+    assert list(got) == list(clean)
+    for key in clean:
+        if key not in timing:
+            same = got[key] == clean[key] or (isinstance(clean[key], float) and np.isnan(clean[key]) and np.isnan(got[key]))
+            assert same, (key, got[key], clean[key])
+
+
 def test_evaluate_main_takes_the_new_flags_beside_the_generator(weights, tmp_path, capsys):
     """--rhythm and --discriminator PATH (a checkpoint with DataParallel keys) under --baseline_generator: one JSON line with the new
     keys beside the old ones; without the flags the line has none of them."""

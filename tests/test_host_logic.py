@@ -330,6 +330,162 @@ def test_evaluate_dataset_resamples_a_non_finite_early_batch(tmp_path):
         ev.evaluate_dataset(Unchecked(0), str(tmp_path), 26, batch_size=2, seed=3, verbose=False)
 
 
+class _SeenBatches:
+    """Base of the stand-ins below: counts, per method, which batch's ground truth (or mel) it was handed.  `firsts`: batch -> the
+    flattened first clip of that batch's input; anything else (sampled poses, latents) is not counted."""
+
+    def __init__(self, firsts):
+        self.firsts, self.seen = firsts, {}
+
+    def note(self, method, x):
+        row = torch.as_tensor(x)[0].reshape(-1)
+        for k, first in enumerate(self.firsts):
+            if row.shape == first.shape and torch.equal(row, first):
+                self.seen[(method, k)] = self.seen.get((method, k), 0) + 1
+
+
+class _AllFamilies:
+    """Pure-torch stand-ins for every score family of evaluate_dataset, each a deterministic function of one clip's input (no reduction
+    across the batch), so a clip's row cannot depend on the pass that produced it."""
+    idx, w = torch.arange(64) % 26, torch.linspace(-1.0, 1.5, 64)
+
+    class Encoder(_SeenBatches):
+        def latent(self, x):
+            self.note("latent", x)
+            B, T = x.shape[0], x.shape[1]
+            return (x.reshape(B, T, 26)[:, :, _AllFamilies.idx] * _AllFamilies.w).transpose(1, 2).contiguous()
+
+    class M2SNet(_SeenBatches):
+        def __init__(self, firsts, mel_firsts):
+            super().__init__(firsts)
+            self.mels = _SeenBatches(mel_firsts)
+
+        def music_latent(self, mel):
+            self.mels.note("music_latent", mel)
+            mel = torch.as_tensor(mel)
+            T = (mel.shape[1] - 1) // 3 + 1
+            return mel[:, :3 * T:3, :64].contiguous()
+
+        def motion_latent(self, x):
+            self.note("motion_latent", x)
+            B, T = x.shape[0], x.shape[1]
+            return (0.1 * x.reshape(B, T, 26)[:, :, _AllFamilies.idx] * _AllFamilies.w).transpose(1, 2).contiguous()
+
+        def fuse(self, mus, mot):
+            return torch.sigmoid(4.0 * (mus * mot.transpose(1, 2)).sum(2))
+
+        def fuse_pairs(self, mus, mot):
+            p = torch.stack([torch.stack([self.fuse(mus[i:i + 1], mot[j:j + 1])[0] for j in range(mot.shape[0])]) for i in range(mus.shape[0])])
+            return {"mean": p.mean(2), "above": (p > 0.5).sum(2).int(), "below": (p < 0.5).sum(2).int(),
+                    "count": torch.full(p.shape[:2], p.shape[2], dtype=torch.int32)}
+
+    class Rhythm(_SeenBatches):
+        def psd(self, x):
+            self.note("psd", x)
+            return (x.reshape(x.shape[0], -1, 26)[:, :32] ** 2).mean(2)
+
+        def contour_and_std(self, x):
+            self.note("contour_and_std", x)
+            B, T = x.shape[0], x.shape[1]
+            W = (T - 60) // 30 + 1
+            x = x.reshape(B, T, 26)
+            return x[:, :30 * W].reshape(B, W, 30 * 26).abs().mean(2), x.reshape(B, -1).std(1)
+
+        def motion_beats(self, x):
+            self.note("motion_beats", x)
+            x = x.reshape(x.shape[0], -1, 26)
+            return (x[:, :, 0] > x[:, :, 1] + 1.0).to(torch.uint8)
+
+        def beat_scores(self, motion_beats, music_beats, music_stride=1, counts=False):
+            mo, mu = motion_beats.float(), torch.as_tensor(music_beats).float()
+            at = (mu * torch.arange(mu.shape[1])).sum(1) * music_stride          # (zeros behind a clip's last beat change nothing)
+            scores = torch.stack([mo.mean(1) + 1e-4 * at, mo[:, ::2].mean(1) - 1e-4 * at], dim=1)
+            n = torch.stack([mu.sum(1), mo.sum(1)], dim=1).to(torch.int32)
+            return (scores, n) if counts else scores
+
+    class Critic(_SeenBatches):
+        def forward(self, x):
+            self.note("forward", x)
+            return (x.reshape(x.shape[0], -1) * 0.01).sum(1)
+
+
+def test_evaluate_dataset_resamples_a_batch_with_every_score_family_on(tmp_path, monkeypatch):
+    """The re-sample path with the latent, sync (+ retrieval), movement and beat scores all switched on: whichever batch is poisoned,
+    every key but the timings is exactly the clean run's, the checked path ran once, every stand-in saw the poisoned batch's ground
+    truth twice and every other batch's once, and each batch's ground truth is stacked once per pass, not once per family."""
+    from diffusion_conductor_amd import evaluate as ev
+    rng = np.random.default_rng(2)
+    n, T, bs = 5, 256, 2                                            # (T = 256: the smallest the rhythm scores accept)
+    mels, gts = rng.random((n, 3 * T - 2, 128), dtype=np.float32), rng.standard_normal((n, T, 13, 2)).astype(np.float32)
+    beats = {}
+    for i in range(n):
+        d = tmp_path / f"clip{i:02d}"
+        d.mkdir()
+        np.save(d / "mel.npy", mels[i])
+        np.save(d / "motion.npy", gts[i])
+        beats[f"clip{i:02d}"] = (np.arange(3 * T - 2 - 7 * i) % (40 + i) == 3).astype(np.uint8)       # lengths differ: padded per batch
+    firsts = [torch.from_numpy(gts[k]).reshape(-1) for k in range(0, n, bs)]
+    mel_firsts = [torch.from_numpy(mels[k]).reshape(-1) for k in range(0, n, bs)]
+
+    class Enc:
+        check_numerics = True
+
+    class FakeTrainer:
+        def __init__(self, poison):
+            self.encoder, self.poison, self.calls, self.checked_calls = Enc(), poison, 0, 0
+
+        def generate_music_motion(self, mel, dim_pose, noise=None, **kw):
+            k = self.calls
+            self.calls += 1
+            out = noise * 0.5 + torch.as_tensor(mel)[:, ::3, :dim_pose]
+            if self.encoder.check_numerics:
+                self.checked_calls += 1
+                return out
+            if k == self.poison:
+                out = out.clone()
+                out[0, 5, 3] = float("inf")
+            return out
+
+    stacks = []                                                     # clips per np.stack of ground truths (arrays of T * 26 values)
+    stack = np.stack
+
+    def recording_stack(arrays, *a, **kw):
+        if np.size(arrays[0]) == T * 26:
+            stacks.append(len(arrays))
+        return stack(arrays, *a, **kw)
+    monkeypatch.setattr(ev.np, "stack", recording_stack)
+
+    def run(poison):
+        tr = FakeTrainer(poison)
+        parts = {"motion_encoder": _AllFamilies.Encoder(firsts), "m2snet": _AllFamilies.M2SNet(firsts, mel_firsts),
+                 "rhythm": _AllFamilies.Rhythm(firsts), "discriminator": _AllFamilies.Critic(firsts)}
+        del stacks[:]
+        r = ev.evaluate_dataset(tr, str(tmp_path), 26, batch_size=bs, seed=3, verbose=False, music_beats=beats, beat_stride=3,
+                                retrieval=True, diversity_seed=1, **parts)
+        return tr, parts, r, list(stacks)
+
+    timing = {"seconds", "frames_per_s", "steady_frames_per_s", "main_thread_s", "metrics_s", "m2s_retrieval_s"}
+    _, _, clean, _ = run(-1)
+    assert {"fgd", "m2s_sync_gen", "m2s_mean_rank_gen", "rde", "w_distance", "bc_gen", "beat_align_real"} <= set(clean)
+    assert all(v == v for k, v in clean.items() if isinstance(v, float))          # (a NaN would equal nothing below)
+    for poison in (0, 1, 2):                                         # first, middle, last (a batch of one clip)
+        tr, parts, got, stacked = run(poison)
+        assert list(got) == list(clean)
+        for key in clean:
+            if key not in timing:
+                assert got[key] == clean[key], (poison, key)
+        assert tr.checked_calls == 1 and tr.calls == 4, (poison, tr.calls, tr.checked_calls)
+        assert tr.encoder.check_numerics is True                     # restored
+        seen = dict(parts["m2snet"].mels.seen)
+        for p in parts.values():
+            seen.update(p.seen)
+        assert sorted({m for m, _ in seen}) == ["contour_and_std", "forward", "latent", "motion_beats", "motion_latent", "music_latent", "psd"]
+        for (method, k), count in seen.items():
+            assert count == (2 if k == poison else 1), (poison, method, k, count)
+        # one stack of the ground truth per batch pass, shared by the four families: three batches and the re-sampled one
+        assert stacked == [2, 2, 1] + [1 if poison == 2 else 2], (poison, stacked)
+
+
 def _isa_of(src, tmp_path):
     """Device ISA + resource remarks of one HIP source (hipcc cross-compiles without a GPU)."""
     import shutil
