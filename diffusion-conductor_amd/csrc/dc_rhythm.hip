@@ -20,7 +20,8 @@
 //   k_sd           one workgroup per clip, 26 channels x 32 time lanes; two passes (mean first) on x - x[0], so a constant is exact.
 //   k_disc_conv    one stage of the critic: Conv1d(k = 5, zero padding 2) as a k-ordered chain, K = 5 CIN tap-major, one wave = 32
 //                  conv frames of one clip x 64 channels, + bias, ReLU, and MaxPool1d(5, stride S) in the epilogue: lane S q takes the
-//                  maximum of lanes S q .. S q + 4 and writes pooled frame p0 + q; a wave advances by (27 / S + 1) pooled frames.
+//                  maximum of lanes S q .. S q + 4 (nanmax: a NaN frame in the window wins, as in torch's max_pool1d) and writes pooled
+//                  frame p0 + q; a wave advances by (27 / S + 1) pooled frames.
 //   k_disc_head    fc 64 -> 32 -> 32 -> 1 per pooled frame, chained in registers (as k_gan_head); k_disc_mean: mean over the frames.
 //
 // Beat consistency (BC) and Beat Align from supplied music beats:
@@ -356,8 +357,8 @@ __global__ __launch_bounds__(64 * R_WAVES) void k_disc_conv(const float* __restr
             float m0 = v0, m1 = v1;
 #pragma unroll
             for (int i = 1; i < kDiscTaps; ++i) {      // MaxPool1d(5): conv frames t .. t + 4 sit on lanes l .. l + 4
-                m0 = fmaxf(m0, __shfl_down(v0, i));
-                m1 = fmaxf(m1, __shfl_down(v1, i));
+                m0 = nanmax(m0, __shfl_down(v0, i));      // (fmaxf would return the finite operand: torch's pool keeps a NaN)
+                m1 = nanmax(m1, __shfl_down(v1, i));
             }
             y0[e] = m0;
             y1[e] = m1;

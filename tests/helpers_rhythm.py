@@ -22,6 +22,26 @@ def fixture_pair(T, n=2):
     return real, synthetic_generated_motion(real, seed=GEN_SEED + T)
 
 
+# (T, frames) of the critic's non-finite cases: one value of clip 1 overwritten at channel POISON_CHANNEL of one frame.  Around the
+# middle of a clip in each alignment of the stride-3 pool (a window of 5 holds nothing but NaN frames only when it starts at t - 2),
+# at both ends (Conv1d's zero padding) and at T = 44 on frame 43, the last frame of the last pool window.
+CRITIC_NAN_CASES = ((41, (20, 21, 22)), (125, (62, 63, 64)), (209, (104, 105, 106)), (900, (450, 451, 452)), (900, (0, 899)), (44, (43,)))
+POISON_CLIP, POISON_CHANNEL = 1, 5
+
+
+def poisoned(x, frame, value=np.nan, clip=POISON_CLIP):
+    """A copy of the motions x [B, T, 13, 2] with `value` at (clip, frame, channel POISON_CHANNEL)."""
+    bad = np.array(x, np.float32).reshape(x.shape[0], x.shape[1], 26)
+    bad[clip, frame, POISON_CHANNEL] = value
+    return bad.reshape(x.shape)
+
+
+def value_class(a):
+    """0 finite, 1 +inf, 2 -inf, 3 NaN, element by element."""
+    a = np.asarray(a, np.float64)
+    return np.where(np.isnan(a), 3, np.where(np.isposinf(a), 1, np.where(np.isneginf(a), 2, 0))).astype(np.int8)
+
+
 def _clips(x):
     x = np.asarray(x, np.float64)
     return x.reshape(x.shape[0], x.shape[1], 26)
@@ -91,7 +111,8 @@ def critic_features(weights, x):
         W, b = np.asarray(weights[f"motion_encoder.{i}.weight"], np.float64), np.asarray(weights[f"motion_encoder.{i}.bias"], np.float64)
         L = h.shape[1]
         hp = np.pad(h, ((0, 0), (2, 2), (0, 0)))
-        y = sum(hp[:, tap:tap + L] @ W[:, :, tap].T for tap in range(5)) + b
+        with np.errstate(invalid="ignore"):                             # (inf - inf of a poisoned input is the NaN the tests look for)
+            y = sum(hp[:, tap:tap + L] @ W[:, :, tap].T for tap in range(5)) + b
         y = np.maximum(y, 0.0)
         Lo = (L - 5) // stride + 1
         h = np.stack([y[:, stride * p:stride * p + 5].max(axis=1) for p in range(Lo)], axis=1)

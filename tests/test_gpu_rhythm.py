@@ -16,6 +16,10 @@ scores of order 5).
   RDE, at 2 x 900 and through the evaluator   measured 1.55e-7   bound 7e-7
   SCE                                         measured 4.47e-7   bound 2e-6
   W-distance                                  measured 1.71e-7   bound 7e-7
+tests/test_gpu_rhythm_edges.py holds further lengths - pooled lengths, Welch columns and contour windows on the kernels' wave and
+workgroup edges, pixel-scale motion - to the same bounds, imported from here.  Measured there: features 7.38e-7, score 3.50e-7,
+contour 2.81e-7, SD 1.56e-7, PSD bins 0 and 1 1.48e-6, and the PSD 1.46e-5 (bin 1 at T = 640, 2.9e-7 of itself: the unit's price,
+DESIGN.md section 13), which leaves PSD_TOL at twice the largest measurement over all cases instead of four times.
 """
 import ctypes as C
 

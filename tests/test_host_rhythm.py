@@ -92,6 +92,53 @@ def test_critic_restatement_reproduces_the_reference(g16, weights, T):
     assert np.abs(H.critic_score(weights, gen) - g16[f"d_gen_T{T}"]).max() <= float(g16["ref_vs_fp64_score"])
 
 
+def _torch_critic_features(weights, x):
+    """Discriminator_1DCNN.motion_encoder with torch's own operators on the CPU in fp32: [B, T, 13, 2] -> [B, 64, L3]."""
+    F = torch.nn.functional
+    h = torch.from_numpy(np.asarray(x, np.float32)).flatten(start_dim=2).transpose(1, 2)
+    for i, stride in ((0, 3), (3, 2), (6, 2)):
+        w, b = (torch.from_numpy(np.asarray(weights[f"motion_encoder.{i}.{leaf}"], np.float32)) for leaf in ("weight", "bias"))
+        h = F.max_pool1d(torch.relu(F.conv1d(h, w, b, padding=2)), kernel_size=5, stride=stride)
+    return h.numpy()
+
+
+def _torch_contour(x):
+    """strengh_contour_error's contour of one batch (loss.py:129-141) with torch on the CPU in fp32: [B, T, 13, 2] -> [B, W]."""
+    m = torch.from_numpy(np.asarray(x, np.float32))
+    v = torch.zeros_like(m)
+    v[:, 1:] = m[:, :-1] - m[:, 1:]
+    v = torch.abs(v.flatten(start_dim=2).mean(dim=2))
+    return torch.nn.functional.avg_pool1d(v.unsqueeze(0), kernel_size=60, stride=30).squeeze(0).numpy()
+
+
+def test_the_oracles_non_finite_values_are_torchs(weights):
+    """What the GPU tests of non-finite inputs compare against is torch's: on every poisoned input of tests/test_gpu_rhythm_edges.py the
+    fp64 restatement's NaN / +inf / -inf / finite classes are, element by element, those of conv1d + relu + max_pool1d (the critic) and
+    of avg_pool1d (the contour) on the CPU in fp32.  A maximum that returns its non-NaN operand (np.fmax, fmaxf) loses the NaN
+    wherever a pool window also holds a finite frame: shown once, at T = 41 with the NaN on frame 21."""
+    for T, frames in H.CRITIC_NAN_CASES:
+        real = H.fixture_pair(T, n=3)[0]
+        for t in frames:
+            for value in (np.nan,) + ((np.inf, -np.inf) if T == 125 else ()):
+                bad = H.poisoned(real, t, value)
+                ref, got = H.critic_features(weights, bad), _torch_critic_features(weights, bad)
+                assert got.shape == ref.shape
+                assert np.array_equal(H.value_class(got), H.value_class(ref)), (T, t, value)
+                assert not H.value_class(ref[[0, 2]]).any() and H.value_class(ref[1]).any(), (T, t, value)
+                assert np.isnan(H.critic_score(weights, features=ref)[1]) and np.isfinite(H.critic_score(weights, features=ref)[[0, 2]]).all()
+    y = np.maximum(np.asarray(H.poisoned(H.fixture_pair(41, n=3)[0], 21), np.float64).reshape(3, 41, 26)[1, :, H.POISON_CHANNEL], 0)
+    assert np.isnan(y[3 * 6:3 * 6 + 5].max()) and np.isfinite(np.fmax.reduce(y[3 * 6:3 * 6 + 5]))
+    T = 270
+    real = H.fixture_pair(T, n=3)[0]
+    for t, windows in ((95, (2, 3)), (0, (0,)), (T - 1, (7,))):
+        bad = H.poisoned(real, t)
+        ref, got = H.contour(bad), _torch_contour(bad)
+        assert got.shape == ref.shape == (3, 8)
+        assert np.array_equal(np.isnan(got), np.isnan(ref)) and list(np.nonzero(np.isnan(ref[1]))[0]) == list(windows), (t, windows)
+        assert not np.isnan(ref[[0, 2]]).any() and np.isnan(H.sd(bad)[1]) and np.isfinite(H.sd(bad)[[0, 2]]).all()
+        assert np.isnan(torch.std(torch.from_numpy(bad).flatten(start_dim=2), dim=1).mean(dim=1).numpy()).tolist() == [False, True, False]
+
+
 # SCE is a float32 logarithm of size <= 16 in the reference and in metrics.py alike, so neither can be closer to the exact value than
 # the spacing of float32 there (9.5e-7 in [8, 16)).  Each chain - a float32 mean of at most 59 squares (torch's reduction order there,
 # numpy's here: a few 6e-8 relative, which is the same absolute size in the logarithm), times 1e7, plus 1, log, each rounded once -
