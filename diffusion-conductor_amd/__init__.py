@@ -27,4 +27,7 @@ def __getattr__(name):   # lazy: torch is only imported when the classes are use
     if name in ("evaluate_dataset", "smooth_motion", "mse_loss", "list_clips", "validation_dataset", "validation_grid"):
         from . import evaluate
         return getattr(evaluate, name)
+    if name in ("MelSpectrogram", "extract_mel_feature", "load_audio", "mel_features_host"):
+        from . import mel
+        return getattr(mel, name)
     raise AttributeError(name)

@@ -1,8 +1,8 @@
 // dc_pack.h - host-only half of the weight preparation (no kernels, no HIP call): 16-bit conversions, the MFMA fragment
 // packers, the 256-byte-aligned host arena, the MusicEncoder's folded image, M2SNet's fuse head, the M2S-GAN generator's image, the
-// ST-GCN motion encoder's, the M2S-GAN critic's and the Welch table.  Included by dc_api.hip (denoiser image, dc_pack_weight),
-// dc_music.hip, dc_m2snet.hip, dc_m2sgan.hip, dc_stgcn.hip and dc_rhythm.hip; the single copy of every rounding routine they must
-// agree on bit for bit.
+// ST-GCN motion encoder's, the M2S-GAN critic's, the Welch table and the mel front end's tables.  Included by dc_api.hip (denoiser
+// image, dc_pack_weight), dc_music.hip, dc_m2snet.hip, dc_m2sgan.hip, dc_stgcn.hip, dc_rhythm.hip and dc_mel.hip; the single copy of
+// every rounding routine they must agree on bit for bit.
 #pragma once
 #include <stdint.h>
 
@@ -762,3 +762,62 @@ inline std::vector<float> welch_table() {
     }
     return tab;
 }
+
+// ---- mel front end: window, twiddles, sparse Slaney filterbank (kernel: dc_mel.hip) ---------------------------------
+// librosa.feature.melspectrogram(y, sr, n_mels = 128, hop_length = 256) with its defaults: n_fft = 2048, the periodic Hann window,
+// librosa.filters.mel(sr, 2048, 128) - Slaney's scale (linear below 1 kHz at 200 / 3 Hz per mel, logarithmic above with step
+// ln(6.4) / 27), n_mels + 2 edge frequencies linspace'd in mel from 0 to sr / 2, triangles max(0, min(lower, upper)) scaled by
+// 2 / (f[i + 2] - f[i]).  Everything in fp64, rounded once.  A filter is stored as its run of non-zero bins: at 22050 Hz 4 .. 53 of
+// the 1025, 2018 weights in all where the dense matrix has 131 200.
+constexpr int kMelFft = 2048, kMelHop = 256, kMelBands = 128, kMelBins = kMelFft / 2 + 1;
+inline double mel_to_hz(double m) { return m >= 15.0 ? 1000.0 * std::exp((std::log(6.4) / 27.0) * (m - 15.0)) : (200.0 / 3.0) * m; }
+inline double hz_to_mel(double f) { return f >= 1000.0 ? 15.0 + std::log(f / 1000.0) / (std::log(6.4) / 27.0) : f / (200.0 / 3.0); }
+struct MelTables {
+    std::vector<float> window;                   // [2048]  0.5 - 0.5 cos(2 pi n / 2048)
+    std::vector<float> twiddle;                  // [2048][2]  cos, -sin of 2 pi j / 2048
+    std::vector<int32_t> first, count, offset;   // [128]  filter m covers bins first .. first + count - 1, its weights at `offset`
+    std::vector<float> weights;                  // the filters' non-zero runs, one after the other
+};
+inline MelTables mel_tables(int sr) {
+    const double pi = 3.14159265358979323846;
+    MelTables t;
+    t.window.resize(kMelFft);
+    t.twiddle.resize((size_t)2 * kMelFft);
+    for (int n = 0; n < kMelFft; ++n) {
+        const double a = 2.0 * pi * n / kMelFft;
+        t.window[n] = (float)(0.5 - 0.5 * std::cos(a));
+        t.twiddle[2 * n] = (float)std::cos(a);
+        t.twiddle[2 * n + 1] = (float)-std::sin(a);
+    }
+    // numpy.linspace(0, hz_to_mel(sr / 2), 130): i * step + start, the last element the stop itself
+    const double top = hz_to_mel(0.5 * sr), step = top / (kMelBands + 1);
+    std::vector<double> f(kMelBands + 2);
+    for (int i = 0; i < kMelBands + 2; ++i) f[i] = mel_to_hz(i == kMelBands + 1 ? top : i * step);
+    t.first.resize(kMelBands);
+    t.count.resize(kMelBands);
+    t.offset.resize(kMelBands);
+    std::vector<double> row(kMelBins);
+    for (int m = 0; m < kMelBands; ++m) {
+        const double d0 = f[m + 1] - f[m], d1 = f[m + 2] - f[m + 1], norm = 2.0 / (f[m + 2] - f[m]);
+        int lo = kMelBins, hi = -1;
+        for (int k = 0; k < kMelBins; ++k) {
+            const double fk = k * ((double)sr / kMelFft);
+            const double lower = -(f[m] - fk) / d0, upper = (f[m + 2] - fk) / d1;
+            const double w = std::fmax(0.0, std::fmin(lower, upper)) * norm;
+            row[k] = w;
+            if ((float)w != 0.f) {
+                if (k < lo) lo = k;
+                hi = k;
+            }
+        }
+        t.first[m] = hi < 0 ? 0 : lo;
+        t.count[m] = hi < 0 ? 0 : hi - lo + 1;
+        t.offset[m] = (int32_t)t.weights.size();
+        for (int k = t.first[m]; k < t.first[m] + t.count[m]; ++k) t.weights.push_back((float)row[k]);
+    }
+    return t;
+}
+
+// The reference's int(len(y) / sr * 90) (Diffusion_Stage/tools/visualization.py:160): a double division, a double product, truncation.
+// (n * 90 / sr in integers disagrees for some n; the one copy the library and its bindings use.)
+inline int32_t mel_out_frames(int64_t n, int32_t sr) { return (int32_t)((double)n / (double)sr * 90.0); }

@@ -43,6 +43,7 @@ EXPORTS = [
     "dc_rhythm_create", "dc_rhythm_destroy", "dc_rhythm_psd", "dc_rhythm_contour", "dc_rhythm_motion_beats", "dc_rhythm_beat_scores",
     "dc_discriminator_create", "dc_discriminator_destroy", "dc_discriminator_set_param", "dc_discriminator_finalize",
     "dc_discriminator_features", "dc_discriminator_score",
+    "dc_mel_create", "dc_mel_destroy", "dc_mel_tables", "dc_mel_out_frames", "dc_mel_pass_clips", "dc_mel_power", "dc_mel_features",
 ]
 
 UPDATE_CLIP_DENOISED, UPDATE_EPSILON = 1, 2          # flags of dc_sampler_ddim_loop_ex
@@ -66,7 +67,7 @@ class DcError(RuntimeError):
 
 
 SOURCES = ("dc_kernels.hip", "dc_api.hip", "dc_music.hip", "dc_layer16.hip", "dc_stgcn.hip", "dc_m2snet.hip", "dc_loss.hip", "dc_m2sgan.hip",
-           "dc_rhythm.hip", "dc_bilstm.hip")
+           "dc_rhythm.hip", "dc_bilstm.hip", "dc_mel.hip")
 HEADERS = ("dc_common.h", "dc_dev.h", "dc_form.h", "dc_handle.h", "dc_launch.h", "dc_mfma_f32.h", "dc_music.h", "dc_pack.h")
 EXTRA_FLAGS = {}      # per-source compiler flags
 
@@ -243,6 +244,16 @@ def lib():
     L.dc_discriminator_finalize.argtypes = [C.c_void_p]
     L.dc_discriminator_features.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     L.dc_discriminator_score.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    L.dc_mel_create.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+    L.dc_mel_destroy.argtypes = [C.c_void_p]
+    L.dc_mel_destroy.restype = None
+    L.dc_mel_tables.argtypes = [C.c_int32, fp, fp, ip, ip, fp, C.c_int32, ip]
+    L.dc_mel_out_frames.argtypes = [C.c_int64, C.c_int32]
+    L.dc_mel_out_frames.restype = C.c_int32
+    L.dc_mel_pass_clips.argtypes = [C.c_int32]
+    L.dc_mel_pass_clips.restype = C.c_int32
+    L.dc_mel_power.argtypes = [C.c_void_p, C.c_void_p, ip, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    L.dc_mel_features.argtypes = [C.c_void_p, C.c_void_p, ip, C.c_int32, C.c_int32, ip, C.c_int32, C.c_void_p, C.c_void_p]
     _lib = L
     return L
 
@@ -1268,4 +1279,86 @@ class NativeDiscriminator(_NativeHandle):
         out = torch.empty((B,), dtype=torch.float32, device=motion.device)
         with torch.cuda.device(motion.device):
             _check(lib().dc_discriminator_score(self._h, motion.data_ptr(), B, T, out.data_ptr(), self._stream()))
+        return out
+
+
+# ---------------------------------------------------------------------------------------
+# the mel spectrogram of a waveform (extract_mel_feature)
+# ---------------------------------------------------------------------------------------
+MEL_FFT, MEL_HOP, MEL_BANDS, MEL_BINS = 2048, 256, 128, 1025
+MEL_PAD = {"constant": 0, "reflect": 1}             # DC_MEL_PAD_*
+
+
+def mel_tables(sr=22050):
+    """dc_mel_tables (host only): what a dc_mel of `sr` uploads - {"window" fp32 [2048], "twiddle" fp32 [2048, 2], "first" / "count"
+    int32 [128], "weights" fp32 [sum(count)]}: filter m covers bins first[m] .. first[m] + count[m] - 1 with the next count[m] weights."""
+    win, tw = np.empty(MEL_FFT, np.float32), np.empty((MEL_FFT, 2), np.float32)
+    first, count, total = np.empty(MEL_BANDS, np.int32), np.empty(MEL_BANDS, np.int32), np.zeros(1, np.int32)
+    _check(lib().dc_mel_tables(int(sr), _fptr(win), _fptr(tw), _iptr(first), _iptr(count), None, 0, _iptr(total)))
+    wts = np.empty(int(total[0]), np.float32)
+    _check(lib().dc_mel_tables(int(sr), None, None, None, None, _fptr(wts), wts.size, None))
+    return {"window": win, "twiddle": tw, "first": first, "count": count, "weights": wts}
+
+
+def mel_out_frames(n, sr=22050):
+    """dc_mel_out_frames (host only): the reference's int(n / sr * 90)."""
+    return int(lib().dc_mel_out_frames(int(n), int(sr)))
+
+
+def mel_pass_clips(N):
+    """dc_mel_pass_clips (host only): clips per pass of NativeMel.features at N samples."""
+    return int(lib().dc_mel_pass_clips(int(N)))
+
+
+class NativeMel(_NativeHandle):
+    """Owns one dc_mel (no parameters: ready after create).  Shapes the library refuses raise ValueError before the call."""
+    _prefix = "dc_mel"
+
+    def __init__(self, device=0, sr=22050, pad_mode="constant"):
+        if pad_mode not in MEL_PAD:
+            raise ValueError(f"pad_mode must be one of {sorted(MEL_PAD)}, got {pad_mode!r}")
+        if int(sr) < 1:
+            raise ValueError(f"sr must be >= 1, got {sr}")
+        self._h = C.c_void_p()
+        _check(lib().dc_mel_create(int(device), int(sr), MEL_PAD[pad_mode], C.byref(self._h)))
+        self.device, self.sr, self.pad_mode = int(device), int(sr), pad_mode
+
+    def _wave(self, wave, lengths):
+        self._ok(wave)
+        assert wave.dim() == 2, tuple(wave.shape)
+        B, N = int(wave.shape[0]), int(wave.shape[1])
+        if B < 1 or N < MEL_FFT:
+            raise ValueError(f"waveforms {tuple(wave.shape)}: at least one clip of at least {MEL_FFT} samples")
+        ln = None
+        if lengths is not None:
+            ln = np.ascontiguousarray(np.asarray(lengths).reshape(-1), np.int32)
+            if ln.shape != (B,) or ln.min() < MEL_FFT or ln.max() > N:
+                raise ValueError(f"lengths must hold {B} values in [{MEL_FFT}, {N}], got {ln.tolist()}")
+        return B, N, ln
+
+    def power(self, wave, lengths=None):
+        """wave fp32 [B, N] on the device, `lengths` None or B host ints -> the mel power fp32 [B, 1 + N // 256, 128]: dc_mel_power."""
+        import torch
+        B, N, ln = self._wave(wave, lengths)
+        out = torch.empty((B, 1 + N // MEL_HOP, MEL_BANDS), dtype=torch.float32, device=wave.device)
+        with torch.cuda.device(wave.device):
+            _check(lib().dc_mel_power(self._h, wave.data_ptr(), None if ln is None else _iptr(ln), B, N, out.data_ptr(), self._stream()))
+        return out
+
+    def features(self, wave, lengths=None, out_frames=None):
+        """wave fp32 [B, N] on the device, `lengths` and `out_frames` None or B host ints -> fp32 [B, Tm, 128], Tm the largest output
+        length (default per clip: mel_out_frames of its length): dc_mel_features."""
+        import torch
+        B, N, ln = self._wave(wave, lengths)
+        if out_frames is None:
+            tm = np.array([mel_out_frames(n, self.sr) for n in (ln if ln is not None else [N] * B)], np.int32)
+        else:
+            tm = np.ascontiguousarray(np.asarray(out_frames).reshape(-1), np.int32)
+        if tm.shape != (B,) or tm.min() < 1:
+            raise ValueError(f"out_frames must hold {B} values >= 1, got {tm.tolist()}")
+        Tm = int(tm.max())
+        out = torch.empty((B, Tm, MEL_BANDS), dtype=torch.float32, device=wave.device)
+        with torch.cuda.device(wave.device):
+            _check(lib().dc_mel_features(self._h, wave.data_ptr(), None if ln is None else _iptr(ln), B, N, _iptr(tm), Tm, out.data_ptr(),
+                                         self._stream()))
         return out

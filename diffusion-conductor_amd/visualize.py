@@ -1,19 +1,24 @@
 """Drop-in for the sampling half of the reference's ``tools/visualization.py`` command line.
 
-    python -m diffusion_conductor_amd.visualize --opt_path <.../opt.txt> --music_path <mel.npy | dir of *.npy> \
-        --npy_path out.npy --gpu_id 0 [--smooth] [--model latest.tar] [--seed 0]
+    python -m diffusion_conductor_amd.visualize --opt_path <.../opt.txt> --music_path <mel.npy | dir of *.npy | song.wav | dir of *.wav> \
+        --npy_path out.npy --gpu_id 0 [--smooth] [--model latest.tar] [--seed 0] [--save_mel mel.npy]
 
 Same flags and call sequence as Diffusion_Stage/tools/visualization.py:180-223: ``get_opt`` (this package's reader of the
 training run's ``opt.txt``; the reference's is utils/get_opt.py:29-105) -> ``build_models`` (:169-178) -> ``DDPMTrainer`` ->
 ``trainer.load(<model_dir>/latest.tar)`` -> ``eval_mode`` -> ``generate_music_motion(mel, opt.dim_pose)`` -> reshape
 ``[T,13,2]`` (:217-218) -> (``smooth_motion(kernel=19)``, :126, with ``--smooth``) -> ``np.save(npy_path)``.
 
-What stays out (rendering is out of scope; the image has no librosa / cv2 / moviepy): the mp3 -> mel
-extraction (``extract_mel_feature`` :152-167) and the video rendering.  ``--music_path`` therefore takes the mel spectrogram
-itself: a ``.npy`` of shape ``[5400,128]`` (what ``extract_mel_feature`` returns and the dataset stores as ``mel.npy``), or
-a directory of such files, which are sampled as ONE batch.  The reference parses ``--npy_path`` but never writes it
-(``plot_music2motion`` :143 ignores the argument); here it receives the keypoints: ``[T,13,2]`` for one clip,
-``[B,T,13,2]`` for a directory.
+``--music_path`` takes the music in either form: the mel spectrogram itself - a ``.npy`` of shape ``[5400,128]`` (what
+``extract_mel_feature`` :152-167 returns and the dataset stores as ``mel.npy``), or a directory of such files, which are sampled
+as ONE batch - or the audio: a PCM ``.wav`` file, or a directory whose audio files are ``*.wav`` and which holds no ``*.npy``.
+Audio goes through ``mel.load_audio`` (22050 Hz) and ``mel.MelSpectrogram.features`` on the GPU (csrc/dc_mel.hip) - several files
+zero-padded to the longest and run as one batch with their lengths, a shorter file's mel rows behind its own length being 0 - and
+from there into the code path a ``.npy`` takes; ``--save_mel PATH`` writes the mel that was computed (``[Tm,128]`` for one file,
+``[B,Tm,128]`` for a directory).  ``load_mels`` itself still reads mels only.
+
+What stays out (rendering is out of scope; the image has no librosa / cv2 / moviepy): mp3 decoding and the
+video rendering.  The reference parses ``--npy_path`` but never writes it (``plot_music2motion`` :143 ignores the argument); here
+it receives the keypoints: ``[T,13,2]`` for one clip, ``[B,T,13,2]`` for a directory.
 """
 from __future__ import annotations
 
@@ -109,10 +114,34 @@ def load_mels(music_path):
     return mel.astype(np.float32), [os.path.basename(music_path)]
 
 
+def audio_files(music_path):
+    """The WAV files `--music_path` names - the file itself, or the sorted *.wav of a directory that holds no *.npy -, or None when
+    the path is `load_mels`'s to read."""
+    if os.path.isdir(music_path):
+        names = sorted(os.listdir(music_path))
+        if any(f.endswith('.npy') for f in names):
+            return None
+        return [pjoin(music_path, f) for f in names if f.lower().endswith('.wav')] or None
+    return [music_path] if music_path.lower().endswith('.wav') else None
+
+
+def mels_from_audio(files, device, sr=22050):
+    """WAV files -> (mel fp32 [Tm,128] for one file, [B,Tm,128] for several, their names): each file loaded at `sr`, the batch
+    zero-padded to the longest and run through MelSpectrogram.features with the files' lengths."""
+    from .mel import MelSpectrogram, load_audio
+    waves = [load_audio(f, sr)[0] for f in files]
+    batch = np.zeros((len(waves), max(w.shape[0] for w in waves)), np.float32)
+    for i, w in enumerate(waves):
+        batch[i, :w.shape[0]] = w
+    mel = MelSpectrogram(device, sr).features(batch, [w.shape[0] for w in waves]).cpu().numpy()
+    return (mel[0] if len(files) == 1 else mel), [os.path.basename(f) for f in files]
+
+
 def make_parser():
     parser = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     parser.add_argument('--opt_path', type=str, required=True, help='Opt path')
-    parser.add_argument('--music_path', type=str, required=True, help='mel spectrogram .npy [5400,128] (or a directory of them)')
+    parser.add_argument('--music_path', type=str, required=True, help='mel spectrogram .npy [5400,128] (or a directory of them), or a PCM .wav file (or a directory of them)')
+    parser.add_argument('--save_mel', type=str, default="", help='with audio in --music_path: where to np.save the mel that was computed')
     parser.add_argument('--motion_length', type=int, default=60, help='kept for compatibility (reference asserts <= 196)')
     parser.add_argument('--result_path', type=str, default="test_sample.gif", help='ignored: rendering is not part of this package')
     parser.add_argument('--npy_path', type=str, default="", help='Path to save the keypoints sequence')
@@ -160,7 +189,13 @@ def main(argv=None):
     if args.takes < 1:
         raise SystemExit("--takes must be at least 1")
     with torch.no_grad():
-        mel, names = load_mels(args.music_path)
+        wavs = audio_files(args.music_path)
+        mel, names = load_mels(args.music_path) if wavs is None else mels_from_audio(wavs, device)
+        if args.save_mel:
+            if wavs is None:
+                raise SystemExit("--save_mel writes the mel computed from audio: --music_path names a mel already")
+            np.save(args.save_mel, mel)
+            print("saved", args.save_mel, mel.shape)
         if args.takes > 1:
             if args.full_length and mel.shape[-2] > 3 * opt.max_motion_length:
                 raise SystemExit("--takes samples one window per take: it does not combine with --full_length on a longer mel")

@@ -743,6 +743,58 @@ DC_EXPORT int dc_discriminator_features(dc_discriminator* d, const float* d_moti
  * features and the mean over the L3 frames -> d_out fp32 [B]. */
 DC_EXPORT int dc_discriminator_score(dc_discriminator* d, const float* d_motion, int32_t B, int32_t T, float* d_out, void* stream);
 
+/* ---- The mel spectrogram of a waveform: the first step of "audio in, poses out" -------------------------------------------------
+ * extract_mel_feature (Diffusion_Stage/tools/visualization.py:152-167 = Contrastive_Stage/utils/music_utils.py:8-23 =
+ * ProspectiveCup/utils/music_utils.py) behind librosa.load, implemented in csrc/dc_mel.hip.  Fixed: n_fft = 2048, hop = 256,
+ * n_mels = 128, the periodic Hann window, center = True, power 2.  All arithmetic is fp32 on tables built in fp64 on the host and
+ * rounded once; no atomics, every sum in a fixed order: a clip's numbers are bit-identical on a rerun, alone or in a batch with
+ * clips of other lengths, and in any chunking.  A non-finite sample makes its clip's features NaN in every element, as numpy's
+ * max does through `ref` (a maximum that is +inf counts as NaN: the reference's transform leaves inf - inf there), and touches no
+ * other clip.  A handle serves ONE stream at a time (its workspace is shared by its calls); not thread-safe.
+ *
+ * dc_mel owns the window, the FFT twiddles and the sparse Slaney filterbank of its sample rate, and a workspace.  `sr` (the
+ * reference's librosa.load resamples to 22050) moves the filterbank and the default output length only; `pad_mode` is how
+ * librosa.stft pads the n_fft / 2 samples in front of and behind the clip: DC_MEL_PAD_CONSTANT zeros (librosa >= 0.10),
+ * DC_MEL_PAD_REFLECT y[1024 .. 1] and y[n-2 .. n-1025] (librosa < 0.10) - the reference pins no version; the two differ in the
+ * first and last four frames.  DC_ERR_INVALID: sr < 1, another pad_mode, a NULL `out`. */
+typedef struct dc_mel dc_mel;
+#define DC_MEL_PAD_CONSTANT 0
+#define DC_MEL_PAD_REFLECT 1
+DC_EXPORT int dc_mel_create(int32_t device, int32_t sr, int32_t pad_mode, dc_mel** out);
+DC_EXPORT void dc_mel_destroy(dc_mel* h);
+
+/* Host only, no device: what dc_mel_create uploads for `sr` (any pointer may be NULL).  h_window fp32 [2048]: 0.5 - 0.5 cos(2 pi n /
+ * 2048); h_twiddle fp32 [2048][2]: cos and -sin of 2 pi j / 2048; the filterbank librosa.filters.mel(sr, 2048, 128) - Slaney scale and
+ * norm - as runs of non-zero bins: filter m covers bins h_first[m] .. h_first[m] + h_count[m] - 1 of the 1025, its weights follow those
+ * of filter m - 1 in h_weights (`max_weights` floats of room; *h_total receives their number, 2018 at 22050 Hz).  DC_ERR_INVALID: sr < 1,
+ * h_weights too small. */
+DC_EXPORT int dc_mel_tables(int32_t sr, float* h_window, float* h_twiddle, int32_t* h_first, int32_t* h_count, float* h_weights,
+                            int32_t max_weights, int32_t* h_total);
+/* Host only: the reference's int(len(y) / sr * 90) (visualization.py:160) - a double division, a double product, truncation - the
+ * default output length of n samples; 0 for n < 0 or sr < 1. */
+DC_EXPORT int32_t dc_mel_out_frames(int64_t n, int32_t sr);
+/* Host only: the clips dc_mel_features runs per pass at N samples (its power plane stays within 512 MiB; at most 32). */
+DC_EXPORT int32_t dc_mel_pass_clips(int32_t N);
+
+/* Replaces librosa.feature.melspectrogram(y=y, sr=sr, n_mels=128, hop_length=256).T (visualization.py:162) per clip: d_wave fp32
+ * [B, N], h_lengths host int32 [B] or NULL (every clip N samples; samples behind a clip's length are not read) -> d_pow fp32
+ * [B, F, 128], F = 1 + N / 256 frames of the padded signal; rows behind a clip's own 1 + n_b / 256 frames are 0.  One fused pass per
+ * frame - window, 2048-point real FFT in LDS, re^2 + im^2, the sparse triangles -: a spectrum never goes to global memory.
+ * DC_ERR_INVALID before anything is enqueued: B < 1, N < 2048, a length outside [2048, N] (librosa only warns below one window),
+ * a NULL pointer. */
+DC_EXPORT int dc_mel_power(dc_mel* h, const float* d_wave, const int32_t* h_lengths, int32_t B, int32_t N, float* d_pow, void* stream);
+
+/* Replaces extract_mel_feature's lines :159-167 per clip: dc_mel_power into the workspace, then librosa.power_to_db(mel, ref=np.max)
+ * - dB = 10 log10(max(p, 1e-10)) - 10 log10(max(ref, 1e-10)) with ref the maximum over the clip's OWN frames, clamped at
+ * max_dB - 80 -, |dB + 80| / 80, np.flip along the bands (output channel c is band 127 - c) and cv2.resize's INTER_LINEAR along time
+ * from the clip's F_b frames to Tm_b: x = (float)((j + 0.5) (F_b / Tm_b) - 0.5) in double, i = floor(x), w = x - i; i < 0 -> (0, 0);
+ * i >= F_b - 1 -> (F_b - 1, 0); out = v[i] (1 - w) + v[i + 1] w in fp32.  Tm_b = h_out_frames[b] (host int32 [B]) or, with NULL,
+ * dc_mel_out_frames of the clip's length; rows behind Tm_b are 0.  d_mel fp32 [B, Tm, 128] is the layout dc_sampler_encode_music
+ * reads.  A silent clip is exactly 1.0 everywhere.  DC_ERR_INVALID before anything is enqueued: dc_mel_power's, Tm < 1, an output
+ * length outside [1, Tm]. */
+DC_EXPORT int dc_mel_features(dc_mel* h, const float* d_wave, const int32_t* h_lengths, int32_t B, int32_t N, const int32_t* h_out_frames,
+                              int32_t Tm, float* d_mel, void* stream);
+
 /* ---- Held-out denoising losses: the forward value of the objective a checkpoint was trained on ---------------------------------
  * GaussianDiffusion.training_losses (models/gaussian_diffusion.py:1002-1090) and the weighting of DDPMTrainer.backward_G
  * (trainers/ddpm_trainer.py:223-268) as an EVALUATOR: one model evaluation per clip and noise level, no gradients.  The model
