@@ -39,6 +39,11 @@ typedef __attribute__((ext_vector_type(8))) float f32x8;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(16))) _Float16 f16x16;
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
+
+#define DEV __device__ __forceinline__
+// torch.relu and the running maximum of torch's max-pools: a NaN stays NaN (fmaxf is v_max_f32, which returns the non-NaN operand)
+DEV float relu(float y) { return y < 0.f ? 0.f : y; }
+DEV float nanmax(float m, float v) { return (v > m || v != v) ? v : m; }
 #else
 struct bf16x8 { uint16_t v[8]; };
 #endif

@@ -6,8 +6,6 @@
 #include <type_traits>
 #include "dc_common.h"
 
-#define DEV __device__ __forceinline__
-
 namespace dc {
 
 template <class T> struct V8;

@@ -3015,26 +3015,6 @@ __global__ __launch_bounds__(256) void k_cond_ca_kv(const DcModel* __restrict__ 
         }                                                \
     } while (0)
 
-// Kernels that use more than 64 KiB of dynamic LDS need hipFuncAttributeMaxDynamicSharedMemorySize, and the attribute is
-// per DEVICE: `done` is a per-kernel bit mask of the devices that already have it (a process may hold samplers on several GPUs).
-static hipError_t lds_optin(const void* fn, int bytes, unsigned long long& done) {
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (dev < 64 && ((done >> dev) & 1ull)) return hipSuccess;
-    e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e == hipSuccess && dev < 64) done |= 1ull << dev;
-    return e;
-}
-static int cu_count() {     // of the current device
-    static int n[64] = {0};
-    int dev = 0;
-    hipGetDevice(&dev);
-    if (dev < 0 || dev >= 64) dev = 0;
-    if (!n[dev]) hipDeviceGetAttribute(&n[dev], hipDeviceAttributeMultiprocessorCount, dev);
-    return n[dev];
-}
-
 // Diagnosis pass behind a DC_STATUS_NONFINITE report: do the FiLM tiles (fp16) hold an inf / nan?  n8 = number of 16-byte pieces.
 __global__ __launch_bounds__(256) void k_scan_f16_nonfinite(const u32x8* __restrict__ e, size_t n32, int* __restrict__ status) {
     unsigned acc = 0;
@@ -3137,7 +3117,7 @@ hipError_t dc_launch_ca_partials(hipStream_t st, const DcModel* dm, const void* 
 
 hipError_t dc_launch_cond_pp64(hipStream_t st, const float* xf, const void* wpack, const float* b, float* out_f32, int M, int G, int T, int Tx) {
     static unsigned long long optin_done = 0;
-    if (hipError_t e = lds_optin((const void*)k_cond_pp64, 131072, optin_done)) return e;
+    if (hipError_t e = dc_lds_optin((const void*)k_cond_pp64, 131072, optin_done)) return e;
     hipLaunchKernelGGL(k_cond_pp64, dim3((G + 7) / 8), dim3(512), 131072, st, xf, (const bf16x8*)wpack, b, out_f32, M, T, G, Tx);
     return LAUNCH_CHECK();
 }
@@ -3148,7 +3128,7 @@ hipError_t dc_launch_ca_partials64(hipStream_t st, const DcModel* dm, const floa
     hipLaunchKernelGGL(k_cond_rstd, dim3((ntok + 255) / 256), dim3(256), 0, st, xf, gram, rstd, M, T, Tx, ntok);
     if (hipError_t e = hipGetLastError()) return e;
     static unsigned long long optin_done = 0;
-    if (hipError_t e = lds_optin((const void*)k_cond_ca_partials64, 65536, optin_done)) return e;
+    if (hipError_t e = dc_lds_optin((const void*)k_cond_ca_partials64, 65536, optin_done)) return e;
     hipLaunchKernelGGL(k_cond_ca_partials64, dim3((G + 7) / 8, L), dim3(512), 65536, st, dm, xf, gram + DC_GRAM_SHIFT, rstd, recs, M, T, G, Tx);
     return LAUNCH_CHECK();
 }
@@ -3202,8 +3182,9 @@ template <class T16>
 static hipError_t launch_film3_t(hipStream_t st, const DcFilmArgs& a) {
     const size_t shm = 4 * DC_KS_E * 1024 + 64;        // slab + the pair counter
     static unsigned long long optin_done = 0;
-    if (hipError_t e = lds_optin((const void*)k_film_gemm3<T16>, (int)shm, optin_done)) return e;
-    const int ncu = cu_count();
+    if (hipError_t e = dc_lds_optin((const void*)k_film_gemm3<T16>, (int)shm, optin_done)) return e;
+    int ncu = 0;
+    if (hipError_t e = dc_cu_count(&ncu)) return e;
     // One workgroup per CU for big batches; for small ones (the reference samples ONE clip per call: 15 token blocks) the
     // (token block x round) units are spread over more workgroups than there are token blocks, down to one unit each - several
     // workgroups then build the same slab, but a slab fill costs ~6 us and a block's 12 rounds ~60 us when one workgroup sweeps them
@@ -3221,7 +3202,7 @@ static hipError_t launch_film3_t(hipStream_t st, const DcFilmArgs& a) {
         const int nf = film_extra_workgroups(nunit, nblk, ea->ne, ncu);
         if (nf <= 0) return hipErrorInvalidValue;
         static unsigned long long optin4 = 0;
-        if (hipError_t e = lds_optin((const void*)k_film_embed<T16>, (int)shm, optin4)) return e;
+        if (hipError_t e = dc_lds_optin((const void*)k_film_embed<T16>, (int)shm, optin4)) return e;
         k_film_embed<T16><<<dim3(nf + ea->ne), dim3(512), shm, st>>>(W16, a.bias16, E, a.G, a.NT, a.round0, a.nround, a.pp, a.temb, a.t_clip, a.T,
                                                                      a.B, a.clk, a.rate_in, a.rate_out, a.iter_base, *ea, a.status);
         return hipGetLastError();
@@ -3231,14 +3212,14 @@ static hipError_t launch_film3_t(hipStream_t st, const DcFilmArgs& a) {
             if (!std::is_same<T16, _Float16>::value || ea->upc <= 0) return hipErrorInvalidValue;
             const size_t shm2 = 8192 + 65 * 1024 + 9 * 4 * 32 * 4 + 65 * 1024;
             static unsigned long long optin3 = 0;
-            if (hipError_t e = lds_optin((const void*)k_film_embed<T16, __bf16, true>, (int)shm2, optin3)) return e;
+            if (hipError_t e = dc_lds_optin((const void*)k_film_embed<T16, __bf16, true>, (int)shm2, optin3)) return e;
             k_film_embed<T16, __bf16, true><<<dim3(nwg), dim3(512), shm2, st>>>(W16, a.bias16, E, a.G, a.NT, a.round0, a.nround, a.pp, a.temb,
                                                                                 a.t_clip, a.T, a.B, a.clk, a.rate_in, a.rate_out, a.iter_base, *ea,
                                                                                 a.status);
             return hipGetLastError();
         }
         static unsigned long long optin2 = 0;
-        if (hipError_t e = lds_optin((const void*)k_film_embed<T16>, (int)shm, optin2)) return e;
+        if (hipError_t e = dc_lds_optin((const void*)k_film_embed<T16>, (int)shm, optin2)) return e;
         k_film_embed<T16><<<dim3(nwg), dim3(512), shm, st>>>(W16, a.bias16, E, a.G, a.NT, a.round0, a.nround, a.pp, a.temb, a.t_clip, a.T, a.B,
                                                              a.clk, a.rate_in, a.rate_out, a.iter_base, *ea, a.status);
         return hipGetLastError();
@@ -3279,7 +3260,7 @@ static hipError_t launch_embed_t(hipStream_t st, const DcModel* dm, const float*
     const size_t shm = !WGR ? 0 : SP ? 8192 + 65 * 1024 + 9 * 4 * 32 * 4 + 65 * 1024 : 8192 + 65536 + 8192 + 9 * 4 * 32 * 4 + 33 * 1024;
     if (WGR) {
         static unsigned long long optin_done = 0;
-        if (hipError_t e = lds_optin((const void*)k_embed_front<T16, SP, WGR, false, NARROW>, (int)shm, optin_done)) return e;
+        if (hipError_t e = dc_lds_optin((const void*)k_embed_front<T16, SP, WGR, false, NARROW>, (int)shm, optin_done)) return e;
     }
     k_embed_front<T16, SP, WGR, false, NARROW><<<dim3((WGR && upc) ? B * upc : (G + NW - 1) / NW), dim3(NW * 64), shm, st>>>(dm, x, hbuf, recs, length, M, T, G, B,
                                                                                                                          clk, 0, Tx, WGR ? upc : 0);
@@ -3306,7 +3287,7 @@ static hipError_t launch_layer_t(hipStream_t st, const DcLayerArgs& a, int l, co
     // two stage images (+1 KiB constants each); non-split adds the attention-frag region and the FiLM rings
     const size_t shm = SP ? 2 * 65 * 1024 + (WGR ? 16384 + 6144 : 0) : 2 * 33 * 1024 + 16384 + 8 * 8192 + 6144;
     static unsigned long long optin_done = 0;   // > 64 KiB of dynamic LDS needs the opt-in
-    if (hipError_t e = lds_optin((const void*)k_layer<T16, SP, DBG, STAMP, WGR, NARROW, G1>, (int)shm, optin_done)) return e;
+    if (hipError_t e = dc_lds_optin((const void*)k_layer<T16, SP, DBG, STAMP, WGR, NARROW, G1>, (int)shm, optin_done)) return e;
     k_layer<T16, SP, DBG, STAMP, WGR, NARROW, G1><<<dim3((WGR && upc) ? a.B * upc : (a.G + NW - 1) / NW), dim3(NW * 64), shm, st>>>(
         a.dm, l, a.hbuf, (const f16x16*)a.E, a.NT, (const v8<T16>*)a_sa, (const v8<T16>*)a_ca, a.recs, a.length, a.xin, a.xout, a.out_mode,
         a.coef_cur, a.snap_cur, a.snaps, a.M, a.T, a.G, a.B, dbg, stamps, rec_stride, a.iter_base, a.Tx, WGR ? upc : 0, a.e_groups, a.e_period, a.e_wrap, a.e_magic,
@@ -3344,7 +3325,7 @@ static hipError_t launch_full_t(hipStream_t st, const DcLayerArgs& a, int l, con
                                 int stop_after) {
     const int WPC = (KT + 7) / 8;
     static unsigned long long optin_done = 0;   // key-tile double buffer (32 KiB) + per-wave query fragments (64 KiB) > 64 KiB of dynamic LDS
-    if (hipError_t e = lds_optin((const void*)k_layer_full<T16, SP>, DC_FULL_LDS, optin_done)) return e;
+    if (hipError_t e = dc_lds_optin((const void*)k_layer_full<T16, SP>, DC_FULL_LDS, optin_done)) return e;
     k_layer_full<T16, SP><<<dim3(a.B * WPC), dim3(512), DC_FULL_LDS, st>>>(
         a.dm, l, a.hbuf, (const f16x16*)a.E, a.NT, (const v8<T16>*)kv_cur, (v8<T16>*)kv_next, (const v8<T16>*)kv_ca, a.length, a.xin, a.xout,
         a.out_mode, a.coef_cur, a.snap_cur, a.snaps, a.M, a.T, a.B, KT, WPC, stop_after, a.e_groups, a.e_period, a.e_wrap, a.e_magic, a.upd);

@@ -3,6 +3,28 @@
 #include <hip/hip_runtime.h>
 #include "dc_common.h"
 
+// Kernels that use more than 64 KiB of dynamic LDS need hipFuncAttributeMaxDynamicSharedMemorySize, and the attribute is
+// per DEVICE: `done` is a per-kernel bit mask of the devices that already have it (a process may hold samplers on several GPUs).
+inline hipError_t dc_lds_optin(const void* fn, int bytes, unsigned long long& done) {
+    int dev = 0;
+    if (hipError_t e = hipGetDevice(&dev)) return e;
+    if (dev < 64 && ((done >> dev) & 1ull)) return hipSuccess;
+    if (hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes)) return e;
+    if (dev < 64) done |= 1ull << dev;
+    return hipSuccess;
+}
+// CUs of the current device (asked once per device)
+inline hipError_t dc_cu_count(int* ncu) {
+    static int n[64] = {0};
+    int dev = 0;
+    if (hipError_t e = hipGetDevice(&dev)) return e;
+    int& slot = n[dev & 63];
+    if (!slot)
+        if (hipError_t e = hipDeviceGetAttribute(&slot, hipDeviceAttributeMultiprocessorCount, dev)) return e;
+    *ncu = slot;
+    return hipSuccess;
+}
+
 hipError_t dc_launch_begin_step(hipStream_t st, int* iter, const int* t_of_iter, const float* coef_of_iter,
                                 const int* snap_of_iter, int* t_clip, float* coef_cur, int* snap_cur, int B);
 hipError_t dc_launch_temb_table(hipStream_t st, const float* freqs, const float* w0t, const float* b0,

@@ -961,12 +961,7 @@ template <class T16, bool G1>
 hipError_t launch_layer16_t(hipStream_t st, const DcLayerArgs& a, int l, const void* a_ca16, int upc, size_t rec_stride, int nu_in,
                             size_t stride_in, unsigned long long* gran, unsigned tag_base) {
     static unsigned long long done = 0;      // > 64 KiB of dynamic LDS needs the opt-in, per device
-    int dev = 0;
-    if (hipError_t e = hipGetDevice(&dev)) return e;
-    if (dev >= 64 || !((done >> dev) & 1ull)) {
-        if (hipError_t e = hipFuncSetAttribute((const void*)k_layer16<T16, G1>, hipFuncAttributeMaxDynamicSharedMemorySize, L16_LDS)) return e;
-        if (dev < 64) done |= 1ull << dev;
-    }
+    if (hipError_t e = dc_lds_optin((const void*)k_layer16<T16, G1>, L16_LDS, done)) return e;
     k_layer16<T16, G1><<<dim3(a.B * upc), dim3(256), L16_LDS, st>>>(a.dm, l, a.hbuf, (const f16x16*)a.E, a.NT, (const v8<T16>*)a_ca16, a.recs,
                                                                     a.length, a.xin, a.xout, a.out_mode, a.coef_cur, a.snap_cur, a.snaps, a.M,
                                                                     a.T, a.B, upc, rec_stride, nu_in, stride_in, a.iter_base, a.Tx, a.upd, gran,

@@ -35,8 +35,6 @@
 
 namespace {
 
-using dc_f32::nanmax;
-
 constexpr int M_HALF = kMelFft / 2;                          // points of the complex transform
 constexpr int M_FPW = 8;                                     // frames per workgroup
 constexpr int M_WAVES = 4;                                   // waves per workgroup: one frame each, M_FPW / M_WAVES rounds

@@ -5,19 +5,11 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "dc_common.h"
-
-#ifndef DEV
-#define DEV __device__ __forceinline__
-#endif
+#include "dc_common.h"   // DEV, relu, nanmax
 
 namespace dc_f32 {
 
 DEV f32x16 mfma2(float a, float b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
-// torch.relu: NaN stays NaN (fmaxf is v_max_f32, which returns the non-NaN operand)
-DEV float relu(float y) { return y < 0.f ? 0.f : y; }
-// the running maximum of torch's max_pool1d: a NaN in `m` or in `v` stays (dc_music.hip keeps its own copy beside its own relu)
-DEV float nanmax(float m, float v) { return (v > m || v != v) ? v : m; }
 
 // the row (channel) of its 32-row tile that accumulator register r of lane half h holds (dc_pack.h's tile_row, on the device)
 DEV int tile_channel(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }

@@ -24,11 +24,10 @@
 #include <cstring>
 #include <type_traits>
 
-#include "dc_common.h"
+#include "dc_common.h"   // DEV, relu, nanmax
+#include "dc_launch.h"   // dc_lds_optin, dc_cu_count
 
 namespace {
-
-#define DEV __device__ __forceinline__
 
 DEV f32x16 mfma(bf16x8 a, bf16x8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
 DEV f32x16 mma3(bf16x8 ah, bf16x8 al, bf16x8 bh, bf16x8 bl, f32x16 acc) {
@@ -50,16 +49,13 @@ DEV void split8(const float (&v)[8], bf16x8& hi, bf16x8& lo) {
         lo[j] = (__bf16)(v[j] - (float)h);
     }
 }
-// torch.relu and max_pool2d: NaN stays NaN (fmaxf is v_max_f32, which returns the non-NaN operand; dc_mfma_f32.h has the same rule)
-DEV float relu(float y) { return y < 0.f ? 0.f : y; }
-// ... as two pinned instructions: in k_me_stem's phase A at 128 registers the compiler's own pair costs 12 more spilled registers
+// relu (dc_common.h) as two pinned instructions: in k_me_stem's phase A at 128 registers the compiler's own pair costs 12 more spilled registers
 // (k_me_stem<8, 64, false>: 752 -> 847 us per 32 clips; pinned: the parent's 10 spills)
 DEV float relu_pinned(float y) {
     float r;
     asm("v_cmp_gt_f32 vcc, 0, %1\n\tv_cndmask_b32_e64 %0, %1, 0, vcc" : "=v"(r) : "v"(y) : "vcc");
     return r;
 }
-DEV float nanmax(float m, float v) { return (v > m || v != v) ? v : m; }
 DEV f32x16 zero16() {
     f32x16 x;
 #pragma unroll
@@ -117,29 +113,21 @@ DEV float val4(const f16x4& h, const f16x4&, int e) { return (float)h[e]; }
 // ---------------------------------------------------------------------------------------------------------
 // 3x3 reflect-padded convolution + folded BatchNorm + ReLU (+ residual).  RES: 0 none, 1 identity, 2 1x1 conv + BN.
 // Weight fragments (A operand, natural k = tap*CIN + ci): [hi: NKS][lo: NKS] then for RES == 2 [hi: KC][lo: KC].
-// CIN == 1 reads the fp32 mel directly: its single k-step holds the 9 taps (k = tap), split in registers.
 // ---------------------------------------------------------------------------------------------------------
-template <int CIN, int COUT, int RES>
-__global__ __launch_bounds__(256) void k_me_conv(const float* __restrict__ mel, const bf16x8* __restrict__ in_hi,
-                                                 const bf16x8* __restrict__ in_lo, __bf16* __restrict__ out_hi,
-                                                 __bf16* __restrict__ out_lo, const bf16x8* __restrict__ w,
-                                                 const float* __restrict__ bias_ft, const float* __restrict__ rbias_ft,
-                                                 int Bc, int H, int W, int tiles_per_wave) {
-    constexpr int KC = CIN >= 16 ? CIN / 16 : 1;
-    constexpr int NKS = CIN >= 16 ? 9 * KC : 1;
-    constexpr int NF = 2 * NKS + (RES == 2 ? 2 * KC : 0);
+// conv1.0 alone (1 -> 16 channels, no residual; the first of DC_ME_NO_STEM=1's three launches, split planes): it reads the fp32 mel
+// directly, its single k-step holds the 9 taps (k = tap), split in registers.  A wave owns 32 consecutive pixels of one image row.
+__global__ __launch_bounds__(256) void k_me_conv10(const float* __restrict__ mel, __bf16* __restrict__ out_hi, __bf16* __restrict__ out_lo,
+                                                   const bf16x8* __restrict__ w /* hi, lo */, const float* __restrict__ bias_ft, int Bc, int H,
+                                                   int W, int tiles_per_wave) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     bf16x8* wl = reinterpret_cast<bf16x8*>(lds);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int n = lane & 31, kh = lane >> 5;
-    for (int f = wave; f < NF; f += 4) wl[f * 64 + lane] = w[f * 64 + lane];
+    for (int f = wave; f < 2; f += 4) wl[f * 64 + lane] = w[f * 64 + lane];
     __syncthreads();
-    f32x16 bias, rbias;
+    f32x16 bias;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        bias[r] = bias_ft[kh * 16 + r];
-        rbias[r] = RES == 2 ? rbias_ft[kh * 16 + r] : 0.f;
-    }
+    for (int r = 0; r < 16; ++r) bias[r] = bias_ft[kh * 16 + r];
     const int xt_per_row = W / 32;
     const long long total = (long long)Bc * H * xt_per_row;
     const long long t0 = ((long long)blockIdx.x * 4 + wave) * tiles_per_wave;
@@ -150,73 +138,31 @@ __global__ __launch_bounds__(256) void k_me_conv(const float* __restrict__ mel, 
         const int y = (int)((tile / xt_per_row) % H);
         const int b = (int)(tile / ((long long)xt_per_row * H));
         const int x = xt * 32 + n;
-        f32x16 acc = zero16();
-        if constexpr (CIN == 1) {
-            float v[8];
+        float v[8];
 #pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const int t = 8 * kh + j;
-                const int yy = reflect(y + t / 3 - 1, H), xx = reflect(x + t % 3 - 1, W);
-                v[j] = t < 9 ? mel[((size_t)b * H + yy) * W + xx] : 0.f;
-            }
-            bf16x8 bh, bl;
-            split8(v, bh, bl);
-            acc = mma3(wl[lane], wl[64 + lane], bh, bl, acc);
-        } else {
-#pragma unroll
-            for (int tap = 0; tap < 9; ++tap) {
-                const int yy = reflect(y + tap / 3 - 1, H), xx = reflect(x + tap % 3 - 1, W);
-                const size_t base = (((size_t)b * H + yy) * W + xx) * (CIN / 8) + kh;
-#pragma unroll
-                for (int kc = 0; kc < KC; ++kc) {
-                    const bf16x8 bh = in_hi[base + 2 * kc], bl = in_lo[base + 2 * kc];
-                    const int ks = tap * KC + kc;
-                    acc = mma3(wl[ks * 64 + lane], wl[(NKS + ks) * 64 + lane], bh, bl, acc);
-                }
-            }
+        for (int j = 0; j < 8; ++j) {
+            const int t = 8 * kh + j;
+            const int yy = reflect(y + t / 3 - 1, H), xx = reflect(x + t % 3 - 1, W);
+            v[j] = t < 9 ? mel[((size_t)b * H + yy) * W + xx] : 0.f;
         }
+        bf16x8 bh, bl;
+        split8(v, bh, bl);
+        const f32x16 acc = mma3(wl[lane], wl[64 + lane], bh, bl, zero16());
         const size_t pix = ((size_t)b * H + y) * W + x;
-        f32x16 res = zero16();
-        if constexpr (RES == 2) {
 #pragma unroll
-            for (int kc = 0; kc < KC; ++kc) {
-                const bf16x8 bh = in_hi[pix * (CIN / 8) + kh + 2 * kc], bl = in_lo[pix * (CIN / 8) + kh + 2 * kc];
-                res = mma3(wl[(2 * NKS + kc) * 64 + lane], wl[(2 * NKS + KC + kc) * 64 + lane], bh, bl, res);
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < COUT / 8; ++q) {
+        for (int q = 0; q < 2; ++q) {
             const int c0 = 8 * q + 4 * kh;          // this lane's 4 consecutive output channels of register group q
-            float v[4];
+            float o[4];
 #pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = relu(acc[4 * q + e] + bias[4 * q + e]);
-            if constexpr (RES == 1) {
-                const __bf16* ph = reinterpret_cast<const __bf16*>(in_hi) + pix * CIN + c0;
-                const __bf16* pl = reinterpret_cast<const __bf16*>(in_lo) + pix * CIN + c0;
-                const bf16x4 xh = *reinterpret_cast<const bf16x4*>(ph), xl = *reinterpret_cast<const bf16x4*>(pl);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] += (float)xh[e] + (float)xl[e];
-            }
-            if constexpr (RES == 2) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) v[e] += res[4 * q + e] + rbias[4 * q + e];
-            }
-            bf16x4 oh, ol;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const __bf16 h = (__bf16)v[e];
-                oh[e] = h;
-                ol[e] = (__bf16)(v[e] - (float)h);
-            }
-            *reinterpret_cast<bf16x4*>(out_hi + pix * COUT + c0) = oh;
-            *reinterpret_cast<bf16x4*>(out_lo + pix * COUT + c0) = ol;
+            for (int e = 0; e < 4; ++e) o[e] = relu(acc[4 * q + e] + bias[4 * q + e]);
+            put4(o, out_hi + pix * 16 + c0, out_lo + pix * 16 + c0);
         }
     }
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// The same convolution for CIN >= 16 from an LDS-resident input tile.  k_me_conv reads every tap of every pixel from
-// L1 / L2 (18 KiB of loads per 2 KiB of unique input: 2.3 TB/s of HBM at best); here a persistent 4-wave workgroup
+// The layers with CIN >= 16, from an LDS-resident input tile.  Reading every tap of every pixel from L1 / L2 is 18 KiB
+// of loads per 2 KiB of unique input (2.3 TB/s of HBM at best); here a persistent 4-wave workgroup
 // copies a (ROWS + 2) x (32 NXS + 2)-pixel halo tile of both planes into LDS by LDS-DMA (reflect padding by index) once
 // and feeds all nine taps from there.  LDS piece order [plane][16-channel chunk][channel half][row][pixel] x 16 B: the
 // B operand of one tap is 32 consecutive pieces per channel half - conflict-free ds_read_b128 - and a tap shift is a
@@ -684,82 +630,37 @@ __global__ __launch_bounds__(512, SP ? 2 : 4) void k_me_mid(const typename PL<SP
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// max_pool2d on the plane pair; padding never wins (torch pads with -inf) and a NaN always does (nanmax).  One thread per (pixel, 8 channels).
-// hi + lo is exact in fp32 (<= 17 significant bits), so the maximum re-splits into the very planes it came from.
-// ---------------------------------------------------------------------------------------------------------
+// max_pool2d; padding never wins (torch pads with -inf) and a NaN always does.  One thread per (pixel, 8 channels).
 // Sliding window along time: a thread owns (clip, output column, 8 channels) and walks NY consecutive output rows,
 // keeping the last KH row maxima (each the maximum over the KW taps of one input row) in registers; an output row
 // costs SH new input rows instead of KH (5x5 stride 1: 5x fewer loads than one thread per output).
-// XO adjacent output columns per thread: their windows overlap ((XO - 1) SW + KW input columns instead of XO KW) - two columns need 7
-// loads per plane and input row instead of 10, but 173 VGPRs instead of 48 cost the occupancy that hides the loads: no faster (round 5).
-template <int KH, int KW, int SH, int SW, int PH, int PW, int XO>
-__global__ __launch_bounds__(256) void k_me_pool(const bf16x8* __restrict__ in_hi, const bf16x8* __restrict__ in_lo,
-                                                 bf16x8* __restrict__ out_hi, bf16x8* __restrict__ out_lo, int Bc, int H, int W,
-                                                 int C8, int Ho, int Wo, int NY) {
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    const int strips = (Ho + NY - 1) / NY;
-    const int Wq = (Wo + XO - 1) / XO;
-    const long long total = (long long)Bc * strips * Wq * C8;
-    if (idx >= total) return;
-    const int c8 = (int)(idx % C8);
-    const int xo0 = (int)((idx / C8) % Wq) * XO;
-    const int sy = (int)((idx / ((long long)C8 * Wq)) % strips);
-    const int b = (int)(idx / ((long long)C8 * Wq * strips));
-    constexpr int NC = (XO - 1) * SW + KW;      // input columns the thread's XO windows cover
-    float ring[KH][XO][8];                      // ring[k][i] = row maximum of input row (next_row - KH + k) over output i's window, oldest first
-    auto row_max = [&](int yy, float (&m)[XO][8]) {
+// (Two adjacent output columns per thread share 3 of their 10 loads per input row, at 173 VGPRs instead of 48: no faster,
+// profiles/r05_ab_pool.txt.)
+// ---------------------------------------------------------------------------------------------------------
+// The window of a plane pair: eight fp32 values under nanmax.  hi + lo is exact in fp32 (<= 17 significant bits), so the maximum
+// re-splits into the very planes it came from.
+struct PoolWinS {
+    float m[8];
+};
+DEV void pool_clear(PoolWinS& w) {
 #pragma unroll
-        for (int i = 0; i < XO; ++i)
-#pragma unroll
-            for (int j = 0; j < 8; ++j) m[i][j] = -INFINITY;
-        if (yy < 0 || yy >= H) return;
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            const int xx = xo0 * SW - PW + c;
-            if (xx < 0 || xx >= W) continue;
-            const size_t o = (((size_t)b * H + yy) * W + xx) * C8 + c8;
-            const bf16x8 h = in_hi[o], l = in_lo[o];
-#pragma unroll
-            for (int i = 0; i < XO; ++i)
-                if (c >= i * SW && c < i * SW + KW) {
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) m[i][j] = nanmax(m[i][j], (float)h[j] + (float)l[j]);
-                }
-        }
-    };
-    const int yo0 = sy * NY, yo1 = min(yo0 + NY, Ho);
-#pragma unroll
-    for (int k = 0; k < KH; ++k) row_max(yo0 * SH - PH + k, ring[k]);
-    for (int yo = yo0; yo < yo1; ++yo) {
-#pragma unroll
-        for (int i = 0; i < XO; ++i) {
-            if (xo0 + i >= Wo) continue;
-            float m[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                m[j] = ring[0][i][j];
-#pragma unroll
-                for (int k = 1; k < KH; ++k) m[j] = nanmax(m[j], ring[k][i][j]);
-            }
-            bf16x8 oh, ol;
-            split8(m, oh, ol);
-            const size_t oidx = (((size_t)b * Ho + yo) * Wo + xo0 + i) * C8 + c8;
-            out_hi[oidx] = oh;
-            out_lo[oidx] = ol;
-        }
-        if (yo + 1 < yo1) {              // advance the window by SH input rows
-#pragma unroll
-            for (int k = 0; k + SH < KH; ++k)
-#pragma unroll
-                for (int i = 0; i < XO; ++i)
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) ring[k][i][j] = ring[k + SH][i][j];
-#pragma unroll
-            for (int k = (KH > SH ? KH - SH : 0); k < KH; ++k) row_max((yo + 1) * SH - PH + k, ring[k]);
-        }
-    }
+    for (int j = 0; j < 8; ++j) w.m[j] = -INFINITY;
 }
-// The same sliding window on ONE fp16 plane: the maximum of fp16 values is one of them, so the window works on the packed values
+DEV void pool_take(PoolWinS& w, bf16x8 h, bf16x8 l) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) w.m[j] = nanmax(w.m[j], (float)h[j] + (float)l[j]);
+}
+DEV void pool_merge(PoolWinS& w, const PoolWinS& o) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) w.m[j] = nanmax(w.m[j], o.m[j]);
+}
+DEV void pool_put(const PoolWinS& w, bf16x8* hi, bf16x8* lo, size_t o) {
+    bf16x8 oh, ol;
+    split8(w.m, oh, ol);
+    hi[o] = oh;
+    lo[o] = ol;
+}
+// The window of ONE fp16 plane: the maximum of fp16 values is one of them, so the window works on the packed values
 // (v_pk_max_f16: 4 instructions per 8 channels and tap, 4 registers per row maximum) and the output is exact.
 // v_pk_max_f16 drops a NaN like fmaxf, and max_pool2d keeps it: beside the maximum the window carries a = fma(x, 0, a), +0 until a
 // value is NaN (v_pk_fma_f16: one more instruction per tap; the magnitude bits through v_pk_max_u16 cost two and 46 us per 32 clips),
@@ -770,7 +671,14 @@ struct PoolWin {
     f16x8 m;           // maximum of the non-NaN values
     f16x8 a;           // +0, or NaN
 };
-DEV void pool_take(PoolWin& w, f16x8 x) {
+DEV void pool_clear(PoolWin& w) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        w.m[j] = (_Float16)(-INFINITY);
+        w.a[j] = (_Float16)0.f;
+    }
+}
+DEV void pool_take(PoolWin& w, f16x8 x, f16x8) {
     f16x8 z;
 #pragma unroll
     for (int j = 0; j < 8; ++j) z[j] = (_Float16)0.f;
@@ -782,9 +690,14 @@ DEV void pool_merge(PoolWin& w, const PoolWin& o) {
     w.a = w.a + o.a;
 }
 DEV f16x8 pool_value(const PoolWin& w) { return __builtin_bit_cast(f16x8, __builtin_bit_cast(i16x8, w.m) | __builtin_bit_cast(i16x8, w.a)); }
-template <int KH, int KW, int SH, int SW, int PH, int PW>
-__global__ __launch_bounds__(256) void k_me_pool16(const f16x8* __restrict__ in, f16x8* __restrict__ out, int Bc, int H, int W, int C8, int Ho,
-                                                   int Wo, int NY) {
+DEV void pool_put(const PoolWin& w, f16x8* hi, f16x8*, size_t o) { hi[o] = pool_value(w); }
+
+template <int KH, int KW, int SH, int SW, int PH, int PW, bool SP>
+__global__ __launch_bounds__(256) void k_me_pool(const typename PL<SP>::v8* __restrict__ in_hi, const typename PL<SP>::v8* __restrict__ in_lo,
+                                                 typename PL<SP>::v8* __restrict__ out_hi, typename PL<SP>::v8* __restrict__ out_lo, int Bc, int H,
+                                                 int W, int C8, int Ho, int Wo, int NY) {
+    using Win = std::conditional_t<SP, PoolWinS, PoolWin>;
+    constexpr int LO = PL<SP>::N - 1;           // single plane: the lo operand is the hi one again, a dead value
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     const int strips = (Ho + NY - 1) / NY;
     const long long total = (long long)Bc * strips * Wo * C8;
@@ -793,21 +706,18 @@ __global__ __launch_bounds__(256) void k_me_pool16(const f16x8* __restrict__ in,
     const int xo = (int)((idx / C8) % Wo);
     const int sy = (int)((idx / ((long long)C8 * Wo)) % strips);
     const int b = (int)(idx / ((long long)C8 * Wo * strips));
-    PoolWin none;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        none.m[j] = (_Float16)(-INFINITY);
-        none.a[j] = (_Float16)0.f;
-    }
-    PoolWin ring[KH];
+    Win none;
+    pool_clear(none);
+    Win ring[KH];                               // ring[k] = row maximum of input row (next_row - KH + k) over the window's columns, oldest first
     auto row_max = [&](int yy) {
-        PoolWin m = none;
+        Win m = none;
         if (yy < 0 || yy >= H) return m;
 #pragma unroll
         for (int c = 0; c < KW; ++c) {
             const int xx = xo * SW - PW + c;
             if (xx < 0 || xx >= W) continue;
-            pool_take(m, in[(((size_t)b * H + yy) * W + xx) * C8 + c8]);
+            const size_t o = (((size_t)b * H + yy) * W + xx) * C8 + c8;
+            pool_take(m, in_hi[o], (LO ? in_lo : in_hi)[o]);
         }
         return m;
     };
@@ -815,11 +725,11 @@ __global__ __launch_bounds__(256) void k_me_pool16(const f16x8* __restrict__ in,
 #pragma unroll
     for (int k = 0; k < KH; ++k) ring[k] = row_max(yo0 * SH - PH + k);
     for (int yo = yo0; yo < yo1; ++yo) {
-        PoolWin m = ring[0];
+        Win m = ring[0];
 #pragma unroll
         for (int k = 1; k < KH; ++k) pool_merge(m, ring[k]);
-        out[(((size_t)b * Ho + yo) * Wo + xo) * C8 + c8] = pool_value(m);
-        if (yo + 1 < yo1) {
+        pool_put(m, out_hi, out_lo, (((size_t)b * Ho + yo) * Wo + xo) * C8 + c8);
+        if (yo + 1 < yo1) {              // advance the window by SH input rows
 #pragma unroll
             for (int k = 0; k + SH < KH; ++k) ring[k] = ring[k + SH];
 #pragma unroll
@@ -1022,135 +932,134 @@ long long dc_music_workspace_bytes(const dc_music* m) { return m ? m->ws_bytes :
 
 namespace {
 
-template <int CIN, int COUT, int RES>
-hipError_t launch_conv(hipStream_t st, const ConvDev& c, const float* mel, const bf16x8* ih, const bf16x8* il, bf16x8* oh,
-                       bf16x8* ol, int Bc, int H, int W) {
-    constexpr int KC = CIN >= 16 ? CIN / 16 : 1, NKS = CIN >= 16 ? 9 * KC : 1, NF = 2 * NKS + (RES == 2 ? 2 * KC : 0);
+#define ME_TRY(x)                         \
+    do {                                  \
+        hipError_t e_ = (x);              \
+        if (e_ != hipSuccess) return e_;  \
+    } while (0)
+
+// a plane pair in HBM (single plane: lo = nullptr), its element view for the kernels' stores, and a format's copy of a weight held in both
+template <bool SP>
+struct Planes {
+    typename PL<SP>::v8 *hi, *lo;
+};
+template <bool SP>
+typename PL<SP>::e* elems(typename PL<SP>::v8* p) { return reinterpret_cast<typename PL<SP>::e*>(p); }
+template <bool SP>
+auto frags(const bf16x8* w, const f16x8* w16) {
+    if constexpr (SP) return w; else return w16;
+}
+
+// Every launcher: the mel has 128 bins, so W is 128, 64 or 32 and a multiple of the kernel's tile width; any other W is an error.
+hipError_t launch_conv10(hipStream_t st, const ConvDev& c, const float* mel, const Planes<true>& out, int Bc, int H, int W) {
     constexpr int TPW = 4;
+    if (W % 32 != 0) return hipErrorInvalidValue;
     const long long tiles = (long long)Bc * H * (W / 32);
     const unsigned grid = (unsigned)((tiles + 4 * TPW - 1) / (4 * TPW));
-    k_me_conv<CIN, COUT, RES><<<dim3(grid), dim3(256), NF * 1024, st>>>(mel, ih, il, reinterpret_cast<__bf16*>(oh),
-                                                                      reinterpret_cast<__bf16*>(ol), c.w, c.bias, c.rbias, Bc, H, W,
-                                                                      TPW);
+    k_me_conv10<<<dim3(grid), dim3(256), 2 * 1024, st>>>(mel, elems<true>(out.hi), elems<true>(out.lo), c.w, c.bias, Bc, H, W, TPW);
     return hipGetLastError();
 }
-// per-device state of the launchers: CU count and the large-LDS opt-in (hipFuncSetAttribute applies per device)
-struct MeDev {
-    int dev = 0, ncu = 0;
-};
-hipError_t me_device(MeDev& d) {
-    static int ncu_of[64] = {0};
-    if (hipError_t e = hipGetDevice(&d.dev)) return e;
-    int& n = ncu_of[d.dev & 63];
-    if (!n)
-        if (hipError_t e = hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, d.dev)) return e;
-    d.ncu = n;
-    return hipSuccess;
-}
-hipError_t me_optin(const void* fn, int bytes, unsigned long long& done, int dev) {
-    if (dev < 64 && ((done >> dev) & 1ull)) return hipSuccess;
-    if (hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes)) return e;
-    if (dev < 64) done |= 1ull << dev;
-    return hipSuccess;
-}
-// LDS-tiled form (CIN >= 16); W must be a multiple of the tile width
-template <int CIN, int COUT, int RES, int ROWS, int NXS>
-hipError_t launch_conv_t(hipStream_t st, const ConvDev& c, const bf16x8* ih, const bf16x8* il, bf16x8* oh, bf16x8* ol, int Bc, int H,
-                         int W) {
-    constexpr int KC = CIN / 16, NKS = 9 * KC, NF = 2 * NKS + (RES == 2 ? 2 * KC : 0);
-    constexpr int NP = 2 * KC * 2 * (ROWS + 2) * (32 * NXS + 2), NDMA = (NP + 63) / 64;
+// LDS-tiled form (CIN >= 16)
+template <int CIN, int COUT, int RES, int ROWS, int NXS, bool SP>
+hipError_t launch_conv_t(hipStream_t st, const ConvDev& c, const Planes<SP>& in, const Planes<SP>& out, int Bc, int H, int W) {
+    constexpr int NPL = PL<SP>::N, KC = CIN / 16, NF = NPL * (9 * KC + (RES == 2 ? KC : 0));
+    constexpr int NP = NPL * KC * 2 * (ROWS + 2) * (32 * NXS + 2), NDMA = (NP + 63) / 64;
     constexpr int SHM = (NF + NDMA) * 1024;
-    if (W % (32 * NXS) != 0) return launch_conv<CIN, COUT, RES>(st, c, nullptr, ih, il, oh, ol, Bc, H, W);
     static unsigned long long optin = 0;
-    MeDev d;
-    if (hipError_t e = me_device(d)) return e;
-    const int ncu = d.ncu;
-    const auto fn = k_me_conv_t<CIN, COUT, RES, ROWS, NXS, true>;
-    if (hipError_t e = me_optin((const void*)fn, SHM, optin, d.dev)) return e;
+    int ncu = 0;
+    ME_TRY(dc_cu_count(&ncu));
+    if (W % (32 * NXS) != 0) return hipErrorInvalidValue;
+    const auto fn = k_me_conv_t<CIN, COUT, RES, ROWS, NXS, SP>;
+    ME_TRY(dc_lds_optin((const void*)fn, SHM, optin));
     const long long ntiles = (long long)Bc * ((H + ROWS - 1) / ROWS) * (W / (32 * NXS));
     const unsigned grid = (unsigned)std::min<long long>(ntiles, 2LL * ncu);
-    fn<<<dim3(grid), dim3(256), SHM, st>>>(ih, il, reinterpret_cast<__bf16*>(oh), reinterpret_cast<__bf16*>(ol), c.w, c.bias, c.rbias, H, W,
+    fn<<<dim3(grid), dim3(256), SHM, st>>>(in.hi, in.lo, elems<SP>(out.hi), elems<SP>(out.lo), frags<SP>(c.w, c.w16), c.bias, c.rbias, H, W,
                                            (int)ntiles);
-    return hipGetLastError();
-}
-// ... on one fp16 plane (W a multiple of the tile width: the mel has 128 bins)
-template <int CIN, int COUT, int RES, int ROWS, int NXS>
-hipError_t launch_conv_t16(hipStream_t st, const ConvDev& c, const f16x8* in, f16x8* out, int Bc, int H, int W) {
-    constexpr int KC = CIN / 16, NKS = 9 * KC, NF = NKS + (RES == 2 ? KC : 0);
-    constexpr int NP = KC * 2 * (ROWS + 2) * (32 * NXS + 2), NDMA = (NP + 63) / 64;
-    constexpr int SHM = (NF + NDMA) * 1024;
-    if (W % (32 * NXS) != 0) return hipErrorInvalidValue;
-    static unsigned long long optin = 0;
-    MeDev d;
-    if (hipError_t e = me_device(d)) return e;
-    const auto fn = k_me_conv_t<CIN, COUT, RES, ROWS, NXS, false>;
-    if (hipError_t e = me_optin((const void*)fn, SHM, optin, d.dev)) return e;
-    const long long ntiles = (long long)Bc * ((H + ROWS - 1) / ROWS) * (W / (32 * NXS));
-    const unsigned grid = (unsigned)std::min<long long>(ntiles, 2LL * d.ncu);
-    fn<<<dim3(grid), dim3(256), SHM, st>>>(in, nullptr, reinterpret_cast<_Float16*>(out), nullptr, c.w16, c.bias, c.rbias, H, W, (int)ntiles);
     return hipGetLastError();
 }
 // conv1.0 -> conv1.1 -> conv1.2 fused (W a multiple of 64); DC_ME_NO_STEM=1 keeps the three separate launches (split planes only)
 template <bool SP>
-hipError_t launch_stem(hipStream_t st, const dc_music* m, const float* mel, typename PL<SP>::v8* oh, typename PL<SP>::v8* ol, int Bc, int H, int W) {
+hipError_t launch_stem(hipStream_t st, const dc_music* m, const float* mel, const Planes<SP>& out, int Bc, int H, int W) {
     constexpr int ROWS = 8, TX = 64, NPL = PL<SP>::N;
     constexpr int NBP = ((ROWS + 2) * (TX + 2) + 15) / 16 * 16;
     constexpr int SHM = 2 * NPL * (ROWS + 4) * (TX + 4) * 16 + 2 * NPL * NBP * 16 + (ROWS + 6) * (TX + 6) * 4 + (SP ? 0 : 144 * 4);
     static unsigned long long optin = 0;
-    MeDev d;
-    if (hipError_t e = me_device(d)) return e;
+    int ncu = 0;
+    ME_TRY(dc_cu_count(&ncu));
     if (W % TX != 0) return hipErrorInvalidValue;
-    if (hipError_t e = me_optin((const void*)k_me_stem<ROWS, TX, SP>, SHM, optin, d.dev)) return e;
+    ME_TRY(dc_lds_optin((const void*)k_me_stem<ROWS, TX, SP>, SHM, optin));
     const long long ntiles = (long long)Bc * ((H + ROWS - 1) / ROWS) * (W / TX);
-    const unsigned grid = (unsigned)std::min<long long>(ntiles, (SP ? 1 : 2) * (long long)d.ncu);
-    using E = typename PL<SP>::e;
-    const typename PL<SP>::v8* w;
-    if constexpr (SP) w = m->stem_w; else w = m->stem_w16;
-    k_me_stem<ROWS, TX, SP><<<dim3(grid), dim3(512), SHM, st>>>(mel, reinterpret_cast<E*>(oh), reinterpret_cast<E*>(ol), w, m->stem_b, m->stem_wa, H,
-                                                                W, (int)ntiles);
+    const unsigned grid = (unsigned)std::min<long long>(ntiles, (SP ? 1 : 2) * (long long)ncu);
+    k_me_stem<ROWS, TX, SP><<<dim3(grid), dim3(512), SHM, st>>>(mel, elems<SP>(out.hi), elems<SP>(out.lo), frags<SP>(m->stem_w, m->stem_w16),
+                                                                m->stem_b, m->stem_wa, H, W, (int)ntiles);
     return hipGetLastError();
 }
 // conv2.0 -> conv2.1 fused (W a multiple of 32); DC_ME_NO_MID=1 keeps the two separate launches (split planes only)
 template <bool SP>
-hipError_t launch_mid(hipStream_t st, const dc_music* m, const typename PL<SP>::v8* ih, const typename PL<SP>::v8* il, typename PL<SP>::v8* oh,
-                      typename PL<SP>::v8* ol, int Bc, int H, int W) {
+hipError_t launch_mid(hipStream_t st, const dc_music* m, const Planes<SP>& in, const Planes<SP>& out, int Bc, int H, int W) {
     constexpr int ROWS = 8, TX = 32, NPL = PL<SP>::N;
     constexpr int NPA = 2 * NPL * (ROWS + 4) * (TX + 4), NDMA = (NPA + 63) / 64, NBP = ((ROWS + 2) * (TX + 2) + 15) / 16 * 16;
     constexpr int SHM = 28 * NPL * 1024 + NDMA * 1024 + 4 * NPL * NBP * 16 + (SP ? 0 : 96 * 4);
     static unsigned long long optin = 0;
-    MeDev d;
-    if (hipError_t e = me_device(d)) return e;
+    int ncu = 0;
+    ME_TRY(dc_cu_count(&ncu));
     if (W % TX != 0) return hipErrorInvalidValue;
-    if (hipError_t e = me_optin((const void*)k_me_mid<ROWS, TX, SP>, SHM, optin, d.dev)) return e;
+    ME_TRY(dc_lds_optin((const void*)k_me_mid<ROWS, TX, SP>, SHM, optin));
     const long long ntiles = (long long)Bc * ((H + ROWS - 1) / ROWS) * (W / TX);
-    const unsigned grid = (unsigned)std::min<long long>(ntiles, (SP ? 1 : 2) * (long long)d.ncu);
-    using E = typename PL<SP>::e;
-    const typename PL<SP>::v8 *w0, *w1;
-    if constexpr (SP) { w0 = m->conv[3].w; w1 = m->conv[4].w; } else { w0 = m->conv[3].w16; w1 = m->conv[4].w16; }
-    k_me_mid<ROWS, TX, SP><<<dim3(grid), dim3(512), SHM, st>>>(ih, il, reinterpret_cast<E*>(oh), reinterpret_cast<E*>(ol), w0, m->conv[3].bias,
-                                                               m->conv[3].rbias, w1, m->conv[4].bias, H, W, (int)ntiles);
+    const unsigned grid = (unsigned)std::min<long long>(ntiles, (SP ? 1 : 2) * (long long)ncu);
+    const ConvDev &c0 = m->conv[3], &c1 = m->conv[4];
+    k_me_mid<ROWS, TX, SP><<<dim3(grid), dim3(512), SHM, st>>>(in.hi, in.lo, elems<SP>(out.hi), elems<SP>(out.lo), frags<SP>(c0.w, c0.w16), c0.bias,
+                                                               c0.rbias, frags<SP>(c1.w, c1.w16), c1.bias, H, W, (int)ntiles);
     return hipGetLastError();
 }
 constexpr int kPoolNY = 24;                // output rows per thread: (NY + KH - 1) / NY of the minimum input traffic (3 ... 24: same time)
-template <int KH, int KW, int SH, int SW, int PH, int PW>
-hipError_t launch_pool(hipStream_t st, const bf16x8* ih, const bf16x8* il, bf16x8* oh, bf16x8* ol, int Bc, int H, int W, int C,
-                       int Ho, int Wo) {
-    constexpr int NY = kPoolNY;
-#ifndef DC_ME_POOL_XO
-#define DC_ME_POOL_XO 1                    // adjacent output columns per thread (2 measured 4.43 vs 4.37 ms per encode_music: 173 VGPRs, profiles/r05_ab_pool.txt)
-#endif
-    constexpr int XO = DC_ME_POOL_XO;
-    const long long total = (long long)Bc * ((Ho + NY - 1) / NY) * ((Wo + XO - 1) / XO) * (C / 8);
-    k_me_pool<KH, KW, SH, SW, PH, PW, XO><<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st>>>(ih, il, oh, ol, Bc, H, W, C / 8, Ho, Wo, NY);
+template <int KH, int KW, int SH, int SW, int PH, int PW, bool SP>
+hipError_t launch_pool(hipStream_t st, const Planes<SP>& in, const Planes<SP>& out, int Bc, int H, int W, int C, int Ho, int Wo) {
+    // (DC_ME_POOL_NY: diagnostic of the single-plane pools.  Rows per thread 6 / 12 / 24 / 48 / 96: the three pools together 719 / 730 / 682 / 805 / 1 116 us per 32 clips)
+    static const int NY16 = getenv("DC_ME_POOL_NY") ? std::max(1, atoi(getenv("DC_ME_POOL_NY"))) : kPoolNY;
+    const int NY = SP ? kPoolNY : NY16;
+    const long long total = (long long)Bc * ((Ho + NY - 1) / NY) * Wo * (C / 8);
+    k_me_pool<KH, KW, SH, SW, PH, PW, SP><<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st>>>(in.hi, in.lo, out.hi, out.lo, Bc, H, W, C / 8,
+                                                                                                     Ho, Wo, NY);
     return hipGetLastError();
 }
-template <int KH, int KW, int SH, int SW, int PH, int PW>
-hipError_t launch_pool16(hipStream_t st, const f16x8* in, f16x8* out, int Bc, int H, int W, int C, int Ho, int Wo) {
-    // (DC_ME_POOL_NY: diagnostic.  Rows per thread 6 / 12 / 24 / 48 / 96: the three pools together 719 / 730 / 682 / 805 / 1 116 us per 32 clips)
-    static const int NY = getenv("DC_ME_POOL_NY") ? std::max(1, atoi(getenv("DC_ME_POOL_NY"))) : kPoolNY;
-    const long long total = (long long)Bc * ((Ho + NY - 1) / NY) * Wo * (C / 8);
-    k_me_pool16<KH, KW, SH, SW, PH, PW><<<dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st>>>(in, out, Bc, H, W, C / 8, Ho, Wo, NY);
-    return hipGetLastError();
+
+// One pass: Bc clips of Tm mel frames through the encoder in format SP, the activations ping-ponging between the plane pairs a and b
+// (single plane: the hi buffers, half of each is used).  xp may be null.
+template <bool SP>
+hipError_t encode_pass(hipStream_t st, const dc_music* m, const float* mel, int Bc, int Tm, float* xo, float* xp) {
+    using V8 = typename PL<SP>::v8;
+    const int T = dc_music_frames(Tm);
+    Planes<SP> a{reinterpret_cast<V8*>(m->a_hi), SP ? reinterpret_cast<V8*>(m->a_lo) : nullptr};
+    Planes<SP> b{reinterpret_cast<V8*>(m->b_hi), SP ? reinterpret_cast<V8*>(m->b_lo) : nullptr};
+    if (!(SP && getenv("DC_ME_NO_STEM"))) {
+        ME_TRY(launch_stem<SP>(st, m, mel, a, Bc, Tm, 128));
+    } else if constexpr (SP) {
+        ME_TRY(launch_conv10(st, m->conv[0], mel, a, Bc, Tm, 128));
+        ME_TRY((launch_conv_t<16, 16, 1, 8, 2, SP>(st, m->conv[1], a, b, Bc, Tm, 128)));
+        ME_TRY((launch_conv_t<16, 16, 1, 8, 2, SP>(st, m->conv[2], b, a, Bc, Tm, 128)));
+    }
+    ME_TRY((launch_pool<5, 5, 1, 2, 2, 2, SP>(st, a, b, Bc, Tm, 128, 16, Tm, 64)));
+    if (!(SP && getenv("DC_ME_NO_MID"))) {
+        ME_TRY(launch_mid<SP>(st, m, b, a, Bc, Tm, 64));
+    } else if constexpr (SP) {
+        ME_TRY((launch_conv_t<16, 32, 2, 8, 2, SP>(st, m->conv[3], b, a, Bc, Tm, 64)));
+        ME_TRY((launch_conv_t<32, 32, 1, 8, 1, SP>(st, m->conv[4], a, b, Bc, Tm, 64)));
+        std::swap(a, b);        // two launches leave conv2.1's output where one leaves its input
+    }
+    ME_TRY((launch_pool<5, 5, 3, 2, 2, 2, SP>(st, a, b, Bc, Tm, 64, 32, T, 32)));
+    ME_TRY((launch_conv_t<32, 32, 1, 8, 1, SP>(st, m->conv[5], b, a, Bc, T, 32)));
+    ME_TRY((launch_conv_t<32, 32, 1, 8, 1, SP>(st, m->conv[6], a, b, Bc, T, 32)));
+    ME_TRY((launch_pool<3, 3, 1, 2, 1, 1, SP>(st, b, a, Bc, T, 32, 32, T, 16)));
+    const int M = Bc * T;
+    const unsigned grid = (unsigned)((M + 127) / 128);
+    k_me_head<SP><<<dim3(grid), dim3(256), 0, st>>>(a.hi, a.lo, frags<SP>(m->w4, m->w4_16), m->b4, xo, M);
+    ME_TRY(hipGetLastError());
+    if (xp) {
+        k_me_proj<<<dim3(grid), dim3(256), 0, st>>>(xo, m->wp, m->bp, xp, M);
+        ME_TRY(hipGetLastError());
+    }
+    return hipSuccess;
 }
 
 }  // namespace
@@ -1199,69 +1108,11 @@ hipError_t dc_music_encode(dc_music* m, const float* d_mel, int B, int Tm, float
         m->cap = ncap;
         m->cap_tm = ntm;
     }
-    bf16x8 *ah = m->a_hi, *al = m->a_lo, *bh = m->b_hi, *bl = m->b_lo;
-#define ME_TRY(x)                         \
-    do {                                  \
-        hipError_t e_ = (x);              \
-        if (e_ != hipSuccess) return e_;  \
-    } while (0)
-    if (dc_music_format(m)) {              // one fp16 plane per activation (the hi buffers; half of each is used)
-        f16x8 *pa = reinterpret_cast<f16x8*>(m->a_hi), *pb = reinterpret_cast<f16x8*>(m->b_hi);
-        for (int b0 = 0; b0 < B; b0 += chunk) {
-            const int Bc = std::min(chunk, B - b0);
-            const float* mel = d_mel + (size_t)b0 * Tm * 128;
-            ME_TRY(launch_stem<false>(st, m, mel, pa, nullptr, Bc, Tm, 128));
-            ME_TRY((launch_pool16<5, 5, 1, 2, 2, 2>(st, pa, pb, Bc, Tm, 128, 16, Tm, 64)));
-            ME_TRY(launch_mid<false>(st, m, pb, nullptr, pa, nullptr, Bc, Tm, 64));
-            ME_TRY((launch_pool16<5, 5, 3, 2, 2, 2>(st, pa, pb, Bc, Tm, 64, 32, T, 32)));
-            ME_TRY((launch_conv_t16<32, 32, 1, 8, 1>(st, m->conv[5], pb, pa, Bc, T, 32)));
-            ME_TRY((launch_conv_t16<32, 32, 1, 8, 1>(st, m->conv[6], pa, pb, Bc, T, 32)));
-            ME_TRY((launch_pool16<3, 3, 1, 2, 1, 1>(st, pb, pa, Bc, T, 32, 32, T, 16)));
-            const int M = Bc * T;
-            const unsigned grid = (unsigned)((M + 127) / 128);
-            float* xo = d_xf_out + (size_t)b0 * T * 64;
-            k_me_head<false><<<dim3(grid), dim3(256), 0, st>>>(pa, nullptr, m->w4_16, m->b4, xo, M);
-            ME_TRY(hipGetLastError());
-            if (d_xf_proj) {
-                k_me_proj<<<dim3(grid), dim3(256), 0, st>>>(xo, m->wp, m->bp, d_xf_proj + (size_t)b0 * T * 64, M);
-                ME_TRY(hipGetLastError());
-            }
-        }
-        return hipSuccess;
-    }
+    const auto pass = dc_music_format(m) ? encode_pass<false> : encode_pass<true>;
     for (int b0 = 0; b0 < B; b0 += chunk) {
-        const int Bc = std::min(chunk, B - b0);
-        const float* mel = d_mel + (size_t)b0 * Tm * 128;
-        if (!getenv("DC_ME_NO_STEM")) {
-            ME_TRY(launch_stem<true>(st, m, mel, ah, al, Bc, Tm, 128));
-        } else {
-            ME_TRY((launch_conv<1, 16, 0>(st, m->conv[0], mel, nullptr, nullptr, ah, al, Bc, Tm, 128)));
-            ME_TRY((launch_conv_t<16, 16, 1, 8, 2>(st, m->conv[1], ah, al, bh, bl, Bc, Tm, 128)));
-            ME_TRY((launch_conv_t<16, 16, 1, 8, 2>(st, m->conv[2], bh, bl, ah, al, Bc, Tm, 128)));
-        }
-        ME_TRY((launch_pool<5, 5, 1, 2, 2, 2>(st, ah, al, bh, bl, Bc, Tm, 128, 16, Tm, 64)));
-        if (!getenv("DC_ME_NO_MID")) {
-            ME_TRY(launch_mid<true>(st, m, bh, bl, ah, al, Bc, Tm, 64));
-            std::swap(ah, bh);      // (the two-launch form leaves conv2.1's output in b)
-            std::swap(al, bl);
-        } else {
-            ME_TRY((launch_conv_t<16, 32, 2, 8, 2>(st, m->conv[3], bh, bl, ah, al, Bc, Tm, 64)));
-            ME_TRY((launch_conv_t<32, 32, 1, 8, 1>(st, m->conv[4], ah, al, bh, bl, Bc, Tm, 64)));
-        }
-        ME_TRY((launch_pool<5, 5, 3, 2, 2, 2>(st, bh, bl, ah, al, Bc, Tm, 64, 32, T, 32)));
-        ME_TRY((launch_conv_t<32, 32, 1, 8, 1>(st, m->conv[5], ah, al, bh, bl, Bc, T, 32)));
-        ME_TRY((launch_conv_t<32, 32, 1, 8, 1>(st, m->conv[6], bh, bl, ah, al, Bc, T, 32)));
-        ME_TRY((launch_pool<3, 3, 1, 2, 1, 1>(st, ah, al, bh, bl, Bc, T, 32, 32, T, 16)));
-        const int M = Bc * T;
-        const unsigned grid = (unsigned)((M + 127) / 128);
-        float* xo = d_xf_out + (size_t)b0 * T * 64;
-        k_me_head<true><<<dim3(grid), dim3(256), 0, st>>>(bh, bl, m->w4, m->b4, xo, M);
-        ME_TRY(hipGetLastError());
-        if (d_xf_proj) {
-            k_me_proj<<<dim3(grid), dim3(256), 0, st>>>(xo, m->wp, m->bp, d_xf_proj + (size_t)b0 * T * 64, M);
-            ME_TRY(hipGetLastError());
-        }
+        const size_t f0 = (size_t)b0 * T * 64;
+        ME_TRY(pass(st, m, d_mel + (size_t)b0 * Tm * 128, std::min(chunk, B - b0), Tm, d_xf_out + f0, d_xf_proj ? d_xf_proj + f0 : nullptr));
     }
-#undef ME_TRY
     return hipSuccess;
 }
+#undef ME_TRY

@@ -28,7 +28,7 @@ def clip_tol(fmt):
 # ---- shapes, from the kernels' constants ----------------------------------------------------------------------------------------
 STEM_ROWS = 8           # launch_stem ROWS (k_me_stem: 8 x 64-pixel tiles over Tm x 128)
 MID_ROWS = 8            # launch_mid ROWS (k_me_mid: 8 x 32 over Tm x 64)
-CONV3_ROWS = 8          # launch_conv_t<32, 32, 1, 8, 1> ROWS (conv3.0, conv3.1: 8 x 32 over T x 32)
+CONV3_ROWS = 8          # launch_conv_t<32, 32, 1, 8, 1, SP> ROWS (conv3.0, conv3.1: 8 x 32 over T x 32)
 POOL_NY = 24            # kPoolNY: output rows a pool thread walks (pool1 on Tm, pool2 and pool3 on T)
 HEAD_WAVE = 32          # k_me_head / k_me_proj: frames per wave ...
 HEAD_WG = 128           # ... and per workgroup, over B * T

@@ -107,6 +107,20 @@ def test_lengths_around_every_tile_edge(model):
     g.done()
 
 
+@pytest.mark.parametrize("env", ({"DC_ME_NO_STEM": "1"}, {"DC_ME_NO_MID": "1"}, {"DC_ME_NO_STEM": "1", "DC_ME_NO_MID": "1"}),
+                         ids=("no_stem", "no_mid", "neither"))
+def test_separate_launches_around_the_tile_edges(model, env):
+    """The split format's separate launches - conv1 as conv1.0 (k_me_conv10, bf16x3 MFMAs where the fused stem runs fp32 FMAs) and two
+    tiled launches, conv2 as two tiled launches that leave their result in the other buffer - at B = 3 and Tm around the 8-row tiles,
+    down to 4 mel frames: the fused forms' bounds, per clip and per frame."""
+    g = Group("separate launches " + "+".join(sorted(env)))
+    for Tm in (4, 7, 8, 9, 25, 97):
+        assert Tm in H.TILE_TMS
+        mel = batch_mel(3, Tm, first=Tm)
+        g.check(_encode(model, mel, "split", env), _oracle(("white", 3, Tm, Tm), state_dict_np(), mel), "split", f"Tm={Tm}")
+    g.done()
+
+
 def test_second_round_of_the_persistent_tile_loops(model):
     """grid = min(tiles, k CUs): with T = 216 frames per clip (27 conv3 tiles) and the smallest B whose B x 27 tiles exceed 2 CUs, every
     persistent kernel - conv3 included - runs tiles in a second round (the stem and mid kernels have over 3 000 tiles); one clip more

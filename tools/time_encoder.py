@@ -4,7 +4,7 @@
 HIP events around `--iters` back-to-back encodes after `--warmup` untimed ones, repeated `--reps` times per format; prints the median
 and the spread of the per-encode time.  One JSON line at the end.  DC_DDIM_LIB=<another build of the same ABI> times that build:
 alternate the two commands on one box to compare them (every process loads one library).  `--dump FILE.npz` also writes xf_out and
-xf_proj of three small seeded shapes in both formats, to compare two builds bit for bit (`--compare A.npz B.npz` does, without a GPU).
+xf_proj of three small seeded shapes in both formats, and of the first in the split format's separate launches, to compare two builds bit for bit (`--compare A.npz B.npz` does, without a GPU).
 
     python tools/time_encoder.py [--clips 32] [--frames 5400] [--reps 20] [--iters 5] [--warmup 3] [--dump FILE.npz]
     python tools/time_encoder.py --compare A.npz B.npz
@@ -20,6 +20,8 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 DUMP_SHAPES = ((3, 25), (3, 97), (3, 385))
+DUMP_SEPARATE = {"no_stem": {"DC_ME_NO_STEM": "1"}, "no_mid": {"DC_ME_NO_MID": "1"},
+                 "no_stem_no_mid": {"DC_ME_NO_STEM": "1", "DC_ME_NO_MID": "1"}}      # at DUMP_SHAPES[0], split format
 
 
 def compare(a, b):
@@ -59,6 +61,19 @@ def main():
                 xp, xo = nat.encode_music(mel)
                 torch.cuda.synchronize()
                 out[f"{B}x{Tm}_{fmt}_xf_proj"], out[f"{B}x{Tm}_{fmt}_xf_out"] = xp.cpu().numpy(), xo.cpu().numpy()
+        # the split format's separate launches (the library reads the switches per call)
+        B, Tm = DUMP_SHAPES[0]
+        mel = torch.from_numpy(batch_mel(B, Tm, first=Tm)).cuda()
+        nat.set_encoder_format("split")
+        for name, env in DUMP_SEPARATE.items():
+            os.environ.update(env)
+            try:
+                xp, xo = nat.encode_music(mel)
+                torch.cuda.synchronize()
+            finally:
+                for k in env:
+                    del os.environ[k]
+            out[f"{B}x{Tm}_split_{name}_xf_proj"], out[f"{B}x{Tm}_split_{name}_xf_out"] = xp.cpu().numpy(), xo.cpu().numpy()
         os.makedirs(os.path.dirname(os.path.abspath(a.dump)), exist_ok=True)
         np.savez(a.dump, **out)
     mel = torch.from_numpy(batch_mel(a.clips, a.frames)).cuda()
