@@ -892,11 +892,8 @@ int enqueue_step(dc_sampler* s, hipStream_t st, const Step& c, const Switches& w
     la.upd = DcUpdate{s->d_zslot, s->d_status, (c.loop_mode ? s->upd_flags : 0) | f.upd_flags, folded ? graph_step : -1, nullptr, s->d_kslot, s->d_x0_prev};
     DcLayerArgs la_stamps = la;      // (stage stamps of layer 3 in diagnostic builds: DcUpdate::stamps carries the buffer)
     la_stamps.upd.stamps = s->d_stamps;
-    if (s->cfg.no_eff) {
-        LAUNCH(K_EMBED, dc_launch_embed_front_full(st, fs, ss, dmod, c.x_src, s->d_h, s->d_kv_sa[0], M, T, B, s->KT));
-        for (int l = 0; l < nl_run; ++l)        // (stage stamps: tools/stage_stamps_full.py + a -DDC_FULL_STAMPS build)
-            LAUNCH(K_LAYER, dc_launch_layer_full(st, fs, ss, (want_stamps && l == 3) ? la_stamps : la, l, s->d_kv_sa[l & 1], s->d_kv_sa[(l + 1) & 1],
-                                                 s->d_kv_ca, s->KT, (l == nl_run - 1) ? f.stop_stage : 0));
+    // behind the last layer of a windows or guided step, which stored the raw output: the kernel that combines it and updates x
+    const auto post_update = [&]() -> int {
         if (f.windows)
             LAUNCH(K_WINDOWS, dc_launch_windows_update(st, s->d_raw, c.x_dst, s->d_xp, f.guided ? 2 : 1, s->user_B(), s->win_W, Tx, s->win_L, s->cfg.input_feats,
                                                        s->d_winslot, coef_src, snap_src, s->d_snaps, iter_base, s->d_wslot, la.upd));
@@ -904,6 +901,13 @@ int enqueue_step(dc_sampler* s, hipStream_t st, const Step& c, const Switches& w
             LAUNCH(K_GUIDE, dc_launch_guided_update(st, s->d_raw, c.x_dst, (size_t)s->user_B() * Tx * s->cfg.input_feats, coef_src, snap_src,
                                                     s->d_snaps, iter_base, s->d_wslot, la.upd));
         return DC_OK;
+    };
+    if (s->cfg.no_eff) {
+        LAUNCH(K_EMBED, dc_launch_embed_front_full(st, fs, ss, dmod, c.x_src, s->d_h, s->d_kv_sa[0], M, T, B, s->KT));
+        for (int l = 0; l < nl_run; ++l)        // (stage stamps: tools/stage_stamps_full.py + a -DDC_FULL_STAMPS build)
+            LAUNCH(K_LAYER, dc_launch_layer_full(st, fs, ss, (want_stamps && l == 3) ? la_stamps : la, l, s->d_kv_sa[l & 1], s->d_kv_sa[(l + 1) & 1],
+                                                 s->d_kv_ca, s->KT, (l == nl_run - 1) ? f.stop_stage : 0));
+        return post_update();
     }
     const DcLayerForm lf{fs, ss, f.wgr, f.narrow, f.g1_tiles, f.upc, f.rec_stride, f.idle_path};
     if (f.fuse_embed || f.fuse_extra || c.embedded) {
@@ -925,13 +929,7 @@ int enqueue_step(dc_sampler* s, hipStream_t st, const Step& c, const Switches& w
         LAUNCH(K_LAYER, dc_launch_layer(st, lf, la, l, s->d_a_sa, s->d_a_ca, (l == nl_run - 1) ? f.stop_stage : 0,
                                         ((l == 3 || l == 4) && want_stamps) ? s->d_stamps : nullptr));
     }
-    if (f.windows)
-        LAUNCH(K_WINDOWS, dc_launch_windows_update(st, s->d_raw, c.x_dst, s->d_xp, f.guided ? 2 : 1, s->user_B(), s->win_W, Tx, s->win_L, s->cfg.input_feats,
-                                                   s->d_winslot, coef_src, snap_src, s->d_snaps, iter_base, s->d_wslot, la.upd));
-    else if (f.guided)
-        LAUNCH(K_GUIDE, dc_launch_guided_update(st, s->d_raw, c.x_dst, (size_t)s->user_B() * Tx * s->cfg.input_feats, coef_src, snap_src,
-                                                s->d_snaps, iter_base, s->d_wslot, la.upd));
-    return DC_OK;
+    return post_update();
 }
 
 int sync_in(dc_sampler* s, hipStream_t user) {

@@ -1653,12 +1653,13 @@ DEV float ddim_update(float mo, float xt, const float* __restrict__ c, int flags
 // slot, so one buffer serves in place.  Without the flag nothing is loaded or stored and the result is ddim_update's, bit for bit.
 // Known values are replaced behind this (known_replace).
 // ------------------------------------------------------------------------------------
+DEV float history_term(float xn, float kappa, float pred, float prev) { return xn + kappa * (pred - prev); }
 DEV float multistep_update(float mo, float xt, const float* __restrict__ c, const DcUpdate& upd, bool noisy, float z, bool& bad, size_t o) {
     float pred;
     float xn = ddim_update(mo, xt, c, upd.flags, noisy, z, bad, pred);
     if (upd.flags & DC_UPD_MULTISTEP) {
         float* hp = upd.x0_prev + o;
-        xn += c[8] * (pred - *hp);
+        xn = history_term(xn, c[8], pred, *hp);
         *hp = pred;
     }
     return xn;
@@ -1681,4 +1682,34 @@ DEV KnownPtrs known_ptrs(const DcUpdate& upd) {
 DEV float known_replace(float xn, const KnownPtrs& k, size_t o, const float* __restrict__ c) {
     if (k.mask && k.mask[o] != 0.f) xn = c[2] * k.val[o] + c[5] * k.noise[o];
     return xn;
+}
+
+// ------------------------------------------------------------------------------------
+// One step's update, as every kernel that ends a step applies it (the last layer's epilogue - k_layer's two forms, k_layer_full,
+// k_layer16 - and, behind a last layer that stored the raw output, k_guided_update and k_windows_update).  step_update reads the
+// step's scalars once per thread; n is the element count of the loop's state ([B][Tx][P], or a windows loop's [Bp][L][P]):
+//   * graph-captured loop: coef_cur / snap_cur are the per-iteration tables, *iter_base is the iteration at which the graph replay
+//     began and upd.step the step's number inside the graph - row and slot iter_base, noise row upd.step + *iter_base;
+//   * eager loop (iter_base null): they are the scalars k_begin_step prepared for this step - row and slot 0, noise row snap_cur[1].
+//   c = the coefficient row, snap = the snapshot slot that is due (or -1), zrow = this iteration's N(0, 1) draws (eta > 0): row
+//   `iteration` of the caller's [S][n] tensor, or - DC_UPD_ZSTEP - the one-iteration buffer k_step_noise refilled at the step's head.
+// step_update_element is x_{t-1} of element o from the model's output mo and x_t: ddim_update, the history term, known_replace.  The
+// caller stores it to x and, when su.snap >= 0, to snaps[su.snap n + o], and ORs DC_STATUS_NONFINITE into *upd.status when `bad`.
+// ------------------------------------------------------------------------------------
+struct StepUpdate {
+    const float* c;
+    int snap;
+    bool noisy;
+    const float* zrow;
+    KnownPtrs kn;
+};
+DEV StepUpdate step_update(const float* __restrict__ coef_cur, const int* __restrict__ snap_cur, const int* __restrict__ iter_base,
+                           const DcUpdate& upd, size_t n) {
+    const int ib = iter_base ? *iter_base : 0;
+    StepUpdate su{coef_cur + DC_COEF * ib, snap_cur[ib], (upd.flags & DC_UPD_NOISY) != 0, nullptr, known_ptrs(upd)};
+    if (su.noisy) su.zrow = *upd.zslot + ((upd.flags & DC_UPD_ZSTEP) ? (size_t)0 : (size_t)(iter_base ? upd.step + ib : snap_cur[1]) * n);
+    return su;
+}
+DEV float step_update_element(const StepUpdate& su, const DcUpdate& upd, float mo, float xt, size_t o, bool& bad) {
+    return known_replace(multistep_update(mo, xt, su.c, upd, su.noisy, su.noisy ? su.zrow[o] : 0.f, bad, o), su.kn, o, su.c);
 }

@@ -63,9 +63,9 @@ __global__ __launch_bounds__(256) void k_known_blend(float* __restrict__ x, cons
 // followed by their B unconditional shadows, both reading the same x_t.  k_fill_rows64 broadcasts one 64-vector of the null pair over the
 // shadows' rows of a feature image; k_guided_update runs behind the step's last layer, which has stored the raw model output of all 2 B
 // clips (out_mode 0):   out = c + (w - 1) (c - u)   in fp32, in this order and without contraction, so that w = 1 returns c bit for bit
-// whenever u is finite; then ddim_update and known_replace exactly as the layer epilogue applies them, the step's scalars read the
-// same way (folded: through *iter_base; else k_begin_step's).  x_{t-1} goes to BOTH halves of x.  One thread per 4 consecutive
-// elements, 16-byte accesses where n and every base allow.
+// whenever u is finite; then the step's update as the layer epilogue applies it (step_update, dc_dev.h), on the thread's four elements
+// (update_quad).  x_{t-1} goes to BOTH halves of x.  One thread per 4 consecutive elements, 16-byte accesses where n and every base
+// allow (quad_ld / quad_st: a quad of any fp32 tensor, scalar where `vec` is off or the quad is short).
 // ------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_fill_rows64(float* __restrict__ dst, size_t rows, const DcNull64 v) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;           // one f32x4 per thread
@@ -80,7 +80,7 @@ DEV float guide_combine(float c, float u, float wm1) {
     const float p = wm1 * d;
     return c + p;
 }
-DEV void guide_ld4(float (&o)[4], const float* __restrict__ p, size_t i, int cnt, bool vec) {
+DEV void quad_ld(float (&o)[4], const float* __restrict__ p, size_t i, int cnt, bool vec) {
     if (vec) {
         const f32x4 t = *reinterpret_cast<const f32x4*>(p + i);
 #pragma unroll
@@ -90,7 +90,7 @@ DEV void guide_ld4(float (&o)[4], const float* __restrict__ p, size_t i, int cnt
         for (int j = 0; j < 4; ++j) o[j] = j < cnt ? p[i + j] : 0.f;
     }
 }
-DEV void guide_st4(float* __restrict__ p, size_t i, const float (&v)[4], int cnt, bool vec) {
+DEV void quad_st(float* __restrict__ p, size_t i, const float (&v)[4], int cnt, bool vec) {
     if (vec) {
         *reinterpret_cast<f32x4*>(p + i) = f32x4{v[0], v[1], v[2], v[3]};
     } else {
@@ -99,6 +99,31 @@ DEV void guide_st4(float* __restrict__ p, size_t i, const float (&v)[4], int cnt
             if (j < cnt) p[i + j] = v[j];
     }
 }
+// What k_guided_update and k_windows_update do behind their own combine, on the quad (i, cnt, vec) of the loop's state tensor x [n]
+// (guided: the first half of x; windows: xp), c and u being the model's output for the two halves (u unused unless `guided`): flag a
+// non-finite c or u, combine, the step's update (step_update, dc_dev.h; the history term on the quad's own loads of x0_prev), then
+// x0_prev, the due snapshot and the status word.  x_{t-1} comes back in xn: where it goes besides is the caller's.
+DEV void update_quad(float (&xn)[4], const float (&c)[4], const float (&u)[4], bool guided, float wm1, const float* __restrict__ x,
+                     float* __restrict__ snaps, size_t n, size_t i, int cnt, bool vec, const StepUpdate& su, const DcUpdate& upd) {
+    const bool multi = (upd.flags & DC_UPD_MULTISTEP) != 0;
+    float xt[4], z[4] = {0.f, 0.f, 0.f, 0.f}, pred[4], prev[4] = {0.f, 0.f, 0.f, 0.f};
+    if (multi) quad_ld(prev, upd.x0_prev, i, cnt, vec);
+    quad_ld(xt, x, i, cnt, vec);
+    if (su.noisy) quad_ld(z, su.zrow, i, cnt, vec);
+    bool bad = false;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        bad = bad || (j < cnt && !(fabsf(c[j]) <= 3.0e38f && fabsf(u[j]) <= 3.0e38f));
+        bool badj = false;
+        xn[j] = ddim_update(guided ? guide_combine(c[j], u[j], wm1) : c[j], xt[j], su.c, upd.flags, su.noisy, z[j], badj, pred[j]);
+        if (multi) xn[j] = history_term(xn[j], su.c[8], pred[j], prev[j]);
+        bad = bad || (j < cnt && badj);
+        if (j < cnt) xn[j] = known_replace(xn[j], su.kn, i + j, su.c);
+    }
+    if (multi) quad_st(upd.x0_prev, i, pred, cnt, vec);
+    if (su.snap >= 0) quad_st(snaps + (size_t)su.snap * n, i, xn, cnt, vec);
+    if (bad && upd.status) atomicOr(upd.status, DC_STATUS_NONFINITE);
+}
 __global__ __launch_bounds__(256) void k_guided_update(const float* __restrict__ raw /*[2][n]*/, float* __restrict__ x /*[2][n]*/, size_t n,
                                                        const float* __restrict__ coef_cur, const int* __restrict__ snap_cur,
                                                        float* __restrict__ snaps, const int* __restrict__ iter_base,
@@ -106,39 +131,16 @@ __global__ __launch_bounds__(256) void k_guided_update(const float* __restrict__
     const size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
     if (i >= n) return;
     const int cnt = (int)(n - i < 4 ? n - i : 4);
-    const int ib = iter_base ? *iter_base : 0;
-    const float* cc = coef_cur + DC_COEF * ib;
-    const int snap = snap_cur[ib];
-    const bool noisy = (upd.flags & DC_UPD_NOISY) != 0;
-    const float* zrow = nullptr;
-    if (noisy) zrow = *upd.zslot + ((upd.flags & DC_UPD_ZSTEP) ? (size_t)0 : (size_t)(iter_base ? upd.step + ib : snap_cur[1]) * n);
-    const KnownPtrs kn = known_ptrs(upd);
-    const float wm1 = *wslot - 1.f;
+    const StepUpdate su = step_update(coef_cur, snap_cur, iter_base, upd, n);
     // (x, raw and snaps are workspace buffers: their halves and slots are 16-byte aligned whenever n is a multiple of 4)
     const auto a16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    const bool multi = (upd.flags & DC_UPD_MULTISTEP) != 0;
-    const bool vec = (n & 3) == 0 && a16(raw) && a16(x) && a16(snaps) && a16(zrow) && a16(upd.x0_prev);
-    float c[4], u[4], xt[4], z[4] = {0.f, 0.f, 0.f, 0.f}, xn[4], pred[4], prev[4] = {0.f, 0.f, 0.f, 0.f};
-    if (multi) guide_ld4(prev, upd.x0_prev, i, cnt, vec);
-    guide_ld4(c, raw, i, cnt, vec);
-    guide_ld4(u, raw + n, i, cnt, vec);
-    guide_ld4(xt, x, i, cnt, vec);
-    if (noisy) guide_ld4(z, zrow, i, cnt, vec);
-    bool bad = false;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        bad = bad || (j < cnt && !(fabsf(c[j]) <= 3.0e38f && fabsf(u[j]) <= 3.0e38f));
-        bool badj = false;
-        xn[j] = ddim_update(guide_combine(c[j], u[j], wm1), xt[j], cc, upd.flags, noisy, z[j], badj, pred[j]);
-        if (multi) xn[j] += cc[8] * (pred[j] - prev[j]);      // (multistep_update, dc_dev.h, on this thread's four elements)
-        bad = bad || (j < cnt && badj);
-        if (j < cnt) xn[j] = known_replace(xn[j], kn, i + j, cc);
-    }
-    guide_st4(x, i, xn, cnt, vec);
-    guide_st4(x + n, i, xn, cnt, vec);
-    if (multi) guide_st4(upd.x0_prev, i, pred, cnt, vec);
-    if (snap >= 0) guide_st4(snaps + (size_t)snap * n, i, xn, cnt, vec);
-    if (bad && upd.status) atomicOr(upd.status, DC_STATUS_NONFINITE);
+    const bool vec = (n & 3) == 0 && a16(raw) && a16(x) && a16(snaps) && a16(su.zrow) && a16(upd.x0_prev);
+    float c[4], u[4], xn[4];
+    quad_ld(c, raw, i, cnt, vec);
+    quad_ld(u, raw + n, i, cnt, vec);
+    update_quad(xn, c, u, true, *wslot - 1.f, x, snaps, n, i, cnt, vec, su, upd);
+    quad_st(x, i, xn, cnt, vec);
+    quad_st(x + n, i, xn, cnt, vec);
 }
 
 // ------------------------------------------------------------------------------------
@@ -149,9 +151,8 @@ __global__ __launch_bounds__(256) void k_guided_update(const float* __restrict__
 // behind the step's last layer, which has stored the raw model output of all clips (out_mode 0), on one thread per 4 consecutive PIECE
 // elements:   out = sum_k w[k][f - s_k] raw_k[f - s_k]   over the windows that cover frame f, ascending k, fp32 without contraction,
 // the accumulator starting from the first product (a frame under one window, whose weight is exactly 1, keeps its raw value bit for
-// bit); guided: the two halves are blended each, then combined as k_guided_update combines them; then ddim_update, the multistep term
-// and known_replace exactly as there, every tensor of the update in piece space.  x_{t-1} goes to xp and to every covering window's
-// slot of the internal x (both halves).  Starts and weights come from the device tables *win names: another plan of the same
+// bit); guided: the two halves are blended each, then combined as k_guided_update combines them; then update_quad as there, every tensor of
+// the update in piece space.  x_{t-1} goes to xp and to every covering window's slot of the internal x (both halves).  Starts and weights come from the device tables *win names: another plan of the same
 // (Bp, W, T, L) replays the captured graph.  16-byte accesses where counts, bases and a window's offset allow, scalar ones elsewhere.
 // ------------------------------------------------------------------------------------
 __global__ void k_set_windows(DcWindows* slot, const int* start, const float* weight) { slot->start = start, slot->weight = weight; }
@@ -173,7 +174,7 @@ __global__ __launch_bounds__(256) void k_windows_gather(const float* __restrict_
     const size_t src = (c2 % Bp) * LP + (size_t)start[c2 / Bp] * P + q;
     float v[4];
     if (cnt == 4 && q + 3 < TP) {      // one clip: four consecutive piece elements
-        guide_ld4(v, xp, src, 4, (src & 3) == 0 && a16(xp));
+        quad_ld(v, xp, src, 4, (src & 3) == 0 && a16(xp));
     } else {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -182,7 +183,7 @@ __global__ __launch_bounds__(256) void k_windows_gather(const float* __restrict_
             v[j] = xp[(cc % Bp) * LP + (size_t)start[cc / Bp] * P + qj];
         }
     }
-    guide_st4(xw, i, v, cnt, (n_win & 3) == 0 && a16(xw));
+    quad_st(xw, i, v, cnt, (n_win & 3) == 0 && a16(xw));
 }
 __global__ __launch_bounds__(256) void k_windows_update(const float* __restrict__ raw /*[halves W Bp][T][P]*/, float* __restrict__ xw /*the same*/,
                                                         float* __restrict__ xp /*[Bp][L][P]*/, size_t n /* Bp L P */, int Bp, int W, int T, int L,
@@ -193,20 +194,13 @@ __global__ __launch_bounds__(256) void k_windows_update(const float* __restrict_
     const size_t i = ((size_t)blockIdx.x * 256 + threadIdx.x) * 4;
     if (i >= n) return;
     const int cnt = (int)(n - i < 4 ? n - i : 4);
-    const int ib = iter_base ? *iter_base : 0;
-    const float* cc = coef_cur + DC_COEF * ib;
-    const int snap = snap_cur[ib];
-    const bool noisy = (upd.flags & DC_UPD_NOISY) != 0;
-    const float* zrow = nullptr;
-    if (noisy) zrow = *upd.zslot + ((upd.flags & DC_UPD_ZSTEP) ? (size_t)0 : (size_t)(iter_base ? upd.step + ib : snap_cur[1]) * n);
-    const KnownPtrs kn = known_ptrs(upd);
+    const StepUpdate su = step_update(coef_cur, snap_cur, iter_base, upd, n);
     const bool guided = halves == 2;
     const float wm1 = guided ? *wslot - 1.f : 0.f;
     const int* __restrict__ start = win->start;
     const float* __restrict__ weight = win->weight;
     const auto a16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    const bool multi = (upd.flags & DC_UPD_MULTISTEP) != 0;
-    const bool vec = (n & 3) == 0 && a16(xp) && a16(snaps) && a16(zrow) && a16(upd.x0_prev);      // the piece-space tensors
+    const bool vec = (n & 3) == 0 && a16(xp) && a16(snaps) && a16(su.zrow) && a16(upd.x0_prev);      // the piece-space tensors
     const bool vec_w = a16(raw) && a16(xw);                                                       // the window-space ones, offset permitting
     const size_t TP = (size_t)T * P, LP = (size_t)L * P, half = (size_t)W * Bp * TP;
     // this thread's elements: piece b, offsets r .. r + cnt - 1 inside it (the last quad of a piece whose size is no multiple of 4 runs
@@ -227,8 +221,8 @@ __global__ __launch_bounds__(256) void k_windows_update(const float* __restrict_
             const size_t o = ((size_t)k * Bp + b) * TP + (r - row0);
             const bool v4 = vec_w && (o & 3) == 0;
             float rc[4], ru[4];
-            guide_ld4(rc, raw, o, 4, v4);
-            if (guided) guide_ld4(ru, raw + half, o, 4, v4);
+            quad_ld(rc, raw, o, 4, v4);
+            if (guided) quad_ld(ru, raw + half, o, 4, v4);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const float wj = wk[(r + j - row0) / P];
@@ -248,23 +242,9 @@ __global__ __launch_bounds__(256) void k_windows_update(const float* __restrict_
             seen |= 1u << j;
         }
     }
-    float xt[4], z[4] = {0.f, 0.f, 0.f, 0.f}, xn[4], pred[4], prev[4] = {0.f, 0.f, 0.f, 0.f};
-    if (multi) guide_ld4(prev, upd.x0_prev, i, cnt, vec);
-    guide_ld4(xt, xp, i, cnt, vec);
-    if (noisy) guide_ld4(z, zrow, i, cnt, vec);
-    bool bad = false;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        bad = bad || (j < cnt && !(fabsf(c[j]) <= 3.0e38f && fabsf(u[j]) <= 3.0e38f));
-        bool badj = false;
-        xn[j] = ddim_update(guided ? guide_combine(c[j], u[j], wm1) : c[j], xt[j], cc, upd.flags, noisy, z[j], badj, pred[j]);
-        if (multi) xn[j] += cc[8] * (pred[j] - prev[j]);      // (multistep_update, dc_dev.h, on this thread's four elements)
-        bad = bad || (j < cnt && badj);
-        if (j < cnt) xn[j] = known_replace(xn[j], kn, i + j, cc);
-    }
-    guide_st4(xp, i, xn, cnt, vec);
-    if (multi) guide_st4(upd.x0_prev, i, pred, cnt, vec);
-    if (snap >= 0) guide_st4(snaps + (size_t)snap * n, i, xn, cnt, vec);
+    float xn[4];
+    update_quad(xn, c, u, guided, wm1, xp, snaps, n, i, cnt, vec, su, upd);
+    quad_st(xp, i, xn, cnt, vec);
     // x_{t-1} into every covering window's slot of the internal x: the walk above, storing
     for (int k = 0; k < W; ++k) {
         const size_t row0 = (size_t)start[k] * P, row1 = row0 + TP;
@@ -272,8 +252,8 @@ __global__ __launch_bounds__(256) void k_windows_update(const float* __restrict_
         if (one_piece && cnt == 4 && row0 <= r && r + 3 < row1) {
             const size_t o = ((size_t)k * Bp + b) * TP + (r - row0);
             const bool v4 = vec_w && (o & 3) == 0;
-            guide_st4(xw, o, xn, 4, v4);
-            if (guided) guide_st4(xw + half, o, xn, 4, v4);
+            quad_st(xw, o, xn, 4, v4);
+            if (guided) quad_st(xw + half, o, xn, 4, v4);
             continue;
         }
 #pragma unroll
@@ -284,7 +264,6 @@ __global__ __launch_bounds__(256) void k_windows_update(const float* __restrict_
             if (guided) xw[half + o] = xn[j];
         }
     }
-    if (bad && upd.status) atomicOr(upd.status, DC_STATUS_NONFINITE);
 }
 
 // ------------------------------------------------------------------------------------
@@ -1988,24 +1967,18 @@ void k_layer(const DcModel* __restrict__ dm, int l, float* __restrict__ hbuf, co
             }
             f32x16 xv = splat(0.f);
             if (active && live) {
-                const size_t xrow = (size_t)xb * Tx + xn;
-                const int ib = iter_base ? *iter_base : 0;
-                const float* cc = coef_cur + DC_COEF * ib;
-                const int snap = snap_cur[ib];
-                const bool noisy = (upd.flags & DC_UPD_NOISY) != 0;
-                const float* zrow = nullptr;
-                if (noisy) zrow = *upd.zslot + ((upd.flags & DC_UPD_ZSTEP) ? (size_t)0 : (size_t)(iter_base ? upd.step + ib : snap_cur[1]) * B * Tx * P);
-                const KnownPtrs kn = known_ptrs(upd);
+                const size_t xrow = (size_t)xb * Tx + xn, n = (size_t)B * Tx * P;
+                const StepUpdate su = step_update(coef_cur, snap_cur, iter_base, upd, n);
                 bool bad = false;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
                     const int f = tile_row(r, cx.hh);
                     if (f < P) {
                         const size_t o = xrow * P + f;
-                        // (known values go in BEFORE xv takes the element: the next step's embedding below reads the registers, not xout)
-                        const float xnew = known_replace(multistep_update(x0[0][r], xtv[r], cc, upd, noisy, noisy ? zrow[o] : 0.f, bad, o), kn, o, cc);
+                        // (known values are in BEFORE xv takes the element: the next step's embedding below reads the registers, not xout)
+                        const float xnew = step_update_element(su, upd, x0[0][r], xtv[r], o, bad);
                         xout[o] = xnew;
-                        if (snap >= 0) snaps[(size_t)snap * B * Tx * P + o] = xnew;
+                        if (su.snap >= 0) snaps[(size_t)su.snap * n + o] = xnew;
                         xv[r] = xnew;
                     }
                 }
@@ -2045,24 +2018,17 @@ void k_layer(const DcModel* __restrict__ dm, int l, float* __restrict__ hbuf, co
         }
         if (bad && upd.status) atomicOr(upd.status, DC_STATUS_NONFINITE);
     } else {
-        // graph-captured loop: coef_cur / snap_cur point at this step's slot of the per-iteration tables and *iter_base is
-        // the iteration at which the graph replay began; otherwise they are the scalars k_begin_step prepared
-        const int ib = iter_base ? *iter_base : 0;
-        coef_cur += DC_COEF * ib;
-        const int snap = snap_cur[ib];
-        const bool noisy = (upd.flags & DC_UPD_NOISY) != 0;
-        const float* zrow = nullptr;
-        if (noisy) zrow = *upd.zslot + ((upd.flags & DC_UPD_ZSTEP) ? (size_t)0 : (size_t)(iter_base ? upd.step + ib : snap_cur[1]) * B * Tx * P);
-        const KnownPtrs kn = known_ptrs(upd);
+        const size_t n = (size_t)B * Tx * P;
+        const StepUpdate su = step_update(coef_cur, snap_cur, iter_base, upd, n);
         bool bad = false;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int f = tile_row(r, cx.hh);
             if (f < P) {
                 const size_t o = xrow * P + f;
-                const float xnew = known_replace(multistep_update(x0[0][r], xin[o], coef_cur, upd, noisy, noisy ? zrow[o] : 0.f, bad, o), kn, o, coef_cur);
+                const float xnew = step_update_element(su, upd, x0[0][r], xin[o], o, bad);
                 xout[o] = xnew;
-                if (snap >= 0) snaps[(size_t)snap * B * Tx * P + o] = xnew;
+                if (su.snap >= 0) snaps[(size_t)su.snap * n + o] = xnew;
             }
         }
         if (bad && upd.status) atomicOr(upd.status, DC_STATUS_NONFINITE);
@@ -2926,19 +2892,16 @@ __global__ __launch_bounds__(512, 2) void k_layer_full(const DcModel* __restrict
             }
         }
     } else {
-        const int snap = snap_cur[0];
-        const bool noisy = (upd.flags & DC_UPD_NOISY) != 0;
-        const float* zrow = nullptr;                                                      // (k_begin_step runs every step on this path)
-        if (noisy) zrow = *upd.zslot + ((upd.flags & DC_UPD_ZSTEP) ? (size_t)0 : (size_t)snap_cur[1] * M * P);
-        const KnownPtrs kn = known_ptrs(upd);
+        const size_t n = (size_t)M * P;
+        const StepUpdate su = step_update(coef_cur, snap_cur, nullptr, upd, n);      // (k_begin_step runs every step on this path)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int f = tile_row(r, cx.hh);
             if (f < P) {
                 const size_t o = (size_t)cx.tok * P + f;
-                const float xn = known_replace(multistep_update(x0[0][r], xin[o], coef_cur, upd, noisy, noisy ? zrow[o] : 0.f, bad, o), kn, o, coef_cur);
+                const float xn = step_update_element(su, upd, x0[0][r], xin[o], o, bad);
                 xout[o] = xn;
-                if (snap >= 0) snaps[(size_t)snap * M * P + o] = xn;
+                if (su.snap >= 0) snaps[(size_t)su.snap * n + o] = xn;
             }
         }
     }

@@ -911,15 +911,8 @@ void k_layer16(const DcModel* __restrict__ dm, int l, float* __restrict__ hbuf, 
                 }
             }
     } else {
-        // graph-captured loop: coef_cur / snap_cur point at this step's slot of the per-iteration tables and *iter_base is the
-        // iteration at which the graph replay began; otherwise they are the scalars k_begin_step prepared
-        const int ib = iter_base ? *iter_base : 0;
-        coef_cur += DC_COEF * ib;
-        const int snap = snap_cur[ib];
-        const bool noisy = (upd.flags & DC_UPD_NOISY) != 0;
-        const float* zrow = nullptr;
-        if (noisy) zrow = *upd.zslot + ((upd.flags & DC_UPD_ZSTEP) ? (size_t)0 : (size_t)(iter_base ? upd.step + ib : snap_cur[1]) * B * Tx * P);
-        const KnownPtrs kn = known_ptrs(upd);
+        const size_t n = (size_t)B * Tx * P;
+        const StepUpdate su = step_update(coef_cur, snap_cur, iter_base, upd, n);
 #pragma unroll
         for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
@@ -927,9 +920,9 @@ void k_layer16(const DcModel* __restrict__ dm, int l, float* __restrict__ hbuf, 
                 const int ft = 16 * rb + 4 * c.q4 + i;
                 if (ft < P) {
                     const size_t o = xrow * P + ft;
-                    const float xnew = known_replace(multistep_update(x0[rb][i], xin[o], coef_cur, upd, noisy, noisy ? zrow[o] : 0.f, bad, o), kn, o, coef_cur);
+                    const float xnew = step_update_element(su, upd, x0[rb][i], xin[o], o, bad);
                     xout[o] = xnew;
-                    if (snap >= 0) snaps[(size_t)snap * B * Tx * P + o] = xnew;
+                    if (su.snap >= 0) snaps[(size_t)su.snap * n + o] = xnew;
                 }
             }
     }

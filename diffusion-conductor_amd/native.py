@@ -72,17 +72,20 @@ HEADERS = ("dc_common.h", "dc_dev.h", "dc_form.h", "dc_handle.h", "dc_launch.h",
 EXTRA_FLAGS = {}      # per-source compiler flags
 
 
-def build_library(force: bool = False, verbose: bool = False) -> str:
+def build_library(force: bool = False, verbose: bool = False, out: str = None, objdir: str = None, extra_flags=()) -> str:
     """Compile csrc/*.hip for gfx950 into libdc_ddim.so (hipcc cross-compiles without a GPU).  Each source becomes an
-    object under build/ (compiled in parallel, rebuilt only when it or a header changed), then one link."""
+    object under build/ (compiled in parallel, rebuilt only when it or a header changed), then one link.  A/B variants
+    (tools/ab.sh): `out` names another library, `objdir` its own object directory (objects built with other flags must
+    not mix), `extra_flags` go to every compile."""
+    out = out or LIB_PATH
     srcs = [os.path.join(CSRC, f) for f in SOURCES if os.path.exists(os.path.join(CSRC, f))]
     hdrs = [os.path.join(CSRC, f) for f in HEADERS if os.path.exists(os.path.join(CSRC, f))] + \
         [os.path.join(os.path.dirname(_HERE), "include", "dc_ddim.h")]
     hmax = max(os.path.getmtime(h) for h in hdrs)
-    bdir = os.path.join(_HERE, "build")
+    bdir = objdir or os.path.join(_HERE, "build")
     os.makedirs(bdir, exist_ok=True)
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wno-unused-value"]
+    flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wno-unused-value", *extra_flags]
     objs, jobs = [], []
     for src in srcs:
         obj = os.path.join(bdir, os.path.basename(src).replace(".hip", ".o"))
@@ -95,12 +98,12 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
     for cmd, p in jobs:
         if p.wait() != 0:
             raise subprocess.CalledProcessError(p.returncode, cmd)
-    if jobs or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < max(os.path.getmtime(o) for o in objs):
-        cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", *objs, "-o", LIB_PATH]
+    if jobs or not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(o) for o in objs):
+        cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", *objs, "-o", out]
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.run(cmd, check=True)
-    return LIB_PATH
+    return out
 
 
 _lib = None

@@ -7,10 +7,15 @@ set -e
 R="$(cd "$(dirname "$0")/.." && pwd)"
 case "$1" in
   build)
-    cd "$R/diffusion-conductor_amd/csrc"
-    V="$2"; shift 2
-    hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -fvisibility=hidden -shared -Wno-unused-value "$@" dc_kernels.hip dc_api.hip dc_music.hip dc_layer16.hip -o "../libdc_ddim_$V.alt"
-    ls -la "../libdc_ddim_$V.alt" ;;
+    V="$2"; shift 2      # (native.build_library: every source of native.SOURCES, objects under build/ab_$V, rebuilt only when stale)
+    cd "$R" && python - "$V" "$@" <<'PY'
+import sys
+import diffusion_conductor_amd  # noqa: F401
+from diffusion_conductor_amd import native
+v, d = sys.argv[1], native._HERE
+print(native.build_library(verbose=True, out=f"{d}/libdc_ddim_{v}.alt", objdir=f"{d}/build/ab_{v}", extra_flags=sys.argv[2:]))
+PY
+    ;;
   run)
     cd "$R"
     shift
